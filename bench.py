@@ -7,6 +7,11 @@
 A "step" is one VVIntegrator step of the whole box: synthetic force provider (plays OpenMM's calcForcesAndEnergy,
 IN the timed region) + the fused middle-scheme integrator path (TGNH thermostat, Drude hard wall).  State is
 resident in HBM before the timed region starts.  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement".
+
+A plain run sets up, warms up, times EXACTLY K steps once and prints the headline line.  --full adds everything else the
+benchmark measures: short regions repeated (median), rocprofv3 child runs, roofline, integrator-alone and constrained figures,
+the other configurations, the large box, the CPU baseline and the sharded series of a scaling run.
+--dump-outputs DIR writes the state the timed steps left behind (positions, velocities, thermostat) as DIR/<name>.npy.
 """
 import argparse
 import importlib
@@ -182,7 +187,7 @@ def rocprof_child(args, extra, seconds=240):
     tmp = tempfile.mkdtemp(prefix="vvbench_", dir="/tmp")
     try:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "run", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-               "--child", "--precision", args.precision, "--forces", args.forces, "--steps-per-graph", str(args.steps_per_graph)] + extra
+               "--child", "--full", "--precision", args.precision, "--forces", args.forces, "--steps-per-graph", str(args.steps_per_graph)] + extra
         env = dict(os.environ, VVHIP_BENCH_CHILD="1", TMPDIR="/tmp")
         # own session + output to a file: on a time-out the WHOLE group goes (rocprofv3 is a wrapper; its python grandchild would
         # otherwise keep the pipes open and share the GPU with the timed region of this process)
@@ -365,6 +370,28 @@ def roofline_block(ctx, n_local, times, rec=None, src=None, note=None, ref_key=N
     return out
 
 
+DUMP_MAX_ROWS = 800_000          # --dump-outputs: positions + velocities + sample index of at most this many particles (< 64 MB)
+
+
+def dump_outputs(path, pos, vel, nh):
+    """What a caller of the timed path receives after its last step: positions [nm] and velocities [nm/ps] of every particle (float64,
+    mixed precision: the f32 position plus its f32 correction), and the Nose-Hoover chain state of the three thermostat groups.  Above
+    DUMP_MAX_ROWS particles a fixed, seeded sample of them is written, with its particle indices in sample_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if len(pos) > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(20241008).choice(len(pos), DUMP_MAX_ROWS, replace=False))
+        arrays["sample_index"] = idx.astype(np.float64)
+        pos, vel = pos[idx], vel[idx]
+    arrays["positions"] = pos
+    arrays["velocities"] = vel
+    for field in ("eta", "eta_dot", "eta_dotdot", "ke2", "vscale"):
+        arrays["thermostat_" + field] = np.array(getattr(nh, field))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -391,6 +418,10 @@ def main():
     ap.add_argument("--no-rocprof", action="store_true", help="do not spawn the rocprofv3 child runs; roofline.frac then comes from the dispatch-timestamp clock")
     ap.add_argument("--no-other-configs", action="store_true", help="skip config.other_configs (C4, C5, C2, C1 under the driver's flags)")
     ap.add_argument("--hbonds", action="store_true", help="constraints solved in-kernel: HBonds (SHAKE) for the ionic liquids, rigid water (SETTLE) for C2; not the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeat short timed regions (median), rocprofv3 child runs, roofline, secondary blocks, CPU baseline, sharded series")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write positions / velocities / thermostat state of the last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     # ---- N > 1 without a launcher: become the launcher (child process; nothing below runs in this process)
@@ -399,7 +430,7 @@ def main():
 
     # ---- rocprofv3 child runs, BEFORE this process initialises the GPU (kernel durations as the profiler reports them, measured live)
     prof = {}
-    if not args.child and not args.headline_only and not args.no_rocprof and args.gpus == 1 and not args.eager and not args.force_dist:
+    if args.full and not args.child and not args.headline_only and not args.no_rocprof and args.gpus == 1 and not args.eager and not args.force_dist:
         base = ["--config", args.config] + (["--synthetic"] if args.synthetic else [])
         short = ["--steps", "200", "--warmup", "40"] if args.config.startswith("C3x") else ["--steps", "4000", "--warmup", "400"]
         # (bounded: a child normally takes 3-15 s; if the first one cannot run, the others are not tried -- same reason, same answer)
@@ -714,11 +745,12 @@ def main():
             el = float(t.item())
         return el
 
-    # EXACTLY K steps between two fences (barrier + synchronize), slowest rank.  A K-step region shorter than 50 ms (K = 20 is
-    # ~0.3 ms) is dominated by the jitter of one host synchronisation, so it is measured up to 25 times back to back (the simulation
-    # simply runs on) and the MEDIAN K-step time is reported; `timed_repeats` and the spread are in the line.
+    # EXACTLY K steps between two fences (barrier + synchronize), slowest rank.  With --full, a K-step region shorter than 50 ms (K = 20
+    # is ~0.3 ms) is dominated by the jitter of one host synchronisation, so it is measured up to 25 times back to back (the simulation
+    # simply runs on) and the MEDIAN K-step time is reported; `timed_repeats` and the spread are in the line.  A plain run times the K
+    # steps once, so that the state it ends on (--dump-outputs) is the same from run to run.
     samples = [timed_k_steps()]
-    if samples[0] < 0.05:
+    if args.full and samples[0] < 0.05:
         reps = int(min(24, max(4, 0.1 / max(samples[0], 1e-6))))        # the same on every rank: samples[0] is the max over ranks
         for _ in range(reps):
             samples.append(timed_k_steps())
@@ -739,6 +771,16 @@ def main():
     x = ctx.getPositions()
     if not np.isfinite(x).all():
         raise SystemExit("non-finite positions after the timed run")
+    if args.dump_outputs:
+        v = ctx.getVelocities()
+        if use_dist:                          # every rank holds its own shard; the shards are contiguous and in rank order
+            shards = [None] * world
+            dist.all_gather_object(shards, (x, v))
+            x_all, v_all = np.concatenate([s[0] for s in shards]), np.concatenate([s[1] for s in shards])
+        else:
+            x_all, v_all = x, v
+        if rank == 0:
+            dump_outputs(args.dump_outputs, x_all, v_all, ctx.getNHState())
 
     out = None
     if rank == 0:
@@ -811,13 +853,26 @@ def main():
             ts.append(time.perf_counter() - t0)
         return k / statistics.median(ts)
 
+    def finish():
+        ctx.close()
+        if use_dist:
+            dist.destroy_process_group()
+        if rank == 0:          # last thing on stdout (librccl prints a banner of its own when the process group comes up)
+            sys.stdout.flush()
+            try:
+                import ctypes
+                ctypes.CDLL(None).fflush(None)      # librccl's banner sits in the C stdio buffer until exit otherwise
+            except Exception:
+                pass
+            print(json.dumps(out), flush=True)
+
+    if not args.full or args.child or args.headline_only:          # a plain run, and the run rocprofv3 wraps: the headline is all it needs
+        finish()
+        return
+
     # ---- the integrator path alone: forces resident in HBM (static buffer, zeroed: thermostatted free flight -- the same loads, stores
     # and arithmetic as with any other force values, and nothing that can run away), no provider kernel in the loop.  The physical
     # state is saved and put back: the particles leave their tether sites meanwhile.
-    if args.child or args.headline_only:          # the run rocprofv3 wraps: the headline loop is all it needs
-        ctx.close()
-        print(json.dumps(out), flush=True)
-        return
     if world == 1 and rank == 0 and not use_dist and args.forces == "tether" and not args.eager:
         snap = (ctx.getPosq(), ctx.getPosqCorrection(), ctx.getVelm(), ctx.getNHState())
         prov = ctx.force_provider
@@ -1147,17 +1202,7 @@ def main():
             if isinstance(blkl, dict):
                 blkl["note"] = "third series of a scaling run: the regime in which sharding pays; compare with config.large_n of the N = 1 line"
             out["config"]["large_n_sharded"] = blkl
-    ctx.close()
-    if use_dist:
-        dist.destroy_process_group()
-    if rank == 0:          # last thing on stdout (librccl prints a banner of its own when the process group comes up)
-        sys.stdout.flush()
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)      # librccl's banner sits in the C stdio buffer until exit otherwise
-        except Exception:
-            pass
-        print(json.dumps(out), flush=True)
+    finish()
 
 
 if __name__ == "__main__":

@@ -74,7 +74,7 @@ def test_bench_two_ranks_share_one_gpu_mailbox():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29545", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device",
-           "--steps", "400", "--warmup", "100", "--no-cpu-baseline", "--large-n", "C3x8"]
+           "--steps", "400", "--warmup", "100", "--full", "--no-cpu-baseline", "--large-n", "C3x8"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -97,7 +97,7 @@ def test_bench_second_series_large_box_sharded_two_ranks():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29565", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--dist-mode", "python",
-           "--steps", "100", "--warmup", "20", "--no-cpu-baseline", "--large-n", "C3x8"]
+           "--steps", "100", "--warmup", "20", "--full", "--no-cpu-baseline", "--large-n", "C3x8"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -173,7 +173,7 @@ def test_distributed_code_path_costs_nothing_at_one_rank():
     vals = {}
     for label, extra in (("plain", []), ("dist", ["--force-dist"]), ("plain2", []), ("dist2", ["--force-dist"]), ("plain_long", []), ("dist_long", ["--force-dist"])):
         steps, warmup = ("4000", "400") if label.endswith("long") else ("20", "5")          # the driver's flags; one long run beside them
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup, "--no-cpu-baseline",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", steps, "--warmup", warmup, "--full", "--no-cpu-baseline",
                             "--no-rocprof", "--large-n", "none"] + extra, capture_output=True, text=True, env=env, timeout=900)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])

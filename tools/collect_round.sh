@@ -12,7 +12,7 @@ timeout 900 python tools/probes/fused_ab.py C3,C4,C5,C2,C1,C3hb,C5hb,C2hb 3 > $O
 [ -f tools/probes/libs/libvvhip_r05.so ] && ROUNDS=3 timeout 600 bash tools/probes/ab_lib_rates.sh "C3 C4 C5 C2 C1 C3hb C5hb C2hb" tools/probes/libs/libvvhip_r05.so openmm-velocityverlet_amd/lib/libvvhip.so > $O/r05_vs_r06_ab.txt 2>&1
 CLASSIC=1 timeout 600 python tools/probes/fused_ab.py C3,C4,C5,C2 2 10000 > $O/classic_scheme_ab.txt 2>&1
 timeout 600 python tools/probes/shard_step.py C4 8,4,2 > $O/shard_step.txt 2>&1
-( time python bench.py > $O/bench_default_timed.json 2> $O/bench_default_timed.stderr ) 2> $O/bench_default_wallclock.txt
+( time python bench.py --full > $O/bench_default_timed.json 2> $O/bench_default_timed.stderr ) 2> $O/bench_default_wallclock.txt
 bash tools/profile_round.sh $T C3 > /dev/null 2>&1
 bash tools/profile_round.sh $T C4 > /dev/null 2>&1
 EXTRA=--hbonds SUF=_hbonds bash tools/profile_round.sh $T C3 > /dev/null 2>&1

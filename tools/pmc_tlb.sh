@@ -11,7 +11,7 @@ rocprofv3 -L > "$OUT/counters_available.txt" 2>&1
 P=0
 for SET in "TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_LATENCY_sum"; do
     P=$((P+1))
-    rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$OUT/pmc_tlb$P" -o run -- python3 "$ROOT/bench.py" --config "$CFG" --large-n none --steps 400 --warmup 100 --no-cpu-baseline --no-rocprof --headline-only > "$OUT/pmc_tlb_${CFG}_$P.log" 2>&1
+    rocprofv3 --pmc $SET --kernel-trace --output-format csv -d "$OUT/pmc_tlb$P" -o run -- python3 "$ROOT/bench.py" --full --config "$CFG" --large-n none --steps 400 --warmup 100 --no-cpu-baseline --no-rocprof --headline-only > "$OUT/pmc_tlb_${CFG}_$P.log" 2>&1
 done
 python3 - "$OUT" "$TAG" "$CFG" <<'PY' > "$OUT/pmc_tlb_$CFG.json"
 import csv, glob, json, os, re, sys

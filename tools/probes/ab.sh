@@ -7,7 +7,7 @@ cp $L /tmp/base.so
 for i in 1 2 3; do
   for which in base variant; do
     if [ $which = base ]; then cp /tmp/base.so $L; else cp $V $L; fi
-    python bench.py --steps 4000 --warmup 400 --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --steps 4000 --warmup 400 --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); ln=d['config'].get('large_n'); print('$which', d['value'], d['roofline']['avg_launch_us'], {k:v['avg_launch_us'] for k,v in ln['roofline'].items()} if ln else '')"
   done
 done

@@ -7,7 +7,7 @@ cp $L /tmp/base.so
 for i in $(seq 1 ${ROUNDS:-2}); do
   for v in "$@"; do
     if [ "$v" = base ]; then cp /tmp/base.so $L; else cp "$v" $L; fi
-    python bench.py $ARGS --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    python bench.py --full $ARGS --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$(basename $v)', d['value'], d['roofline']['avg_launch_us'], d['roofline']['frac'])"
   done
 done
