@@ -295,6 +295,25 @@ int vvhip_calc_viscosity(vvhip_plan* plan, double* v_max, double* inv_viscosity)
 /* 1/2 sum m v^2 over all massive particles of this shard (blocks; the reference forwards computeKineticEnergy to OpenMM's
  * integration utilities, CudaVVKernels.cpp:233-235 -- a stand-alone host has no such service). kJ/mol. */
 int vvhip_compute_kinetic_energy(vvhip_plan* plan, double* kinetic_energy);
+/* Drude temperature report: the temperatures of the molecules' centres of mass, of the atoms inside them and of the Drude pairs'
+ * relative motion in the current velocities, as examples/ommhelper/reporter/drudetemperaturereporter.py defines them, over ALL
+ * particles (NH and Langevin subsets, images and sites alike; massless particles add nothing).  ke = KE_COM, KE_Atom, KE_Drude in
+ * kJ/mol, t = T_COM, T_Atom, T_Drude in K; T = 2 KE / (dof R), R = 8.31446261815324e-3 kJ/(mol K), and 0 where dof <= 0 (a System
+ * without Drude pairs reports T_Drude = 0).  Runs in the plan's stream behind what is queued, blocks, copies 56 bytes back, and
+ * touches no state of the step (accumulators, thermostat, status words, captured graphs).  The sums are fixed point: the same
+ * velocities give the same bits whatever the launch shape or the split into shards.  A term outside the fixed-point range (a velocity
+ * far beyond physical values, NaN) gives VVHIP_ERR_OVERFLOW for this call only; a plan whose shard cuts a molecule gives
+ * VVHIP_ERR_UNSUPPORTED.
+ * A SHARD reports its own particles' sums and the WHOLE system's DOFs: add the raw sums of all shards (vvhip_drude_report_raw, int64
+ * sums) and turn the total into numbers with vvhip_drude_report_combine -- the single-GPU result, bit for bit. */
+int vvhip_drude_temperatures(vvhip_plan* plan, double ke[3], double t[3]);
+/* DOFs of the report (COM, Atom, Drude) for the whole system; host only, works on an unbound plan. */
+int vvhip_drude_report_dof(const vvhip_plan* plan, double dof[3]);
+/* The report's raw sums of 2 KE: (hi, lo) words of sum m|v|^2, of the Drude pairs' term and of the COM term (value = (hi + lo 2^-F) 2^-U,
+ * F and U fixed per system: vvhip_drude_report_combine's business); blocks like vvhip_drude_temperatures. */
+int vvhip_drude_report_raw(vvhip_plan* plan, int64_t raw[6]);
+/* ke / t from raw sums (one shard's, or the element-wise sum over all shards); host only. */
+int vvhip_drude_report_combine(const vvhip_plan* plan, const int64_t raw[6], double ke[3], double t[3]);
 /* Device pointer of the plan-owned forceExtra array (real3[n]); getForceExtra() of the reference
  * (CudaVVKernels.h:86-88). */
 int vvhip_force_extra(vvhip_plan* plan, void** device_ptr);

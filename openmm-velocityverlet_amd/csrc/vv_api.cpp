@@ -237,6 +237,15 @@ struct vvhip_plan {
     int dbg_parity = 0;
     long long* d_dbg = nullptr;                   // instrumented build only (vvhip_debug_timestamps)
     int dbg_block = 0;
+    // Drude temperature report (vvhip_drude_temperatures): its tables (HostPlan::report_*) and its own scratch, nothing shared with the step
+    int32_t* d_rep_lane_mol = nullptr;
+    double* d_rep_lane_mass = nullptr;
+    double* d_rep_lane_mu = nullptr;
+    double* d_rep_mol_mass = nullptr;
+    int4* d_rep_cross = nullptr;
+    double* d_rep_cross_mu = nullptr;
+    long long* d_rep = nullptr;                   // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
+    long long* h_rep = nullptr;                   // pinned: the result words as copied back
 };
 
 static void drop_graphs(vvhip_plan* p) {
@@ -854,8 +863,11 @@ void vvhip_plan_destroy(vvhip_plan* p) {
         (void) hipStreamSynchronize(p->stream);
         for (void* ptr : {(void*) p->d_slots, (void*) p->d_slot_image, (void*) p->d_slot_rand, (void*) p->d_slot_shake, (void*) p->d_slot_shake_param, (void*) p->d_slot_vsite, (void*) p->d_vsite_params, (void*) p->d_vsite_atom, (void*) p->d_slot_big, (void*) p->d_bigacc, (void*) p->d_image_pairs,
                           p->d_fextra, p->d_old_delta, p->d_pos_delta, p->d_comv, (void*) p->d_comw, (void*) p->d_seg_mass, (void*) p->d_seg_base, (void*) p->d_slot_m, (void*) p->d_slot_f, (void*) p->d_cosz, (void*) p->d_epoch, (void*) p->d_acc, (void*) p->d_rv, (void*) p->d_nh, (void*) p->d_lane_const, (void*) p->d_dbg, (void*) p->d_dbg_span,
-                          p->rec.posq, p->rec.corr, p->rec.velm, p->rec.force, p->rec.fextra, p->rec.random, (void*) p->rec.nh, (void*) p->rec.epoch})
+                          p->rec.posq, p->rec.corr, p->rec.velm, p->rec.force, p->rec.fextra, p->rec.random, (void*) p->rec.nh, (void*) p->rec.epoch,
+                          (void*) p->d_rep_lane_mol, (void*) p->d_rep_lane_mass, (void*) p->d_rep_lane_mu, (void*) p->d_rep_mol_mass, (void*) p->d_rep_cross,
+                          (void*) p->d_rep_cross_mu, (void*) p->d_rep})
             if (ptr) (void) hipFree(ptr);
+        if (p->h_rep) (void) hipHostFree(p->h_rep);
         drop_graphs(p);
         if (p->comm) (void) rccl_api().commDestroy(p->comm);
         mailbox_release(p);
@@ -991,6 +1003,21 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
     for (int c = 0; c < 2; c++) init[c].rv_delay = 6;      // where the wait of the fused step's rendezvous starts (it tunes itself from there)
     HIP_TRY(p, hipMemcpy(p->d_nh, init, sizeof(init), hipMemcpyHostToDevice));
     HIP_TRY(p, hipMalloc((void**) &p->d_lane_const, VVHIP_NUM_TG * sizeof(vv::ChainLaneBlock)));
+    {   // Drude temperature report: tables and scratch of its own
+        auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
+            HIP_TRY(p, hipMalloc(dst, std::max<size_t>(bytes, 16)));
+            if (bytes) HIP_TRY(p, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+            return VVHIP_OK;
+        };
+        TRY(upload((void**) &p->d_rep_lane_mol, hp.report_lane_mol.data(), hp.report_lane_mol.size() * sizeof(int32_t)));
+        TRY(upload((void**) &p->d_rep_lane_mass, hp.report_lane_mass.data(), hp.report_lane_mass.size() * sizeof(double)));
+        TRY(upload((void**) &p->d_rep_lane_mu, hp.report_lane_mu.data(), hp.report_lane_mu.size() * sizeof(double)));
+        TRY(upload((void**) &p->d_rep_mol_mass, hp.report_mol_mass.data(), hp.report_mol_mass.size() * sizeof(double)));
+        TRY(upload((void**) &p->d_rep_cross, hp.report_cross.data(), hp.report_cross.size() * sizeof(int32_t)));
+        TRY(upload((void**) &p->d_rep_cross_mu, hp.report_cross_mu.data(), hp.report_cross_mu.size() * sizeof(double)));
+        HIP_TRY(p, hipMalloc((void**) &p->d_rep, (8 + 6 * hp.report_mol_mass.size()) * sizeof(long long)));
+        HIP_TRY(p, hipHostMalloc((void**) &p->h_rep, 8 * sizeof(long long)));
+    }
     HIP_TRY(p, hipHostMalloc((void**) &p->h_status, 4 * sizeof(unsigned int), hipHostMallocMapped));
     std::memset(p->h_status, 0, 4 * sizeof(unsigned int));
     HIP_TRY(p, hipHostGetDevicePointer((void**) &p->d_status, p->h_status, 0));
@@ -1368,6 +1395,64 @@ int vvhip_compute_kinetic_energy(vvhip_plan* p, double* kinetic_energy) {   // H
     *kinetic_energy = 0.5 * acc[0];
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ Drude temperature report
+int vvhip_drude_report_dof(const vvhip_plan* p, double dof[3]) {
+    if (!p || !dof) return VVHIP_ERR_INVALID;
+    for (int g = 0; g < 3; g++) dof[g] = p->hp.report_dof[g];
+    return VVHIP_OK;
+}
+int vvhip_drude_report_raw(vvhip_plan* p, int64_t raw[6]) {
+    NEED_BOUND(p);
+    if (!raw) return VVHIP_ERR_INVALID;
+    const vv::HostPlan& hp = p->hp;
+    if (!hp.report_unsupported.empty()) return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + hp.report_unsupported);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "Drude temperature report: not inside a graph capture");
+    TRY(settle_recovery(p));
+    const int nmol = (int) hp.report_mol_mass.size();
+    HIP_TRY(p, hipMemsetAsync(p->d_rep, 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
+    vv::ReportArgs a{};
+    a.velm = p->buf.velm; a.slots = p->d_slots;
+    a.lane_mol = p->d_rep_lane_mol; a.lane_mass = p->d_rep_lane_mass; a.lane_mu = p->d_rep_lane_mu;
+    a.mol_mass = p->d_rep_mol_mass; a.cross = p->d_rep_cross; a.cross_mu = p->d_rep_cross_mu;
+    a.out = p->d_rep; a.mol_p = p->d_rep + 8;
+    a.nwaves = hp.info.num_waves; a.nmol = nmol; a.ncross = (int) hp.report_cross_mu.size();
+    a.frac_bits = hp.report_frac_bits;
+    a.unit = std::ldexp(1.0, hp.report_unit_bits); a.frac_scale = std::ldexp(1.0, hp.report_frac_bits);
+    a.inv_unit = std::ldexp(1.0, -hp.report_unit_bits); a.inv_full = std::ldexp(1.0, -hp.report_unit_bits - hp.report_frac_bits);
+    a.limit = hp.report_limit;
+    HIP_TRY(p, vv::launch_report(hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->h_rep, p->d_rep, vv::REP_WORDS * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (p->h_rep[vv::REP_FLAG])
+        return fail(p, VVHIP_ERR_OVERFLOW, "Drude temperature report: a kinetic-energy or momentum term is NaN or beyond the fixed-point range; no numbers");
+    std::memcpy(raw, p->h_rep, 6 * sizeof(int64_t));
+    return VVHIP_OK;
+}
+int vvhip_drude_report_combine(const vvhip_plan* p, const int64_t raw[6], double ke[3], double t[3]) {
+    if (!p || !raw) return VVHIP_ERR_INVALID;
+    const int F = p->hp.report_frac_bits, U = p->hp.report_unit_bits;
+    auto join = [F, U](int64_t hi, int64_t lo) {        // (hi + lo 2^-F) 2^-U with the carry of lo (of either sign) moved into hi first
+        const int64_t carry = lo >> F;                  // (arithmetic shift: floor)
+        return (double) (hi + carry) * std::ldexp(1.0, -U) + (double) (lo - carry * ((int64_t) 1 << F)) * std::ldexp(1.0, -U - F);
+    };
+    const int T = vv::REP_TOTAL, D = vv::REP_DRUDE, M = vv::REP_COM;
+    const double two_ke[3] = {join(raw[M], raw[M + 1]),
+                              join(raw[T] - raw[M] - raw[D], raw[T + 1] - raw[M + 1] - raw[D + 1]),      // KE_Atom = KE_total - KE_COM - KE_Drude
+                              join(raw[D], raw[D + 1])};
+    constexpr double R = 8.31446261815324e-3;
+    for (int g = 0; g < 3; g++) {
+        const double k = 0.5 * two_ke[g], dof = p->hp.report_dof[g];
+        if (ke) ke[g] = k;
+        if (t) t[g] = dof > 0 ? 2 * k / (dof * R) : 0.0;
+    }
+    return VVHIP_OK;
+}
+int vvhip_drude_temperatures(vvhip_plan* p, double ke[3], double t[3]) {
+    int64_t raw[6];
+    TRY(vvhip_drude_report_raw(p, raw));
+    return vvhip_drude_report_combine(p, raw, ke, t);
+}
+
 int vvhip_update_image_positions(vvhip_plan* p) {          // HOST:904-934
     NEED_BOUND(p);
     if (!p->hp.has_images) return VVHIP_OK;

@@ -231,4 +231,26 @@ struct TetherArgs {
     int32_t dbg_parity, dbg_pad_;
 };
 
+// Drude temperature report (vv_dev_report.inc, vvhip_drude_temperatures).  Sums in two-word fixed point: with y = x 2^unit_bits a term x
+// is split into hi = floor(y) and lo = rint((y - hi) 2^frac_bits) (resolution 2^-(unit_bits + frac_bits), ~1e-18 at 0.1 M particles),
+// the words are summed as integers (exact, in any order), and the host joins them.
+// out[REP_*]: total of m|v|^2, of the pairs' mu|u_d - u_c|^2, of the molecules' |P|^2/M (hi, lo each), then the overflow flag.
+enum { REP_TOTAL = 0, REP_DRUDE = 2, REP_COM = 4, REP_FLAG = 6, REP_WORDS = 7 };
+struct ReportArgs {
+    const void* velm;
+    const int2* slots;
+    const int32_t* lane_mol;        // [64*waves] shard-local molecule of the lane's particle, -1: none / massless
+    const double* lane_mass;        // [64*waves] mass, 0 where massless
+    const double* lane_mu;          // [64*waves] reduced mass of the pair on a Drude lane whose parent is in the same molecule, else 0
+    const double* mol_mass;         // [nmol] molecule masses (> 0)
+    const int4* cross;              // [ncross] (Drude, parent, molecule of the Drude, of the parent) of pairs across two molecules
+    const double* cross_mu;         // [ncross]
+    long long* mol_p;               // [nmol][6] momentum (x, y, z) as (hi, lo) word pairs
+    long long* out;                 // [REP_WORDS]
+    int32_t nwaves, nmol, ncross, frac_bits;
+    double unit, frac_scale;        // 2^unit_bits, 2^frac_bits
+    double inv_unit, inv_full;      // 2^-unit_bits, 2^-(unit_bits + frac_bits)
+    double limit;                   // largest |term| taken (beyond it, or NaN: the flag)
+};
+
 }  // namespace vv

@@ -12,3 +12,4 @@
 #include "vv_dev_chain.inc"
 #include "vv_dev_kernel_b.inc"
 #include "vv_dev_misc.inc"
+#include "vv_dev_report.inc"

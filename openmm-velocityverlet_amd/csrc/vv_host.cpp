@@ -941,6 +941,54 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
                 if (hp.has_images && image_of[a + sb] >= 0) hp.slot_image[(size_t) w * 64 + l] = image_of[a + sb] - sb;
                 if (hp.has_ld) hp.slot_rand[(size_t) w * 64 + l] = rand_of[a + sb];
             }
+
+    // ---- Drude temperature report (vv_host.hpp: report_*).  DOFs as examples/ommhelper/reporter/drudetemperaturereporter.py counts them:
+    // COM 3 n_M (- 3 with a CMMotionRemover), atomic 3 n_m - 3 n_M - n_c - 3 n_p (the remover does not enter), Drude 3 n_p.
+    {
+        int n_massive = 0, n_mol_massive = 0;
+        for (int i = 0; i < n; i++) if (sys.masses[i] > 0) n_massive++;
+        for (int m = 0; m < nmol; m++) if (mol_mass[m] > 0) n_mol_massive++;
+        hp.report_dof[0] = 3.0 * n_mol_massive - (sys.has_cm_motion_remover ? 3.0 : 0.0);
+        hp.report_dof[1] = 3.0 * n_massive - 3.0 * n_mol_massive - sys.num_constraints - 3.0 * npairs_all;
+        hp.report_dof[2] = 3.0 * npairs_all;
+        // every sum has at most n terms (also over all shards): lo < 2^(61 - bits(n)) and |x| 2^16 < 2^(61 - bits(n)) keep both words' sums
+        // inside int64.  The limit on a term (2.7e8 at 0.1 M particles, 2e6 at 9 M: kJ/mol for m|v|^2, Da nm/ps for m v) is far above
+        // physical values; a velocity beyond it makes the report fail, never the step.
+        int bits = 1;
+        while (bits < 40 && ((int64_t) 1 << bits) <= (int64_t) n) bits++;
+        hp.report_unit_bits = 16;
+        hp.report_frac_bits = 61 - bits;
+        hp.report_limit = std::ldexp(1.0, 61 - bits - hp.report_unit_bits);
+        std::vector<int32_t> local(nmol, -1);
+        for (int i = sb; i < se; i++) if (sys.masses[i] > 0) local[sys.mol_id[i]] = 0;
+        for (int m = 0; m < nmol; m++)
+            if (local[m] == 0) { local[m] = (int32_t) hp.report_mol_mass.size(); hp.report_mol_mass.push_back(mol_mass[m]); }
+        for (int i = 0; i < n && hp.report_unsupported.empty(); i++)
+            if (!in_shard(i) && sys.masses[i] > 0 && local[sys.mol_id[i]] >= 0)
+                hp.report_unsupported = "the particle shard cuts a molecule: its centre-of-mass velocity needs particles of another shard";
+        auto reduced = [&](int d, int c) {
+            const double md = sys.masses[d], mc = sys.masses[c];
+            return md > 0 && mc > 0 ? md * mc / (md + mc) : 0.0;
+        };
+        const size_t ns = (size_t) nwaves * 64;
+        hp.report_lane_mol.assign(ns, -1);
+        hp.report_lane_mass.assign(ns, 0.0);
+        hp.report_lane_mu.assign(ns, 0.0);
+        for (size_t k = 0; k < ns; k++) {
+            const int32_t a = slots[2 * k];
+            if (a < 0) continue;
+            const int i = a + sb;
+            if (sys.masses[i] > 0) { hp.report_lane_mass[k] = sys.masses[i]; hp.report_lane_mol[k] = local[sys.mol_id[i]]; }
+            if (is_drude[i] && sys.mol_id[partner[i]] == sys.mol_id[i]) hp.report_lane_mu[k] = reduced(i, partner[i]);
+        }
+        for (int k = 0; k < npairs_all; k++) {
+            const int d = sys.drude_pairs[2 * k], c = sys.drude_pairs[2 * k + 1];
+            if (!in_shard(d) || sys.mol_id[d] == sys.mol_id[c]) continue;
+            const int32_t rec[4] = {d - sb, c - sb, local[sys.mol_id[d]], local[sys.mol_id[c]]};
+            hp.report_cross.insert(hp.report_cross.end(), rec, rec + 4);
+            hp.report_cross_mu.push_back(reduced(d, c));
+        }
+    }
     return hp;
 }
 

@@ -77,6 +77,18 @@ struct HostPlan {
     int32_t num_big = 0;               // molecules with more than 64 thermostatted particles (COM temperature group only)
     double big_scale = 1.0;            // fixed-point scale of their sum(m v) accumulators
     std::vector<int32_t> image_pairs;  // (image, parent) shard-relative, for the stand-alone image kernel
+    // Drude temperature report (vvhip_drude_temperatures; vv_dev_report.inc).  Built from the System alone: independent of the COM temperature
+    // group and of thermostat membership, so a molecule's lanes may lie in several waves.
+    double report_dof[3] = {0, 0, 0};          // COM, atomic, Drude degrees of freedom of the WHOLE system (also for a shard)
+    int32_t report_unit_bits = 16, report_frac_bits = 40;   // fixed point of the sums (vv_args.hpp: ReportArgs)
+    double report_limit = 0;                   // largest |term| the sums take without leaving int64 (n terms at most)
+    std::vector<int32_t> report_lane_mol;      // [64*waves] shard-local molecule of the lane's particle; -1: no particle or massless
+    std::vector<double> report_lane_mass;      // [64*waves] mass of the lane's particle, 0 where massless
+    std::vector<double> report_lane_mu;        // [64*waves] on a Drude lane whose parent is in the same molecule: the pair's reduced mass; else 0
+    std::vector<double> report_mol_mass;       // [shard molecules] molecules with a massive particle in the shard, by molecule id
+    std::vector<int32_t> report_cross;         // 4 per pair across two molecules: Drude, parent (shard-relative), their shard-local molecules (-1: no mass)
+    std::vector<double> report_cross_mu;       // ... and its reduced mass
+    std::string report_unsupported;            // why this plan cannot report (a shard that cuts a molecule); empty otherwise
     // reference-style tables, kept for inspection / tests (global particle indices)
     std::vector<int32_t> particles_nh, molecules_nh, normal_nh, pairs_nh, normal_ld, pairs_ld;
 };

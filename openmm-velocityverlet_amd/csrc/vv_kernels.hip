@@ -29,6 +29,8 @@
 
 #include <hip/hip_ext.h>
 
+#include <algorithm>
+
 #include "vv_host.hpp"
 #include "vv_rtc.hpp"
 
@@ -472,6 +474,17 @@ hipError_t launch_image_pairs(int precision, void* posq, void* corr, const int2*
     if (npairs <= 0) return hipSuccess;
     const int blocks = (npairs + 255) / 256;
     VV_DISPATCH(vv_kernel_images, dim3(blocks), dim3(256), 0, s, posq, corr, pairs, npairs, mirror);
+    return hipGetLastError();
+}
+hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    const int wpb = block_threads / 64;
+    const int g1 = std::max(1, std::min((a.nwaves + wpb - 1) / wpb, grid_cap));
+    VV_DISPATCH(vv_kernel_report_lanes, dim3((unsigned) g1), dim3(block_threads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    const int items = a.nmol + a.ncross;
+    if (e != hipSuccess || items == 0) return e;
+    const int g2 = std::max(1, std::min((items + block_threads - 1) / block_threads, grid_cap));
+    VV_DISPATCH(vv_kernel_report_molecules, dim3((unsigned) g2), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
 #endif      // VV_KERNELS_PART != 2

@@ -47,5 +47,8 @@ bool sf_kernels_use_mass_table(int kernel);
 hipError_t launch_fill_normals(float4* out, uint32_t count, uint64_t seed, unsigned long long* epoch, hipStream_t s);
 hipError_t launch_image_pairs(int precision, void* posq, void* corr, const int2* pairs, int npairs, double mirror,
                               hipStream_t s);
+// The Drude temperature report's two passes (vv_dev_report.inc) over a.nwaves waves and a.nmol + a.ncross items: blocks of block_threads,
+// at most grid_cap of them per pass (the kernels stride beyond).  a.mol_p and a.out must be zero on entry.
+hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -139,3 +139,20 @@ class ShardedStepper:
                 H.check(H.lib.vvhip_step_middle_phase(ctx.plan, ph, 0), ctx.plan)
                 if ph < self.nphase - 1 and self.backend is not None:
                     self._all_reduce(ph)
+
+
+def drude_temperatures(ctx, group=None):
+    """The Drude temperature report of a sharded run: every rank's raw fixed-point sums (vvhip_drude_report_raw: its own particles)
+    summed over the process group, then turned into (KE_COM, KE_Atom, KE_Drude, T_COM, T_Atom, T_Drude) with the whole system's DOFs.
+    int64 sums are associative: every rank gets the single-process result bit for bit.  Collective: every rank of the group calls it."""
+    import torch
+    import torch.distributed as dist
+    raw = torch.from_numpy(ctx.drude_report_raw())
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        if dist.get_backend(group) == "nccl":
+            dev = raw.to("cuda")
+            dist.all_reduce(dev, op=dist.ReduceOp.SUM, group=group)
+            raw = dev.cpu()
+        else:
+            dist.all_reduce(raw, op=dist.ReduceOp.SUM, group=group)
+    return ctx.drude_report_combine(raw.numpy())

@@ -138,6 +138,13 @@ class VVIntegrator:
             return (0.0, 0.0)
         return self._context._viscosity()
 
+    def getDrudeTemperatures(self):
+        """(KE_COM, KE_Atom, KE_Drude) in kJ/mol and (T_COM, T_Atom, T_Drude) in K of the current velocities, as one tuple of six
+        (vvhip_drude_temperatures: computed on the device, 56 bytes copied back).  Raises when the integrator is not bound."""
+        if self._context is None:
+            raise H.VVHipError(H.ERR_INVALID, "This Integrator is not bound to a context!")
+        return self._context.getDrudeTemperatures()
+
     # ---- internals
     def _params(self) -> H.Params:
         return H.Params(self._temperature, self._frequency, self._drudeTemperature, self._drudeFrequency, self._stepSize,
@@ -203,6 +210,17 @@ def plan_layout(system: SystemSpec, integrator: "VVIntegrator", precision: str =
     finally:
         H.lib.vvhip_plan_destroy(plan)
     return info, slots
+
+
+def drude_report_dof(system: SystemSpec, integrator: "VVIntegrator", precision: str = "mixed", shard=None):
+    """Host-only: the degrees of freedom (COM, Atom, Drude) of the Drude temperature report, always those of the whole system."""
+    plan, _, _ = create_plan(system, integrator, precision, shard)
+    try:
+        dof = (C.c_double * 3)()
+        H.check(H.lib.vvhip_drude_report_dof(plan, C.byref(dof)), plan)
+    finally:
+        H.lib.vvhip_plan_destroy(plan)
+    return tuple(dof)
 
 
 def plan_launch_shape(system: SystemSpec, integrator: "VVIntegrator", precision: str = "mixed", shard=None):
@@ -340,6 +358,27 @@ class Context:
         st = self.getNHState()
         kb = 8.31446261815324e-3
         return [st.ke2[g] / (self.info.dof[g] * kb) if self.info.dof[g] > 0 else 0.0 for g in range(3)]
+
+    def getDrudeTemperatures(self):
+        """(KE_COM, KE_Atom, KE_Drude, T_COM, T_Atom, T_Drude) in kJ/mol and K of the current velocities, over all particles, as
+        examples/ommhelper/reporter/drudetemperaturereporter.py defines them (include/vvhip.h: vvhip_drude_temperatures).  T_Drude is 0
+        for a System without Drude pairs.  A shard reports its own particles' energies: see distributed.drude_temperatures."""
+        ke, t = (C.c_double * 3)(), (C.c_double * 3)()
+        H.check(H.lib.vvhip_drude_temperatures(self.plan, C.byref(ke), C.byref(t)), self.plan)
+        return tuple(ke) + tuple(t)
+
+    def drude_report_raw(self) -> np.ndarray:
+        """The report's raw fixed-point sums (int64[6]) of this plan's particles: what the shards add up (vvhip_drude_report_raw)."""
+        raw = (C.c_int64 * 6)()
+        H.check(H.lib.vvhip_drude_report_raw(self.plan, C.byref(raw)), self.plan)
+        return np.array(raw, dtype=np.int64)
+
+    def drude_report_combine(self, raw) -> tuple:
+        """The six numbers of getDrudeTemperatures from raw sums (one shard's, or the sum over all shards)."""
+        r = (C.c_int64 * 6)(*[int(x) for x in raw])
+        ke, t = (C.c_double * 3)(), (C.c_double * 3)()
+        H.check(H.lib.vvhip_drude_report_combine(self.plan, C.byref(r), C.byref(ke), C.byref(t)), self.plan)
+        return tuple(ke) + tuple(t)
 
     def getNHState(self) -> H.NHState:
         s = H.NHState()

@@ -117,6 +117,8 @@ def _load():
         "vvhip_apply_electric_force": [vp], "vvhip_apply_cosine_force": [vp], "vvhip_calc_velocity_bias": [vp],
         "vvhip_remove_velocity_bias": [vp], "vvhip_restore_velocity_bias": [vp],
         "vvhip_calc_viscosity": [vp, P(dbl), P(dbl)], "vvhip_compute_kinetic_energy": [vp, P(dbl)], "vvhip_force_extra": [vp, P(vp)],
+        "vvhip_drude_temperatures": [vp, P(dbl * 3), P(dbl * 3)], "vvhip_drude_report_dof": [vp, P(dbl * 3)],
+        "vvhip_drude_report_raw": [vp, P(C.c_int64 * 6)], "vvhip_drude_report_combine": [vp, P(C.c_int64 * 6), P(dbl * 3), P(dbl * 3)],
         "vvhip_device_count": [P(C.c_int)], "vvhip_set_device": [C.c_int],
         "vvhip_malloc": [P(vp), C.c_size_t], "vvhip_free": [vp],
         "vvhip_memcpy_h2d": [vp, vp, C.c_size_t], "vvhip_memcpy_d2h": [vp, vp, C.c_size_t],

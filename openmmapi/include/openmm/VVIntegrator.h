@@ -66,6 +66,10 @@ public:
     void setCosAcceleration(double a) { cosAcceleration = a; }
     std::vector<double> getViscosity();          // {vMax [nm/ps], 1/viscosity}
 
+    // ---- Drude temperature report of the current velocities (openmm/VVReportKernels.h; its kernel is created on the first call):
+    // {KE_COM, KE_Atom, KE_Drude [kJ/mol], T_COM, T_Atom, T_Drude [K]}
+    std::vector<double> getDrudeTemperatures();
+
     // ---- what initialize() derives (read by the platform kernels)
     const std::vector<int>& getParticlesNH() const { return particlesNH; }
     const std::vector<int>& getParticlesLD() const { return particlesLD; }
@@ -109,6 +113,8 @@ private:
     std::vector<double> moleculeMasses, moleculeInvMasses;
     std::vector<std::pair<int, int> > imagePairs;
     Kernel vvKernel, nhKernel, ldKernel, imgKernel, efKernel, ppKernel;
+    Kernel reportKernel;         // created lazily by getDrudeTemperatures()
+    bool hasReportKernel = false;
 };
 
 }  // namespace OpenMM

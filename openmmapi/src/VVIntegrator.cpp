@@ -10,6 +10,7 @@
 #include "openmm/DrudeForce.h"
 #include "openmm/OpenMMException.h"
 #include "openmm/VVKernels.h"
+#include "openmm/VVReportKernels.h"
 #include "openmm/internal/ContextImpl.h"
 
 using namespace OpenMM;
@@ -88,6 +89,8 @@ void VVIntegrator::initialize(ContextImpl& ctx) {                // REF:92-188
         throw OpenMMException("Langevin thermostat and periodic perturbation shouldn't be used together");
 
     context = &ctx;
+    reportKernel = Kernel();
+    hasReportKernel = false;
     owner = &ctx.getOwner();
     Platform& platform = ctx.getPlatform();                     // REF:160-187: step kernel first, the others may borrow from it
     if (useMiddleScheme) {
@@ -120,7 +123,8 @@ void VVIntegrator::initialize(ContextImpl& ctx) {                // REF:92-188
 }
 
 void VVIntegrator::cleanup() {                                   // REF:190-197
-    vvKernel = nhKernel = ldKernel = imgKernel = efKernel = ppKernel = Kernel();
+    vvKernel = nhKernel = ldKernel = imgKernel = efKernel = ppKernel = reportKernel = Kernel();
+    hasReportKernel = false;
 }
 
 std::vector<std::string> VVIntegrator::getKernelNames() {        // REF:199-209
@@ -227,6 +231,18 @@ void VVIntegrator::propagateNHChain(std::vector<double>& eta, std::vector<double
             etaDot[k] = (etaDot[k] * damp + etaDotDot[k] * h4) * damp;
         }
     }
+}
+
+std::vector<double> VVIntegrator::getDrudeTemperatures() {
+    if (context == NULL) throw OpenMMException("This Integrator is not bound to a context!");
+    if (!hasReportKernel) {                    // not among initialize()'s kernels: a context that never reports creates the reference's seven only
+        reportKernel = context->getPlatform().createKernel(CalcDrudeTemperaturesKernel::Name(), *context);
+        reportKernel.getAs<CalcDrudeTemperaturesKernel>().initialize(context->getSystem(), *this);
+        hasReportKernel = true;
+    }
+    double ke[3] = {0, 0, 0}, t[3] = {0, 0, 0};
+    reportKernel.getAs<CalcDrudeTemperaturesKernel>().calcDrudeTemperatures(*context, *this, ke, t);
+    return {ke[0], ke[1], ke[2], t[0], t[1], t[2]};
 }
 
 std::vector<double> VVIntegrator::getViscosity() {               // REF:378-383

@@ -12,6 +12,7 @@
 #include "openmm/VVIntegrator.h"
 #include "openmm/VVKernels.h"
 #include "openmm/FusedVVStepKernel.h"
+#include "openmm/VVReportKernels.h"
 #include "vvhip.h"
 
 namespace OpenMM {
@@ -166,6 +167,18 @@ public:
     void removeVelocityBias(ContextImpl& context, const VVIntegrator& integrator);
     void restoreVelocityBias(ContextImpl& context, const VVIntegrator& integrator);
     void calcViscosity(ContextImpl& context, const VVIntegrator& integrator, double& vMax, double& invVis);
+private:
+    HipContext& cu;
+    std::shared_ptr<HipVVPlan> plan;
+};
+
+// The Drude temperature report (openmm/VVReportKernels.h) on the step kernel's plan: vvhip_drude_temperatures.  Uses nothing of VVIntegrator
+// beyond what the reference's header has too (oracle/Makefile: refplugin builds this file against it).
+class HipCalcDrudeTemperaturesKernel : public CalcDrudeTemperaturesKernel {
+public:
+    HipCalcDrudeTemperaturesKernel(std::string name, const Platform& platform, HipContext& cu) : CalcDrudeTemperaturesKernel(name, platform), cu(cu) {}
+    void initialize(const System& system, const VVIntegrator& integrator);
+    void calcDrudeTemperatures(ContextImpl& context, const VVIntegrator& integrator, double ke[3], double t[3]);
 private:
     HipContext& cu;
     std::shared_ptr<HipVVPlan> plan;

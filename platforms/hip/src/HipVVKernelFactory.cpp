@@ -15,7 +15,8 @@ extern "C" void registerKernelFactories() {
         HipVVKernelFactory* factory = new HipVVKernelFactory();   // lives as long as the platform, like the reference's
         for (const std::string& name : {IntegrateMiddleStepKernel::Name(), IntegrateVVStepKernel::Name(), ModifyDrudeNoseKernel::Name(),
                                         ModifyDrudeLangevinKernel::Name(), ModifyImageChargeKernel::Name(),
-                                        ModifyElectricFieldKernel::Name(), ModifyCosineAccelerateKernel::Name()})
+                                        ModifyElectricFieldKernel::Name(), ModifyCosineAccelerateKernel::Name(),
+                                        CalcDrudeTemperaturesKernel::Name()})      // (created on demand by VVIntegrator::getDrudeTemperatures)
             platform.registerKernelFactory(name, factory);
     } catch (const std::exception&) {
         // no HIP platform in this OpenMM: nothing to attach to (the reference swallows the same case, :52-54)
@@ -40,5 +41,6 @@ KernelImpl* HipVVKernelFactory::createKernelImpl(std::string name, const Platfor
     if (name == ModifyImageChargeKernel::Name()) return new HipModifyImageChargeKernel(name, platform, cu);
     if (name == ModifyElectricFieldKernel::Name()) return new HipModifyElectricFieldKernel(name, platform, cu);
     if (name == ModifyCosineAccelerateKernel::Name()) return new HipModifyCosineAccelerateKernel(name, platform, cu);
+    if (name == CalcDrudeTemperaturesKernel::Name()) return new HipCalcDrudeTemperaturesKernel(name, platform, cu);
     throw OpenMMException((std::string("Tried to create kernel with illegal kernel name '") + name + "'").c_str());
 }

@@ -448,3 +448,10 @@ void HipModifyCosineAccelerateKernel::calcViscosity(ContextImpl&, const VVIntegr
     plan->syncParameters(it);
     plan->check(vvhip_calc_viscosity(plan->get(), &vMax, &invVis));
 }
+
+void HipCalcDrudeTemperaturesKernel::initialize(const System&, const VVIntegrator&) { ContextSelector selector(cu); plan = HipVVPlan::find(cu); }
+void HipCalcDrudeTemperaturesKernel::calcDrudeTemperatures(ContextImpl&, const VVIntegrator&, double ke[3], double t[3]) {
+    plan->flush();                             // stages recorded for a fused step run first: the report sees the velocities the host sees
+    cu.setAsCurrent();
+    plan->check(vvhip_drude_temperatures(plan->get(), ke, t));
+}

@@ -48,6 +48,10 @@ VV_UNIT(getCosAcceleration,  _u.nanometer / _u.picosecond ** 2)
            _u.Quantity(val[1], _u.picosecond / (_u.dalton * _u.item) * _u.nanometer).in_units_of((_u.pascal * _u.second) ** -1))
 %}
 
+%pythonappend OpenMM::VVIntegrator::getDrudeTemperatures() %{
+    val = tuple(_u.Quantity(x, _u.kilojoule_per_mole) for x in val[:3]) + tuple(_u.Quantity(x, _u.kelvin) for x in val[3:])
+%}
+
 /* protected Integrator plumbing stays out of Python */
 %ignore OpenMM::VVIntegrator::propagateNHChain;
 %include "openmm/VVIntegrator.h"
