@@ -314,6 +314,51 @@ int vvhip_drude_report_dof(const vvhip_plan* plan, double dof[3]);
 int vvhip_drude_report_raw(vvhip_plan* plan, int64_t raw[6]);
 /* ke / t from raw sums (one shard's, or the element-wise sum over all shards); host only. */
 int vvhip_drude_report_combine(const vvhip_plan* plan, const int64_t raw[6], double ke[3], double t[3]);
+
+/* ---------------------------------------------------------------- series: samples recorded on the device
+ * A device buffer of rows, configured once per plan.  The plan counts full steps (host side): vvhip_step_middle, vvhip_step_vv_second,
+ * the last phase of vvhip_step_middle_phase and the steps of vvhip_run_graph / vvhip_run_eager each advance the count by one; the split
+ * per-KernelImpl entry points (vvhip_middle_kick ... vvhip_middle_finish, vvhip_run_eager_unfused) do not, and take no rows.  After every
+ * step whose count is a multiple of `interval`, the step entry point itself enqueues one row in the plan's stream: the Drude report's two
+ * passes (vvhip_drude_report_raw's kernels, on scratch of the series' own) and one append kernel.  Inside a captured graph the row launches
+ * are part of the graph: replays record rows without any host synchronisation.  The row index comes from a device-side cursor; a row past
+ * `capacity` is not written but counted as dropped, and the cursor advances either way.  Nothing else of the step changes: a plan without
+ * a series launches what it launched before, and a series leaves positions, velocities and thermostat state bit for bit as they were.
+ * Row j (0-based, since the start or the last reset) holds the state after step interval * (k0 + j); vvhip_series_read returns that step
+ * of row 0.  The graph cache keys on the steps of the graph that take rows: when `interval` divides the graph's length or the length
+ * divides `interval`, each parity needs at most two executables and steady-state replays re-capture nothing.  Start, stop and a
+ * change of box or parameters drop the captured graphs (the box and cos acceleration of a row are baked into its kernel arguments). */
+#define VVHIP_SERIES_DRUDE 1        /* the Drude report's raw words (drude_raw, drude_overflow) */
+#define VVHIP_SERIES_THERMOSTAT 2   /* the thermostat state as vvhip_get_nh_state would return it after the step, plus box and cos acceleration */
+typedef struct {
+    int64_t drude_raw[6];           /* vvhip_drude_report_raw's six words of this shard's particles (0 without VVHIP_SERIES_DRUDE) */
+    int64_t drude_overflow;         /* != 0: a term left the fixed-point range (vvhip_drude_report_raw would fail); the row's words are void */
+    int64_t reserved;               /* 0 */
+    vvhip_nh_state nh;              /* d_nh of the parity current after the step (0 without VVHIP_SERIES_THERMOSTAT) */
+    double box[3];                  /* periodic box and cos acceleration the step ran with: with nh.v_bias the inputs of vvhip_calc_viscosity */
+    double cos_acceleration;
+} vvhip_series_row;
+typedef struct {
+    int32_t row_bytes;              /* sizeof(vvhip_series_row) */
+    int32_t off_drude_raw, off_nh, off_box;     /* byte offsets of the parts inside a row */
+    int32_t active, interval, capacity, mask;   /* the series as configured (active = 0: none) */
+    int64_t steps;                  /* full steps the plan has counted since vvhip_bind */
+    int64_t graph_captures;         /* graph executables captured since vvhip_bind (the cache's misses) */
+} vvhip_series_layout;
+/* Starts (or restarts, dropping what was recorded) a series on a bound plan: interval >= 1 steps, capacity >= 1 rows, mask of
+ * VVHIP_SERIES_*.  VVHIP_SERIES_DRUDE on a plan that cannot report gives VVHIP_ERR_UNSUPPORTED (as vvhip_drude_report_raw).  Synchronises. */
+int vvhip_series_start(vvhip_plan* plan, int32_t interval, int32_t capacity, int32_t mask);
+/* Synchronises, copies min(rows recorded, capacity, max_rows) rows to rows_out (may be null with max_rows = 0), and returns the rows
+ * recorded (n_rows: at most capacity), the step of row 0 and the rows dropped for want of capacity.  reset != 0 empties the buffer: the
+ * next row then becomes row 0 and continues the schedule without gap or repeat. */
+int vvhip_series_read(vvhip_plan* plan, vvhip_series_row* rows_out, int32_t max_rows, int32_t* n_rows, int64_t* first_step,
+                      int64_t* dropped, int32_t reset);
+/* Stops the series: no more rows are enqueued; the buffer is released. */
+int vvhip_series_stop(vvhip_plan* plan);
+/* The row layout, the series' configuration and the step / capture counters; host only, works on an unbound plan. */
+int vvhip_series_info(const vvhip_plan* plan, vvhip_series_layout* out);
+/* Test hook: 1 if the guard row behind the buffer's last row still holds its fill pattern (nothing was written past capacity). */
+int vvhip_debug_series_guard(vvhip_plan* plan, int32_t* intact);
 /* Device pointer of the plan-owned forceExtra array (real3[n]); getForceExtra() of the reference
  * (CudaVVKernels.h:86-88). */
 int vvhip_force_extra(vvhip_plan* plan, void** device_ptr);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -153,6 +154,9 @@ struct vvhip_plan {
         struct Run { int kind, nsteps, spg; const void* site; double kt, kd; };
         std::vector<Run> runs;
         long long recoveries = 0;
+        long long step_count = 0;                 // the series' schedule: the step counter and the device-side row cursor
+        unsigned long long* series_cursor = nullptr;
+        bool series_saved = false;
     } rec;
     // plan-owned device state
     int2* d_slots = nullptr;
@@ -200,6 +204,7 @@ struct vvhip_plan {
         const void* site = nullptr;
         double kt = 0, kd = 0;
         uint32_t random_end = 0;               // prepareRandomNumbers cursor after the graph's last step
+        std::vector<int> rows;                 // steps of the graph (1 .. steps) that append a series row: part of the key
     };
     // (round 6: up to four graph lengths per parity -- a host that replays a short graph in front of a long one keeps both)
     static constexpr int kGraphWays = 4;
@@ -246,6 +251,18 @@ struct vvhip_plan {
     double* d_rep_cross_mu = nullptr;
     long long* d_rep = nullptr;                   // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
     long long* h_rep = nullptr;                   // pinned: the result words as copied back
+    // Series (vvhip_series_*): full steps counted since vvhip_bind (the step entry points advance it, a capture walks it through the
+    // graph's steps and puts it back, a replay advances it by the graph's length), and the rows the steps append on the device
+    long long step_count = 0;
+    long long graph_captures = 0;
+    struct Series {
+        bool on = false;
+        int interval = 0, capacity = 0, mask = 0;
+        long long k0 = 0;                         // row 0 is step interval * k0
+        vvhip_series_row* d_rows = nullptr;       // [capacity + 1]: behind the last row a guard row (vvhip_debug_series_guard)
+        unsigned long long* d_cursor = nullptr;   // [2] rows appended (past capacity too), rows dropped
+        long long* d_scratch = nullptr;           // the report's scratch for the rows (as d_rep), zero between rows
+    } series;
 };
 
 static void drop_graphs(vvhip_plan* p) {
@@ -253,11 +270,20 @@ static void drop_graphs(vvhip_plan* p) {
         for (auto& g : row)
             if (g.exec) { (void) hipGraphExecDestroy(g.exec); g.exec = nullptr; }
 }
+static int step_done(vvhip_plan* p);
+// The steps i = 1 .. steps after step counter c0 that append a series row (empty without a series)
+static std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps) {
+    std::vector<int> r;
+    if (!p->series.on) return r;
+    const long long k = p->series.interval;
+    for (long long i = k - c0 % k; i <= steps; i += k) r.push_back((int) i);
+    return r;
+}
 // the slot of parity q that holds (or will hold) the graph with this key
-static vvhip_plan::GraphSlot& graph_slot(vvhip_plan* p, int q, int steps, const void* site, double kt, double kd) {
+static vvhip_plan::GraphSlot& graph_slot(vvhip_plan* p, int q, int steps, const void* site, double kt, double kd, const std::vector<int>& rows) {
     auto& row = p->graph[q & 1];
     for (auto& g : row)
-        if (g.exec && g.steps == steps && g.site == site && g.kt == kt && g.kd == kd) return g;
+        if (g.exec && g.steps == steps && g.site == site && g.kt == kt && g.kd == kd && g.rows == rows) return g;
     for (auto& g : row)
         if (!g.exec) return g;
     return row[p->graph_next[q & 1]++ % vvhip_plan::kGraphWays];
@@ -865,7 +891,8 @@ void vvhip_plan_destroy(vvhip_plan* p) {
                           p->d_fextra, p->d_old_delta, p->d_pos_delta, p->d_comv, (void*) p->d_comw, (void*) p->d_seg_mass, (void*) p->d_seg_base, (void*) p->d_slot_m, (void*) p->d_slot_f, (void*) p->d_cosz, (void*) p->d_epoch, (void*) p->d_acc, (void*) p->d_rv, (void*) p->d_nh, (void*) p->d_lane_const, (void*) p->d_dbg, (void*) p->d_dbg_span,
                           p->rec.posq, p->rec.corr, p->rec.velm, p->rec.force, p->rec.fextra, p->rec.random, (void*) p->rec.nh, (void*) p->rec.epoch,
                           (void*) p->d_rep_lane_mol, (void*) p->d_rep_lane_mass, (void*) p->d_rep_lane_mu, (void*) p->d_rep_mol_mass, (void*) p->d_rep_cross,
-                          (void*) p->d_rep_cross_mu, (void*) p->d_rep})
+                          (void*) p->d_rep_cross_mu, (void*) p->d_rep, (void*) p->series.d_rows, (void*) p->series.d_cursor, (void*) p->series.d_scratch,
+                          (void*) p->rec.series_cursor})
             if (ptr) (void) hipFree(ptr);
         if (p->h_rep) (void) hipHostFree(p->h_rep);
         drop_graphs(p);
@@ -919,7 +946,7 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
         const bool same = b->velm == o.velm && b->posq == o.posq && b->posq_correction == o.posq_correction && b->force == o.force &&
                           b->pos_delta == o.pos_delta && b->random == o.random && b->random_size == o.random_size;
         if (b->velm != o.velm) p->mass_tab_valid = false;
-        if (!same) drop_graphs(p);
+        if (!same || p->series.on) drop_graphs(p);      // (a series row reads velm through its captured arguments too)
     }
     // a re-bind that moves the plan to another stream: whatever the plan still has in flight on the old one (fills, steps) must be
     // complete before work enqueued on the new one can touch the same buffers
@@ -1186,7 +1213,7 @@ static int step_middle_fused(vvhip_plan* p, uint32_t random_index, bool* taken) 
     return VVHIP_OK;
 }
 
-int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
+static int middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
     NEED_BOUND(p);
     NEED_FUSABLE(p);
     const bool rk = use_rekick(p);
@@ -1217,6 +1244,11 @@ int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
     }
     return fail(p, VVHIP_ERR_INVALID, "phase out of range");
 }
+// (the last phase completes the step: it is counted, and takes its series row)
+int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
+    TRY(middle_phase(p, phase, random_index));
+    return phase == vvhip_step_middle_phases(p) - 1 ? step_done(p) : VVHIP_OK;
+}
 
 int vvhip_accumulators(vvhip_plan* p, int phase, void** device_ptr, int32_t* count) {
     NEED_BOUND(p);
@@ -1243,8 +1275,7 @@ static int exchange_accumulators(vvhip_plan* p, int phase) {
     return VVHIP_OK;
 }
 
-int vvhip_step_middle(vvhip_plan* p, uint32_t random_index) {
-    NEED_BOUND(p);
+static int step_middle(vvhip_plan* p, uint32_t random_index) {
     if (!p->hp.params.use_middle_scheme) return fail(p, VVHIP_ERR_INVALID, "plan was created for the classic scheme");
     {   // one launch where the plan allows it (bit for bit the two launches below)
         bool taken = false;
@@ -1253,10 +1284,15 @@ int vvhip_step_middle(vvhip_plan* p, uint32_t random_index) {
     }
     const int n = vvhip_step_middle_phases(p);
     for (int ph = 0; ph < n; ph++) {
-        TRY(vvhip_step_middle_phase(p, ph, random_index));
+        TRY(middle_phase(p, ph, random_index));
         if (ph < n - 1) TRY(exchange_accumulators(p, ph));
     }
     return VVHIP_OK;
+}
+int vvhip_step_middle(vvhip_plan* p, uint32_t random_index) {
+    NEED_BOUND(p);
+    TRY(step_middle(p, random_index));
+    return step_done(p);
 }
 
 // NH half-step used by the classic scheme (API:295-304, 327-336); `b_extra` is fused into the scaling kernel.
@@ -1302,7 +1338,8 @@ int vvhip_step_vv_second(vvhip_plan* p, uint32_t random_index) {   // API:316-33
     if (ex) { ex |= vv::A_FE_STORE; p->fextra_dirty = true; }   // the first half of the NEXT step kicks with these (API:316-323)
     else if (p->fextra_dirty || p->fextra_external) ex = vv::A_FE_LOAD;      // no source: the kick adds what the array still holds (see fextra_virtual)
     NEED_FUSABLE(p);
-    return nh_half(p, vv::A_KICK_HALF | ex | cons_a(p), random_index, 0);
+    TRY(nh_half(p, vv::A_KICK_HALF | ex | cons_a(p), random_index, 0));
+    return step_done(p);
 }
 
 // ------------------------------------------------------------------------------------------ kernel-interface level
@@ -1396,6 +1433,21 @@ int vvhip_compute_kinetic_energy(vvhip_plan* p, double* kinetic_energy) {   // H
     return VVHIP_OK;
 }
 // ------------------------------------------------------------------------------------------ Drude temperature report
+// The two passes' arguments on `scratch` ([8] result words, then [6 per molecule] momentum words; zero on entry)
+static vv::ReportArgs report_args(const vvhip_plan* p, long long* scratch) {
+    const vv::HostPlan& hp = p->hp;
+    vv::ReportArgs a{};
+    a.velm = p->buf.velm; a.slots = p->d_slots;
+    a.lane_mol = p->d_rep_lane_mol; a.lane_mass = p->d_rep_lane_mass; a.lane_mu = p->d_rep_lane_mu;
+    a.mol_mass = p->d_rep_mol_mass; a.cross = p->d_rep_cross; a.cross_mu = p->d_rep_cross_mu;
+    a.out = scratch; a.mol_p = scratch + 8;
+    a.nwaves = hp.info.num_waves; a.nmol = (int) hp.report_mol_mass.size(); a.ncross = (int) hp.report_cross_mu.size();
+    a.frac_bits = hp.report_frac_bits;
+    a.unit = std::ldexp(1.0, hp.report_unit_bits); a.frac_scale = std::ldexp(1.0, hp.report_frac_bits);
+    a.inv_unit = std::ldexp(1.0, -hp.report_unit_bits); a.inv_full = std::ldexp(1.0, -hp.report_unit_bits - hp.report_frac_bits);
+    a.limit = hp.report_limit;
+    return a;
+}
 int vvhip_drude_report_dof(const vvhip_plan* p, double dof[3]) {
     if (!p || !dof) return VVHIP_ERR_INVALID;
     for (int g = 0; g < 3; g++) dof[g] = p->hp.report_dof[g];
@@ -1410,17 +1462,7 @@ int vvhip_drude_report_raw(vvhip_plan* p, int64_t raw[6]) {
     TRY(settle_recovery(p));
     const int nmol = (int) hp.report_mol_mass.size();
     HIP_TRY(p, hipMemsetAsync(p->d_rep, 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
-    vv::ReportArgs a{};
-    a.velm = p->buf.velm; a.slots = p->d_slots;
-    a.lane_mol = p->d_rep_lane_mol; a.lane_mass = p->d_rep_lane_mass; a.lane_mu = p->d_rep_lane_mu;
-    a.mol_mass = p->d_rep_mol_mass; a.cross = p->d_rep_cross; a.cross_mu = p->d_rep_cross_mu;
-    a.out = p->d_rep; a.mol_p = p->d_rep + 8;
-    a.nwaves = hp.info.num_waves; a.nmol = nmol; a.ncross = (int) hp.report_cross_mu.size();
-    a.frac_bits = hp.report_frac_bits;
-    a.unit = std::ldexp(1.0, hp.report_unit_bits); a.frac_scale = std::ldexp(1.0, hp.report_frac_bits);
-    a.inv_unit = std::ldexp(1.0, -hp.report_unit_bits); a.inv_full = std::ldexp(1.0, -hp.report_unit_bits - hp.report_frac_bits);
-    a.limit = hp.report_limit;
-    HIP_TRY(p, vv::launch_report(hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
+    HIP_TRY(p, vv::launch_report(hp.precision, report_args(p, p->d_rep), p->block_threads, p->grid_cap_a, p->stream));
     HIP_TRY(p, hipMemcpyAsync(p->h_rep, p->d_rep, vv::REP_WORDS * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     if (p->h_rep[vv::REP_FLAG])
@@ -1451,6 +1493,124 @@ int vvhip_drude_temperatures(vvhip_plan* p, double ke[3], double t[3]) {
     int64_t raw[6];
     TRY(vvhip_drude_report_raw(p, raw));
     return vvhip_drude_report_combine(p, raw, ke, t);
+}
+
+// ------------------------------------------------------------------------------------------ series (vvhip_series_*)
+// One row behind the step just enqueued (or captured): the report's passes on the series' scratch, then the append kernel, which also
+// zeroes that scratch again.  Three kernel launches, no memset and no host synchronisation.
+static int series_row(vvhip_plan* p) {
+    vvhip_plan::Series& S = p->series;
+    vv::SeriesArgs a{};
+    if (S.mask & VVHIP_SERIES_DRUDE) {
+        HIP_TRY(p, vv::launch_report(p->hp.precision, report_args(p, S.d_scratch), p->block_threads, p->grid_cap_a, p->stream));
+        a.rep_out = S.d_scratch; a.rep_mol_p = S.d_scratch + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
+    }
+    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh[p->parity].s;
+    a.rows = S.d_rows; a.cursor = S.d_cursor; a.capacity = S.capacity;
+    for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
+    a.cos_acceleration = p->hp.params.cos_acceleration;
+    HIP_TRY(p, vv::launch_series_append(a, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// A full step has been enqueued (or captured): count it, and append a row when it is due.
+static int step_done(vvhip_plan* p) {
+    p->step_count++;
+    if (p->series.on && p->step_count % p->series.interval == 0) return series_row(p);
+    return VVHIP_OK;
+}
+static void series_release(vvhip_plan* p) {
+    vvhip_plan::Series& S = p->series;
+    for (void* ptr : {(void*) S.d_rows, (void*) S.d_cursor, (void*) S.d_scratch})
+        if (ptr) (void) hipFree(ptr);
+    S.d_rows = nullptr; S.d_cursor = nullptr; S.d_scratch = nullptr;
+    S.on = false; S.interval = S.capacity = S.mask = 0; S.k0 = 0;
+}
+static constexpr int kGuardByte = 0xA5;
+int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_t mask) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (interval < 1) return fail(p, VVHIP_ERR_INVALID, "series: interval must be >= 1 step");
+    if (capacity < 1) return fail(p, VVHIP_ERR_INVALID, "series: capacity must be >= 1 row");
+    if (mask == 0 || (mask & ~(VVHIP_SERIES_DRUDE | VVHIP_SERIES_THERMOSTAT)))
+        return fail(p, VVHIP_ERR_INVALID, "series: mask must be a non-empty set of VVHIP_SERIES_DRUDE / VVHIP_SERIES_THERMOSTAT");
+    if ((mask & VVHIP_SERIES_DRUDE) && !p->hp.report_unsupported.empty())
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + p->hp.report_unsupported);
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    TRY(settle_recovery(p));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (rows of a series before may still be in flight)
+    series_release(p);
+    drop_graphs(p);
+    vvhip_plan::Series& S = p->series;
+    const size_t row_bytes = sizeof(vvhip_series_row), scratch = (8 + 6 * p->hp.report_mol_mass.size()) * sizeof(long long);
+    HIP_TRY(p, hipMalloc((void**) &S.d_rows, ((size_t) capacity + 1) * row_bytes));
+    HIP_TRY(p, hipMalloc((void**) &S.d_cursor, 2 * sizeof(unsigned long long)));
+    HIP_TRY(p, hipMalloc((void**) &S.d_scratch, scratch));
+    HIP_TRY(p, hipMemsetAsync(S.d_rows, 0, (size_t) capacity * row_bytes, p->stream));
+    HIP_TRY(p, hipMemsetAsync((char*) S.d_rows + (size_t) capacity * row_bytes, kGuardByte, row_bytes, p->stream));
+    HIP_TRY(p, hipMemsetAsync(S.d_cursor, 0, 2 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(S.d_scratch, 0, scratch, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    S.on = true; S.interval = interval; S.capacity = capacity; S.mask = mask;
+    S.k0 = p->step_count / interval + 1;               // the first multiple of interval after the current step
+    return VVHIP_OK;
+}
+int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_rows, int32_t* n_rows, int64_t* first_step, int64_t* dropped,
+                      int32_t reset) {
+    NEED_BOUND(p);
+    if (max_rows < 0 || (max_rows > 0 && !rows_out)) return VVHIP_ERR_INVALID;
+    vvhip_plan::Series& S = p->series;
+    if (!S.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    TRY(settle_recovery(p));                            // (a repaired run rewrites its rows first)
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    unsigned long long cur[2];
+    HIP_TRY(p, hipMemcpy(cur, S.d_cursor, sizeof(cur), hipMemcpyDeviceToHost));
+    const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) S.capacity);
+    const long long copy = std::min<long long>(n, max_rows);
+    if (copy > 0) HIP_TRY(p, hipMemcpy(rows_out, S.d_rows, (size_t) copy * sizeof(vvhip_series_row), hipMemcpyDeviceToHost));
+    if (n_rows) *n_rows = (int32_t) n;
+    if (first_step) *first_step = (int64_t) S.interval * S.k0;
+    if (dropped) *dropped = (int64_t) cur[1];
+    if (reset) {
+        HIP_TRY(p, hipMemsetAsync(S.d_cursor, 0, 2 * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        S.k0 += (long long) cur[0];                     // (dropped rows included: their steps are gone)
+    }
+    return VVHIP_OK;
+}
+int vvhip_series_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    if (!p->series.on) return VVHIP_OK;
+    TRY(settle_recovery(p));
+    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    series_release(p);
+    drop_graphs(p);
+    return VVHIP_OK;
+}
+int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_series_layout r{};
+    r.row_bytes = (int32_t) sizeof(vvhip_series_row);
+    r.off_drude_raw = (int32_t) offsetof(vvhip_series_row, drude_raw);
+    r.off_nh = (int32_t) offsetof(vvhip_series_row, nh);
+    r.off_box = (int32_t) offsetof(vvhip_series_row, box);
+    r.active = p->series.on; r.interval = p->series.interval; r.capacity = p->series.capacity; r.mask = p->series.mask;
+    r.steps = p->step_count;
+    r.graph_captures = p->graph_captures;
+    *out = r;
+    return VVHIP_OK;
+}
+int vvhip_debug_series_guard(vvhip_plan* p, int32_t* intact) {
+    NEED_BOUND(p);
+    if (!intact) return VVHIP_ERR_INVALID;
+    if (!p->series.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    unsigned char g[sizeof(vvhip_series_row)];
+    HIP_TRY(p, hipMemcpy(g, p->series.d_rows + p->series.capacity, sizeof(g), hipMemcpyDeviceToHost));
+    *intact = 1;
+    for (unsigned char c : g) if (c != kGuardByte) *intact = 0;
+    return VVHIP_OK;
 }
 
 int vvhip_update_image_positions(vvhip_plan* p) {          // HOST:904-934
@@ -1625,6 +1785,12 @@ static int recovery_snapshot(vvhip_plan* p) {
     HIP_TRY(p, hipMemcpyAsync(r.nh, p->d_nh, 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(p, hipMemcpyAsync(r.epoch, p->d_epoch, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     r.parity = p->parity; r.random_pos = p->random_pos; r.fextra_dirty = p->fextra_dirty; r.fextra_virtual = p->fextra_virtual;
+    r.step_count = p->step_count;
+    r.series_saved = p->series.on;                  // (a series cannot start or stop while the snapshot is unverified: both settle it first)
+    if (r.series_saved) {
+        if (!r.series_cursor) HIP_TRY(p, hipMalloc((void**) &r.series_cursor, 2 * sizeof(unsigned long long)));
+        HIP_TRY(p, hipMemcpyAsync(r.series_cursor, p->series.d_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+    }
     r.runs.clear();
     r.valid = true;
     return VVHIP_OK;
@@ -1660,6 +1826,10 @@ int recover_rendezvous(vvhip_plan* p) {
     if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
     HIP_TRY(p, hipMemsetAsync(p->d_rv + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
     p->parity = r.parity; p->random_pos = r.random_pos; p->fextra_dirty = r.fextra_dirty; p->fextra_virtual = r.fextra_virtual;
+    // the series' rows of the failed steps are written again, at the same places, by the repeat
+    p->step_count = r.step_count;
+    if (r.series_saved && p->series.on)
+        HIP_TRY(p, hipMemcpyAsync(p->series.d_cursor, r.series_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     for (int w = 1; w < 4; w++) __atomic_store_n(&p->h_status[w], 0u, __ATOMIC_RELAXED);
     p->fused = false;
     p->fused_checked_b = 0;
@@ -1697,21 +1867,27 @@ static int plan_step(vvhip_plan* p, const void* site, double k_tether, double k_
 
 // Capture + instantiate + upload the graph of `steps_per_graph` steps for thermostat parity `q`, unless that slot already holds it.
 // Nothing is launched: the physical state is untouched.
-static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* site, double k_tether, double k_drude) {
+// The graph is captured at step counter c0 (where its replays start): its series rows sit at the steps series_rows_in(c0) names.
+static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* site, double k_tether, double k_drude, long long c0,
+                        vvhip_plan::GraphSlot** out = nullptr) {
     hipStream_t s = p->stream;
     TRY(ensure_mass_table(p));                       // a one-off fill must not be recorded into the replayed graph
-    vvhip_plan::GraphSlot& g = graph_slot(p, q, steps_per_graph, site, k_tether, k_drude);
-    if (g.exec && g.steps == steps_per_graph && g.site == site && g.kt == k_tether && g.kd == k_drude) return VVHIP_OK;
+    const std::vector<int> rows = series_rows_in(p, c0, steps_per_graph);
+    vvhip_plan::GraphSlot& g = graph_slot(p, q, steps_per_graph, site, k_tether, k_drude, rows);
+    if (out) *out = &g;
+    if (g.exec && g.steps == steps_per_graph && g.site == site && g.kt == k_tether && g.kd == k_drude && g.rows == rows) return VVHIP_OK;
     if (g.exec) { (void) hipStreamSynchronize(s); (void) hipGraphExecDestroy(g.exec); g.exec = nullptr; }      // (a replay of the one that goes may still be in flight)
     // The capture walks the host-side cursors (parity, Langevin random slice) through the graph's steps; they are put back
     // afterwards, because nothing has run yet.  A replay moves them to the graph's end (vvhip_run_graph).
     const int parity0 = p->parity;
     const uint32_t random0 = p->random_pos;
     const bool fextra_dirty0 = p->fextra_dirty, fextra_virtual0 = p->fextra_virtual;
+    const long long step0 = p->step_count;
     p->parity = q & 1;
+    p->step_count = c0;
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) { p->parity = parity0; return hip_fail(p, e, "hipStreamBeginCapture"); }
+    if (e != hipSuccess) { p->parity = parity0; p->step_count = step0; return hip_fail(p, e, "hipStreamBeginCapture"); }
     p->capturing = true;
     int rc = VVHIP_OK;
     // Langevin: a captured graph begins with a refill of the random buffer (the device generator's epoch advances per refill), so every replay draws new numbers
@@ -1720,13 +1896,15 @@ static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* s
     e = hipStreamEndCapture(s, &graph);
     g.random_end = p->random_pos;
     p->parity = parity0; p->random_pos = random0; p->fextra_dirty = fextra_dirty0; p->fextra_virtual = fextra_virtual0;
+    p->step_count = step0;
     if (rc != VVHIP_OK) { if (graph) (void) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return hip_fail(p, e, "hipStreamEndCapture");
     e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
     (void) hipGraphDestroy(graph);
     if (e != hipSuccess) { g.exec = nullptr; return hip_fail(p, e, "hipGraphInstantiate"); }
     (void) hipGraphUpload(g.exec, s);                // pay the first launch's set-up here, not in the caller's timed region
-    g.steps = steps_per_graph; g.site = site; g.kt = k_tether; g.kd = k_drude;
+    g.steps = steps_per_graph; g.site = site; g.kt = k_tether; g.kd = k_drude; g.rows = rows;
+    p->graph_captures++;
     return VVHIP_OK;
 }
 
@@ -1737,8 +1915,8 @@ int vvhip_graph_prepare(vvhip_plan* p, int steps_per_graph, const void* site, do
     if (steps_per_graph < 1) return VVHIP_ERR_INVALID;
     if (steps_per_graph % 2) steps_per_graph += 1;   // the thermostat double-buffers by step parity: a graph must hold an even number of steps
     if (!p->stream) return fail(p, VVHIP_ERR_INVALID, "graph capture needs a non-null stream in vvhip_buffers.stream");
-    TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude));
-    return prepare_slot(p, p->parity ^ 1, steps_per_graph, site, k_tether, k_drude);
+    TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count));
+    return prepare_slot(p, p->parity ^ 1, steps_per_graph, site, k_tether, k_drude, p->step_count);
 }
 
 int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* site, double k_tether, double k_drude) {
@@ -1756,10 +1934,17 @@ int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* 
     if (!middle && site && nsteps > 0) TRY(vvhip_synth_tether_force(p, site, k_tether, k_drude));
     int done = 0;
     if (nsteps >= steps_per_graph) {
-        TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude));     // no-op when the slot of this parity is ready
-        const vvhip_plan::GraphSlot& g = graph_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude);
-        for (; done + steps_per_graph <= nsteps; done += steps_per_graph) HIP_TRY(p, hipGraphLaunch(g.exec, s));
-        p->random_pos = g.random_end;                // an even number of steps: the parity is where it was
+        vvhip_plan::GraphSlot* g = nullptr;
+        TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count, &g));     // no-op when the slot of this parity is ready
+        for (; done + steps_per_graph <= nsteps; done += steps_per_graph) {
+            // with a series the replays' rows fall on other steps of the graph as the counter moves on: the graph whose rows fit
+            // (at most two when the interval and the graph's length divide one another; otherwise the cache may capture again)
+            if (p->series.on && done > 0 && series_rows_in(p, p->step_count, steps_per_graph) != g->rows)
+                TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count, &g));
+            HIP_TRY(p, hipGraphLaunch(g->exec, s));
+            p->step_count += steps_per_graph;
+        }
+        p->random_pos = g->random_end;               // an even number of steps: the parity is where it was
         if (!middle && extra_flags(p)) p->fextra_dirty = true;
         if (middle && cos_on(p) && !p->hp.has_ld && !p->hp.has_ef) p->fextra_virtual = true;    // what the replayed steps' phase 0 would have set
     }

@@ -253,4 +253,17 @@ struct ReportArgs {
     double limit;                   // largest |term| taken (beyond it, or NaN: the flag)
 };
 
+// Series row (vv_dev_report.inc: vv_kernel_series_append, include/vvhip.h: vvhip_series_row).  The row index is read from the device-side
+// cursor, so a replayed graph (same arguments every time) appends where the last row ended.
+struct SeriesArgs {
+    long long* rep_out;             // [REP_WORDS] the report's result words, zeroed after they are copied; null: no Drude part
+    long long* rep_mol_p;           // [rep_mol_words] the report's momentum words, zeroed for the next row
+    const vvhip_nh_state* nh;       // the thermostat copy current after the step; null: no thermostat part
+    vvhip_series_row* rows;         // [capacity]
+    unsigned long long* cursor;     // [0] rows appended since the start / last reset (past capacity too), [1] rows dropped
+    int64_t rep_mol_words;
+    int32_t capacity, pad_;
+    double box[3], cos_acceleration;
+};
+
 }  // namespace vv

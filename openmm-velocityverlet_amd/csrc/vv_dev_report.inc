@@ -112,3 +112,33 @@ __global__ void __launch_bounds__(512) vv_kernel_report_molecules(const ReportAr
     if (bad) atomicOr((unsigned long long*) &a.out[REP_FLAG], 1ull);
     rep_block_add(s, a.out, REP_COM, REP_DRUDE);
 }
+
+// Series row (vvhip_series_*): block 0 appends one row at the device-side cursor -- the report's result words (then zeroes them), the
+// thermostat copy current after the step, the box and the cos acceleration -- or counts it as dropped past capacity; every block zeroes
+// its share of the report's momentum words, so the next row's passes start from clean scratch without a memset in the stream.
+// (Pass 2 cannot zero the momentum words itself: a pair across two molecules reads another molecule's words in the same pass.)
+#ifndef VV_DEVICE_NO_PLAIN_KERNELS
+__global__ void __launch_bounds__(256) vv_kernel_series_append(const SeriesArgs a) {
+    constexpr int W = (int) (sizeof(vvhip_series_row) / 8), NHW = (int) (sizeof(vvhip_nh_state) / 8);
+    constexpr int OFF_NH = (int) (__builtin_offsetof(vvhip_series_row, nh) / 8), OFF_BOX = (int) (__builtin_offsetof(vvhip_series_row, box) / 8);
+    static_assert(__builtin_offsetof(vvhip_series_row, drude_raw) == 0 && __builtin_offsetof(vvhip_series_row, drude_overflow) == 8 * REP_FLAG, "row layout");
+    static_assert(OFF_BOX == OFF_NH + NHW && W == OFF_BOX + 4, "row layout");
+    const int t = threadIdx.x;
+    if (blockIdx.x == 0) {
+        const unsigned long long c = a.cursor[0];
+        long long w = 0;
+        if (t < REP_WORDS) { if (a.rep_out) w = a.rep_out[t]; }
+        else if (t >= OFF_NH && t < OFF_BOX) { if (a.nh) w = ((const long long*) a.nh)[t - OFF_NH]; }
+        else if (t >= OFF_BOX && t < W) w = __double_as_longlong(t - OFF_BOX < 3 ? a.box[t - OFF_BOX] : a.cos_acceleration);
+        if (c < (unsigned long long) a.capacity && t < W) ((long long*) (a.rows + c))[t] = w;
+        if (a.rep_out && t < REP_WORDS) a.rep_out[t] = 0;
+        __syncthreads();                                        // (every thread has read the cursor)
+        if (t == 0) {
+            a.cursor[0] = c + 1;
+            if (c >= (unsigned long long) a.capacity) a.cursor[1] = a.cursor[1] + 1;
+        }
+    }
+    if (a.rep_out)
+        for (long long i = (long long) blockIdx.x * blockDim.x + t; i < a.rep_mol_words; i += (long long) gridDim.x * blockDim.x) a.rep_mol_p[i] = 0;
+}
+#endif

@@ -487,6 +487,11 @@ hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, 
     VV_DISPATCH(vv_kernel_report_molecules, dim3((unsigned) g2), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s) {
+    const long long g = a.rep_out ? std::min<long long>((a.rep_mol_words + 255) / 256, grid_cap) : 1;
+    hipLaunchKernelGGL(vv_kernel_series_append, dim3((unsigned) std::max<long long>(1, g)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

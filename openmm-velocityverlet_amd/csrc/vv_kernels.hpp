@@ -50,5 +50,7 @@ hipError_t launch_image_pairs(int precision, void* posq, void* corr, const int2*
 // The Drude temperature report's two passes (vv_dev_report.inc) over a.nwaves waves and a.nmol + a.ncross items: blocks of block_threads,
 // at most grid_cap of them per pass (the kernels stride beyond).  a.mol_p and a.out must be zero on entry.
 hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// One series row (vv_dev_report.inc: vv_kernel_series_append) behind the report's passes (or alone: a.rep_out null).
+hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s);
 
 }  // namespace vv

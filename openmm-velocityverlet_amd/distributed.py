@@ -156,3 +156,24 @@ def drude_temperatures(ctx, group=None):
         else:
             dist.all_reduce(raw, op=dist.ReduceOp.SUM, group=group)
     return ctx.drude_report_combine(raw.numpy())
+
+
+def drude_temperature_series(ctx, group=None, reset=False):
+    """A sharded run's series (Context.series_read): every rank's raw rows -- six fixed-point sums and the overflow flag per row, of its
+    own particles -- summed over the process group in one all-reduce, then turned into KE / T with the whole system's DOFs.  Every rank
+    gets the single-process series bit for bit; the thermostat part is the same on every rank already (it comes from exchanged sums).
+    Collective: every rank of the group calls it, with the same series configuration and the same steps behind it."""
+    import torch
+    import torch.distributed as dist
+
+    def combine(words):
+        t = torch.from_numpy(np.ascontiguousarray(words, dtype=np.int64))
+        if dist.is_initialized() and dist.get_world_size(group) > 1:
+            if dist.get_backend(group) == "nccl":
+                dev = t.to("cuda")
+                dist.all_reduce(dev, op=dist.ReduceOp.SUM, group=group)
+                t = dev.cpu()
+            else:
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        return t.numpy()
+    return ctx.series_read(reset=reset, combine=combine)

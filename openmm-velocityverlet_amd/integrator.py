@@ -14,6 +14,7 @@ by the C++ adapters in platforms/hip.  All arithmetic happe
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -238,6 +239,42 @@ def plan_launch_shape(system: SystemSpec, integrator: "VVIntegrator", precision:
 DEFAULT_TUNE: dict = {}      # see Context(tune=...)
 
 
+@dataclasses.dataclass
+class Series:
+    """Rows of a device-side series (Context.series_read; include/vvhip.h: vvhip_series_row), one per sampled step.  The Drude fields are
+    None without the Drude part, the thermostat and viscosity fields None without the thermostat part."""
+    step: np.ndarray                       # int64 [n]: the step after which the row was taken
+    dropped: int                           # rows not recorded for want of capacity (their steps follow the last row)
+    raw: Optional[np.ndarray] = None       # int64 [n, 6]: the report's raw sums (vvhip_drude_report_raw) of this plan's particles
+    ok: Optional[np.ndarray] = None        # bool [n]: the row's fixed-point sums stayed in range (ke / t are NaN where not)
+    ke: Optional[np.ndarray] = None        # [n, 3] KE_COM, KE_Atom, KE_Drude (kJ/mol), as getDrudeTemperatures
+    t: Optional[np.ndarray] = None         # [n, 3] T_COM, T_Atom, T_Drude (K)
+    eta: Optional[np.ndarray] = None       # [n, 3, MAX_CHAINS] ... the fields of getNHState() after the row's step
+    eta_dot: Optional[np.ndarray] = None
+    eta_dotdot: Optional[np.ndarray] = None
+    ke2: Optional[np.ndarray] = None
+    vscale: Optional[np.ndarray] = None
+    v_bias: Optional[np.ndarray] = None
+    box: Optional[np.ndarray] = None       # [n, 3] and [n]: what the row's step ran with
+    cos_acceleration: Optional[np.ndarray] = None
+    v_max: Optional[np.ndarray] = None     # [n] nm/ps and 1/viscosity as getViscosity() returns them (0 without the cos acceleration)
+    inv_viscosity: Optional[np.ndarray] = None
+
+    def __len__(self):
+        return len(self.step)
+
+
+def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
+    """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
+    v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
+    vol = box[:, 0] * box[:, 1] * box[:, 2]
+    k = 2 * 3.1415926 / box[:, 2]
+    on = cos_acc != 0
+    inv = np.zeros_like(v)
+    inv[on] = v[on] * vol[on] * inv_mass_total / cos_acc[on] * k[on] * k[on]
+    return np.where(on, v, 0.0), inv
+
+
 class Context:
     """Device state + force provider around one VVIntegrator.
 
@@ -379,6 +416,50 @@ class Context:
         ke, t = (C.c_double * 3)(), (C.c_double * 3)()
         H.check(H.lib.vvhip_drude_report_combine(self.plan, C.byref(r), C.byref(ke), C.byref(t)), self.plan)
         return tuple(ke) + tuple(t)
+
+    # ---- series: samples recorded on the device inside the steps (include/vvhip.h: vvhip_series_*)
+    def series_start(self, interval: int, capacity: int = 4096, drude: bool = True, thermostat: bool = True):
+        """Record a row after every step whose number is a multiple of `interval` (steps counted since the context was made, through _step,
+        run_eager and run_graph alike; run_eager_unfused takes no rows), into a device buffer of `capacity` rows.  No host synchronisation
+        until series_read.  Restarting drops what was recorded."""
+        mask = (H.SERIES_DRUDE if drude else 0) | (H.SERIES_THERMOSTAT if thermostat else 0)
+        H.check(H.lib.vvhip_series_start(self.plan, int(interval), int(capacity), mask), self.plan)
+
+    def series_stop(self):
+        H.check(H.lib.vvhip_series_stop(self.plan), self.plan)
+
+    def series_info(self) -> H.SeriesLayout:
+        out = H.SeriesLayout()
+        H.check(H.lib.vvhip_series_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def series_read(self, reset: bool = False, combine=None) -> Series:
+        """The rows recorded so far (synchronises).  reset=True empties the buffer; the series then continues without gap or repeat.
+        `combine`: raw int64 [n, 7] (six sums + overflow flag) -> the same with the shards' words added (distributed.drude_temperature_series)."""
+        info = self.series_info()
+        rows = (H.SeriesRow * info.capacity)()
+        n, first, dropped = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        H.check(H.lib.vvhip_series_read(self.plan, rows, info.capacity, C.byref(n), C.byref(first), C.byref(dropped), int(bool(reset))), self.plan)
+        a = np.ctypeslib.as_array(rows)[: n.value]
+        out = Series(step=first.value + info.interval * np.arange(n.value, dtype=np.int64), dropped=int(dropped.value))
+        if info.mask & H.SERIES_DRUDE:
+            words = np.concatenate([a["drude_raw"], a["drude_overflow"][:, None]], axis=1).astype(np.int64)
+            if combine is not None:
+                words = np.asarray(combine(words), dtype=np.int64)
+            out.raw, out.ok = words[:, :6].copy(), words[:, 6] == 0
+            out.ke, out.t = np.full((n.value, 3), np.nan), np.full((n.value, 3), np.nan)
+            for j in range(n.value):
+                if out.ok[j]:
+                    r = self.drude_report_combine(out.raw[j])
+                    out.ke[j], out.t[j] = r[:3], r[3:]
+        if info.mask & H.SERIES_THERMOSTAT:
+            nh = a["nh"]
+            for f in ("eta", "eta_dot", "eta_dotdot", "ke2", "vscale", "v_bias"):
+                setattr(out, f, np.array(nh[f], dtype=np.float64))
+            out.box, out.cos_acceleration = np.array(a["box"], dtype=np.float64), np.array(a["cos_acceleration"], dtype=np.float64)
+            out.v_max, out.inv_viscosity = _viscosity_of_rows(out.v_bias, out.box, out.cos_acceleration, self.info.inv_mass_total,
+                                                              self.precision == "single")
+        return out
 
     def getNHState(self) -> H.NHState:
         s = H.NHState()

@@ -4,10 +4,18 @@
 the same tab-separated columns (step, T_COM, T_Atom, T_Drude, KE_COM, KE_Atom, KE_Drude) -- but takes the numbers from
 ``simulation.integrator.getDrudeTemperatures()`` (computed on the GPU, 56 bytes copied back) instead of downloading every velocity
 and looping over molecules and pairs on the host.  It asks OpenMM for no state at all.
+
+``write_drude_temperature_series`` / ``write_viscosity_series`` write the rows of a device-side series (``Context.series_read``,
+``distributed.drude_temperature_series``) into the files that reporter and examples/ommhelper/reporter/viscosityreporter.py write:
+the same header and columns, one line per row, so that a long graph run keeps its sampled observables without stopping the GPU
+for every sample.
 """
 from __future__ import annotations
 
 HEADER = '#"Step"\t"T_COM"\t"T_Atom"\t"T_Drude"\t"KE_COM"\t"KE_Atom"\t"KE_Drude"'
+VISCOSITY_HEADER = '#"Step"\t"Acceleration (nm/ps^2)"\t"VelocityAmplitude (nm/ps)"\t"1/Viscosity (1/Pa.s)"'
+# 1/viscosity as the integrator returns it, in nm ps / (Da item), to 1/(Pa s): 1 Da nm^-1 ps^-1 = 1e18 / N_A Pa s
+INV_VISCOSITY_TO_PER_PA_S = 6.02214076e23 * 1e-18
 
 
 def _plain(x, unit_name):
@@ -61,3 +69,46 @@ class DrudeTemperatureReporter:
             self.close()
         except Exception:
             pass
+
+
+def _open(file, append):
+    """(stream, close it afterwards?) for a path or an open text stream."""
+    if hasattr(file, "write"):
+        return file, False
+    return open(file, "a" if append else "w"), True
+
+
+def write_drude_temperature_series(file, series, append=False, header=True):
+    """The rows of a series with its Drude part (Context.series_read) as DrudeTemperatureReporter writes them for the same steps and
+    numbers: the header (unless header=False: a file continued from an earlier piece of the same run), then one tab-separated line
+    (step, T_COM, T_Atom, T_Drude, KE_COM, KE_Atom, KE_Drude) per row.  `file`: a path or an open text stream."""
+    if series.ke is None:
+        raise ValueError("the series has no Drude part (series_start(drude=True))")
+    out, own = _open(file, append)
+    try:
+        if header:
+            print(HEADER, file=out)
+        for j in range(len(series.step)):
+            print(int(series.step[j]), *[float(x) for x in series.t[j]], *[float(x) for x in series.ke[j]], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_viscosity_series(file, series, append=False, header=True):
+    """The rows of a series with its thermostat part as examples/ommhelper/reporter/viscosityreporter.py writes them: its header, then
+    step, cos acceleration (nm/ps^2), velocity amplitude vMax (nm/ps) and 1/viscosity (1/(Pa s)) per row, tab-separated."""
+    if series.v_max is None:
+        raise ValueError("the series has no thermostat part (series_start(thermostat=True))")
+    out, own = _open(file, append)
+    try:
+        if header:
+            print(VISCOSITY_HEADER, file=out)
+        for j in range(len(series.step)):
+            print(int(series.step[j]), float(series.cos_acceleration[j]), float(series.v_max[j]),
+                  float(series.inv_viscosity[j]) * INV_VISCOSITY_TO_PER_PA_S, sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()

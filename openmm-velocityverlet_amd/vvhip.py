@@ -87,6 +87,21 @@ class NHState(C.Structure):
                 ("v_bias", C.c_double)]
 
 
+SERIES_DRUDE, SERIES_THERMOSTAT = 1, 2
+
+
+class SeriesRow(C.Structure):
+    """One row of a device-side series (include/vvhip.h: vvhip_series_row)."""
+    _fields_ = [("drude_raw", C.c_int64 * 6), ("drude_overflow", C.c_int64), ("reserved", C.c_int64), ("nh", NHState),
+                ("box", C.c_double * 3), ("cos_acceleration", C.c_double)]
+
+
+class SeriesLayout(C.Structure):
+    _fields_ = [("row_bytes", C.c_int32), ("off_drude_raw", C.c_int32), ("off_nh", C.c_int32), ("off_box", C.c_int32),
+                ("active", C.c_int32), ("interval", C.c_int32), ("capacity", C.c_int32), ("mask", C.c_int32),
+                ("steps", C.c_int64), ("graph_captures", C.c_int64)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -119,6 +134,8 @@ def _load():
         "vvhip_calc_viscosity": [vp, P(dbl), P(dbl)], "vvhip_compute_kinetic_energy": [vp, P(dbl)], "vvhip_force_extra": [vp, P(vp)],
         "vvhip_drude_temperatures": [vp, P(dbl * 3), P(dbl * 3)], "vvhip_drude_report_dof": [vp, P(dbl * 3)],
         "vvhip_drude_report_raw": [vp, P(C.c_int64 * 6)], "vvhip_drude_report_combine": [vp, P(C.c_int64 * 6), P(dbl * 3), P(dbl * 3)],
+        "vvhip_series_start": [vp, i32, i32, i32], "vvhip_series_stop": [vp], "vvhip_series_info": [vp, P(SeriesLayout)],
+        "vvhip_series_read": [vp, vp, i32, P(i32), P(C.c_int64), P(C.c_int64), i32], "vvhip_debug_series_guard": [vp, P(i32)],
         "vvhip_device_count": [P(C.c_int)], "vvhip_set_device": [C.c_int],
         "vvhip_malloc": [P(vp), C.c_size_t], "vvhip_free": [vp],
         "vvhip_memcpy_h2d": [vp, vp, C.c_size_t], "vvhip_memcpy_d2h": [vp, vp, C.c_size_t],
