@@ -359,6 +359,49 @@ int vvhip_series_stop(vvhip_plan* plan);
 int vvhip_series_info(const vvhip_plan* plan, vvhip_series_layout* out);
 /* Test hook: 1 if the guard row behind the buffer's last row still holds its fill pattern (nothing was written past capacity). */
 int vvhip_debug_series_guard(vvhip_plan* plan, int32_t* intact);
+/* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
+ * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
+ * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the
+ * System with mass > 0 -- NH and Langevin subsets, Drude particles and their parents alike --
+ *     M = sum m_i,   P = sum m_i v_i,   V = P / M,   v_i <- v_i - V   for every i with m_i > 0
+ * with m_i the System's masses as the plan holds them.  Massless particles (images, virtual sites) are neither summed nor touched;
+ * positions, velm.w, forces, thermostat state, accumulators, rendezvous words and the four status words are not touched.  This is the
+ * documented behaviour of OpenMM's kernel stated in float64, not pinned against OpenMM.
+ * Two kernels (sum, subtract) in the plan's stream, nothing in between; the sums are fixed point, so the same velocities give the same
+ * V bits whatever the launch shape or wave layout (csrc/vv_args.hpp: CmmArgs states the quantisation).  A term m v outside the
+ * fixed-point range (NaN included) makes that removal a no-op and counts it as skipped; no status word is raised.
+ * Schedule: with frequency f the removal runs IN FRONT OF every full step whose 0-based index -- the plan's step count before the step,
+ * the counter of the series -- is a multiple of f: vvhip_step_middle, vvhip_step_vv_first, phase 0 of vvhip_step_middle_phase and the
+ * steps of vvhip_run_graph / vvhip_run_eager enqueue it; the split per-KernelImpl entry points and vvhip_run_eager_unfused do not
+ * (inside OpenMM the platform's remover runs and this stays off).  A series row "after step k" is recorded before the removal in
+ * front of step k + 1.  Inside a captured graph the removals are part of the graph, and the steps that carry one are part of the
+ * graph-cache key: when f divides the graph's length or the length divides f, steady-state replays re-capture nothing.  A repaired
+ * rendezvous (vvhip_recovery_count) repeats the removals at the same steps and restores the record's counters with the snapshot.
+ * Nothing is on by default: a plan that never calls vvhip_cm_motion_start launches what it launched before. */
+typedef struct {
+    int32_t frequency;              /* steps between removals; 0: none scheduled */
+    int32_t reserved;               /* 0 */
+    int64_t removals;               /* scheduled removals done since vvhip_cm_motion_start */
+    int64_t skipped;                /* ... skipped because a term left the fixed-point range (nothing was subtracted) */
+    double last_v[3];               /* the V of the last scheduled removal, nm/ps (NaN after a skipped one, 0 before the first) */
+    double total_mass;              /* M, Da */
+} vvhip_cm_motion_record;
+/* Schedules a removal in front of every `frequency`-th step (restarts with the new frequency and a cleared record if already on); drops
+ * the captured graphs.  Refused, in this order: frequency < 1 (VVHIP_ERR_INVALID); a plan described with has_cm_motion_remover = 0
+ * (VVHIP_ERR_INVALID: the thermostat's degrees of freedom would not match); a sharded plan (VVHIP_ERR_UNSUPPORTED: a shard's momentum is
+ * partial); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID). */
+int vvhip_cm_motion_start(vvhip_plan* plan, int32_t frequency);
+/* No further removals; drops the captured graphs.  The record stays readable. */
+int vvhip_cm_motion_stop(vvhip_plan* plan);
+/* One removal now, in the plan's stream behind what is queued; blocks and returns the V it subtracted (24 bytes back; v_removed may be
+ * NULL).  Independent of the schedule, its record, the step counter and has_cm_motion_remover: a plain operation on the velocities, as
+ * after setVelocities.  Refused on a sharded plan (VVHIP_ERR_UNSUPPORTED).  A term out of range gives VVHIP_ERR_OVERFLOW for this call
+ * only, with the velocities untouched. */
+int vvhip_remove_cm_motion(vvhip_plan* plan, double v_removed[3]);
+/* Synchronises and copies the schedule's record; VVHIP_ERR_OVERFLOW (record filled) if a scheduled removal was skipped.  The host-only
+ * fields (frequency, total_mass) are filled on an unbound plan too. */
+int vvhip_cm_motion_read(vvhip_plan* plan, vvhip_cm_motion_record* out);
+
 /* Device pointer of the plan-owned forceExtra array (real3[n]); getForceExtra() of the reference
  * (CudaVVKernels.h:86-88). */
 int vvhip_force_extra(vvhip_plan* plan, void** device_ptr);

@@ -157,6 +157,8 @@ struct vvhip_plan {
         long long step_count = 0;                 // the series' schedule: the step counter and the device-side row cursor
         unsigned long long* series_cursor = nullptr;
         bool series_saved = false;
+        vv::CmmDevRecord* cmm_rec = nullptr;      // the counters of the scheduled removals of the centre-of-mass motion
+        bool cmm_saved = false;
     } rec;
     // plan-owned device state
     int2* d_slots = nullptr;
@@ -205,6 +207,7 @@ struct vvhip_plan {
         double kt = 0, kd = 0;
         uint32_t random_end = 0;               // prepareRandomNumbers cursor after the graph's last step
         std::vector<int> rows;                 // steps of the graph (1 .. steps) that append a series row: part of the key
+        std::vector<int> cmm;                  // steps of the graph (0 .. steps - 1) with a removal of the centre-of-mass motion in front: part of the key
     };
     // (round 6: up to four graph lengths per parity -- a host that replays a short graph in front of a long one keeps both)
     static constexpr int kGraphWays = 4;
@@ -263,6 +266,15 @@ struct vvhip_plan {
         unsigned long long* d_cursor = nullptr;   // [2] rows appended (past capacity too), rows dropped
         long long* d_scratch = nullptr;           // the report's scratch for the rows (as d_rep), zero between rows
     } series;
+    // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
+    // allocated by the first call that needs them
+    struct CmMotion {
+        bool on = false;
+        int frequency = 0;
+        long long* d_words = nullptr;             // [CMM_WORDS] zero between removals
+        vv::CmmDevRecord* d_rec = nullptr;        // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
+        double* h_v = nullptr;                    // pinned: the V of a one-off call as copied back
+    } cmm;
 };
 
 static void drop_graphs(vvhip_plan* p) {
@@ -271,6 +283,7 @@ static void drop_graphs(vvhip_plan* p) {
             if (g.exec) { (void) hipGraphExecDestroy(g.exec); g.exec = nullptr; }
 }
 static int step_done(vvhip_plan* p);
+static int step_begin(vvhip_plan* p);
 // The steps i = 1 .. steps after step counter c0 that append a series row (empty without a series)
 static std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps) {
     std::vector<int> r;
@@ -279,11 +292,20 @@ static std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int st
     for (long long i = k - c0 % k; i <= steps; i += k) r.push_back((int) i);
     return r;
 }
+// The steps i = 0 .. steps - 1 after step counter c0 with a removal of the centre-of-mass motion in front (empty without a schedule)
+static std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps) {
+    std::vector<int> r;
+    if (!p->cmm.on) return r;
+    const long long f = p->cmm.frequency;
+    for (long long i = (f - c0 % f) % f; i < steps; i += f) r.push_back((int) i);
+    return r;
+}
 // the slot of parity q that holds (or will hold) the graph with this key
-static vvhip_plan::GraphSlot& graph_slot(vvhip_plan* p, int q, int steps, const void* site, double kt, double kd, const std::vector<int>& rows) {
+static vvhip_plan::GraphSlot& graph_slot(vvhip_plan* p, int q, int steps, const void* site, double kt, double kd, const std::vector<int>& rows,
+                                         const std::vector<int>& cmm) {
     auto& row = p->graph[q & 1];
     for (auto& g : row)
-        if (g.exec && g.steps == steps && g.site == site && g.kt == kt && g.kd == kd && g.rows == rows) return g;
+        if (g.exec && g.steps == steps && g.site == site && g.kt == kt && g.kd == kd && g.rows == rows && g.cmm == cmm) return g;
     for (auto& g : row)
         if (!g.exec) return g;
     return row[p->graph_next[q & 1]++ % vvhip_plan::kGraphWays];
@@ -892,9 +914,10 @@ void vvhip_plan_destroy(vvhip_plan* p) {
                           p->rec.posq, p->rec.corr, p->rec.velm, p->rec.force, p->rec.fextra, p->rec.random, (void*) p->rec.nh, (void*) p->rec.epoch,
                           (void*) p->d_rep_lane_mol, (void*) p->d_rep_lane_mass, (void*) p->d_rep_lane_mu, (void*) p->d_rep_mol_mass, (void*) p->d_rep_cross,
                           (void*) p->d_rep_cross_mu, (void*) p->d_rep, (void*) p->series.d_rows, (void*) p->series.d_cursor, (void*) p->series.d_scratch,
-                          (void*) p->rec.series_cursor})
+                          (void*) p->rec.series_cursor, (void*) p->rec.cmm_rec, (void*) p->cmm.d_words, (void*) p->cmm.d_rec})
             if (ptr) (void) hipFree(ptr);
         if (p->h_rep) (void) hipHostFree(p->h_rep);
+        if (p->cmm.h_v) (void) hipHostFree(p->cmm.h_v);
         drop_graphs(p);
         if (p->comm) (void) rccl_api().commDestroy(p->comm);
         mailbox_release(p);
@@ -946,7 +969,7 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
         const bool same = b->velm == o.velm && b->posq == o.posq && b->posq_correction == o.posq_correction && b->force == o.force &&
                           b->pos_delta == o.pos_delta && b->random == o.random && b->random_size == o.random_size;
         if (b->velm != o.velm) p->mass_tab_valid = false;
-        if (!same || p->series.on) drop_graphs(p);      // (a series row reads velm through its captured arguments too)
+        if (!same || p->series.on || p->cmm.on) drop_graphs(p);      // (a series row and a scheduled removal read velm through their captured arguments too)
     }
     // a re-bind that moves the plan to another stream: whatever the plan still has in flight on the old one (fills, steps) must be
     // complete before work enqueued on the new one can touch the same buffers
@@ -1153,6 +1176,9 @@ static bool use_rekick(const vvhip_plan* p) {
 // in-kernel constraints kernel A reads the positions of the cluster MEMBERS (their share of the particles, rounded to whole bytes) and
 // both kernels read the cluster word and parameters (4 + 16 bytes per lane) wherever those come from memory, i.e. not in the
 // arithmetic layout, where they are pattern rows in LDS.
+// Not in these numbers: the removal of the centre-of-mass motion, a pair of kernels of its own in front of every f-th step (vv_dev_cmm.inc).
+// Per particle in mixed / double precision: sum = R velm 32 + slot 8 + mass 8 = 48 bytes, subtract = R velm 32 + W velm 32 + slot 8 + mass 8
+// = 80 bytes, 128 for the pair (single: velm is 16 bytes, 32 + 48 = 80); divide by f for the share of a step.
 // Does vvhip_step_middle take the one-launch step for this plan as it stands?  (The kernel itself is looked up at the first step; a pair
 // of stage sets already found wanting says so here.)
 static bool fused_active(const vvhip_plan* p) {
@@ -1246,6 +1272,11 @@ static int middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
 }
 // (the last phase completes the step: it is counted, and takes its series row)
 int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
+    if (phase == 0) {                                     // (the step begins: what middle_phase would refuse is refused before anything is enqueued)
+        NEED_BOUND(p);
+        NEED_FUSABLE(p);
+        TRY(step_begin(p));
+    }
     TRY(middle_phase(p, phase, random_index));
     return phase == vvhip_step_middle_phases(p) - 1 ? step_done(p) : VVHIP_OK;
 }
@@ -1291,6 +1322,9 @@ static int step_middle(vvhip_plan* p, uint32_t random_index) {
 }
 int vvhip_step_middle(vvhip_plan* p, uint32_t random_index) {
     NEED_BOUND(p);
+    if (!p->hp.params.use_middle_scheme) return fail(p, VVHIP_ERR_INVALID, "plan was created for the classic scheme");
+    NEED_FUSABLE(p);
+    TRY(step_begin(p));
     TRY(step_middle(p, random_index));
     return step_done(p);
 }
@@ -1329,6 +1363,7 @@ static int nh_half(vvhip_plan* p, uint32_t a_first, uint32_t random_index, uint3
 int vvhip_step_vv_first(vvhip_plan* p) {                   // API:295-310 (forces for the old positions are in `force`)
     NEED_BOUND(p);
     NEED_FUSABLE(p);
+    TRY(step_begin(p));
     return nh_half(p, 0, 0, vv::B_VV_KICK | tail_flags(p) | cons_b(p));
 }
 
@@ -1440,7 +1475,7 @@ static vv::ReportArgs report_args(const vvhip_plan* p, long long* scratch) {
     a.velm = p->buf.velm; a.slots = p->d_slots;
     a.lane_mol = p->d_rep_lane_mol; a.lane_mass = p->d_rep_lane_mass; a.lane_mu = p->d_rep_lane_mu;
     a.mol_mass = p->d_rep_mol_mass; a.cross = p->d_rep_cross; a.cross_mu = p->d_rep_cross_mu;
-    a.out = scratch; a.mol_p = scratch + 8;
+    a.out = scratch; a.mol_p = scratch ? scratch + 8 : nullptr;
     a.nwaves = hp.info.num_waves; a.nmol = (int) hp.report_mol_mass.size(); a.ncross = (int) hp.report_cross_mu.size();
     a.frac_bits = hp.report_frac_bits;
     a.unit = std::ldexp(1.0, hp.report_unit_bits); a.frac_scale = std::ldexp(1.0, hp.report_frac_bits);
@@ -1516,6 +1551,101 @@ static int series_row(vvhip_plan* p) {
 static int step_done(vvhip_plan* p) {
     p->step_count++;
     if (p->series.on && p->step_count % p->series.interval == 0) return series_row(p);
+    return VVHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
+static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
+static int cmm_ensure(vvhip_plan* p) {
+    vvhip_plan::CmMotion& M = p->cmm;
+    if (M.d_words) return VVHIP_OK;
+    HIP_TRY(p, hipMalloc((void**) &M.d_words, vv::CMM_WORDS * sizeof(long long)));
+    HIP_TRY(p, hipMalloc((void**) &M.d_rec, 2 * sizeof(vv::CmmDevRecord)));
+    HIP_TRY(p, hipHostMalloc((void**) &M.h_v, 3 * sizeof(double)));
+    HIP_TRY(p, hipMemsetAsync(M.d_words, 0, vv::CMM_WORDS * sizeof(long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(M.d_rec, 0, 2 * sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    return VVHIP_OK;
+}
+// The pair of kernels behind what is queued (or captured); which = 0: a scheduled removal, 1: a one-off call (records of their own)
+static int cmm_enqueue(vvhip_plan* p, int which) {
+    TRY(settle_recovery(p));
+    vv::CmmArgs a{};
+    a.rep = report_args(p, nullptr);
+    a.words = p->cmm.d_words;
+    a.rec = p->cmm.d_rec + which;
+    a.inv_total_mass = p->hp.cm_total_mass > 0 ? 1.0 / p->hp.cm_total_mass : 0.0;
+    HIP_TRY(p, vv::launch_cm_motion(p->hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// A full step is about to be enqueued (or captured): the removal in front of it when its index is due.  The one hook of every entry point
+// that starts a step (next to step_done, which ends it).
+static int step_begin(vvhip_plan* p) {
+    if (p->cmm.on && p->step_count % p->cmm.frequency == 0) return cmm_enqueue(p, 0);
+    return VVHIP_OK;
+}
+int vvhip_cm_motion_start(vvhip_plan* p, int32_t frequency) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (frequency < 1) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: frequency must be >= 1 step");
+    if (!p->hp.has_cm_motion_remover)
+        return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: the plan was described without a CMMotionRemover (has_cm_motion_remover = 0), so the thermostat's "
+                                          "degrees of freedom (DOF) still count the 3 of the centre of mass; describe the System with the remover to schedule removals");
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    TRY(settle_recovery(p));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (removals of a schedule before may still be in flight)
+    TRY(cmm_ensure(p));
+    HIP_TRY(p, hipMemsetAsync(p->cmm.d_rec, 0, sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    drop_graphs(p);
+    p->cmm.on = true; p->cmm.frequency = frequency;
+    return VVHIP_OK;
+}
+int vvhip_cm_motion_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    if (!p->cmm.on) return VVHIP_OK;
+    TRY(settle_recovery(p));
+    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    p->cmm.on = false; p->cmm.frequency = 0;
+    drop_graphs(p);
+    return VVHIP_OK;
+}
+int vvhip_remove_cm_motion(vvhip_plan* p, double v_removed[3]) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    TRY(settle_recovery(p));
+    TRY(cmm_ensure(p));
+    TRY(cmm_enqueue(p, 1));
+    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v, p->cmm.d_rec[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (std::isnan(p->cmm.h_v[0]))      // (what the subtract kernel records for a removal it skipped)
+        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+    if (v_removed) std::memcpy(v_removed, p->cmm.h_v, 3 * sizeof(double));
+    return VVHIP_OK;
+}
+int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_cm_motion_record r{};
+    r.frequency = p->cmm.on ? p->cmm.frequency : 0;
+    r.total_mass = p->hp.cm_total_mass;
+    if (p->bound && p->cmm.d_rec) {
+        if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+        TRY(settle_recovery(p));                        // (a repaired run redoes its removals first)
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        vv::CmmDevRecord d{};
+        HIP_TRY(p, hipMemcpy(&d, p->cmm.d_rec, sizeof(d), hipMemcpyDeviceToHost));
+        r.removals = d.removals; r.skipped = d.skipped;
+        for (int k = 0; k < 3; k++) r.last_v[k] = d.last_v[k];
+    }
+    *out = r;
+    if (r.skipped > 0)
+        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: " + std::to_string((long long) r.skipped) + " scheduled removal(s) skipped: a momentum term was NaN or beyond the fixed-point range");
     return VVHIP_OK;
 }
 static void series_release(vvhip_plan* p) {
@@ -1791,6 +1921,11 @@ static int recovery_snapshot(vvhip_plan* p) {
         if (!r.series_cursor) HIP_TRY(p, hipMalloc((void**) &r.series_cursor, 2 * sizeof(unsigned long long)));
         HIP_TRY(p, hipMemcpyAsync(r.series_cursor, p->series.d_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     }
+    r.cmm_saved = p->cmm.d_rec != nullptr;          // (a schedule cannot start or stop while the snapshot is unverified either)
+    if (r.cmm_saved) {
+        if (!r.cmm_rec) HIP_TRY(p, hipMalloc((void**) &r.cmm_rec, sizeof(vv::CmmDevRecord)));
+        HIP_TRY(p, hipMemcpyAsync(r.cmm_rec, p->cmm.d_rec, sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
+    }
     r.runs.clear();
     r.valid = true;
     return VVHIP_OK;
@@ -1830,6 +1965,10 @@ int recover_rendezvous(vvhip_plan* p) {
     p->step_count = r.step_count;
     if (r.series_saved && p->series.on)
         HIP_TRY(p, hipMemcpyAsync(p->series.d_cursor, r.series_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+    // ... and so are the removals of the centre-of-mass motion, at the same steps (the schedule follows the step counter): their counters go
+    // back with it (the scratch words are zero between removals whatever the failed steps computed)
+    if (r.cmm_saved && p->cmm.d_rec)
+        HIP_TRY(p, hipMemcpyAsync(p->cmm.d_rec, r.cmm_rec, sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
     for (int w = 1; w < 4; w++) __atomic_store_n(&p->h_status[w], 0u, __ATOMIC_RELAXED);
     p->fused = false;
     p->fused_checked_b = 0;
@@ -1872,10 +2011,10 @@ static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* s
                         vvhip_plan::GraphSlot** out = nullptr) {
     hipStream_t s = p->stream;
     TRY(ensure_mass_table(p));                       // a one-off fill must not be recorded into the replayed graph
-    const std::vector<int> rows = series_rows_in(p, c0, steps_per_graph);
-    vvhip_plan::GraphSlot& g = graph_slot(p, q, steps_per_graph, site, k_tether, k_drude, rows);
+    const std::vector<int> rows = series_rows_in(p, c0, steps_per_graph), cmm = cmm_steps_in(p, c0, steps_per_graph);
+    vvhip_plan::GraphSlot& g = graph_slot(p, q, steps_per_graph, site, k_tether, k_drude, rows, cmm);
     if (out) *out = &g;
-    if (g.exec && g.steps == steps_per_graph && g.site == site && g.kt == k_tether && g.kd == k_drude && g.rows == rows) return VVHIP_OK;
+    if (g.exec && g.steps == steps_per_graph && g.site == site && g.kt == k_tether && g.kd == k_drude && g.rows == rows && g.cmm == cmm) return VVHIP_OK;
     if (g.exec) { (void) hipStreamSynchronize(s); (void) hipGraphExecDestroy(g.exec); g.exec = nullptr; }      // (a replay of the one that goes may still be in flight)
     // The capture walks the host-side cursors (parity, Langevin random slice) through the graph's steps; they are put back
     // afterwards, because nothing has run yet.  A replay moves them to the graph's end (vvhip_run_graph).
@@ -1903,7 +2042,7 @@ static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* s
     (void) hipGraphDestroy(graph);
     if (e != hipSuccess) { g.exec = nullptr; return hip_fail(p, e, "hipGraphInstantiate"); }
     (void) hipGraphUpload(g.exec, s);                // pay the first launch's set-up here, not in the caller's timed region
-    g.steps = steps_per_graph; g.site = site; g.kt = k_tether; g.kd = k_drude; g.rows = rows;
+    g.steps = steps_per_graph; g.site = site; g.kt = k_tether; g.kd = k_drude; g.rows = rows; g.cmm = cmm;
     p->graph_captures++;
     return VVHIP_OK;
 }
@@ -1939,7 +2078,9 @@ int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* 
         for (; done + steps_per_graph <= nsteps; done += steps_per_graph) {
             // with a series the replays' rows fall on other steps of the graph as the counter moves on: the graph whose rows fit
             // (at most two when the interval and the graph's length divide one another; otherwise the cache may capture again)
-            if (p->series.on && done > 0 && series_rows_in(p, p->step_count, steps_per_graph) != g->rows)
+            // (the same for the steps that carry a removal of the centre-of-mass motion)
+            if (done > 0 && ((p->series.on && series_rows_in(p, p->step_count, steps_per_graph) != g->rows) ||
+                             (p->cmm.on && cmm_steps_in(p, p->step_count, steps_per_graph) != g->cmm)))
                 TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count, &g));
             HIP_TRY(p, hipGraphLaunch(g->exec, s));
             p->step_count += steps_per_graph;

@@ -266,4 +266,27 @@ struct SeriesArgs {
     double box[3], cos_acceleration;
 };
 
+// Removal of the centre-of-mass velocity (vv_dev_cmm.inc, vvhip_cm_motion_*): V = sum m v / sum m over every massive lane, v -= V.
+// The three momentum sums use the report's two-word fixed point (ReportArgs: each term m v_c is split on its own into hi = floor(y),
+// lo = rint((y - hi) 2^frac_bits), y = m v_c 2^unit_bits, and the words are summed as integers), so P is the same bits whatever the
+// launch shape or the wave layout.  Quantisation: a term is rounded to 2^-(unit_bits + frac_bits) Da nm/ps, half of that at most per
+// term; with unit_bits = 16, frac_bits = 61 - bits(n) and n < 2^bits(n) massive particles
+//     |P_fixed - P_exact| <= n 2^-(78 - bits(n)) < 2^(2 bits(n) - 78) Da nm/ps      (5.7e-14 at 0.1 M particles, 9e-10 at 9 M)
+// and |V - P_exact / M| <= that / M + 3 ulp(V) (the join of the two words, the product with the host's 1 / M): below 1e-19 nm/ps at
+// every size a GPU holds -- ten orders of magnitude under a thermal speed.  A term beyond ReportArgs::limit (or NaN) raises the bad word
+// and the removal is skipped: nothing is subtracted.
+// words[0..5] = (hi, lo) of P_x, P_y, P_z; [CMM_BAD] != 0: a term was out of range; [CMM_TICKET] = blocks of the subtract kernel that
+// have read the words (the last one zeroes all eight: the scratch is zero between removals without a memset in the stream).
+enum { CMM_BAD = 6, CMM_TICKET = 7, CMM_WORDS = 8 };
+struct CmmDevRecord {
+    long long removals, skipped;    // removals done / skipped because of the bad word
+    double last_v[3];               // the V of the last removal (NaN after a skipped one)
+};
+struct CmmArgs {
+    ReportArgs rep;                 // velm, slots, lane_mass, nwaves and the fixed point; the report's other tables are not read
+    long long* words;               // [CMM_WORDS]
+    CmmDevRecord* rec;
+    double inv_total_mass;          // 1 / sum of the masses > 0, formed in double on the host (0 without massive particles)
+};
+
 }  // namespace vv

@@ -13,3 +13,4 @@
 #include "vv_dev_kernel_b.inc"
 #include "vv_dev_misc.inc"
 #include "vv_dev_report.inc"
+#include "vv_dev_cmm.inc"

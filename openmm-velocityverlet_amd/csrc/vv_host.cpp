@@ -166,6 +166,8 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
     double mass_total = 0;                                      // HOST:1028-1031
     for (int i = 0; i < n; i++) mass_total += sys.masses[i];
     info.inv_mass_total = 1.0 / mass_total;
+    hp.has_cm_motion_remover = sys.has_cm_motion_remover != 0;
+    for (int i = 0; i < n; i++) if (sys.masses[i] > 0) hp.cm_total_mass += sys.masses[i];
     info.num_particles_nh = (int) hp.particles_nh.size();
     info.num_molecules_nh = (int) hp.molecules_nh.size();
     info.num_normal_nh = (int) hp.normal_nh.size();

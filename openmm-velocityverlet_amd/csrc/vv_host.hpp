@@ -89,6 +89,10 @@ struct HostPlan {
     std::vector<int32_t> report_cross;         // 4 per pair across two molecules: Drude, parent (shard-relative), their shard-local molecules (-1: no mass)
     std::vector<double> report_cross_mu;       // ... and its reduced mass
     std::string report_unsupported;            // why this plan cannot report (a shard that cuts a molecule); empty otherwise
+    // removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc): the description's flag (it only enters the DOF counts) and
+    // the sum of the masses > 0 of the WHOLE system, added up in particle order
+    bool has_cm_motion_remover = false;
+    double cm_total_mass = 0;
     // reference-style tables, kept for inspection / tests (global particle indices)
     std::vector<int32_t> particles_nh, molecules_nh, normal_nh, pairs_nh, normal_ld, pairs_ld;
 };

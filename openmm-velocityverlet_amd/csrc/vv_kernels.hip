@@ -492,6 +492,15 @@ hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s
     hipLaunchKernelGGL(vv_kernel_series_append, dim3((unsigned) std::max<long long>(1, g)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    const int wpb = block_threads / 64;
+    const int g = std::max(1, std::min((a.rep.nwaves + wpb - 1) / wpb, grid_cap));
+    VV_DISPATCH(vv_kernel_cmm_sum, dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    VV_DISPATCH(vv_kernel_cmm_subtract, dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

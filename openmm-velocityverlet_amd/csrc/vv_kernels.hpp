@@ -52,5 +52,8 @@ hipError_t launch_image_pairs(int precision, void* posq, void* corr, const int2*
 hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, int grid_cap, hipStream_t s);
 // One series row (vv_dev_report.inc: vv_kernel_series_append) behind the report's passes (or alone: a.rep_out null).
 hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s);
+// Removal of the centre-of-mass velocity (vv_dev_cmm.inc): the sum kernel, then the subtract kernel, over a.rep.nwaves waves in blocks of
+// block_threads, at most grid_cap of them (the kernels stride beyond).  a.words must be zero on entry and is zero again afterwards.
+hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -461,6 +461,30 @@ class Context:
                                                               self.precision == "single")
         return out
 
+    # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
+    def remove_cm_motion_every(self, frequency: int):
+        """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
+        the series) is a multiple of `frequency`, on the device and inside graph replays: what a CMMotionRemover(frequency) does in
+        OpenMM.  Needs a System described with has_cm_motion_remover (the thermostat then counts 3 degrees of freedom less)."""
+        H.check(H.lib.vvhip_cm_motion_start(self.plan, int(frequency)), self.plan)
+
+    def remove_cm_motion_stop(self):
+        H.check(H.lib.vvhip_cm_motion_stop(self.plan), self.plan)
+
+    def remove_cm_motion(self) -> np.ndarray:
+        """One removal now (blocks): returns the velocity V = sum m v / sum m [nm/ps] that was subtracted from every massive particle.
+        Independent of the schedule and of has_cm_motion_remover."""
+        v = (C.c_double * 3)()
+        H.check(H.lib.vvhip_remove_cm_motion(self.plan, C.byref(v)), self.plan)
+        return np.array(v, dtype=np.float64)
+
+    def cm_motion_record(self) -> H.CmMotionRecord:
+        """frequency, removals done, removals skipped, the last V and the total mass of the scheduled removals (synchronises).  Raises
+        (ERR_OVERFLOW) if a removal was skipped because a momentum term was NaN or out of range."""
+        out = H.CmMotionRecord()
+        H.check(H.lib.vvhip_cm_motion_read(self.plan, C.byref(out)), self.plan)
+        return out
+
     def getNHState(self) -> H.NHState:
         s = H.NHState()
         H.check(H.lib.vvhip_get_nh_state(self.plan, C.byref(s)), self.plan)

@@ -9,10 +9,13 @@ and looping over molecules and pairs on the host.  It asks OpenMM for no state a
 ``distributed.drude_temperature_series``) into the files that reporter and examples/ommhelper/reporter/viscosityreporter.py write:
 the same header and columns, one line per row, so that a long graph run keeps its sampled observables without stopping the GPU
 for every sample.
+
+``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
 
 HEADER = '#"Step"\t"T_COM"\t"T_Atom"\t"T_Drude"\t"KE_COM"\t"KE_Atom"\t"KE_Drude"'
+CM_MOTION_HEADER = '#"Step"\t"Removals"\t"Skipped"\t"Vx (nm/ps)"\t"Vy (nm/ps)"\t"Vz (nm/ps)"'
 VISCOSITY_HEADER = '#"Step"\t"Acceleration (nm/ps^2)"\t"VelocityAmplitude (nm/ps)"\t"1/Viscosity (1/Pa.s)"'
 # 1/viscosity as the integrator returns it, in nm ps / (Da item), to 1/(Pa s): 1 Da nm^-1 ps^-1 = 1e18 / N_A Pa s
 INV_VISCOSITY_TO_PER_PA_S = 6.02214076e23 * 1e-18
@@ -108,6 +111,20 @@ def write_viscosity_series(file, series, append=False, header=True):
         for j in range(len(series.step)):
             print(int(series.step[j]), float(series.cos_acceleration[j]), float(series.v_max[j]),
                   float(series.inv_viscosity[j]) * INV_VISCOSITY_TO_PER_PA_S, sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_cm_motion_record(file, step, record, append=False, header=True):
+    """One line for the record of the scheduled removals of the centre-of-mass motion (Context.cm_motion_record) as it stands at `step`:
+    removals done, removals skipped, and the centre-of-mass velocity the last one subtracted."""
+    out, own = _open(file, append)
+    try:
+        if header:
+            print(CM_MOTION_HEADER, file=out)
+        print(int(step), int(record.removals), int(record.skipped), *[float(x) for x in record.last_v], sep="\t", file=out)
         out.flush()
     finally:
         if own:

@@ -102,6 +102,12 @@ class SeriesLayout(C.Structure):
                 ("steps", C.c_int64), ("graph_captures", C.c_int64)]
 
 
+class CmMotionRecord(C.Structure):
+    """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
+    _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
+                ("last_v", C.c_double * 3), ("total_mass", C.c_double)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -136,6 +142,8 @@ def _load():
         "vvhip_drude_report_raw": [vp, P(C.c_int64 * 6)], "vvhip_drude_report_combine": [vp, P(C.c_int64 * 6), P(dbl * 3), P(dbl * 3)],
         "vvhip_series_start": [vp, i32, i32, i32], "vvhip_series_stop": [vp], "vvhip_series_info": [vp, P(SeriesLayout)],
         "vvhip_series_read": [vp, vp, i32, P(i32), P(C.c_int64), P(C.c_int64), i32], "vvhip_debug_series_guard": [vp, P(i32)],
+        "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
+        "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_device_count": [P(C.c_int)], "vvhip_set_device": [C.c_int],
         "vvhip_malloc": [P(vp), C.c_size_t], "vvhip_free": [vp],
         "vvhip_memcpy_h2d": [vp, vp, C.c_size_t], "vvhip_memcpy_d2h": [vp, vp, C.c_size_t],
