@@ -88,15 +88,24 @@ struct vvhip_plan {
     int split_chain_waves = 44000;   // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
                                      // 1.33 M 14.5 | 14.0 k, 1.78 M 11.4 | 11.1 k, 2.66 M 7.38 | 7.37 k, 4.4 M 4.14 | 4.20 k, 8.9 M 2.16 | 2.21 k (round 2 had it at 12 288)
-    bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
-    bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
     // The reference's kick kernels add forceExtra ALWAYS (K/middle.cu:11-21, K/velocityVerlet.cu:20-22) and the array is only reset in
     // steps that have a source of extra forces (API:238-240, 316-318): once the cos acceleration is set to 0 in a run without Langevin
     // particles or a field, the last cos force stays in forceExtra and every later kick keeps adding it.  The fused middle step computes
-    // extra forces on the fly and leaves the array alone; `fextra_virtual` says the array SHOULD hold the cos force of the last fused
+    // extra forces on the fly and leaves the array alone; `cur.fextra_virtual` says the array SHOULD hold the cos force of the last fused
     // step.  vvhip_set_params materialises it (kernel A from the cached cos(kz)) when the acceleration goes to 0, and a fused kick
     // without sources loads the array whenever it is dirty -- the reference's behaviour to the bit, quirk included.
-    bool fextra_virtual = false;
+    // The host's cursor through the steps: what a graph capture walks through its steps and puts back (prepare_slot) and what a recovery
+    // returns to its snapshot (Recovery::cur)
+    struct Cursor {
+        int parity = 0;                // which copy of the thermostat state / accumulators the next reduction/consumer pair uses
+        uint32_t random_pos = 0;       // prepareRandomNumbers cursor for the plan-driven loops (vvhip_run_*)
+        bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
+        bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
+        // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
+        // the series' rows (vvhip_series_*) and of the removals of the centre-of-mass motion
+        long long step_count = 0;
+    } cur;
+    bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
     bool fextra_external = false;  // the host asked for the pointer (vvhip_force_extra) and may write to it: never assume zeros
     bool no_moments = false;       // test hook "no_moments": keep the three-launch cos sequence (comparison runs)
     // with an arithmetic work-item layout (HostPlan::per) the kernels compute particle indices instead of loading slot words (test hook "periodic_kernels" = 0:
@@ -117,8 +126,9 @@ struct vvhip_plan {
     bool rekick = true;            // fused middle step: kick repeated in kernel B instead of a velm store in kernel A (use_rekick)
     // One launch per step (vv_device.inc: "fused step"): kernels A and B of the middle scheme as one launch of co-resident blocks around an
     // in-kernel rendezvous.  `fused` = allowed (vvhip_debug_tune "fused": A/B comparisons and the bit-for-bit tests switch it off);
-    // d_rv = the rendezvous words, [2 thermostat parities][NUM_ACC][ACC_SLOTS], uncached; fused_checked_* = the last pair of stage sets /
-    // launch shape whose kernel and occupancy were looked up, fused_ok = what came of it.
+    // d_rv = the rendezvous words, [2 thermostat parities][NUM_ACC][ACC_SLOTS], uncached; fused_checks = the pairs of stage sets / launch
+    // shapes whose kernel and occupancy were looked up and what came of it, fused_last = the entry the last attempt used (-1: none since the
+    // cache was emptied).
     bool fused = true;
     // the wait grows when more than blocks / 2^shift blocks needed a second round (test hook "fused_late_shift").  1/16 of the blocks (shift 4,
     // the first choice) let the wait climb where the blocks finish their front unevenly (constraint clusters: 11 units against the best pinned 7);
@@ -127,12 +137,9 @@ struct vvhip_plan {
     int fused_late_shift = 1;
     int fused_poll_delay = -1;     // >= 0: pins the wait between a block's publish and its first poll round, units of 256 clocks (test hook "fused_poll_delay"); -1: self-tuning
     unsigned long long* d_rv = nullptr;
-    uint32_t fused_checked_a = 0, fused_checked_b = 0;
-    int fused_checked_threads = 0, fused_checked_waves = 0;
-    bool fused_ok = false;
     struct FusedCheck { uint32_t a = 0, b = 0; int threads = 0, waves = 0; bool ok = false; };
     FusedCheck fused_checks[4];    // (the classic scheme alternates between the pairs of its two halves)
-    int fused_check_next = 0;
+    int fused_check_next = 0, fused_last = -1;
     long long fused_launches = 0;
     // Recovery from a missed rendezvous (round 6).  The one-launch step needs its blocks resident together; another process's kernel on the
     // device can break that, the blocks' bounded wait then runs out (sticky word [2]) and the step -- and every step enqueued behind it -- has
@@ -148,14 +155,11 @@ struct vvhip_plan {
         void *posq = nullptr, *corr = nullptr, *velm = nullptr, *force = nullptr, *fextra = nullptr, *random = nullptr;
         vv::NHDevState* nh = nullptr;
         unsigned long long* epoch = nullptr;
-        int parity = 0;
-        uint32_t random_pos = 0;
-        bool fextra_dirty = false, fextra_virtual = false;
+        Cursor cur;                               // the host's cursor at the snapshot
         struct Run { int kind, nsteps, spg; const void* site; double kt, kd; };
         std::vector<Run> runs;
         long long recoveries = 0;
-        long long step_count = 0;                 // the series' schedule: the step counter and the device-side row cursor
-        unsigned long long* series_cursor = nullptr;
+        unsigned long long* series_cursor = nullptr;   // the series' device-side row cursor (its schedule, the step counter, is in `cur`)
         bool series_saved = false;
         vv::CmmDevRecord* cmm_rec = nullptr;      // the counters of the scheduled removals of the centre-of-mass motion
         bool cmm_saved = false;
@@ -186,10 +190,8 @@ struct vvhip_plan {
     double* d_cosz = nullptr;      // per-lane cos(2 pi z / Lz) of the current step
     unsigned long long* d_acc = nullptr;   // [2 parities][NUM_ACC][ACC_SLOTS]
     vv::NHDevState* d_nh = nullptr;         // [2 parities]
-    int parity = 0;                         // which copy the next reduction/consumer pair uses
     unsigned long long* d_epoch = nullptr;  // refill counter of the device Gaussian generator
     uint64_t rng_seed = 0;
-    uint32_t random_pos = 0;                // prepareRandomNumbers cursor for the plan-driven loops (vvhip_run_*)
     // HIP-event timing (eager launches only)
     bool timing = false;
     bool timing_kernels_only = false;   // vvhip_timing_enable(plan, 2): dispatch timestamps of kernels A and B only, nothing added to the stream
@@ -254,10 +256,8 @@ struct vvhip_plan {
     double* d_rep_cross_mu = nullptr;
     long long* d_rep = nullptr;                   // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
     long long* h_rep = nullptr;                   // pinned: the result words as copied back
-    // Series (vvhip_series_*): full steps counted since vvhip_bind (the step entry points advance it, a capture walks it through the
-    // graph's steps and puts it back, a replay advances it by the graph's length), and the rows the steps append on the device
-    long long step_count = 0;
     long long graph_captures = 0;
+    // Series (vvhip_series_*): the rows the steps append on the device, scheduled by cur.step_count
     struct Series {
         bool on = false;
         int interval = 0, capacity = 0, mask = 0;
@@ -393,7 +393,7 @@ void fill_scales(vvhip_plan* p) {
     }
     p->acc_scale[3] = pick_scale(40.0 / in.inv_mass_total, 4.0);  // |sum m vx 2cos| <= 2 M |v|max, |v|max ~ 20 nm/ps
     p->acc_inv_scale[3] = 1.0 / p->acc_scale[3];
-    // moments of the cos perturbation (A_KE_MOM): Sbb = sum m b^2 <= M (|cos| <= 1, |b| <= 2), |Sab| <= sqrt(Saa Sbb)
+    // moments of the cos perturbation (ThermoMode::COS_MOMENTS): Sbb = sum m b^2 <= M (|cos| <= 1, |b| <= 2), |Sab| <= sqrt(Saa Sbb)
     const double mass = 1.0 / in.inv_mass_total;
     for (int g = 0; g < 3; g++) {
         p->acc_scale[4 + g] = pick_scale(std::sqrt(total * 1024.0 * 4.0 * mass), 4.0);
@@ -493,10 +493,10 @@ vv::KArgs make_args(vvhip_plan* p, uint32_t flags, uint32_t random_index) {
     a.big_scale = p->hp.big_scale;
     a.big_inv_scale = 1.0 / p->hp.big_scale;
     a.random = (const float4*) p->buf.random;
-    a.acc = p->d_acc + p->parity * acc_stride(p);
-    a.acc_next = p->d_acc + (p->parity ^ 1) * acc_stride(p);
-    a.nh = p->d_nh + p->parity;
-    a.nh_next = p->d_nh + (p->parity ^ 1);
+    a.acc = p->d_acc + p->cur.parity * acc_stride(p);
+    a.acc_next = p->d_acc + (p->cur.parity ^ 1) * acc_stride(p);
+    a.nh = p->d_nh + p->cur.parity;
+    a.nh_next = p->d_nh + (p->cur.parity ^ 1);
     a.chain = make_chain(p, 0);
     a.lane_const = p->d_lane_const;
     a.mb.local = p->mb_local;
@@ -687,55 +687,65 @@ int run_b(vvhip_plan* p, uint32_t flags) {
     int route = vv::ROUTE_COMPILED;
     HIP_TRY(p, vv::launch_b(p->hp.precision, make_args(p, flags, 0), p->block_threads, shared_device_cap(p, p->grid_cap_b), p->stream, t.e0, t.e1, &route));
     if (route == vv::ROUTE_GENERIC) note_generic_launch(p, 1, flags);
-    if (flags & vv::B_CHAIN) p->parity ^= 1;     // the advanced thermostat state now lives in the other copy
+    if (flags & vv::B_CHAIN) p->cur.parity ^= 1;     // the advanced thermostat state now lives in the other copy
     return VVHIP_OK;
 }
 int run_chain(vvhip_plan* p, uint32_t flags) {
     TRY(settle_recovery(p));
     debug_stall(p);
     ScopedTimer t(p, T_OTHER);
-    HIP_TRY(p, vv::launch_chain(make_chain(p, flags), p->d_nh + p->parity, p->d_acc + p->parity * acc_stride(p), p->stream));
+    HIP_TRY(p, vv::launch_chain(make_chain(p, flags), p->d_nh + p->cur.parity, p->d_acc + p->cur.parity * acc_stride(p), p->stream));
     return VVHIP_OK;
 }
 
-// cos perturbation in two launches instead of three: kernel A accumulates the group sums as moments of the biased velocities next
-// to the bias moment itself, kernel B's inline chain finishes the algebra (vv_args.hpp: A_KE_MOM).  Not with molecules larger
-// than a wave or the stand-alone chain launch (long chains, very large systems), which keep the bias -> KE -> scale sequence.
-bool use_moments(const vvhip_plan* p) {
-    return p->hp.params.cos_acceleration != 0 && p->hp.has_nh && p->hp.num_big == 0 && p->hp.params.num_nh_chains <= 4 &&
-           p->hp.info.num_waves < p->split_chain_waves && !p->no_moments;
+bool cos_on(const vvhip_plan* p) { return p->hp.params.cos_acceleration != 0; }
+// How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
+// stands; thermo_mode is the one place that derives it.
+// COS_MOMENTS = the cos perturbation in two launches instead of three: kernel A accumulates the group sums as moments of the biased
+// velocities next to the bias moment itself, kernel B's inline chain finishes the algebra (vv_args.hpp: the moment bits).  Not with
+// molecules larger than a wave or the stand-alone chain launch (long chains, very large systems), which keep the bias -> KE -> scale
+// sequence of COS_THREE_LAUNCH (API:252-259).
+enum class ThermoMode { NO_NH, PLAIN, COS_MOMENTS, COS_THREE_LAUNCH };
+ThermoMode thermo_mode(const vvhip_plan* p) {
+    if (!p->hp.has_nh) return ThermoMode::NO_NH;           // API:251: no NH particles, nothing to reduce
+    if (!cos_on(p)) return ThermoMode::PLAIN;
+    const bool moments = p->hp.num_big == 0 && p->hp.params.num_nh_chains <= 4 && p->hp.info.num_waves < p->split_chain_waves && !p->no_moments;
+    return moments ? ThermoMode::COS_MOMENTS : ThermoMode::COS_THREE_LAUNCH;
 }
 // The mailbox carries the totals between the ranks' kernel-B heads (inline chain): the three kinetic-energy sums, and with the cos
 // perturbation in its moment form also the bias moment and the six group moments -- everything kernel A produced, one exchange per
 // thermostat application.  The three-launch cos sequence (its bias moment is consumed by another kernel A) and the stand-alone
 // chain kernel still go through the collective.
 bool use_mailbox(const vvhip_plan* p) {
-    return p->mb_on && p->hp.params.num_nh_chains <= 4 && (p->hp.params.cos_acceleration == 0 || use_moments(p));
+    return p->mb_on && p->hp.params.num_nh_chains <= 4 && (!cos_on(p) || thermo_mode(p) == ThermoMode::COS_MOMENTS);
 }
 
-// The launch(es) that end in the per-group kinetic energies.  `first` = stage bits that must run before the KE on the
-// same launch if possible (kick, extra forces).  Molecules larger than a wave need their COM summed across waves
-// first (A_COMPART, its own launch after a memset of the small accumulator), so there the stages are split.
-int run_ke(vvhip_plan* p, uint32_t first, uint32_t random_index, bool unbias) {
-    const uint32_t ub = unbias ? (vv::A_UNBIAS_ACC | vv::A_CZ_LOAD) : 0;    // the bias launch of this step cached cos(kz)
-    if (p->hp.num_big == 0) {
-        if (unbias && first) { int rc = run_a(p, first, random_index); if (rc != VVHIP_OK) return rc; first = 0; }
-        return run_a(p, first | vv::A_KE | ub, random_index);
-    }
-    if (first) { int rc = run_a(p, first, random_index); if (rc != VVHIP_OK) return rc; }
+// The launch(es) that end in the per-group kinetic energies: `flags` = A_KE, the unbias bits in front of it (the three-launch cos
+// sequence) and the stage bits that run before the KE on the same launch if possible (kick, extra forces).  Molecules larger than a
+// wave need their COM summed across waves first (A_COMPART, its own launch after a memset of the small accumulator), so there the
+// stages are split.
+int run_ke(vvhip_plan* p, uint32_t flags, uint32_t random_index) {
+    if (p->hp.num_big == 0) return run_a(p, flags, random_index);
+    const uint32_t ub = flags & (vv::A_UNBIAS_ACC | vv::A_CZ_LOAD), first = flags & ~(vv::A_KE | ub);
+    if (first) TRY(run_a(p, first, random_index));
     HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
-    int rc = run_a(p, vv::A_COMPART | ub, 0);
-    return rc != VVHIP_OK ? rc : run_a(p, vv::A_KE | ub, 0);
+    TRY(run_a(p, vv::A_COMPART | ub, 0));
+    return run_a(p, vv::A_KE | ub, 0);
 }
 
 // Scaling kernel with the chain in its head (chain length <= 4), or the stand-alone chain launch in front of it.
-int run_chain_and_b(vvhip_plan* p, uint32_t bflags, bool with_bias) {
+// chain_in_b: the bits kernel B takes when the chain runs in its head, 0 when it runs as its own launch.
+uint32_t chain_in_b(const vvhip_plan* p) {
     // Large systems: the chain registers cost kernel B half its occupancy (140 vs 74 VGPRs), which matters once the kernel is
     // bandwidth bound; there the chain runs as its own one-wave launch and B only reads the scale factors.
     const bool split = p->hp.info.num_waves >= p->split_chain_waves && !use_mailbox(p);
-    if (p->hp.params.num_nh_chains <= 4 && !split) return run_b(p, vv::B_CHAIN | bflags | (use_mailbox(p) ? vv::B_MAILBOX : 0));
-    int rc = run_chain(p, vv::C_CHAIN | (with_bias ? vv::C_BIAS : 0));
-    return rc != VVHIP_OK ? rc : run_b(p, bflags);
+    if (p->hp.params.num_nh_chains > 4 || split) return 0;
+    return vv::B_CHAIN | (use_mailbox(p) ? vv::B_MAILBOX : 0u);
+}
+int run_chain_and_b(vvhip_plan* p, uint32_t bflags, bool with_bias) {
+    const uint32_t chain = chain_in_b(p);
+    if (!chain) TRY(run_chain(p, vv::C_CHAIN | (with_bias ? vv::C_BIAS : 0)));
+    return run_b(p, chain | bflags);
 }
 
 // ---- the one-launch step (vv_device.inc: "fused step")
@@ -762,30 +772,31 @@ bool fused_state_ok(const vvhip_plan* p) {
     if (hp.per.enabled && p->periodic_kernels) return false;                      // the arithmetic layout belongs to the many-pass regime
     return fused_shape_ok(p);
 }
+void forget_fused_checks(vvhip_plan* p) {      // what the lookups found no longer holds (who shares the device, the "fused" hook)
+    for (vvhip_plan::FusedCheck& c : p->fused_checks) c.b = 0;
+    p->fused_last = -1;
+}
 int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_index, bool* taken) {
     *taken = false;
     if (!fused_state_ok(p)) return VVHIP_OK;
     bflags |= vv::B_CHAIN | vv::B_MTAB | (use_mailbox(p) ? vv::B_MAILBOX : 0u);
-    // kernel and occupancy of this pair of stage sets on this launch shape: looked up once
-    if (p->fused_checked_a != aflags || p->fused_checked_b != bflags || p->fused_checked_threads != p->block_threads || p->fused_checked_waves != p->hp.info.num_waves) {
-        for (const vvhip_plan::FusedCheck& c : p->fused_checks)
-            if (c.b != 0 && c.a == aflags && c.b == bflags && c.threads == p->block_threads && c.waves == p->hp.info.num_waves) {
-                p->fused_checked_a = aflags; p->fused_checked_b = bflags; p->fused_checked_threads = c.threads; p->fused_checked_waves = c.waves; p->fused_ok = c.ok;
-            }
+    // kernel and occupancy of this pair of stage sets on this launch shape: looked up once (an entry with b = 0 is empty: bflags never is)
+    p->fused_last = -1;
+    for (int i = 0; i < 4 && p->fused_last < 0; i++) {
+        const vvhip_plan::FusedCheck& c = p->fused_checks[i];
+        if (c.a == aflags && c.b == bflags && c.threads == p->block_threads && c.waves == p->hp.info.num_waves) p->fused_last = i;
     }
-    if (p->fused_checked_a != aflags || p->fused_checked_b != bflags || p->fused_checked_threads != p->block_threads || p->fused_checked_waves != p->hp.info.num_waves) {
-        p->fused_checked_a = aflags; p->fused_checked_b = bflags; p->fused_checked_threads = p->block_threads; p->fused_checked_waves = p->hp.info.num_waves;
+    if (p->fused_last < 0) {
+        p->fused_last = p->fused_check_next++ & 3;
         vv::KArgs q = make_args(p, bflags, random_index);
         q.flags_a = aflags;
         int per_cu = 0;
         const hipError_t e = vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv, p->stream, nullptr, nullptr, nullptr, &per_cu);      // (asks only; launches nothing)
         const int tiles = p->block_threads / 64, blocks = (p->hp.info.num_waves + tiles - 1) / tiles;
-        p->fused_ok = e == hipSuccess && per_cu >= 1 && (long) per_cu * p->num_cus >= blocks;
         if (e != hipSuccess) (void) hipGetLastError();
-        vvhip_plan::FusedCheck& c = p->fused_checks[p->fused_check_next++ & 3];
-        c.a = aflags; c.b = bflags; c.threads = p->block_threads; c.waves = p->hp.info.num_waves; c.ok = p->fused_ok;
+        p->fused_checks[p->fused_last] = {aflags, bflags, p->block_threads, p->hp.info.num_waves, e == hipSuccess && per_cu >= 1 && (long) per_cu * p->num_cus >= blocks};
     }
-    if (!p->fused_ok) return VVHIP_OK;
+    if (!p->fused_checks[p->fused_last].ok) return VVHIP_OK;
     TRY(settle_recovery(p));
     if (!p->fused) return VVHIP_OK;      // (settling may have pinned the plan to two launches)
     TRY(ensure_mass_table(p));
@@ -796,11 +807,11 @@ int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_i
     q.flags_a = aflags;
     q.fused_poll_delay = p->fused_poll_delay;
     // the "a block polled twice" words of this step and of the one before (by thermostat parity), behind the two copies of the rendezvous words
-    q.rv_late_cur = (unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * p->parity;
-    q.rv_late_prev = (const unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * (p->parity ^ 1);
+    q.rv_late_cur = (unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * p->cur.parity;
+    q.rv_late_prev = (const unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * (p->cur.parity ^ 1);
     q.fused_late_shift = p->fused_late_shift;
-    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv + p->parity * kRvCopy, p->stream, t.e0, t.e1, &route, nullptr));
-    p->parity ^= 1;            // the advanced thermostat state now lives in the other copy
+    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv + p->cur.parity * kRvCopy, p->stream, t.e0, t.e1, &route, nullptr));
+    p->cur.parity ^= 1;            // the advanced thermostat state now lives in the other copy
     p->fused_launches++;
     *taken = true;
     return VVHIP_OK;
@@ -813,14 +824,18 @@ uint32_t extra_flags(const vvhip_plan* p) {
     if (p->hp.params.cos_acceleration != 0) f |= vv::A_COS;
     return f;
 }
-uint32_t tail_flags(const vvhip_plan* p) {      // what follows every position update (HOST:203-212, API:266-268)
+// No source of extra forces in a step: its kick adds whatever forceExtra still holds (see Cursor::fextra_virtual)
+uint32_t stale_fextra(const vvhip_plan* p) { return (p->cur.fextra_dirty || p->fextra_external) ? vv::A_FE_LOAD : 0u; }
+// What follows a position update on the split path: the hard wall, and the sites described to the plan (they follow EVERY position
+// update, HOST:203-214) ...
+uint32_t after_positions(const vvhip_plan* p) {
     uint32_t f = 0;
     if (p->hp.params.max_drude_distance > 0 && p->hp.has_pairs) f |= vv::B_HARDWALL;
-    if (p->hp.has_images) f |= vv::B_IMAGE;
     if (!p->hp.slot_vsite.empty()) f |= vv::B_VSITE;
     return f;
 }
-bool cos_on(const vvhip_plan* p) { return p->hp.params.cos_acceleration != 0; }
+// ... and in a whole step the image particles as well (HOST:203-212, API:266-268)
+uint32_t tail_flags(const vvhip_plan* p) { return after_positions(p) | (p->hp.has_images ? vv::B_IMAGE : 0u); }
 bool shake_on(const vvhip_plan* p) { return !p->hp.slot_shake.empty(); }
 // stage bits of the in-kernel constraints the plan holds: hydrogen-type clusters and / or rigid three-site molecules
 uint32_t cons_a(const vvhip_plan* p) { return (p->hp.info.num_shake_clusters > 0 ? vv::A_SHAKE_V : 0u) | (p->hp.info.num_settle_clusters > 0 ? vv::A_SETTLE : 0u) | (p->hp.info.num_general_constraints > 0 ? vv::A_GCONS : 0u); }
@@ -884,7 +899,7 @@ int vvhip_debug_tune(vvhip_plan* p, const char* key, int value) {
     else if (k == "gc_omega_permille") p->hp.gc_omega = value / 1000.0;     // relaxation factor of the general clusters' sweeps (rate scans)
     else if (k == "rekick") p->rekick = value != 0;                         // 0: kernel A stores the kicked velocities, kernel B does not repeat the kick
     else if (k == "no_moments") p->no_moments = value != 0;                 // 1: cos perturbation as three launches (bias, sums, scale)
-    else if (k == "fused") { p->fused = value != 0; p->fused_checked_b = 0; for (vvhip_plan::FusedCheck& c : p->fused_checks) c.b = 0; }
+    else if (k == "fused") { p->fused = value != 0; forget_fused_checks(p); }
     else if (k == "recover") { p->rec.enabled = value != 0; p->rec.valid = false; p->rec.runs.clear(); }      // 0: a missed rendezvous stays fatal (VVHIP_ERR_RENDEZVOUS)
     else if (k == "recover_min_steps") p->rec.min_steps = std::max(1, value);
     else if (k == "fused_late_shift") p->fused_late_shift = std::max(0, std::min(value, 16));
@@ -1100,13 +1115,13 @@ int vvhip_set_params(vvhip_plan* p, const vvhip_params* q) {
     if ((q->cos_acceleration != 0) && p->hp.has_ld)
         return fail(p, VVHIP_ERR_TOPOLOGY, "Langevin thermostat and periodic perturbation shouldn't be used together");
     const bool cos_switch = (p->hp.params.cos_acceleration != 0) != (n.cos_acceleration != 0);
-    if (cos_switch && n.cos_acceleration == 0 && p->bound && p->fextra_virtual && !p->hp.has_ld && !p->hp.has_ef) {
+    if (cos_switch && n.cos_acceleration == 0 && p->bound && p->cur.fextra_virtual && !p->hp.has_ld && !p->hp.has_ef) {
         // forceExtra as the reference would have left it: the cos force of the last step, with the old acceleration (still in hp.params)
         // and the cos(kz) that step cached (K/cosineAccelerate.cu:9)
         TRY(run_a(p, vv::A_COS | vv::A_CZ_LOAD | vv::A_FE_STORE, 0));
-        p->fextra_dirty = true;
+        p->cur.fextra_dirty = true;
     }
-    if (cos_switch) p->fextra_virtual = false;
+    if (cos_switch) p->cur.fextra_virtual = false;
     p->hp.params = n;
     if (cos_switch && !p->launch_shape_forced) pick_launch_shape(p);      // (the cos stage sets of kernel B need more registers: another limit)
     drop_graphs(p);
@@ -1136,7 +1151,7 @@ int vvhip_get_nh_state(vvhip_plan* p, vvhip_nh_state* out) {
     NEED_BOUND(p);
     TRY(settle_recovery(p));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(out, &p->d_nh[p->parity].s, sizeof(*out), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(out, &p->d_nh[p->cur.parity].s, sizeof(*out), hipMemcpyDeviceToHost));
     return VVHIP_OK;
 }
 int vvhip_set_nh_state(vvhip_plan* p, const vvhip_nh_state* in) {
@@ -1146,15 +1161,15 @@ int vvhip_set_nh_state(vvhip_plan* p, const vvhip_nh_state* in) {
     vvhip_nh_state st = *in;
     for (int g = 0; g < VVHIP_NUM_TG; g++)            // the chain's closing element is 0 by construction (API:340-376 never writes it)
         for (int i = std::max(0, std::min(p->hp.params.num_nh_chains, VVHIP_MAX_CHAINS)); i <= VVHIP_MAX_CHAINS; i++) st.eta_dot[g][i] = 0.0;
-    HIP_TRY(p, hipMemcpy(&p->d_nh[p->parity].s, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(&p->d_nh[p->cur.parity].s, &st, sizeof(st), hipMemcpyHostToDevice));
     return VVHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------ fused path
 int vvhip_step_middle_phases(const vvhip_plan* p) {
     if (!p) return VVHIP_ERR_INVALID;
-    if (!p->hp.has_nh) return 1;
-    return (cos_on(p) && !use_moments(p)) ? 3 : 2;
+    const ThermoMode mode = thermo_mode(p);
+    return mode == ThermoMode::NO_NH ? 1 : mode == ThermoMode::COS_THREE_LAUNCH ? 3 : 2;
 }
 
 // The fused middle step without a velm round trip between its kernels: kernel A keeps the kicked velocities in registers, kernel B
@@ -1164,8 +1179,8 @@ int vvhip_step_middle_phases(const vvhip_plan* p) {
 // (test hook "rekick" = 0 switches it off: comparison runs).
 static bool use_rekick(const vvhip_plan* p) {
     const uint32_t ex = extra_flags(p);
-    const bool extra_ok = ex == 0 || (ex == vv::A_COS && use_moments(p));
-    const bool stale_extra = ex == 0 && (p->fextra_dirty || p->fextra_external);      // the kick must add what forceExtra holds
+    const bool extra_ok = ex == 0 || (ex == vv::A_COS && thermo_mode(p) == ThermoMode::COS_MOMENTS);
+    const bool stale_extra = ex == 0 && stale_fextra(p) != 0;      // the kick must add what forceExtra holds
     return p->rekick && p->hp.has_nh && extra_ok && !stale_extra && !shake_on(p) && p->hp.num_big == 0;
 }
 
@@ -1182,8 +1197,8 @@ static bool use_rekick(const vvhip_plan* p) {
 // Does vvhip_step_middle take the one-launch step for this plan as it stands?  (The kernel itself is looked up at the first step; a pair
 // of stage sets already found wanting says so here.)
 static bool fused_active(const vvhip_plan* p) {
-    if (!p->bound || !p->hp.params.use_middle_scheme || !p->hp.info.constraints_fused || !fused_state_ok(p) || (cos_on(p) && !use_moments(p))) return false;
-    return !(p->fused_checked_b != 0 && !p->fused_ok);
+    if (!p->bound || !p->hp.params.use_middle_scheme || !p->hp.info.constraints_fused || !fused_state_ok(p) || thermo_mode(p) == ThermoMode::COS_THREE_LAUNCH) return false;
+    return p->fused_last < 0 || p->fused_checks[p->fused_last].ok;
 }
 
 int vvhip_algorithmic_bytes(const vvhip_plan* p, int32_t* bytes_a, int32_t* bytes_b) {
@@ -1207,7 +1222,7 @@ int vvhip_algorithmic_bytes(const vvhip_plan* p, int32_t* bytes_a, int32_t* byte
     const int ia = per_a ? 0 : 6, ib = per_b ? 0 : 6;
     if (use_rekick(p)) { *bytes_a = v + 24 + ia; *bytes_b = v + 24 + x + v + x + ib; }    // A: R velm, R force;  B: R velm, R force, R pos, W velm, W pos
     else { *bytes_a = v + 24 + v + ia; *bytes_b = v + x + v + x + ib; }                   // A: R velm, R force, W velm;  B: R velm, R pos, W velm, W pos
-    if (cos_on(p)) { *bytes_a += xr; if (use_moments(p)) { *bytes_a += 8; *bytes_b += 8; } }
+    if (cos_on(p)) { *bytes_a += xr; if (thermo_mode(p) == ThermoMode::COS_MOMENTS) { *bytes_a += 8; *bytes_b += 8; } }
     if (shake_on(p)) {
         long members = 0;
         for (size_t i = 0; i < p->hp.slots.size() / 2; i++)
@@ -1221,73 +1236,13 @@ int vvhip_algorithmic_bytes(const vvhip_plan* p, int32_t* bytes_a, int32_t* byte
     return VVHIP_OK;
 }
 
-// The stage sets of the one-launch step: phase 0's kick + sums and phase 1's scaling + drift of vvhip_step_middle_phase, without the
-// hand-over bits between them (A_NOSTORE / B_KICK, the cos(kz) cache load).
-static int step_middle_fused(vvhip_plan* p, uint32_t random_index, bool* taken) {
-    *taken = false;
-    if (!p->hp.params.use_middle_scheme || !p->hp.info.constraints_fused || !fused_state_ok(p)) return VVHIP_OK;
-    const uint32_t stale = (extra_flags(p) == 0 && (p->fextra_dirty || p->fextra_external)) ? vv::A_FE_LOAD : 0u;
-    uint32_t fa = vv::A_KICK_FULL | extra_flags(p) | stale | cons_a(p) | vv::A_KE;
-    uint32_t fb = vv::B_SCALE | vv::B_DRIFT_MIDDLE | tail_flags(p) | cons_b(p);
-    if (cos_on(p)) {
-        if (!use_moments(p)) return VVHIP_OK;
-        fa |= vv::A_BIAS | vv::A_CZ_STORE | vv::A_KE_MOM;
-        fb |= vv::B_UNBIAS | vv::B_KE_MOM;
-    }
-    TRY(run_fused(p, fa, fb, random_index, taken));
-    if (*taken && cos_on(p) && !p->hp.has_ld && !p->hp.has_ef) p->fextra_virtual = true;      // as phase 0 of the two-launch step
-    return VVHIP_OK;
-}
-
-static int middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
-    NEED_BOUND(p);
-    NEED_FUSABLE(p);
-    const bool rk = use_rekick(p);
-    // no source of extra forces in this step: the kick adds whatever forceExtra still holds (see fextra_virtual); with sources the
-    // forces are formed on the fly and the array is out of date from here on
-    const uint32_t stale = (extra_flags(p) == 0 && (p->fextra_dirty || p->fextra_external)) ? vv::A_FE_LOAD : 0u;
-    if (phase == 0 && cos_on(p) && !p->hp.has_ld && !p->hp.has_ef) p->fextra_virtual = true;
-    const uint32_t kick = vv::A_KICK_FULL | extra_flags(p) | stale | cons_a(p) | (rk ? vv::A_NOSTORE : 0);
-    const uint32_t drift = vv::B_DRIFT_MIDDLE | tail_flags(p) | cons_b(p) | (rk ? vv::B_KICK : 0);
-    if (!p->hp.has_nh) {                                   // API:251: no NH particles, nothing to reduce
-        if (phase != 0) return fail(p, VVHIP_ERR_INVALID, "phase out of range");
-        // (with the cos perturbation the kick caches cos(kz) here too: vvhip_set_params rebuilds the stale forceExtra from it)
-        TRY(run_a(p, kick | (cos_on(p) ? vv::A_CZ_STORE : 0u), random_index));
-        return run_b(p, drift);
-    }
-    if (!cos_on(p)) {
-        if (phase == 0) return run_ke(p, kick, random_index, false);
-        if (phase == 1) return run_chain_and_b(p, vv::B_SCALE | drift, false);
-    } else if (use_moments(p)) {                           // bias moment and group moments in one launch
-        // (the per-lane cos(kz) travels from kernel A to kernel B: letting kernel B evaluate its own -- no 8-byte store / load per lane, ~45
-        // more instructions per wave in B -- measured 74.5 k against 74.9 k steps/s at C4, profiles/r04b_ab_C4_cos_variants.txt)
-        if (phase == 0) return run_a(p, kick | vv::A_BIAS | vv::A_CZ_STORE | vv::A_KE | vv::A_KE_MOM, random_index);
-        if (phase == 1) return run_chain_and_b(p, vv::B_SCALE | vv::B_UNBIAS | vv::B_CZ_LOAD | vv::B_KE_MOM | drift, true);
-    } else {                                               // API:252-259: bias -> remove -> scale -> restore
-        if (phase == 0) return run_a(p, kick | vv::A_BIAS | vv::A_CZ_STORE, random_index);
-        if (phase == 1) return run_ke(p, 0, 0, true);
-        if (phase == 2) return run_chain_and_b(p, vv::B_SCALE | vv::B_UNBIAS | vv::B_CZ_LOAD | drift, true);
-    }
-    return fail(p, VVHIP_ERR_INVALID, "phase out of range");
-}
-// (the last phase completes the step: it is counted, and takes its series row)
-int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
-    if (phase == 0) {                                     // (the step begins: what middle_phase would refuse is refused before anything is enqueued)
-        NEED_BOUND(p);
-        NEED_FUSABLE(p);
-        TRY(step_begin(p));
-    }
-    TRY(middle_phase(p, phase, random_index));
-    return phase == vvhip_step_middle_phases(p) - 1 ? step_done(p) : VVHIP_OK;
-}
-
 int vvhip_accumulators(vvhip_plan* p, int phase, void** device_ptr, int32_t* count) {
     NEED_BOUND(p);
     if (!device_ptr || !count) return VVHIP_ERR_INVALID;
-    unsigned long long* cur = p->d_acc + p->parity * acc_stride(p);
-    if (use_moments(p)) { *device_ptr = cur; *count = vv::NUM_ACC * vv::ACC_SLOTS; }                  // everything kernel A produced
-    else if (cos_on(p) && phase == 0) { *device_ptr = cur + 3 * vv::ACC_SLOTS; *count = vv::ACC_SLOTS; }   // bias moment slots only
-    else { *device_ptr = cur; *count = 3 * vv::ACC_SLOTS; }                                          // the three 2KE sums
+    unsigned long long* acc = p->d_acc + p->cur.parity * acc_stride(p);
+    if (thermo_mode(p) == ThermoMode::COS_MOMENTS) { *device_ptr = acc; *count = vv::NUM_ACC * vv::ACC_SLOTS; }   // everything kernel A produced
+    else if (cos_on(p) && phase == 0) { *device_ptr = acc + 3 * vv::ACC_SLOTS; *count = vv::ACC_SLOTS; }        // bias moment slots only
+    else { *device_ptr = acc; *count = 3 * vv::ACC_SLOTS; }                                                   // the three 2KE sums
     return VVHIP_OK;
 }
 
@@ -1306,58 +1261,115 @@ static int exchange_accumulators(vvhip_plan* p, int phase) {
     return VVHIP_OK;
 }
 
-static int step_middle(vvhip_plan* p, uint32_t random_index) {
-    if (!p->hp.params.use_middle_scheme) return fail(p, VVHIP_ERR_INVALID, "plan was created for the classic scheme");
-    {   // one launch where the plan allows it (bit for bit the two launches below)
-        bool taken = false;
-        TRY(step_middle_fused(p, random_index, &taken));
-        if (taken) return VVHIP_OK;
+// ---- A thermostat application with the stages that ride on it, as data: what every step entry point launches, and what
+// vvhip_debug_fused_flags reports.  Phase k < phases - 1 is a launch of kernel A (through run_ke where it ends in the sums: molecules
+// larger than a wave split it), the last phase the chain and kernel B (run_chain_and_b), with the ranks' exchange between the phases;
+// without Nose-Hoover particles the one phase is kernel A, then kernel B, whichever has stages.
+struct ThermoApp {
+    ThermoMode mode = ThermoMode::NO_NH;
+    int phases = 1;
+    struct Launch { uint32_t flags = 0; bool sums = false; } a[2];
+    uint32_t b = 0;
+    bool with_bias = false;                     // the stand-alone chain launch also finishes the bias moment
+    bool one_launch = false;                    // (fused_a, fused_b) can be one launch (run_fused): the same sets without the hand-over bits
+    uint32_t fused_a = 0, fused_b = 0;
+    bool fe_virtual = false;                    // kernel A forms the cos force on the fly, and nothing else: see Cursor::fextra_virtual
+};
+// `a_first` rides in front of the sums (kick, extra forces, velocity constraints), `b_extra` behind the scaling (drift, hard wall, sites,
+// images, position constraints, the classic half kick).  `elide` = the kicked velocities need not travel from kernel A to kernel B
+// through velm: B repeats the kick (use_rekick).
+static ThermoApp compose_application(ThermoMode mode, uint32_t a_first, uint32_t b_extra, bool elide) {
+    ThermoApp t;
+    t.mode = mode;
+    t.fe_virtual = (a_first & (vv::A_COS | vv::A_LD | vv::A_EF | vv::A_FE_STORE)) == vv::A_COS;
+    t.a[0].flags = a_first;
+    t.b = b_extra;
+    if (mode == ThermoMode::NO_NH) return t;
+    const bool cos = mode != ThermoMode::PLAIN;
+    uint32_t front = a_first, back = vv::B_SCALE | b_extra;      // kernel A in front of the sums; kernel B from the scale factors on
+    if (cos) { front |= vv::A_BIAS | vv::A_CZ_STORE; back |= vv::B_UNBIAS; }
+    // (the per-lane cos(kz) travels from kernel A to kernel B: letting kernel B evaluate its own -- no 8-byte store / load per lane, ~45
+    // more instructions per wave in B -- measured 74.5 k against 74.9 k steps/s at C4, profiles/r04b_ab_C4_cos_variants.txt)
+    if (mode == ThermoMode::COS_MOMENTS) { front |= vv::A_KE_MOM; back |= vv::B_KE_MOM; }      // bias moment and group moments in one launch
+    // the hand-over between the launches: the kick through velm or repeated, the cos(kz) cache
+    const uint32_t hand_a = elide ? vv::A_NOSTORE : 0u, hand_b = (elide ? vv::B_KICK : 0u) | (cos ? vv::B_CZ_LOAD : 0u);
+    t.b = back | hand_b;
+    t.with_bias = cos;
+    if (mode == ThermoMode::COS_THREE_LAUNCH) {      // API:252-259: bias -> remove -> scale -> restore; the sums wait for the bias moment's exchange
+        t.phases = 3;
+        t.a[0] = {front | hand_a, false};
+        t.a[1] = {vv::A_KE | vv::A_UNBIAS_ACC | vv::A_CZ_LOAD, true};      // (the bias launch of this step cached cos(kz))
+        return t;
     }
-    const int n = vvhip_step_middle_phases(p);
-    for (int ph = 0; ph < n; ph++) {
-        TRY(middle_phase(p, ph, random_index));
-        if (ph < n - 1) TRY(exchange_accumulators(p, ph));
+    t.phases = 2;
+    t.a[0] = {front | vv::A_KE | hand_a, true};
+    t.one_launch = true;
+    t.fused_a = front | vv::A_KE;
+    t.fused_b = back;
+    return t;
+}
+
+static int run_application_phase(vvhip_plan* p, const ThermoApp& t, int phase, uint32_t random_index) {
+    if (phase < 0 || phase >= t.phases) return fail(p, VVHIP_ERR_INVALID, "phase out of range");
+    if (phase == 0 && t.fe_virtual) p->cur.fextra_virtual = true;
+    if (t.mode == ThermoMode::NO_NH) {
+        if (t.a[0].flags) TRY(run_a(p, t.a[0].flags, random_index));
+        return t.b ? run_b(p, t.b) : VVHIP_OK;
+    }
+    if (phase == t.phases - 1) return run_chain_and_b(p, t.b, t.with_bias);
+    const uint32_t ri = phase == 0 ? random_index : 0;
+    return t.a[phase].sums ? run_ke(p, t.a[phase].flags, ri) : run_a(p, t.a[phase].flags, ri);
+}
+// One launch where the application and the plan allow it (bit for bit the phases)
+static int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_index, bool* taken) {
+    *taken = false;
+    if (!t.one_launch) return VVHIP_OK;
+    TRY(run_fused(p, t.fused_a, t.fused_b, random_index, taken));
+    if (*taken && t.fe_virtual) p->cur.fextra_virtual = true;      // as phase 0 of the launches
+    return VVHIP_OK;
+}
+static int run_application(vvhip_plan* p, const ThermoApp& t, uint32_t random_index, bool exchange = true) {
+    bool taken = false;
+    TRY(run_application_fused(p, t, random_index, &taken));
+    if (taken) return VVHIP_OK;
+    for (int ph = 0; ph < t.phases; ph++) {
+        TRY(run_application_phase(p, t, ph, random_index));
+        if (exchange && ph < t.phases - 1) TRY(exchange_accumulators(p, ph));
     }
     return VVHIP_OK;
+}
+
+// The middle scheme's step (API:237-268) is one application: the full kick in front of the sums, the drift behind the scaling.
+static ThermoApp middle_application(const vvhip_plan* p) {
+    const ThermoMode mode = thermo_mode(p);
+    // with sources of extra forces they are formed on the fly and the forceExtra array is out of date from here on
+    const uint32_t ex = extra_flags(p);
+    uint32_t kick = vv::A_KICK_FULL | (ex ? ex : stale_fextra(p)) | cons_a(p);
+    // (without NH particles the kick caches cos(kz) all the same: vvhip_set_params rebuilds the stale forceExtra from it)
+    if (mode == ThermoMode::NO_NH && cos_on(p)) kick |= vv::A_CZ_STORE;
+    return compose_application(mode, kick, vv::B_DRIFT_MIDDLE | tail_flags(p) | cons_b(p), use_rekick(p));
+}
+// (the last phase completes the step: it is counted, and takes its series row)
+int vvhip_step_middle_phase(vvhip_plan* p, int phase, uint32_t random_index) {
+    NEED_BOUND(p);
+    NEED_FUSABLE(p);
+    if (phase == 0) TRY(step_begin(p));
+    const ThermoApp t = middle_application(p);
+    TRY(run_application_phase(p, t, phase, random_index));
+    return phase == t.phases - 1 ? step_done(p) : VVHIP_OK;
 }
 int vvhip_step_middle(vvhip_plan* p, uint32_t random_index) {
     NEED_BOUND(p);
     if (!p->hp.params.use_middle_scheme) return fail(p, VVHIP_ERR_INVALID, "plan was created for the classic scheme");
     NEED_FUSABLE(p);
     TRY(step_begin(p));
-    TRY(step_middle(p, random_index));
+    TRY(run_application(p, middle_application(p), random_index));
     return step_done(p);
 }
 
 // NH half-step used by the classic scheme (API:295-304, 327-336); `b_extra` is fused into the scaling kernel.
 static int nh_half(vvhip_plan* p, uint32_t a_first, uint32_t random_index, uint32_t b_extra) {
-    if (!p->hp.has_nh) {
-        if (a_first) TRY(run_a(p, a_first, random_index));
-        if (b_extra) TRY(run_b(p, b_extra));
-        return VVHIP_OK;
-    }
-    // one launch per thermostat application where the plan allows it (as the middle scheme's step: sums, rendezvous, chain, scaling)
-    if (!cos_on(p) || use_moments(p)) {
-        bool taken = false;
-        if (!cos_on(p)) TRY(run_fused(p, a_first | vv::A_KE, vv::B_SCALE | b_extra, random_index, &taken));
-        else TRY(run_fused(p, a_first | vv::A_BIAS | vv::A_CZ_STORE | vv::A_KE | vv::A_KE_MOM, vv::B_SCALE | vv::B_UNBIAS | vv::B_KE_MOM | b_extra, random_index, &taken));
-        if (taken) return VVHIP_OK;
-    }
-    if (!cos_on(p)) {
-        TRY(run_ke(p, a_first, random_index, false));
-        TRY(exchange_accumulators(p, 0));
-        return run_chain_and_b(p, vv::B_SCALE | b_extra, false);
-    }
-    if (use_moments(p)) {
-        TRY(run_a(p, a_first | vv::A_BIAS | vv::A_CZ_STORE | vv::A_KE | vv::A_KE_MOM, random_index));
-        TRY(exchange_accumulators(p, 0));
-        return run_chain_and_b(p, vv::B_SCALE | vv::B_UNBIAS | vv::B_CZ_LOAD | vv::B_KE_MOM | b_extra, true);
-    }
-    TRY(run_a(p, a_first | vv::A_BIAS | vv::A_CZ_STORE, random_index));
-    TRY(exchange_accumulators(p, 0));
-    TRY(run_ke(p, 0, 0, true));
-    TRY(exchange_accumulators(p, 1));
-    return run_chain_and_b(p, vv::B_SCALE | vv::B_UNBIAS | vv::B_CZ_LOAD | b_extra, true);
+    return run_application(p, compose_application(thermo_mode(p), a_first, b_extra, false), random_index);
 }
 
 int vvhip_step_vv_first(vvhip_plan* p) {                   // API:295-310 (forces for the old positions are in `force`)
@@ -1370,8 +1382,8 @@ int vvhip_step_vv_first(vvhip_plan* p) {                   // API:295-310 (force
 int vvhip_step_vv_second(vvhip_plan* p, uint32_t random_index) {   // API:316-336 (forces for the new positions)
     NEED_BOUND(p);
     uint32_t ex = extra_flags(p);
-    if (ex) { ex |= vv::A_FE_STORE; p->fextra_dirty = true; }   // the first half of the NEXT step kicks with these (API:316-323)
-    else if (p->fextra_dirty || p->fextra_external) ex = vv::A_FE_LOAD;      // no source: the kick adds what the array still holds (see fextra_virtual)
+    if (ex) { ex |= vv::A_FE_STORE; p->cur.fextra_dirty = true; }   // the first half of the NEXT step kicks with these (API:316-323)
+    else ex = stale_fextra(p);
     NEED_FUSABLE(p);
     TRY(nh_half(p, vv::A_KICK_HALF | ex | cons_a(p), random_index, 0));
     return step_done(p);
@@ -1380,61 +1392,44 @@ int vvhip_step_vv_second(vvhip_plan* p, uint32_t random_index) {   // API:316-33
 // ------------------------------------------------------------------------------------------ kernel-interface level
 int vvhip_reset_extra_force(vvhip_plan* p) {               // K/middle.cu:227-231
     NEED_BOUND(p);
-    if (!p->fextra_dirty && !p->fextra_external) return VVHIP_OK;   // already zero (bind zeroes it; nothing has added to it since the last reset)
-    p->fextra_dirty = false;
+    if (!stale_fextra(p)) return VVHIP_OK;   // already zero (bind zeroes it; nothing has added to it since the last reset)
+    p->cur.fextra_dirty = false;
     ScopedTimer t(p, T_OTHER);
     const size_t nloc = (size_t) (p->hp.shard_end - p->hp.shard_begin);
     HIP_TRY(p, hipMemsetAsync(p->d_fextra, 0, nloc * 3 * sizeof_real(p->hp.precision), p->stream));
     return VVHIP_OK;
 }
-int vvhip_middle_kick(vvhip_plan* p) { NEED_BOUND(p); return run_a(p, ((p->fextra_dirty || p->fextra_external) ? vv::A_FE_LOAD : 0) | vv::A_KICK_FULL, 0); }
+int vvhip_middle_kick(vvhip_plan* p) { NEED_BOUND(p); return run_a(p, stale_fextra(p) | vv::A_KICK_FULL, 0); }
 int vvhip_middle_half_drift1(vvhip_plan* p) { NEED_BOUND(p); return run_a(p, vv::A_POS1, 0); }
 int vvhip_middle_half_drift2(vvhip_plan* p) { NEED_BOUND(p); return run_b(p, vv::B_POS2); }
-int vvhip_middle_finish(vvhip_plan* p) {
-    NEED_BOUND(p);
-    uint32_t f = vv::B_POS3;
-    if (p->hp.params.max_drude_distance > 0 && p->hp.has_pairs) f |= vv::B_HARDWALL;
-    if (!p->hp.slot_vsite.empty()) f |= vv::B_VSITE;      // sites described to the plan follow EVERY position update (HOST:203-214): also on the split path
-    return run_b(p, f);
-}
+int vvhip_middle_finish(vvhip_plan* p) { NEED_BOUND(p); return run_b(p, vv::B_POS3 | after_positions(p)); }
 int vvhip_vv_half_kick(vvhip_plan* p, int update_pos_delta) {
     NEED_BOUND(p);
-    return run_a(p, ((p->fextra_dirty || p->fextra_external) ? vv::A_FE_LOAD : 0) | vv::A_KICK_HALF | (update_pos_delta ? vv::A_POSDELTA_VV : 0), 0);
+    return run_a(p, stale_fextra(p) | vv::A_KICK_HALF | (update_pos_delta ? vv::A_POSDELTA_VV : 0), 0);
 }
-int vvhip_vv_positions(vvhip_plan* p) {
-    NEED_BOUND(p);
-    uint32_t f = vv::B_VV_POS;
-    if (p->hp.params.max_drude_distance > 0 && p->hp.has_pairs) f |= vv::B_HARDWALL;
-    if (!p->hp.slot_vsite.empty()) f |= vv::B_VSITE;      // (as vvhip_middle_finish)
-    return run_b(p, f);
-}
+int vvhip_vv_positions(vvhip_plan* p) { NEED_BOUND(p); return run_b(p, vv::B_VV_POS | after_positions(p)); }
 int vvhip_scale_velocity(vvhip_plan* p) {                  // HOST:670-754 without the download/upload
     NEED_BOUND(p);
     if (!p->hp.has_nh) return VVHIP_OK;
-    {
-        bool taken = false;
-        TRY(run_fused(p, vv::A_KE, vv::B_SCALE, 0, &taken));
-        if (taken) return VVHIP_OK;
-    }
-    TRY(run_ke(p, 0, 0, false));
-    return run_chain_and_b(p, vv::B_SCALE, false);
+    // (the reference's kernel: the plain application whatever the cos perturbation -- its host removes and restores the bias around it --, and no exchange between the ranks)
+    return run_application(p, compose_application(ThermoMode::PLAIN, 0, 0, false), 0, false);
 }
 int vvhip_apply_langevin_force(vvhip_plan* p, uint32_t random_index) {
     NEED_BOUND(p);
     if (!p->hp.has_ld) return VVHIP_OK;
-    p->fextra_dirty = true;
+    p->cur.fextra_dirty = true;
     return run_a(p, vv::A_FE_LOAD | vv::A_LD | vv::A_FE_STORE, random_index);
 }
 int vvhip_apply_electric_force(vvhip_plan* p) {
     NEED_BOUND(p);
     if (!p->hp.has_ef) return VVHIP_OK;
-    p->fextra_dirty = true;
+    p->cur.fextra_dirty = true;
     return run_a(p, vv::A_FE_LOAD | vv::A_EF | vv::A_FE_STORE, 0);
 }
 int vvhip_apply_cosine_force(vvhip_plan* p) {
     NEED_BOUND(p);
-    p->fextra_dirty = true;
-    p->fextra_virtual = false;      // the array holds this step's cos force itself
+    p->cur.fextra_dirty = true;
+    p->cur.fextra_virtual = false;      // the array holds this step's cos force itself
     return run_a(p, vv::A_FE_LOAD | vv::A_COS | vv::A_FE_STORE, 0);
 }
 int vvhip_calc_velocity_bias(vvhip_plan* p) {              // HOST:1061-1082
@@ -1448,7 +1443,7 @@ int vvhip_calc_viscosity(vvhip_plan* p, double* v_max, double* inv_vis) {   // H
     NEED_BOUND(p);
     double v = 0;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(&v, &p->d_nh[p->parity].s.v_bias, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(&v, &p->d_nh[p->cur.parity].s.v_bias, sizeof(double), hipMemcpyDeviceToHost));
     if (p->hp.precision == VVHIP_SINGLE) v = (double) (float) v;             // vMaxBuffer is `mixed`
     const double vol = p->box[0] * p->box[1] * p->box[2];
     if (v_max) *v_max = v;
@@ -1540,7 +1535,7 @@ static int series_row(vvhip_plan* p) {
         HIP_TRY(p, vv::launch_report(p->hp.precision, report_args(p, S.d_scratch), p->block_threads, p->grid_cap_a, p->stream));
         a.rep_out = S.d_scratch; a.rep_mol_p = S.d_scratch + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
     }
-    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh[p->parity].s;
+    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh[p->cur.parity].s;
     a.rows = S.d_rows; a.cursor = S.d_cursor; a.capacity = S.capacity;
     for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
     a.cos_acceleration = p->hp.params.cos_acceleration;
@@ -1549,8 +1544,8 @@ static int series_row(vvhip_plan* p) {
 }
 // A full step has been enqueued (or captured): count it, and append a row when it is due.
 static int step_done(vvhip_plan* p) {
-    p->step_count++;
-    if (p->series.on && p->step_count % p->series.interval == 0) return series_row(p);
+    p->cur.step_count++;
+    if (p->series.on && p->cur.step_count % p->series.interval == 0) return series_row(p);
     return VVHIP_OK;
 }
 
@@ -1581,7 +1576,7 @@ static int cmm_enqueue(vvhip_plan* p, int which) {
 // A full step is about to be enqueued (or captured): the removal in front of it when its index is due.  The one hook of every entry point
 // that starts a step (next to step_done, which ends it).
 static int step_begin(vvhip_plan* p) {
-    if (p->cmm.on && p->step_count % p->cmm.frequency == 0) return cmm_enqueue(p, 0);
+    if (p->cmm.on && p->cur.step_count % p->cmm.frequency == 0) return cmm_enqueue(p, 0);
     return VVHIP_OK;
 }
 int vvhip_cm_motion_start(vvhip_plan* p, int32_t frequency) {
@@ -1681,7 +1676,7 @@ int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_
     HIP_TRY(p, hipMemsetAsync(S.d_scratch, 0, scratch, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     S.on = true; S.interval = interval; S.capacity = capacity; S.mask = mask;
-    S.k0 = p->step_count / interval + 1;               // the first multiple of interval after the current step
+    S.k0 = p->cur.step_count / interval + 1;               // the first multiple of interval after the current step
     return VVHIP_OK;
 }
 int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_rows, int32_t* n_rows, int64_t* first_step, int64_t* dropped,
@@ -1726,7 +1721,7 @@ int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
     r.off_nh = (int32_t) offsetof(vvhip_series_row, nh);
     r.off_box = (int32_t) offsetof(vvhip_series_row, box);
     r.active = p->series.on; r.interval = p->series.interval; r.capacity = p->series.capacity; r.mask = p->series.mask;
-    r.steps = p->step_count;
+    r.steps = p->cur.step_count;
     r.graph_captures = p->graph_captures;
     *out = r;
     return VVHIP_OK;
@@ -1815,7 +1810,7 @@ int vvhip_fused_status(vvhip_plan* p, int32_t* active, int64_t* launches, int32_
         if (p->fused_poll_delay < 0) {
             HIP_TRY(p, hipStreamSynchronize(p->stream));
             unsigned int d = 0;
-            HIP_TRY(p, hipMemcpy(&d, &p->d_nh[p->parity].rv_delay, sizeof(d), hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(&d, &p->d_nh[p->cur.parity].rv_delay, sizeof(d), hipMemcpyDeviceToHost));
             *wait_units = (int32_t) d;
         }
     }
@@ -1864,12 +1859,12 @@ static int next_random_slice(vvhip_plan* p, uint32_t* index, bool force_refill) 
     const vvhip_plan_info& in = p->hp.info;
     const uint32_t need = (uint32_t) std::max(in.num_normal_ld, 1) + 2u * (uint32_t) std::max(in.num_pairs_ld, 1);   // HOST:806-807,863
     if (need > p->buf.random_size) return fail(p, VVHIP_ERR_INVALID, "random buffer smaller than one step's demand");
-    if (force_refill || p->random_pos + need > p->buf.random_size) {
+    if (force_refill || p->cur.random_pos + need > p->buf.random_size) {
         HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch, p->stream));
-        p->random_pos = 0;
+        p->cur.random_pos = 0;
     }
-    *index = p->random_pos;
-    p->random_pos += need;
+    *index = p->cur.random_pos;
+    p->cur.random_pos += need;
     return VVHIP_OK;
 }
 
@@ -1883,7 +1878,7 @@ int vvhip_fill_random(vvhip_plan* p) {
     TRY(settle_recovery(p));
     if (!p->buf.random || !p->buf.random_size) return fail(p, VVHIP_ERR_INVALID, "no random buffer bound");
     HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch, p->stream));
-    p->random_pos = 0;
+    p->cur.random_pos = 0;
     return VVHIP_OK;
 }
 
@@ -1914,8 +1909,7 @@ static int recovery_snapshot(vvhip_plan* p) {
     if (!r.epoch) HIP_TRY(p, hipMalloc((void**) &r.epoch, sizeof(unsigned long long)));
     HIP_TRY(p, hipMemcpyAsync(r.nh, p->d_nh, 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
     HIP_TRY(p, hipMemcpyAsync(r.epoch, p->d_epoch, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
-    r.parity = p->parity; r.random_pos = p->random_pos; r.fextra_dirty = p->fextra_dirty; r.fextra_virtual = p->fextra_virtual;
-    r.step_count = p->step_count;
+    r.cur = p->cur;
     r.series_saved = p->series.on;                  // (a series cannot start or stop while the snapshot is unverified: both settle it first)
     if (r.series_saved) {
         if (!r.series_cursor) HIP_TRY(p, hipMalloc((void**) &r.series_cursor, 2 * sizeof(unsigned long long)));
@@ -1960,9 +1954,8 @@ int recover_rendezvous(vvhip_plan* p) {
     HIP_TRY(p, hipMemsetAsync(p->d_acc, 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
     if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
     HIP_TRY(p, hipMemsetAsync(p->d_rv + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
-    p->parity = r.parity; p->random_pos = r.random_pos; p->fextra_dirty = r.fextra_dirty; p->fextra_virtual = r.fextra_virtual;
-    // the series' rows of the failed steps are written again, at the same places, by the repeat
-    p->step_count = r.step_count;
+    // (with the step counter: the series' rows of the failed steps are written again, at the same places, by the repeat)
+    p->cur = r.cur;
     if (r.series_saved && p->series.on)
         HIP_TRY(p, hipMemcpyAsync(p->series.d_cursor, r.series_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     // ... and so are the removals of the centre-of-mass motion, at the same steps (the schedule follows the step counter): their counters go
@@ -1971,8 +1964,7 @@ int recover_rendezvous(vvhip_plan* p) {
         HIP_TRY(p, hipMemcpyAsync(p->cmm.d_rec, r.cmm_rec, sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
     for (int w = 1; w < 4; w++) __atomic_store_n(&p->h_status[w], 0u, __ATOMIC_RELAXED);
     p->fused = false;
-    p->fused_checked_b = 0;
-    for (vvhip_plan::FusedCheck& c : p->fused_checks) c.b = 0;
+    forget_fused_checks(p);
     drop_graphs(p);
     r.recoveries++;
     r.valid = false;
@@ -2016,26 +2008,22 @@ static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const void* s
     if (out) *out = &g;
     if (g.exec && g.steps == steps_per_graph && g.site == site && g.kt == k_tether && g.kd == k_drude && g.rows == rows && g.cmm == cmm) return VVHIP_OK;
     if (g.exec) { (void) hipStreamSynchronize(s); (void) hipGraphExecDestroy(g.exec); g.exec = nullptr; }      // (a replay of the one that goes may still be in flight)
-    // The capture walks the host-side cursors (parity, Langevin random slice) through the graph's steps; they are put back
-    // afterwards, because nothing has run yet.  A replay moves them to the graph's end (vvhip_run_graph).
-    const int parity0 = p->parity;
-    const uint32_t random0 = p->random_pos;
-    const bool fextra_dirty0 = p->fextra_dirty, fextra_virtual0 = p->fextra_virtual;
-    const long long step0 = p->step_count;
-    p->parity = q & 1;
-    p->step_count = c0;
+    // The capture walks the host's cursor (parity, Langevin random slice, step counter) through the graph's steps; it is put back
+    // afterwards, because nothing has run yet.  A replay moves it to the graph's end (vvhip_run_graph).
+    const vvhip_plan::Cursor cur0 = p->cur;
+    p->cur.parity = q & 1;
+    p->cur.step_count = c0;
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) { p->parity = parity0; p->step_count = step0; return hip_fail(p, e, "hipStreamBeginCapture"); }
+    if (e != hipSuccess) { p->cur = cur0; return hip_fail(p, e, "hipStreamBeginCapture"); }
     p->capturing = true;
     int rc = VVHIP_OK;
     // Langevin: a captured graph begins with a refill of the random buffer (the device generator's epoch advances per refill), so every replay draws new numbers
     for (int i = 0; i < steps_per_graph && rc == VVHIP_OK; i++) rc = plan_step(p, site, k_tether, k_drude, i == 0 && p->hp.has_ld);
     p->capturing = false;
     e = hipStreamEndCapture(s, &graph);
-    g.random_end = p->random_pos;
-    p->parity = parity0; p->random_pos = random0; p->fextra_dirty = fextra_dirty0; p->fextra_virtual = fextra_virtual0;
-    p->step_count = step0;
+    g.random_end = p->cur.random_pos;
+    p->cur = cur0;
     if (rc != VVHIP_OK) { if (graph) (void) hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return hip_fail(p, e, "hipStreamEndCapture");
     e = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
@@ -2054,8 +2042,8 @@ int vvhip_graph_prepare(vvhip_plan* p, int steps_per_graph, const void* site, do
     if (steps_per_graph < 1) return VVHIP_ERR_INVALID;
     if (steps_per_graph % 2) steps_per_graph += 1;   // the thermostat double-buffers by step parity: a graph must hold an even number of steps
     if (!p->stream) return fail(p, VVHIP_ERR_INVALID, "graph capture needs a non-null stream in vvhip_buffers.stream");
-    TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count));
-    return prepare_slot(p, p->parity ^ 1, steps_per_graph, site, k_tether, k_drude, p->step_count);
+    TRY(prepare_slot(p, p->cur.parity, steps_per_graph, site, k_tether, k_drude, p->cur.step_count));
+    return prepare_slot(p, p->cur.parity ^ 1, steps_per_graph, site, k_tether, k_drude, p->cur.step_count);
 }
 
 int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* site, double k_tether, double k_drude) {
@@ -2074,20 +2062,20 @@ int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* 
     int done = 0;
     if (nsteps >= steps_per_graph) {
         vvhip_plan::GraphSlot* g = nullptr;
-        TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count, &g));     // no-op when the slot of this parity is ready
+        TRY(prepare_slot(p, p->cur.parity, steps_per_graph, site, k_tether, k_drude, p->cur.step_count, &g));     // no-op when the slot of this parity is ready
         for (; done + steps_per_graph <= nsteps; done += steps_per_graph) {
             // with a series the replays' rows fall on other steps of the graph as the counter moves on: the graph whose rows fit
             // (at most two when the interval and the graph's length divide one another; otherwise the cache may capture again)
             // (the same for the steps that carry a removal of the centre-of-mass motion)
-            if (done > 0 && ((p->series.on && series_rows_in(p, p->step_count, steps_per_graph) != g->rows) ||
-                             (p->cmm.on && cmm_steps_in(p, p->step_count, steps_per_graph) != g->cmm)))
-                TRY(prepare_slot(p, p->parity, steps_per_graph, site, k_tether, k_drude, p->step_count, &g));
+            if (done > 0 && ((p->series.on && series_rows_in(p, p->cur.step_count, steps_per_graph) != g->rows) ||
+                             (p->cmm.on && cmm_steps_in(p, p->cur.step_count, steps_per_graph) != g->cmm)))
+                TRY(prepare_slot(p, p->cur.parity, steps_per_graph, site, k_tether, k_drude, p->cur.step_count, &g));
             HIP_TRY(p, hipGraphLaunch(g->exec, s));
-            p->step_count += steps_per_graph;
+            p->cur.step_count += steps_per_graph;
         }
-        p->random_pos = g->random_end;               // an even number of steps: the parity is where it was
-        if (!middle && extra_flags(p)) p->fextra_dirty = true;
-        if (middle && cos_on(p) && !p->hp.has_ld && !p->hp.has_ef) p->fextra_virtual = true;    // what the replayed steps' phase 0 would have set
+        p->cur.random_pos = g->random_end;               // an even number of steps: the parity is where it was
+        if (!middle && extra_flags(p)) p->cur.fextra_dirty = true;
+        if (middle && middle_application(p).fe_virtual) p->cur.fextra_virtual = true;    // what the replayed steps' phase 0 would have set
     }
     for (; done < nsteps; done++) TRY(plan_step(p, site, k_tether, k_drude, false));
     return VVHIP_OK;
@@ -2103,11 +2091,11 @@ int vvhip_debug_launch_shape(const vvhip_plan* p, int32_t shape[4]) {
 int vvhip_debug_fused_flags(vvhip_plan* p, int kernel, uint32_t* flags) {
     NEED_BOUND(p);
     if (!flags) return VVHIP_ERR_INVALID;
-    const uint32_t mom_a = use_moments(p) ? (vv::A_KE | vv::A_KE_MOM) : 0, mom_b = use_moments(p) ? vv::B_KE_MOM : 0;
-    const bool rk = use_rekick(p);
-    if (kernel == 0) *flags = vv::A_KICK_FULL | (rk ? vv::A_NOSTORE : 0) | extra_flags(p) | cons_a(p) | (p->hp.has_nh ? (cos_on(p) ? (vv::A_BIAS | vv::A_CZ_STORE | mom_a) : vv::A_KE) : 0);
-    const bool split = p->hp.info.num_waves >= p->split_chain_waves && !use_mailbox(p);    // as run_chain_and_b decides
-    if (kernel != 0) *flags = vv::B_DRIFT_MIDDLE | (rk ? vv::B_KICK : 0) | tail_flags(p) | cons_b(p) | (p->hp.has_nh ? (((p->hp.params.num_nh_chains <= 4 && !split) ? vv::B_CHAIN : 0) | vv::B_SCALE | (cos_on(p) ? (vv::B_UNBIAS | vv::B_CZ_LOAD | mom_b) : 0)) : 0);
+    const ThermoApp t = middle_application(p);
+    // Phase 0's kernel A and the last phase's kernel B.  This accessor has never reported the load of a stale forceExtra, the cos(kz) store of a
+    // plan without NH particles or the mailbox bit: the probes and bench.py time the sets without them, so they are masked out here.
+    if (kernel == 0) *flags = t.a[0].flags & ~(vv::A_FE_LOAD | (t.mode == ThermoMode::NO_NH ? vv::A_CZ_STORE : 0u));
+    else *flags = t.b | (t.mode == ThermoMode::NO_NH ? 0u : chain_in_b(p) & ~vv::B_MAILBOX);
     return VVHIP_OK;
 }
 int vvhip_time_kernel(vvhip_plan* p, int kernel, uint32_t flags, int reps, double* ms_per_launch) {
@@ -2117,15 +2105,15 @@ int vvhip_time_kernel(vvhip_plan* p, int kernel, uint32_t flags, int reps, doubl
     hipEvent_t e0, e1;
     HIP_TRY(p, hipEventCreate(&e0));
     HIP_TRY(p, hipEventCreate(&e1));
-    const int parity = p->parity;
+    const int parity = p->cur.parity;
     const bool was_timing = p->timing;
     p->timing = false;
     int rc = VVHIP_OK;
-    for (int i = 0; i < 3 && rc == VVHIP_OK; i++) { p->parity = parity; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
+    for (int i = 0; i < 3 && rc == VVHIP_OK; i++) { p->cur.parity = parity; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
     HIP_TRY(p, hipEventRecord(e0, p->stream));
-    for (int i = 0; i < reps && rc == VVHIP_OK; i++) { p->parity = parity; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
+    for (int i = 0; i < reps && rc == VVHIP_OK; i++) { p->cur.parity = parity; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
     HIP_TRY(p, hipEventRecord(e1, p->stream));
-    p->parity = parity;
+    p->cur.parity = parity;
     p->timing = was_timing;
     if (rc != VVHIP_OK) return rc;
     HIP_TRY(p, hipEventSynchronize(e1));
@@ -2150,9 +2138,9 @@ int vvhip_debug_timestamps(vvhip_plan* p, uint32_t flags, int block, long long o
     if (!p->d_dbg) HIP_TRY(p, hipMalloc((void**) &p->d_dbg, 128 * sizeof(long long)));
     HIP_TRY(p, hipMemsetAsync(p->d_dbg, 0, 128 * sizeof(long long), p->stream));
     p->dbg_block = block;
-    const int parity = p->parity;
+    const int parity = p->cur.parity;
     int rc = (flags & 0x80000000u) ? run_a(p, flags & 0x7FFFFFFFu, 0) : run_b(p, flags);
-    p->parity = parity;
+    p->cur.parity = parity;
     if (rc != VVHIP_OK) return rc;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     HIP_TRY(p, hipMemcpy(out, p->d_dbg, 128 * sizeof(long long), hipMemcpyDeviceToHost));
@@ -2174,7 +2162,7 @@ int vvhip_debug_timestamps_fused(vvhip_plan* p, int block, long long out[128]) {
     HIP_TRY(p, hipMemsetAsync(p->d_dbg, 0, 128 * sizeof(long long), p->stream));
     p->dbg_block = block;
     bool taken = false;
-    TRY(step_middle_fused(p, 0, &taken));
+    if (p->hp.params.use_middle_scheme && p->hp.info.constraints_fused) TRY(run_application_fused(p, middle_application(p), 0, &taken));
     if (!taken) return fail(p, VVHIP_ERR_UNSUPPORTED, "the plan does not take the one-launch step");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     HIP_TRY(p, hipMemcpy(out, p->d_dbg, 128 * sizeof(long long), hipMemcpyDeviceToHost));
@@ -2195,10 +2183,10 @@ int vvhip_debug_span(vvhip_plan* p, int kernel, uint32_t flags, int reps, double
     const size_t per = (size_t) 4096 * 8 * 2;
     if (!p->d_dbg_span) HIP_TRY(p, hipMalloc((void**) &p->d_dbg_span, 6 * per * sizeof(long long)));
     HIP_TRY(p, hipMemsetAsync(p->d_dbg_span, 0, 6 * per * sizeof(long long), p->stream));
-    const int parity = p->parity;
+    const int parity = p->cur.parity;
     int rc = VVHIP_OK;
-    for (int i = 0; i < reps && rc == VVHIP_OK; i++) { p->parity = parity; p->dbg_parity = i & 1; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
-    p->parity = parity;
+    for (int i = 0; i < reps && rc == VVHIP_OK; i++) { p->cur.parity = parity; p->dbg_parity = i & 1; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
+    p->cur.parity = parity;
     const int last = (reps - 1) & 1;
     p->dbg_parity = 0;
     long long* keep = p->d_dbg_span;
@@ -2364,12 +2352,11 @@ int vvhip_mailbox_connect(vvhip_plan* p, const void* handles) {
     std::vector<unsigned long long*> peers((size_t) p->mb_ranks, nullptr);
     // A second connect: what vvhip_mailbox_destroy does first -- captured step graphs carry the OLD peer table's address and the peers' box
     // addresses in their kernel arguments (a replay after the free below would read unmapped memory), launches still in flight use them too,
-    // and whether the step may be one launch depends on who shares the device (re-evaluated: fused_checked_*).
+    // and whether the step may be one launch depends on who shares the device (re-evaluated: forget_fused_checks).
     TRY(settle_recovery(p));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     drop_graphs(p);
-    p->fused_checked_b = 0;
-    for (vvhip_plan::FusedCheck& c : p->fused_checks) c.b = 0;
+    forget_fused_checks(p);
     p->mb_shared_device = false;       // (a second connect must not count the first one's ranks again)
     p->mb_device_ranks = 1;
     for (void* m : p->mb_opened) (void) hipIpcCloseMemHandle(m);
@@ -2531,19 +2518,19 @@ int vvhip_debug_read_accumulators(vvhip_plan* p, double out[4], int zero_after) 
     NEED_BOUND(p);
     static long long raw[vv::NUM_ACC * vv::ACC_SLOTS];
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(raw, p->d_acc + p->parity * acc_stride(p), 4 * vv::ACC_SLOTS * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(raw, p->d_acc + p->cur.parity * acc_stride(p), 4 * vv::ACC_SLOTS * sizeof(long long), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) {                 // the ABI hands out the three group sums and the bias moment
         long long s = 0;
         for (int j = 0; j < vv::ACC_SLOTS; j++) s += raw[i * vv::ACC_SLOTS + j];
         out[i] = (double) s * p->acc_inv_scale[i];
     }
-    if (zero_after) HIP_TRY(p, hipMemsetAsync(p->d_acc + p->parity * acc_stride(p), 0, 4 * vv::ACC_SLOTS * sizeof(long long), p->stream));
+    if (zero_after) HIP_TRY(p, hipMemsetAsync(p->d_acc + p->cur.parity * acc_stride(p), 0, 4 * vv::ACC_SLOTS * sizeof(long long), p->stream));
     return VVHIP_OK;
 }
 int vvhip_debug_set_scales(vvhip_plan* p, const double scales[4]) {
     NEED_BOUND(p);
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(p->d_nh[p->parity].scales, scales, 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(p->d_nh[p->cur.parity].scales, scales, 4 * sizeof(double), hipMemcpyHostToDevice));
     return VVHIP_OK;
 }
 
