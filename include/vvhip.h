@@ -550,6 +550,10 @@ int vvhip_debug_fused_flags(vvhip_plan* plan, int kernel, uint32_t* flags);     
 int vvhip_debug_launch_shape(const vvhip_plan* plan, int32_t shape[4]);
 int vvhip_debug_step_spans(vvhip_plan* plan, int nsteps, const void* site, double k_tether, double k_drude, double out[36]);   /* instrumented builds only */
 int vvhip_debug_old_delta(vvhip_plan* plan, void** device_ptr);                       /* plan-owned oldDelta (mixed4[n]) */
+/* What all plans of this process own at this moment: count = device, uncached and pinned buffers and hipIpc mappings, bytes = of the
+ * buffers.  Process-wide counters of the owners themselves (csrc/vv_devmem.hpp), so a test can see that a destroyed plan has returned
+ * everything without watching the device's free memory, which moves under other processes' work.  Host only. */
+int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes);
 
 #ifdef __cplusplus
 }

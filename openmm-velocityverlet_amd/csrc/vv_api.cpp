@@ -15,6 +15,7 @@
 #include <unistd.h>
 #include <rccl/rccl.h>      // types and prototypes only: the library is resolved at run time (see rccl_api)
 
+#include "vv_devmem.hpp"
 #include "vv_host.hpp"
 #include "vv_kernels.hpp"
 #include "vv_rtc.hpp"
@@ -136,7 +137,7 @@ struct vvhip_plan {
     // (profiles/r05s_late_shift_scan.txt)
     int fused_late_shift = 1;
     int fused_poll_delay = -1;     // >= 0: pins the wait between a block's publish and its first poll round, units of 256 clocks (test hook "fused_poll_delay"); -1: self-tuning
-    unsigned long long* d_rv = nullptr;
+    vv::DevBuf<unsigned long long> d_rv;
     struct FusedCheck { uint32_t a = 0, b = 0; int threads = 0, waves = 0; bool ok = false; };
     FusedCheck fused_checks[4];    // (the classic scheme alternates between the pairs of its two halves)
     int fused_check_next = 0, fused_last = -1;
@@ -152,45 +153,45 @@ struct vvhip_plan {
     struct Recovery {
         bool enabled = true, valid = false, replaying = false, in_loop = false;
         int min_steps = 64;
-        void *posq = nullptr, *corr = nullptr, *velm = nullptr, *force = nullptr, *fextra = nullptr, *random = nullptr;
-        vv::NHDevState* nh = nullptr;
-        unsigned long long* epoch = nullptr;
+        vv::DevBuf<void> posq, corr, velm, force, fextra, random;
+        vv::DevBuf<vv::NHDevState> nh;
+        vv::DevBuf<unsigned long long> epoch;
         Cursor cur;                               // the host's cursor at the snapshot
         struct Run { int kind, nsteps, spg; const void* site; double kt, kd; };
         std::vector<Run> runs;
         long long recoveries = 0;
-        unsigned long long* series_cursor = nullptr;   // the series' device-side row cursor (its schedule, the step counter, is in `cur`)
+        vv::DevBuf<unsigned long long> series_cursor;  // the series' device-side row cursor (its schedule, the step counter, is in `cur`)
         bool series_saved = false;
-        vv::CmmDevRecord* cmm_rec = nullptr;      // the counters of the scheduled removals of the centre-of-mass motion
+        vv::DevBuf<vv::CmmDevRecord> cmm_rec;     // the counters of the scheduled removals of the centre-of-mass motion
         bool cmm_saved = false;
     } rec;
-    // plan-owned device state
-    int2* d_slots = nullptr;
-    int32_t* d_slot_image = nullptr;
-    int32_t* d_slot_rand = nullptr;
-    int32_t* d_slot_big = nullptr;
-    int32_t* d_slot_shake = nullptr;
-    float4* d_slot_shake_param = nullptr;
-    int2* d_slot_vsite = nullptr;
-    double* d_vsite_params = nullptr;
-    int32_t* d_vsite_atom = nullptr;
-    unsigned long long* d_bigacc = nullptr;
-    int2* d_image_pairs = nullptr;
-    void* d_fextra = nullptr;
-    void* d_old_delta = nullptr;
-    void* d_pos_delta = nullptr;   // used when the caller does not supply one
-    void* d_comv = nullptr;        // per-segment COM velocities handed from kernel A to kernel B
-    double* d_slot_m = nullptr;    // static per-lane RECIP(velm.w) (vv_args.hpp: A_MTAB), filled on the device from velm.w
-    double* d_slot_f = nullptr;    // static per-lane Drude-pair mass fraction (A_MTAB / B_MTAB)
+    // plan-owned device state: every buffer frees itself with the plan (vv_devmem.hpp)
+    vv::DevBuf<int2> d_slots;
+    vv::DevBuf<int32_t> d_slot_image;
+    vv::DevBuf<int32_t> d_slot_rand;
+    vv::DevBuf<int32_t> d_slot_big;
+    vv::DevBuf<int32_t> d_slot_shake;
+    vv::DevBuf<float4> d_slot_shake_param;
+    vv::DevBuf<int2> d_slot_vsite;
+    vv::DevBuf<double> d_vsite_params;
+    vv::DevBuf<int32_t> d_vsite_atom;
+    vv::DevBuf<unsigned long long> d_bigacc;
+    vv::DevBuf<int2> d_image_pairs;
+    vv::DevBuf<void> d_fextra;
+    vv::DevBuf<void> d_old_delta;
+    vv::DevBuf<void> d_pos_delta;  // used when the caller does not supply one
+    vv::DevBuf<void> d_comv;       // per-segment COM velocities handed from kernel A to kernel B
+    vv::DevBuf<double> d_slot_m;   // static per-lane RECIP(velm.w) (vv_args.hpp: A_MTAB), filled on the device from velm.w
+    vv::DevBuf<double> d_slot_f;   // static per-lane Drude-pair mass fraction (A_MTAB / B_MTAB)
     bool mass_tab_a = false, mass_tab_b = true;   // kernel A / B launches read the tables (defaults follow the build; test hooks "mass_tab_a" / "mass_tab_b" override: comparison runs)
     bool mass_tab_valid = false;   // tables match the bound velm.w (vvhip_bind / vvhip_masses_changed reset it)
-    double* d_seg_mass = nullptr;  // static (mass, 1/mass) per COM segment
-    int* d_seg_base = nullptr;     // per wave: COM segments in the waves before it
-    double* d_comw = nullptr;      // per-segment mass-weighted mean of cos(kz) (moment form of the cos perturbation)
-    double* d_cosz = nullptr;      // per-lane cos(2 pi z / Lz) of the current step
-    unsigned long long* d_acc = nullptr;   // [2 parities][NUM_ACC][ACC_SLOTS]
-    vv::NHDevState* d_nh = nullptr;         // [2 parities]
-    unsigned long long* d_epoch = nullptr;  // refill counter of the device Gaussian generator
+    vv::DevBuf<double> d_seg_mass; // static (mass, 1/mass) per COM segment
+    vv::DevBuf<int> d_seg_base;    // per wave: COM segments in the waves before it
+    vv::DevBuf<double> d_comw;     // per-segment mass-weighted mean of cos(kz) (moment form of the cos perturbation)
+    vv::DevBuf<double> d_cosz;     // per-lane cos(2 pi z / Lz) of the current step
+    vv::DevBuf<unsigned long long> d_acc;  // [2 parities][NUM_ACC][ACC_SLOTS]
+    vv::DevBuf<vv::NHDevState> d_nh;        // [2 parities]
+    vv::DevBuf<unsigned long long> d_epoch; // refill counter of the device Gaussian generator
     uint64_t rng_seed = 0;
     // HIP-event timing (eager launches only)
     bool timing = false;
@@ -220,10 +221,10 @@ struct vvhip_plan {
     ncclComm_t comm = nullptr;
     int comm_ranks = 1;
     // ... or the xGMI mailbox (vv_args.hpp: Mailbox): no collective launch, works inside a captured graph
-    unsigned long long* mb_local = nullptr;       // uncached, exported through hipIpc
-    unsigned long long** d_mb_peers = nullptr;    // device array of the peers' mappings
-    unsigned int* d_mb_ctl = nullptr;
-    std::vector<void*> mb_opened;                 // hipIpcOpenMemHandle mappings to close
+    vv::DevBuf<unsigned long long> mb_local;      // uncached, exported through hipIpc
+    vv::DevBuf<unsigned long long*> d_mb_peers;   // device array of the peers' mappings
+    vv::DevBuf<unsigned int> d_mb_ctl;
+    std::vector<vv::IpcMapping> mb_opened;        // the peers' boxes as mapped here
     int mb_ranks = 0, mb_rank = 0;
     bool mb_on = false;
     // A peer's box lives on THIS device (several ranks sharing one GPU: test set-ups): found out by vvhip_mailbox_connect.  Such ranks'
@@ -236,44 +237,44 @@ struct vvhip_plan {
     // read by the host without synchronising: [0] a mailbox wait on the peers ran out (the ranks have diverged), [1] a fixed-point
     // accumulator left its range (|sum| x scale >= 2^62: the thermostat would see garbage).  Checked at the entry of the run loops
     // and in vvhip_synchronize / vvhip_status.
-    unsigned int* h_status = nullptr;
+    vv::PinnedBuf<unsigned int> h_status;
     unsigned int* d_status = nullptr;             // the same words as the device sees them
     bool launch_shape_forced = false;             // a test hook fixed the launch shape ("block_threads", "grid_cap_a / b"): keep it at bind
     int num_cus = 256;                            // hipDeviceProp_t::multiProcessorCount of the bound device
-    vv::ChainLaneBlock* d_lane_const = nullptr;   // [3] chain constants per temperature group (kernel B's thermostat wave)
+    vv::DevBuf<vv::ChainLaneBlock> d_lane_const;  // [3] chain constants per temperature group (kernel B's thermostat wave)
     vv::ChainLaneBlock lane_const_host[VVHIP_NUM_TG] = {};
     bool lane_const_valid = false;
-    long long* d_dbg_span = nullptr;
+    vv::DevBuf<long long> d_dbg_span;
     int dbg_parity = 0;
-    long long* d_dbg = nullptr;                   // instrumented build only (vvhip_debug_timestamps)
+    vv::DevBuf<long long> d_dbg;                  // instrumented build only (vvhip_debug_timestamps)
     int dbg_block = 0;
     // Drude temperature report (vvhip_drude_temperatures): its tables (HostPlan::report_*) and its own scratch, nothing shared with the step
-    int32_t* d_rep_lane_mol = nullptr;
-    double* d_rep_lane_mass = nullptr;
-    double* d_rep_lane_mu = nullptr;
-    double* d_rep_mol_mass = nullptr;
-    int4* d_rep_cross = nullptr;
-    double* d_rep_cross_mu = nullptr;
-    long long* d_rep = nullptr;                   // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
-    long long* h_rep = nullptr;                   // pinned: the result words as copied back
+    vv::DevBuf<int32_t> d_rep_lane_mol;
+    vv::DevBuf<double> d_rep_lane_mass;
+    vv::DevBuf<double> d_rep_lane_mu;
+    vv::DevBuf<double> d_rep_mol_mass;
+    vv::DevBuf<int4> d_rep_cross;
+    vv::DevBuf<double> d_rep_cross_mu;
+    vv::DevBuf<long long> d_rep;                  // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
+    vv::PinnedBuf<long long> h_rep;               // pinned: the result words as copied back
     long long graph_captures = 0;
     // Series (vvhip_series_*): the rows the steps append on the device, scheduled by cur.step_count
     struct Series {
         bool on = false;
         int interval = 0, capacity = 0, mask = 0;
         long long k0 = 0;                         // row 0 is step interval * k0
-        vvhip_series_row* d_rows = nullptr;       // [capacity + 1]: behind the last row a guard row (vvhip_debug_series_guard)
-        unsigned long long* d_cursor = nullptr;   // [2] rows appended (past capacity too), rows dropped
-        long long* d_scratch = nullptr;           // the report's scratch for the rows (as d_rep), zero between rows
+        vv::DevBuf<vvhip_series_row> d_rows;      // [capacity + 1]: behind the last row a guard row (vvhip_debug_series_guard)
+        vv::DevBuf<unsigned long long> d_cursor;  // [2] rows appended (past capacity too), rows dropped
+        vv::DevBuf<long long> d_scratch;          // the report's scratch for the rows (as d_rep), zero between rows
     } series;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
         bool on = false;
         int frequency = 0;
-        long long* d_words = nullptr;             // [CMM_WORDS] zero between removals
-        vv::CmmDevRecord* d_rec = nullptr;        // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
-        double* h_v = nullptr;                    // pinned: the V of a one-off call as copied back
+        vv::DevBuf<long long> d_words;            // [CMM_WORDS] zero between removals
+        vv::DevBuf<vv::CmmDevRecord> d_rec;       // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
+        vv::PinnedBuf<double> h_v;                // pinned: the V of a one-off call as copied back
     } cmm;
 };
 
@@ -469,45 +470,45 @@ vv::KArgs make_args(vvhip_plan* p, uint32_t flags, uint32_t random_index) {
     a.posq = p->buf.posq;
     a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
     a.force = (const long long*) p->buf.force;
-    a.fextra = p->d_fextra;
-    a.pos_delta = p->buf.pos_delta ? p->buf.pos_delta : p->d_pos_delta;
-    a.old_delta = p->d_old_delta;
-    a.comv = p->d_comv;
-    a.comw = p->d_comw;
-    a.seg_mass = p->d_seg_mass;
-    a.seg_base = p->d_seg_base;
-    a.cosz = p->d_cosz;
-    a.slots = p->d_slots;
-    a.slot_m = p->d_slot_m;
-    a.slot_f = p->d_slot_f;
-    a.slot_image = p->d_slot_image;
-    a.slot_rand = p->d_slot_rand;
-    a.slot_shake = p->d_slot_shake;
-    a.slot_shake_param = p->d_slot_shake_param;
-    a.slot_vsite = p->d_slot_vsite;
-    a.vsite_params = p->d_vsite_params;
-    a.vsite_atom = p->d_vsite_atom;
+    a.fextra = p->d_fextra.get();
+    a.pos_delta = p->buf.pos_delta ? p->buf.pos_delta : p->d_pos_delta.get();
+    a.old_delta = p->d_old_delta.get();
+    a.comv = p->d_comv.get();
+    a.comw = p->d_comw.get();
+    a.seg_mass = p->d_seg_mass.get();
+    a.seg_base = p->d_seg_base.get();
+    a.cosz = p->d_cosz.get();
+    a.slots = p->d_slots.get();
+    a.slot_m = p->d_slot_m.get();
+    a.slot_f = p->d_slot_f.get();
+    a.slot_image = p->d_slot_image.get();
+    a.slot_rand = p->d_slot_rand.get();
+    a.slot_shake = p->d_slot_shake.get();
+    a.slot_shake_param = p->d_slot_shake_param.get();
+    a.slot_vsite = p->d_slot_vsite.get();
+    a.vsite_params = p->d_vsite_params.get();
+    a.vsite_atom = p->d_vsite_atom.get();
     a.shake_tol = q.constraint_tolerance > 0 ? q.constraint_tolerance : 1e-5;
-    a.slot_big = p->d_slot_big;
-    a.bigacc = p->d_bigacc;
+    a.slot_big = p->d_slot_big.get();
+    a.bigacc = p->d_bigacc.get();
     a.big_scale = p->hp.big_scale;
     a.big_inv_scale = 1.0 / p->hp.big_scale;
     a.random = (const float4*) p->buf.random;
-    a.acc = p->d_acc + p->cur.parity * acc_stride(p);
-    a.acc_next = p->d_acc + (p->cur.parity ^ 1) * acc_stride(p);
-    a.nh = p->d_nh + p->cur.parity;
-    a.nh_next = p->d_nh + (p->cur.parity ^ 1);
+    a.acc = p->d_acc.get() + p->cur.parity * acc_stride(p);
+    a.acc_next = p->d_acc.get() + (p->cur.parity ^ 1) * acc_stride(p);
+    a.nh = p->d_nh.get() + p->cur.parity;
+    a.nh_next = p->d_nh.get() + (p->cur.parity ^ 1);
     a.chain = make_chain(p, 0);
-    a.lane_const = p->d_lane_const;
-    a.mb.local = p->mb_local;
-    a.mb.peers = p->d_mb_peers;
-    a.mb.ctl = p->d_mb_ctl;
+    a.lane_const = p->d_lane_const.get();
+    a.mb.local = p->mb_local.get();
+    a.mb.peers = p->d_mb_peers.get();
+    a.mb.ctl = p->d_mb_ctl.get();
     a.mb.ranks = p->mb_ranks;
     a.mb.rank = p->mb_rank;
     a.status = p->d_status;
-    a.dbg = p->d_dbg;
+    a.dbg = p->d_dbg.get();
     a.dbg_block = p->dbg_block;
-    a.dbg_span = p->d_dbg_span;
+    a.dbg_span = p->d_dbg_span.get();
     a.dbg_parity = p->dbg_seq >= 0 ? p->dbg_seq++ % 6 : p->dbg_parity;
     a.padded = p->hp.padded_num_atoms;
     a.gc_colors = p->hp.gc_colors;
@@ -586,7 +587,7 @@ int upload_lane_const(vvhip_plan* p) {
     // hosts re-send their parameters every step (the reference re-reads the getters every step): only a real change costs a copy
     if (p->lane_const_valid && std::memcmp(p->lane_const_host, b, sizeof(b)) == 0) return VVHIP_OK;
     (void) hipStreamSynchronize(p->stream);
-    hipError_t e = hipMemcpy(p->d_lane_const, b, sizeof(b), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(p->d_lane_const.get(), b, sizeof(b), hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(p, e, "hipMemcpy(chain constants)");
     std::memcpy(p->lane_const_host, b, sizeof(b));
     p->lane_const_valid = true;
@@ -657,7 +658,7 @@ int shared_device_cap(const vvhip_plan* p, int cap) {
 int ensure_mass_table(vvhip_plan* p) {
     if (!(p->mass_tab_a || p->mass_tab_b) || p->mass_tab_valid) return VVHIP_OK;
     if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "internal: mass tables must be filled before a graph capture starts");
-    HIP_TRY(p, vv::launch_mass_table(p->hp.precision, p->buf.velm, p->d_slots, p->hp.info.num_waves, p->d_slot_m, p->d_slot_f, p->stream));
+    HIP_TRY(p, vv::launch_mass_table(p->hp.precision, p->buf.velm, p->d_slots.get(), p->hp.info.num_waves, p->d_slot_m.get(), p->d_slot_f.get(), p->stream));
     p->mass_tab_valid = true;
     return VVHIP_OK;
 }
@@ -694,7 +695,7 @@ int run_chain(vvhip_plan* p, uint32_t flags) {
     TRY(settle_recovery(p));
     debug_stall(p);
     ScopedTimer t(p, T_OTHER);
-    HIP_TRY(p, vv::launch_chain(make_chain(p, flags), p->d_nh + p->cur.parity, p->d_acc + p->cur.parity * acc_stride(p), p->stream));
+    HIP_TRY(p, vv::launch_chain(make_chain(p, flags), p->d_nh.get() + p->cur.parity, p->d_acc.get() + p->cur.parity * acc_stride(p), p->stream));
     return VVHIP_OK;
 }
 
@@ -728,7 +729,7 @@ int run_ke(vvhip_plan* p, uint32_t flags, uint32_t random_index) {
     if (p->hp.num_big == 0) return run_a(p, flags, random_index);
     const uint32_t ub = flags & (vv::A_UNBIAS_ACC | vv::A_CZ_LOAD), first = flags & ~(vv::A_KE | ub);
     if (first) TRY(run_a(p, first, random_index));
-    HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_bigacc.get(), 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
     TRY(run_a(p, vv::A_COMPART | ub, 0));
     return run_a(p, vv::A_KE | ub, 0);
 }
@@ -791,7 +792,7 @@ int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_i
         vv::KArgs q = make_args(p, bflags, random_index);
         q.flags_a = aflags;
         int per_cu = 0;
-        const hipError_t e = vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv, p->stream, nullptr, nullptr, nullptr, &per_cu);      // (asks only; launches nothing)
+        const hipError_t e = vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv.get(), p->stream, nullptr, nullptr, nullptr, &per_cu);      // (asks only; launches nothing)
         const int tiles = p->block_threads / 64, blocks = (p->hp.info.num_waves + tiles - 1) / tiles;
         if (e != hipSuccess) (void) hipGetLastError();
         p->fused_checks[p->fused_last] = {aflags, bflags, p->block_threads, p->hp.info.num_waves, e == hipSuccess && per_cu >= 1 && (long) per_cu * p->num_cus >= blocks};
@@ -807,10 +808,10 @@ int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_i
     q.flags_a = aflags;
     q.fused_poll_delay = p->fused_poll_delay;
     // the "a block polled twice" words of this step and of the one before (by thermostat parity), behind the two copies of the rendezvous words
-    q.rv_late_cur = (unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * p->cur.parity;
-    q.rv_late_prev = (const unsigned int*) (p->d_rv + 2 * kRvCopy) + vv::ACC_SLOTS * (p->cur.parity ^ 1);
+    q.rv_late_cur = (unsigned int*) (p->d_rv.get() + 2 * kRvCopy) + vv::ACC_SLOTS * p->cur.parity;
+    q.rv_late_prev = (const unsigned int*) (p->d_rv.get() + 2 * kRvCopy) + vv::ACC_SLOTS * (p->cur.parity ^ 1);
     q.fused_late_shift = p->fused_late_shift;
-    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv + p->cur.parity * kRvCopy, p->stream, t.e0, t.e1, &route, nullptr));
+    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv.get() + p->cur.parity * kRvCopy, p->stream, t.e0, t.e1, &route, nullptr));
     p->cur.parity ^= 1;            // the advanced thermostat state now lives in the other copy
     p->fused_launches++;
     *taken = true;
@@ -922,26 +923,14 @@ int vvhip_debug_tune(vvhip_plan* p, const char* key, int value) {
 
 void vvhip_plan_destroy(vvhip_plan* p) {
     if (!p) return;
-    if (p->bound) {
-        (void) hipStreamSynchronize(p->stream);
-        for (void* ptr : {(void*) p->d_slots, (void*) p->d_slot_image, (void*) p->d_slot_rand, (void*) p->d_slot_shake, (void*) p->d_slot_shake_param, (void*) p->d_slot_vsite, (void*) p->d_vsite_params, (void*) p->d_vsite_atom, (void*) p->d_slot_big, (void*) p->d_bigacc, (void*) p->d_image_pairs,
-                          p->d_fextra, p->d_old_delta, p->d_pos_delta, p->d_comv, (void*) p->d_comw, (void*) p->d_seg_mass, (void*) p->d_seg_base, (void*) p->d_slot_m, (void*) p->d_slot_f, (void*) p->d_cosz, (void*) p->d_epoch, (void*) p->d_acc, (void*) p->d_rv, (void*) p->d_nh, (void*) p->d_lane_const, (void*) p->d_dbg, (void*) p->d_dbg_span,
-                          p->rec.posq, p->rec.corr, p->rec.velm, p->rec.force, p->rec.fextra, p->rec.random, (void*) p->rec.nh, (void*) p->rec.epoch,
-                          (void*) p->d_rep_lane_mol, (void*) p->d_rep_lane_mass, (void*) p->d_rep_lane_mu, (void*) p->d_rep_mol_mass, (void*) p->d_rep_cross,
-                          (void*) p->d_rep_cross_mu, (void*) p->d_rep, (void*) p->series.d_rows, (void*) p->series.d_cursor, (void*) p->series.d_scratch,
-                          (void*) p->rec.series_cursor, (void*) p->rec.cmm_rec, (void*) p->cmm.d_words, (void*) p->cmm.d_rec})
-            if (ptr) (void) hipFree(ptr);
-        if (p->h_rep) (void) hipHostFree(p->h_rep);
-        if (p->cmm.h_v) (void) hipHostFree(p->cmm.h_v);
-        drop_graphs(p);
-        if (p->comm) (void) rccl_api().commDestroy(p->comm);
-        mailbox_release(p);
-        if (p->h_status) (void) hipHostFree(p->h_status);
-        for (auto& v : p->events)
-            for (auto& e : v) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
-        for (hipEvent_t e : p->event_pool) (void) hipEventDestroy(e);
-    }
-    delete p;
+    if (p->d_slots) (void) hipStreamSynchronize(p->stream);      // (the first thing vvhip_bind allocates: also a bind that failed half-way may have fills in flight)
+    drop_graphs(p);
+    if (p->comm) (void) rccl_api().commDestroy(p->comm);
+    mailbox_release(p);
+    for (auto& v : p->events)
+        for (auto& e : v) { (void) hipEventDestroy(e.first); (void) hipEventDestroy(e.second); }
+    for (hipEvent_t e : p->event_pool) (void) hipEventDestroy(e);
+    delete p;      // the plan's buffers go with their owners (vv_devmem.hpp)
 }
 
 const char* vvhip_last_error(const vvhip_plan* p) { return p ? p->err.c_str() : "null plan"; }
@@ -996,96 +985,61 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
     const size_t nloc = (size_t) (hp.shard_end - hp.shard_begin);
     const size_t nslots = (size_t) hp.info.num_waves * 64;
     const size_t rs = sizeof_real(hp.precision), ms = sizeof_mixed(hp.precision);
-    HIP_TRY(p, hipMalloc((void**) &p->d_slots, nslots * sizeof(int2)));
-    HIP_TRY(p, hipMemcpy(p->d_slots, hp.slots.data(), nslots * sizeof(int2), hipMemcpyHostToDevice));
+    HIP_TRY(p, vv::upload(p->d_slots, hp.slots));
     if (!hp.slot_image.empty()) {
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_image, nslots * sizeof(int32_t)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_image, hp.slot_image.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (!hp.image_pairs.empty()) {
-            HIP_TRY(p, hipMalloc((void**) &p->d_image_pairs, hp.image_pairs.size() * sizeof(int32_t)));
-            HIP_TRY(p, hipMemcpy(p->d_image_pairs, hp.image_pairs.data(), hp.image_pairs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        HIP_TRY(p, vv::upload(p->d_slot_image, hp.slot_image));
+        if (!hp.image_pairs.empty()) HIP_TRY(p, vv::upload(p->d_image_pairs, hp.image_pairs));
     }
-    if (!hp.slot_rand.empty()) {
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_rand, nslots * sizeof(int32_t)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_rand, hp.slot_rand.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
+    if (!hp.slot_rand.empty()) HIP_TRY(p, vv::upload(p->d_slot_rand, hp.slot_rand));
     if (!hp.slot_shake.empty()) {
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_shake, nslots * sizeof(int32_t)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_shake, hp.slot_shake.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_shake_param, nslots * sizeof(float4)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_shake_param, hp.slot_shake_param.data(), nslots * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY(p, vv::upload(p->d_slot_shake, hp.slot_shake));
+        HIP_TRY(p, vv::upload(p->d_slot_shake_param, hp.slot_shake_param));
     }
     if (!hp.slot_vsite.empty()) {
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_vsite, nslots * sizeof(int2)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_vsite, hp.slot_vsite.data(), nslots * sizeof(int2), hipMemcpyHostToDevice));
-        HIP_TRY(p, hipMalloc((void**) &p->d_vsite_params, hp.vsite_params.size() * sizeof(double)));
-        HIP_TRY(p, hipMemcpy(p->d_vsite_params, hp.vsite_params.data(), hp.vsite_params.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(p, hipMalloc((void**) &p->d_vsite_atom, hp.vsite_atom.size() * sizeof(int32_t)));
-        HIP_TRY(p, hipMemcpy(p->d_vsite_atom, hp.vsite_atom.data(), hp.vsite_atom.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(p, vv::upload(p->d_slot_vsite, hp.slot_vsite));
+        HIP_TRY(p, vv::upload(p->d_vsite_params, hp.vsite_params));
+        HIP_TRY(p, vv::upload(p->d_vsite_atom, hp.vsite_atom));
     }
     if (!hp.slot_big.empty()) {
-        HIP_TRY(p, hipMalloc((void**) &p->d_slot_big, nslots * sizeof(int32_t)));
-        HIP_TRY(p, hipMemcpy(p->d_slot_big, hp.slot_big.data(), nslots * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIP_TRY(p, hipMalloc((void**) &p->d_bigacc, (size_t) hp.num_big * 4 * sizeof(unsigned long long)));
-        HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) hp.num_big * 4 * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, vv::upload(p->d_slot_big, hp.slot_big));
+        HIP_TRY(p, vv::zeros(p->d_bigacc, (size_t) hp.num_big * 4 * sizeof(unsigned long long), p->stream));
     }
-    HIP_TRY(p, hipMalloc(&p->d_fextra, nloc * 3 * rs));            // zero-initialised like HOST:79-89
-    // (every fill of a plan buffer goes into the PLAN's stream: a plain hipMemset only enqueues on the null stream, which a non-blocking
-    // stream does not wait for -- the reset of both accumulator copies at a switch of the cos perturbation (vvhip_set_params) could land a
-    // step later and wipe kernel A's sums; found by the adapter fuzz when a host stall changed the timing, tests/test_cpp_plugin.py)
-    HIP_TRY(p, hipMemsetAsync(p->d_fextra, 0, nloc * 3 * rs, p->stream));
-    HIP_TRY(p, hipMalloc(&p->d_old_delta, nloc * 4 * ms));
-    HIP_TRY(p, hipMemsetAsync(p->d_old_delta, 0, nloc * 4 * ms, p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_cosz, nslots * sizeof(double)));
-    HIP_TRY(p, hipMemsetAsync(p->d_cosz, 0, nslots * sizeof(double), p->stream));
+    // (the fills go into the PLAN's stream, not the null stream: see vv::zeros)
+    HIP_TRY(p, vv::zeros(p->d_fextra, nloc * 3 * rs, p->stream));            // zero-initialised like HOST:79-89
+    HIP_TRY(p, vv::zeros(p->d_old_delta, nloc * 4 * ms, p->stream));
+    HIP_TRY(p, vv::zeros(p->d_cosz, nslots * sizeof(double), p->stream));
     const size_t nseg = std::max<size_t>(hp.seg_mass.size() / 2, 1);
-    HIP_TRY(p, hipMalloc(&p->d_comv, nseg * 4 * ms));
-    HIP_TRY(p, hipMemsetAsync(p->d_comv, 0, nseg * 4 * ms, p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_seg_base, hp.seg_base.size() * sizeof(int32_t)));
-    HIP_TRY(p, hipMemcpy(p->d_seg_base, hp.seg_base.data(), hp.seg_base.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(p, hipMalloc((void**) &p->d_seg_mass, hp.seg_mass.size() * sizeof(double)));
-    HIP_TRY(p, hipMemcpy(p->d_seg_mass, hp.seg_mass.data(), hp.seg_mass.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(p, hipMalloc((void**) &p->d_slot_m, nslots * sizeof(double)));
-    HIP_TRY(p, hipMalloc((void**) &p->d_slot_f, nslots * sizeof(double)));
-    HIP_TRY(p, hipMalloc((void**) &p->d_comw, nseg * sizeof(double)));
-    HIP_TRY(p, hipMemsetAsync(p->d_comw, 0, nseg * sizeof(double), p->stream));
-    HIP_TRY(p, hipMalloc(&p->d_pos_delta, nloc * 4 * ms));
-    HIP_TRY(p, hipMemsetAsync(p->d_pos_delta, 0, nloc * 4 * ms, p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_epoch, sizeof(unsigned long long)));
-    HIP_TRY(p, hipMemsetAsync(p->d_epoch, 0, sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_acc, 2 * kAccN * sizeof(unsigned long long)));
-    HIP_TRY(p, hipMemsetAsync(p->d_acc, 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, vv::zeros(p->d_comv, nseg * 4 * ms, p->stream));
+    HIP_TRY(p, vv::upload(p->d_seg_base, hp.seg_base));
+    HIP_TRY(p, vv::upload(p->d_seg_mass, hp.seg_mass));
+    HIP_TRY(p, p->d_slot_m.alloc(nslots * sizeof(double)));      // (the mass tables are filled on the device: ensure_mass_table)
+    HIP_TRY(p, p->d_slot_f.alloc(nslots * sizeof(double)));
+    HIP_TRY(p, vv::zeros(p->d_comw, nseg * sizeof(double), p->stream));
+    HIP_TRY(p, vv::zeros(p->d_pos_delta, nloc * 4 * ms, p->stream));
+    HIP_TRY(p, vv::zeros(p->d_epoch, sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, vv::zeros(p->d_acc, 2 * kAccN * sizeof(unsigned long long), p->stream));
     // rendezvous words of the fused step: uncached (every block's thermostat wave polls what the other blocks -- on other XCDs, behind other
     // L2s -- have just stored); zero = "no step's word" (tags run from 1)
     // (+ ACC_SLOTS words: the two rows of "polled twice" flags; + 8: the "a rendezvous has failed" word behind them, vv_device.inc: rv_dead_word)
-    HIP_TRY(p, hipExtMallocWithFlags((void**) &p->d_rv, (size_t) (2 * kRvCopy + vv::ACC_SLOTS + 8) * sizeof(unsigned long long), hipDeviceMallocUncached));
-    HIP_TRY(p, hipMemsetAsync(p->d_rv, 0, (size_t) (2 * kRvCopy + vv::ACC_SLOTS + 8) * sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_nh, 2 * sizeof(vv::NHDevState)));
-    vv::NHDevState init[2] = {};
+    HIP_TRY(p, vv::zeros(p->d_rv, (size_t) (2 * kRvCopy + vv::ACC_SLOTS + 8) * sizeof(unsigned long long), p->stream, true));
+    std::vector<vv::NHDevState> init(2);
     for (int c = 0; c < 2; c++)
         for (int g = 0; g < 3; g++) { init[c].s.vscale[g] = 1.0; init[c].scales[g] = 1.0; }
     for (int c = 0; c < 2; c++) init[c].rv_delay = 6;      // where the wait of the fused step's rendezvous starts (it tunes itself from there)
-    HIP_TRY(p, hipMemcpy(p->d_nh, init, sizeof(init), hipMemcpyHostToDevice));
-    HIP_TRY(p, hipMalloc((void**) &p->d_lane_const, VVHIP_NUM_TG * sizeof(vv::ChainLaneBlock)));
-    {   // Drude temperature report: tables and scratch of its own
-        auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
-            HIP_TRY(p, hipMalloc(dst, std::max<size_t>(bytes, 16)));
-            if (bytes) HIP_TRY(p, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-            return VVHIP_OK;
-        };
-        TRY(upload((void**) &p->d_rep_lane_mol, hp.report_lane_mol.data(), hp.report_lane_mol.size() * sizeof(int32_t)));
-        TRY(upload((void**) &p->d_rep_lane_mass, hp.report_lane_mass.data(), hp.report_lane_mass.size() * sizeof(double)));
-        TRY(upload((void**) &p->d_rep_lane_mu, hp.report_lane_mu.data(), hp.report_lane_mu.size() * sizeof(double)));
-        TRY(upload((void**) &p->d_rep_mol_mass, hp.report_mol_mass.data(), hp.report_mol_mass.size() * sizeof(double)));
-        TRY(upload((void**) &p->d_rep_cross, hp.report_cross.data(), hp.report_cross.size() * sizeof(int32_t)));
-        TRY(upload((void**) &p->d_rep_cross_mu, hp.report_cross_mu.data(), hp.report_cross_mu.size() * sizeof(double)));
-        HIP_TRY(p, hipMalloc((void**) &p->d_rep, (8 + 6 * hp.report_mol_mass.size()) * sizeof(long long)));
-        HIP_TRY(p, hipHostMalloc((void**) &p->h_rep, 8 * sizeof(long long)));
-    }
-    HIP_TRY(p, hipHostMalloc((void**) &p->h_status, 4 * sizeof(unsigned int), hipHostMallocMapped));
-    std::memset(p->h_status, 0, 4 * sizeof(unsigned int));
-    HIP_TRY(p, hipHostGetDevicePointer((void**) &p->d_status, p->h_status, 0));
+    HIP_TRY(p, vv::upload(p->d_nh, init));
+    HIP_TRY(p, p->d_lane_const.alloc(VVHIP_NUM_TG * sizeof(vv::ChainLaneBlock)));
+    // Drude temperature report: tables (16 bytes at least: an empty table is still a pointer the kernels take) and scratch of its own
+    HIP_TRY(p, vv::upload(p->d_rep_lane_mol, hp.report_lane_mol, 16));
+    HIP_TRY(p, vv::upload(p->d_rep_lane_mass, hp.report_lane_mass, 16));
+    HIP_TRY(p, vv::upload(p->d_rep_lane_mu, hp.report_lane_mu, 16));
+    HIP_TRY(p, vv::upload(p->d_rep_mol_mass, hp.report_mol_mass, 16));
+    HIP_TRY(p, vv::upload(p->d_rep_cross, hp.report_cross, 16));
+    HIP_TRY(p, vv::upload(p->d_rep_cross_mu, hp.report_cross_mu, 16));
+    HIP_TRY(p, p->d_rep.alloc((8 + 6 * hp.report_mol_mass.size()) * sizeof(long long)));
+    HIP_TRY(p, p->h_rep.alloc(8 * sizeof(long long)));
+    HIP_TRY(p, p->h_status.alloc(4 * sizeof(unsigned int), true));
+    std::memset(p->h_status.get(), 0, 4 * sizeof(unsigned int));
+    HIP_TRY(p, hipHostGetDevicePointer((void**) &p->d_status, p->h_status.get(), 0));
     {   // launch shape for the device this plan is bound to (one block per CU balancing needs the real CU count)
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1127,7 +1081,7 @@ int vvhip_set_params(vvhip_plan* p, const vvhip_params* q) {
     drop_graphs(p);
     if (cos_switch && p->bound) {        // the accumulator copies are laid out by the rows in use: start the new layout from zeros
         HIP_TRY(p, hipStreamSynchronize(p->stream));
-        HIP_TRY(p, hipMemsetAsync(p->d_acc, 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, hipMemsetAsync(p->d_acc.get(), 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
     }
     return upload_lane_const(p);
 }
@@ -1151,7 +1105,7 @@ int vvhip_get_nh_state(vvhip_plan* p, vvhip_nh_state* out) {
     NEED_BOUND(p);
     TRY(settle_recovery(p));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(out, &p->d_nh[p->cur.parity].s, sizeof(*out), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(out, &p->d_nh.get()[p->cur.parity].s, sizeof(*out), hipMemcpyDeviceToHost));
     return VVHIP_OK;
 }
 int vvhip_set_nh_state(vvhip_plan* p, const vvhip_nh_state* in) {
@@ -1161,7 +1115,7 @@ int vvhip_set_nh_state(vvhip_plan* p, const vvhip_nh_state* in) {
     vvhip_nh_state st = *in;
     for (int g = 0; g < VVHIP_NUM_TG; g++)            // the chain's closing element is 0 by construction (API:340-376 never writes it)
         for (int i = std::max(0, std::min(p->hp.params.num_nh_chains, VVHIP_MAX_CHAINS)); i <= VVHIP_MAX_CHAINS; i++) st.eta_dot[g][i] = 0.0;
-    HIP_TRY(p, hipMemcpy(&p->d_nh[p->cur.parity].s, &st, sizeof(st), hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(&p->d_nh.get()[p->cur.parity].s, &st, sizeof(st), hipMemcpyHostToDevice));
     return VVHIP_OK;
 }
 
@@ -1239,7 +1193,7 @@ int vvhip_algorithmic_bytes(const vvhip_plan* p, int32_t* bytes_a, int32_t* byte
 int vvhip_accumulators(vvhip_plan* p, int phase, void** device_ptr, int32_t* count) {
     NEED_BOUND(p);
     if (!device_ptr || !count) return VVHIP_ERR_INVALID;
-    unsigned long long* acc = p->d_acc + p->cur.parity * acc_stride(p);
+    unsigned long long* acc = p->d_acc.get() + p->cur.parity * acc_stride(p);
     if (thermo_mode(p) == ThermoMode::COS_MOMENTS) { *device_ptr = acc; *count = vv::NUM_ACC * vv::ACC_SLOTS; }   // everything kernel A produced
     else if (cos_on(p) && phase == 0) { *device_ptr = acc + 3 * vv::ACC_SLOTS; *count = vv::ACC_SLOTS; }        // bias moment slots only
     else { *device_ptr = acc; *count = 3 * vv::ACC_SLOTS; }                                                   // the three 2KE sums
@@ -1396,7 +1350,7 @@ int vvhip_reset_extra_force(vvhip_plan* p) {               // K/middle.cu:227-23
     p->cur.fextra_dirty = false;
     ScopedTimer t(p, T_OTHER);
     const size_t nloc = (size_t) (p->hp.shard_end - p->hp.shard_begin);
-    HIP_TRY(p, hipMemsetAsync(p->d_fextra, 0, nloc * 3 * sizeof_real(p->hp.precision), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_fextra.get(), 0, nloc * 3 * sizeof_real(p->hp.precision), p->stream));
     return VVHIP_OK;
 }
 int vvhip_middle_kick(vvhip_plan* p) { NEED_BOUND(p); return run_a(p, stale_fextra(p) | vv::A_KICK_FULL, 0); }
@@ -1443,7 +1397,7 @@ int vvhip_calc_viscosity(vvhip_plan* p, double* v_max, double* inv_vis) {   // H
     NEED_BOUND(p);
     double v = 0;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(&v, &p->d_nh[p->cur.parity].s.v_bias, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(&v, &p->d_nh.get()[p->cur.parity].s.v_bias, sizeof(double), hipMemcpyDeviceToHost));
     if (p->hp.precision == VVHIP_SINGLE) v = (double) (float) v;             // vMaxBuffer is `mixed`
     const double vol = p->box[0] * p->box[1] * p->box[2];
     if (v_max) *v_max = v;
@@ -1467,9 +1421,9 @@ int vvhip_compute_kinetic_energy(vvhip_plan* p, double* kinetic_energy) {   // H
 static vv::ReportArgs report_args(const vvhip_plan* p, long long* scratch) {
     const vv::HostPlan& hp = p->hp;
     vv::ReportArgs a{};
-    a.velm = p->buf.velm; a.slots = p->d_slots;
-    a.lane_mol = p->d_rep_lane_mol; a.lane_mass = p->d_rep_lane_mass; a.lane_mu = p->d_rep_lane_mu;
-    a.mol_mass = p->d_rep_mol_mass; a.cross = p->d_rep_cross; a.cross_mu = p->d_rep_cross_mu;
+    a.velm = p->buf.velm; a.slots = p->d_slots.get();
+    a.lane_mol = p->d_rep_lane_mol.get(); a.lane_mass = p->d_rep_lane_mass.get(); a.lane_mu = p->d_rep_lane_mu.get();
+    a.mol_mass = p->d_rep_mol_mass.get(); a.cross = p->d_rep_cross.get(); a.cross_mu = p->d_rep_cross_mu.get();
     a.out = scratch; a.mol_p = scratch ? scratch + 8 : nullptr;
     a.nwaves = hp.info.num_waves; a.nmol = (int) hp.report_mol_mass.size(); a.ncross = (int) hp.report_cross_mu.size();
     a.frac_bits = hp.report_frac_bits;
@@ -1491,13 +1445,13 @@ int vvhip_drude_report_raw(vvhip_plan* p, int64_t raw[6]) {
     if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "Drude temperature report: not inside a graph capture");
     TRY(settle_recovery(p));
     const int nmol = (int) hp.report_mol_mass.size();
-    HIP_TRY(p, hipMemsetAsync(p->d_rep, 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
-    HIP_TRY(p, vv::launch_report(hp.precision, report_args(p, p->d_rep), p->block_threads, p->grid_cap_a, p->stream));
-    HIP_TRY(p, hipMemcpyAsync(p->h_rep, p->d_rep, vv::REP_WORDS * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_rep.get(), 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
+    HIP_TRY(p, vv::launch_report(hp.precision, report_args(p, p->d_rep.get()), p->block_threads, p->grid_cap_a, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->h_rep.get(), p->d_rep.get(), vv::REP_WORDS * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     if (p->h_rep[vv::REP_FLAG])
         return fail(p, VVHIP_ERR_OVERFLOW, "Drude temperature report: a kinetic-energy or momentum term is NaN or beyond the fixed-point range; no numbers");
-    std::memcpy(raw, p->h_rep, 6 * sizeof(int64_t));
+    std::memcpy(raw, p->h_rep.get(), 6 * sizeof(int64_t));
     return VVHIP_OK;
 }
 int vvhip_drude_report_combine(const vvhip_plan* p, const int64_t raw[6], double ke[3], double t[3]) {
@@ -1532,11 +1486,11 @@ static int series_row(vvhip_plan* p) {
     vvhip_plan::Series& S = p->series;
     vv::SeriesArgs a{};
     if (S.mask & VVHIP_SERIES_DRUDE) {
-        HIP_TRY(p, vv::launch_report(p->hp.precision, report_args(p, S.d_scratch), p->block_threads, p->grid_cap_a, p->stream));
-        a.rep_out = S.d_scratch; a.rep_mol_p = S.d_scratch + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
+        HIP_TRY(p, vv::launch_report(p->hp.precision, report_args(p, S.d_scratch.get()), p->block_threads, p->grid_cap_a, p->stream));
+        a.rep_out = S.d_scratch.get(); a.rep_mol_p = S.d_scratch.get() + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
     }
-    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh[p->cur.parity].s;
-    a.rows = S.d_rows; a.cursor = S.d_cursor; a.capacity = S.capacity;
+    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh.get()[p->cur.parity].s;
+    a.rows = S.d_rows.get(); a.cursor = S.d_cursor.get(); a.capacity = S.capacity;
     for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
     a.cos_acceleration = p->hp.params.cos_acceleration;
     HIP_TRY(p, vv::launch_series_append(a, p->grid_cap_a, p->stream));
@@ -1553,12 +1507,10 @@ static int step_done(vvhip_plan* p) {
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static int cmm_ensure(vvhip_plan* p) {
     vvhip_plan::CmMotion& M = p->cmm;
-    if (M.d_words) return VVHIP_OK;
-    HIP_TRY(p, hipMalloc((void**) &M.d_words, vv::CMM_WORDS * sizeof(long long)));
-    HIP_TRY(p, hipMalloc((void**) &M.d_rec, 2 * sizeof(vv::CmmDevRecord)));
-    HIP_TRY(p, hipHostMalloc((void**) &M.h_v, 3 * sizeof(double)));
-    HIP_TRY(p, hipMemsetAsync(M.d_words, 0, vv::CMM_WORDS * sizeof(long long), p->stream));
-    HIP_TRY(p, hipMemsetAsync(M.d_rec, 0, 2 * sizeof(vv::CmmDevRecord), p->stream));
+    if (M.d_words && M.d_rec && M.h_v) return VVHIP_OK;
+    HIP_TRY(p, vv::zeros(M.d_words, vv::CMM_WORDS * sizeof(long long), p->stream));
+    HIP_TRY(p, vv::zeros(M.d_rec, 2 * sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, M.h_v.alloc(3 * sizeof(double)));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     return VVHIP_OK;
 }
@@ -1567,8 +1519,8 @@ static int cmm_enqueue(vvhip_plan* p, int which) {
     TRY(settle_recovery(p));
     vv::CmmArgs a{};
     a.rep = report_args(p, nullptr);
-    a.words = p->cmm.d_words;
-    a.rec = p->cmm.d_rec + which;
+    a.words = p->cmm.d_words.get();
+    a.rec = p->cmm.d_rec.get() + which;
     a.inv_total_mass = p->hp.cm_total_mass > 0 ? 1.0 / p->hp.cm_total_mass : 0.0;
     HIP_TRY(p, vv::launch_cm_motion(p->hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
     return VVHIP_OK;
@@ -1592,7 +1544,7 @@ int vvhip_cm_motion_start(vvhip_plan* p, int32_t frequency) {
     TRY(settle_recovery(p));
     HIP_TRY(p, hipStreamSynchronize(p->stream));      // (removals of a schedule before may still be in flight)
     TRY(cmm_ensure(p));
-    HIP_TRY(p, hipMemsetAsync(p->cmm.d_rec, 0, sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->cmm.d_rec.get(), 0, sizeof(vv::CmmDevRecord), p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     drop_graphs(p);
     p->cmm.on = true; p->cmm.frequency = frequency;
@@ -1617,11 +1569,11 @@ int vvhip_remove_cm_motion(vvhip_plan* p, double v_removed[3]) {
     TRY(settle_recovery(p));
     TRY(cmm_ensure(p));
     TRY(cmm_enqueue(p, 1));
-    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v, p->cmm.d_rec[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     if (std::isnan(p->cmm.h_v[0]))      // (what the subtract kernel records for a removal it skipped)
         return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
-    if (v_removed) std::memcpy(v_removed, p->cmm.h_v, 3 * sizeof(double));
+    if (v_removed) std::memcpy(v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
     return VVHIP_OK;
 }
 int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
@@ -1634,7 +1586,7 @@ int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
         TRY(settle_recovery(p));                        // (a repaired run redoes its removals first)
         HIP_TRY(p, hipStreamSynchronize(p->stream));
         vv::CmmDevRecord d{};
-        HIP_TRY(p, hipMemcpy(&d, p->cmm.d_rec, sizeof(d), hipMemcpyDeviceToHost));
+        HIP_TRY(p, hipMemcpy(&d, p->cmm.d_rec.get(), sizeof(d), hipMemcpyDeviceToHost));
         r.removals = d.removals; r.skipped = d.skipped;
         for (int k = 0; k < 3; k++) r.last_v[k] = d.last_v[k];
     }
@@ -1645,9 +1597,7 @@ int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
 }
 static void series_release(vvhip_plan* p) {
     vvhip_plan::Series& S = p->series;
-    for (void* ptr : {(void*) S.d_rows, (void*) S.d_cursor, (void*) S.d_scratch})
-        if (ptr) (void) hipFree(ptr);
-    S.d_rows = nullptr; S.d_cursor = nullptr; S.d_scratch = nullptr;
+    S.d_rows.reset(); S.d_cursor.reset(); S.d_scratch.reset();
     S.on = false; S.interval = S.capacity = S.mask = 0; S.k0 = 0;
 }
 static constexpr int kGuardByte = 0xA5;
@@ -1667,13 +1617,10 @@ int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_
     drop_graphs(p);
     vvhip_plan::Series& S = p->series;
     const size_t row_bytes = sizeof(vvhip_series_row), scratch = (8 + 6 * p->hp.report_mol_mass.size()) * sizeof(long long);
-    HIP_TRY(p, hipMalloc((void**) &S.d_rows, ((size_t) capacity + 1) * row_bytes));
-    HIP_TRY(p, hipMalloc((void**) &S.d_cursor, 2 * sizeof(unsigned long long)));
-    HIP_TRY(p, hipMalloc((void**) &S.d_scratch, scratch));
-    HIP_TRY(p, hipMemsetAsync(S.d_rows, 0, (size_t) capacity * row_bytes, p->stream));
-    HIP_TRY(p, hipMemsetAsync((char*) S.d_rows + (size_t) capacity * row_bytes, kGuardByte, row_bytes, p->stream));
-    HIP_TRY(p, hipMemsetAsync(S.d_cursor, 0, 2 * sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, hipMemsetAsync(S.d_scratch, 0, scratch, p->stream));
+    HIP_TRY(p, vv::zeros(S.d_rows, ((size_t) capacity + 1) * row_bytes, p->stream));
+    HIP_TRY(p, hipMemsetAsync((char*) S.d_rows.get() + (size_t) capacity * row_bytes, kGuardByte, row_bytes, p->stream));
+    HIP_TRY(p, vv::zeros(S.d_cursor, 2 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, vv::zeros(S.d_scratch, scratch, p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     S.on = true; S.interval = interval; S.capacity = capacity; S.mask = mask;
     S.k0 = p->cur.step_count / interval + 1;               // the first multiple of interval after the current step
@@ -1689,15 +1636,15 @@ int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_row
     TRY(settle_recovery(p));                            // (a repaired run rewrites its rows first)
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     unsigned long long cur[2];
-    HIP_TRY(p, hipMemcpy(cur, S.d_cursor, sizeof(cur), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(cur, S.d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost));
     const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) S.capacity);
     const long long copy = std::min<long long>(n, max_rows);
-    if (copy > 0) HIP_TRY(p, hipMemcpy(rows_out, S.d_rows, (size_t) copy * sizeof(vvhip_series_row), hipMemcpyDeviceToHost));
+    if (copy > 0) HIP_TRY(p, hipMemcpy(rows_out, S.d_rows.get(), (size_t) copy * sizeof(vvhip_series_row), hipMemcpyDeviceToHost));
     if (n_rows) *n_rows = (int32_t) n;
     if (first_step) *first_step = (int64_t) S.interval * S.k0;
     if (dropped) *dropped = (int64_t) cur[1];
     if (reset) {
-        HIP_TRY(p, hipMemsetAsync(S.d_cursor, 0, 2 * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, hipMemsetAsync(S.d_cursor.get(), 0, 2 * sizeof(unsigned long long), p->stream));
         HIP_TRY(p, hipStreamSynchronize(p->stream));
         S.k0 += (long long) cur[0];                     // (dropped rows included: their steps are gone)
     }
@@ -1732,7 +1679,7 @@ int vvhip_debug_series_guard(vvhip_plan* p, int32_t* intact) {
     if (!p->series.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     unsigned char g[sizeof(vvhip_series_row)];
-    HIP_TRY(p, hipMemcpy(g, p->series.d_rows + p->series.capacity, sizeof(g), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(g, p->series.d_rows.get() + p->series.capacity, sizeof(g), hipMemcpyDeviceToHost));
     *intact = 1;
     for (unsigned char c : g) if (c != kGuardByte) *intact = 0;
     return VVHIP_OK;
@@ -1743,7 +1690,7 @@ int vvhip_update_image_positions(vvhip_plan* p) {          // HOST:904-934
     if (!p->hp.has_images) return VVHIP_OK;
     TRY(settle_recovery(p));
     ScopedTimer t(p, T_OTHER);
-    HIP_TRY(p, vv::launch_image_pairs(p->hp.precision, p->buf.posq, p->buf.posq_correction, p->d_image_pairs,
+    HIP_TRY(p, vv::launch_image_pairs(p->hp.precision, p->buf.posq, p->buf.posq_correction, p->d_image_pairs.get(),
                                       (int) p->hp.image_pairs.size() / 2, p->hp.params.mirror_location, p->stream));
     return VVHIP_OK;
 }
@@ -1751,7 +1698,7 @@ int vvhip_force_extra(vvhip_plan* p, void** device_ptr) {
     NEED_BOUND(p);
     if (!device_ptr) return VVHIP_ERR_INVALID;
     p->fextra_external = true;
-    *device_ptr = p->d_fextra;
+    *device_ptr = p->d_fextra.get();
     return VVHIP_OK;
 }
 
@@ -1810,7 +1757,7 @@ int vvhip_fused_status(vvhip_plan* p, int32_t* active, int64_t* launches, int32_
         if (p->fused_poll_delay < 0) {
             HIP_TRY(p, hipStreamSynchronize(p->stream));
             unsigned int d = 0;
-            HIP_TRY(p, hipMemcpy(&d, &p->d_nh[p->cur.parity].rv_delay, sizeof(d), hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(&d, &p->d_nh.get()[p->cur.parity].rv_delay, sizeof(d), hipMemcpyDeviceToHost));
             *wait_units = (int32_t) d;
         }
     }
@@ -1820,9 +1767,9 @@ int vvhip_fused_status(vvhip_plan* p, int32_t* active, int64_t* launches, int32_
 int vvhip_status_clear(vvhip_plan* p) {
     NEED_BOUND(p);
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    std::memset(p->h_status, 0, 4 * sizeof(unsigned int));
-    if (p->d_mb_ctl) HIP_TRY(p, hipMemsetAsync(p->d_mb_ctl, 0, 4 * sizeof(unsigned int), p->stream));
-    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(p->d_rv + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));      // "a rendezvous has failed" (vv_device.inc: rv_dead_word)
+    std::memset(p->h_status.get(), 0, 4 * sizeof(unsigned int));
+    if (p->d_mb_ctl) HIP_TRY(p, hipMemsetAsync(p->d_mb_ctl.get(), 0, 4 * sizeof(unsigned int), p->stream));
+    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(p->d_rv.get() + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));      // "a rendezvous has failed" (vv_device.inc: rv_dead_word)
     p->rec.valid = false;          // (a snapshot from before the failure the caller has just acknowledged is nobody's to restore)
     p->rec.runs.clear();
     return VVHIP_OK;
@@ -1844,8 +1791,8 @@ int vvhip_synth_tether_force(vvhip_plan* p, const void* site, double k_tether, d
     ScopedTimer t(p, T_OTHER, true);
     // (instrumented build: the provider stamps its waves only while vvhip_debug_step_spans numbers the launches -- its grid is not capped like the
     // kernels', and rows beyond the span buffer's 4096 per launch would be written past its end)
-    vv::TetherArgs ta{p->buf.posq, site, p->buf.velm, (long long*) p->buf.force, p->d_slots,
-                      p->hp.padded_num_atoms, p->hp.info.num_waves, k_tether, k_drude, p->dbg_seq >= 0 ? p->d_dbg_span : nullptr, p->dbg_parity, 0};
+    vv::TetherArgs ta{p->buf.posq, site, p->buf.velm, (long long*) p->buf.force, p->d_slots.get(),
+                      p->hp.padded_num_atoms, p->hp.info.num_waves, k_tether, k_drude, p->dbg_seq >= 0 ? p->d_dbg_span.get() : nullptr, p->dbg_parity, 0};
     if (p->dbg_seq >= 0) ta.dbg_parity = p->dbg_seq++ % 6;       // vvhip_debug_step_spans: every launch of the sequence stamps rows of its own
     HIP_TRY(p, vv::launch_tether(p->hp.precision, ta, p->block_threads, p->stream, t.e0, t.e1));
     return VVHIP_OK;
@@ -1860,7 +1807,7 @@ static int next_random_slice(vvhip_plan* p, uint32_t* index, bool force_refill) 
     const uint32_t need = (uint32_t) std::max(in.num_normal_ld, 1) + 2u * (uint32_t) std::max(in.num_pairs_ld, 1);   // HOST:806-807,863
     if (need > p->buf.random_size) return fail(p, VVHIP_ERR_INVALID, "random buffer smaller than one step's demand");
     if (force_refill || p->cur.random_pos + need > p->buf.random_size) {
-        HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch, p->stream));
+        HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch.get(), p->stream));
         p->cur.random_pos = 0;
     }
     *index = p->cur.random_pos;
@@ -1877,7 +1824,7 @@ int vvhip_fill_random(vvhip_plan* p) {
     NEED_BOUND(p);
     TRY(settle_recovery(p));
     if (!p->buf.random || !p->buf.random_size) return fail(p, VVHIP_ERR_INVALID, "no random buffer bound");
-    HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch, p->stream));
+    HIP_TRY(p, vv::launch_fill_normals((float4*) p->buf.random, p->buf.random_size, p->rng_seed, p->d_epoch.get(), p->stream));
     p->cur.random_pos = 0;
     return VVHIP_OK;
 }
@@ -1897,28 +1844,28 @@ static size_t rec_bytes(const vvhip_plan* p, int which) {
 }
 static int recovery_snapshot(vvhip_plan* p) {
     vvhip_plan::Recovery& r = p->rec;
-    void** dst[6] = {&r.posq, &r.corr, &r.velm, &r.force, &r.fextra, &r.random};
-    const void* src[6] = {p->buf.posq, p->buf.posq_correction, p->buf.velm, p->buf.force, p->d_fextra, p->buf.random};
+    vv::DevBuf<void>* dst[6] = {&r.posq, &r.corr, &r.velm, &r.force, &r.fextra, &r.random};
+    const void* src[6] = {p->buf.posq, p->buf.posq_correction, p->buf.velm, p->buf.force, p->d_fextra.get(), p->buf.random};
     for (int i = 0; i < 6; i++) {
         const size_t n = rec_bytes(p, i);
         if (!n) continue;
-        if (!*dst[i]) HIP_TRY(p, hipMalloc(dst[i], n));
-        HIP_TRY(p, hipMemcpyAsync(*dst[i], src[i], n, hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(p, dst[i]->ensure(n));      // (a re-bind may have brought a larger random buffer)
+        HIP_TRY(p, hipMemcpyAsync(dst[i]->get(), src[i], n, hipMemcpyDeviceToDevice, p->stream));
     }
-    if (!r.nh) HIP_TRY(p, hipMalloc((void**) &r.nh, 2 * sizeof(vv::NHDevState)));
-    if (!r.epoch) HIP_TRY(p, hipMalloc((void**) &r.epoch, sizeof(unsigned long long)));
-    HIP_TRY(p, hipMemcpyAsync(r.nh, p->d_nh, 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(p, hipMemcpyAsync(r.epoch, p->d_epoch, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(p, r.nh.ensure(2 * sizeof(vv::NHDevState)));
+    HIP_TRY(p, r.epoch.ensure(sizeof(unsigned long long)));
+    HIP_TRY(p, hipMemcpyAsync(r.nh.get(), p->d_nh.get(), 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(r.epoch.get(), p->d_epoch.get(), sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     r.cur = p->cur;
     r.series_saved = p->series.on;                  // (a series cannot start or stop while the snapshot is unverified: both settle it first)
     if (r.series_saved) {
-        if (!r.series_cursor) HIP_TRY(p, hipMalloc((void**) &r.series_cursor, 2 * sizeof(unsigned long long)));
-        HIP_TRY(p, hipMemcpyAsync(r.series_cursor, p->series.d_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(p, r.series_cursor.ensure(2 * sizeof(unsigned long long)));
+        HIP_TRY(p, hipMemcpyAsync(r.series_cursor.get(), p->series.d_cursor.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     }
-    r.cmm_saved = p->cmm.d_rec != nullptr;          // (a schedule cannot start or stop while the snapshot is unverified either)
+    r.cmm_saved = (bool) p->cmm.d_rec;          // (a schedule cannot start or stop while the snapshot is unverified either)
     if (r.cmm_saved) {
-        if (!r.cmm_rec) HIP_TRY(p, hipMalloc((void**) &r.cmm_rec, sizeof(vv::CmmDevRecord)));
-        HIP_TRY(p, hipMemcpyAsync(r.cmm_rec, p->cmm.d_rec, sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(p, r.cmm_rec.ensure(sizeof(vv::CmmDevRecord)));
+        HIP_TRY(p, hipMemcpyAsync(r.cmm_rec.get(), p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
     }
     r.runs.clear();
     r.valid = true;
@@ -1942,26 +1889,26 @@ int recover_rendezvous(vvhip_plan* p) {
     for (const auto& run : r.runs) steps += run.nsteps;
     std::fprintf(stderr, "libvvhip: the one-launch step's blocks did not meet within 0.2 s (another process's kernels on the device?): the last %lld step(s) "
                          "are repeated from the plan's snapshot with two launches per step, and the plan keeps two launches from here on\n", steps);
-    void* src[6] = {r.posq, r.corr, r.velm, r.force, r.fextra, r.random};
-    void* dst[6] = {p->buf.posq, p->buf.posq_correction, p->buf.velm, p->buf.force, p->d_fextra, const_cast<void*>(p->buf.random)};
+    void* src[6] = {r.posq.get(), r.corr.get(), r.velm.get(), r.force.get(), r.fextra.get(), r.random.get()};
+    void* dst[6] = {p->buf.posq, p->buf.posq_correction, p->buf.velm, p->buf.force, p->d_fextra.get(), const_cast<void*>(p->buf.random)};
     for (int i = 0; i < 6; i++) {
         const size_t n = rec_bytes(p, i);
         if (n && src[i]) HIP_TRY(p, hipMemcpyAsync(dst[i], src[i], n, hipMemcpyDeviceToDevice, p->stream));
     }
-    HIP_TRY(p, hipMemcpyAsync(p->d_nh, r.nh, 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
-    HIP_TRY(p, hipMemcpyAsync(p->d_epoch, r.epoch, sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->d_nh.get(), r.nh.get(), 2 * sizeof(vv::NHDevState), hipMemcpyDeviceToDevice, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->d_epoch.get(), r.epoch.get(), sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     // both accumulator copies are zero between steps; whatever the failed steps left in them goes
-    HIP_TRY(p, hipMemsetAsync(p->d_acc, 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
-    if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc, 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, hipMemsetAsync(p->d_rv + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_acc.get(), 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
+    if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc.get(), 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(p->d_rv.get() + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
     // (with the step counter: the series' rows of the failed steps are written again, at the same places, by the repeat)
     p->cur = r.cur;
     if (r.series_saved && p->series.on)
-        HIP_TRY(p, hipMemcpyAsync(p->series.d_cursor, r.series_cursor, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(p, hipMemcpyAsync(p->series.d_cursor.get(), r.series_cursor.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, p->stream));
     // ... and so are the removals of the centre-of-mass motion, at the same steps (the schedule follows the step counter): their counters go
     // back with it (the scratch words are zero between removals whatever the failed steps computed)
     if (r.cmm_saved && p->cmm.d_rec)
-        HIP_TRY(p, hipMemcpyAsync(p->cmm.d_rec, r.cmm_rec, sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
+        HIP_TRY(p, hipMemcpyAsync(p->cmm.d_rec.get(), r.cmm_rec.get(), sizeof(vv::CmmDevRecord), hipMemcpyDeviceToDevice, p->stream));
     for (int w = 1; w < 4; w++) __atomic_store_n(&p->h_status[w], 0u, __ATOMIC_RELAXED);
     p->fused = false;
     forget_fused_checks(p);
@@ -2135,15 +2082,15 @@ int vvhip_debug_timestamps(vvhip_plan* p, uint32_t flags, int block, long long o
     (void) flags; (void) block; (void) out;
     return fail(p, VVHIP_ERR_UNSUPPORTED, "not an instrumented build");
 #else
-    if (!p->d_dbg) HIP_TRY(p, hipMalloc((void**) &p->d_dbg, 128 * sizeof(long long)));
-    HIP_TRY(p, hipMemsetAsync(p->d_dbg, 0, 128 * sizeof(long long), p->stream));
+    HIP_TRY(p, p->d_dbg.ensure(128 * sizeof(long long)));
+    HIP_TRY(p, hipMemsetAsync(p->d_dbg.get(), 0, 128 * sizeof(long long), p->stream));
     p->dbg_block = block;
     const int parity = p->cur.parity;
     int rc = (flags & 0x80000000u) ? run_a(p, flags & 0x7FFFFFFFu, 0) : run_b(p, flags);
     p->cur.parity = parity;
     if (rc != VVHIP_OK) return rc;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(out, p->d_dbg, 128 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(out, p->d_dbg.get(), 128 * sizeof(long long), hipMemcpyDeviceToHost));
     return VVHIP_OK;
 #endif
 }
@@ -2158,14 +2105,14 @@ int vvhip_debug_timestamps_fused(vvhip_plan* p, int block, long long out[128]) {
     (void) block; (void) out;
     return fail(p, VVHIP_ERR_UNSUPPORTED, "not an instrumented build");
 #else
-    if (!p->d_dbg) HIP_TRY(p, hipMalloc((void**) &p->d_dbg, 128 * sizeof(long long)));
-    HIP_TRY(p, hipMemsetAsync(p->d_dbg, 0, 128 * sizeof(long long), p->stream));
+    HIP_TRY(p, p->d_dbg.ensure(128 * sizeof(long long)));
+    HIP_TRY(p, hipMemsetAsync(p->d_dbg.get(), 0, 128 * sizeof(long long), p->stream));
     p->dbg_block = block;
     bool taken = false;
     if (p->hp.params.use_middle_scheme && p->hp.info.constraints_fused) TRY(run_application_fused(p, middle_application(p), 0, &taken));
     if (!taken) return fail(p, VVHIP_ERR_UNSUPPORTED, "the plan does not take the one-launch step");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(out, p->d_dbg, 128 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(out, p->d_dbg.get(), 128 * sizeof(long long), hipMemcpyDeviceToHost));
     return VVHIP_OK;
 #endif
 }
@@ -2181,21 +2128,18 @@ int vvhip_debug_span(vvhip_plan* p, int kernel, uint32_t flags, int reps, double
     return fail(p, VVHIP_ERR_UNSUPPORTED, "not an instrumented build");
 #else
     const size_t per = (size_t) 4096 * 8 * 2;
-    if (!p->d_dbg_span) HIP_TRY(p, hipMalloc((void**) &p->d_dbg_span, 6 * per * sizeof(long long)));
-    HIP_TRY(p, hipMemsetAsync(p->d_dbg_span, 0, 6 * per * sizeof(long long), p->stream));
+    HIP_TRY(p, p->d_dbg_span.ensure(6 * per * sizeof(long long)));
+    HIP_TRY(p, hipMemsetAsync(p->d_dbg_span.get(), 0, 6 * per * sizeof(long long), p->stream));
     const int parity = p->cur.parity;
     int rc = VVHIP_OK;
     for (int i = 0; i < reps && rc == VVHIP_OK; i++) { p->cur.parity = parity; p->dbg_parity = i & 1; rc = kernel == 0 ? run_a(p, flags, 0) : run_b(p, flags); }
     p->cur.parity = parity;
     const int last = (reps - 1) & 1;
     p->dbg_parity = 0;
-    long long* keep = p->d_dbg_span;
-    p->d_dbg_span = nullptr;                       // later launches run unstamped
-    if (rc != VVHIP_OK) { p->d_dbg_span = keep; return rc; }
+    if (rc != VVHIP_OK) return rc;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     std::vector<long long> h(2 * per);
-    HIP_TRY(p, hipMemcpy(h.data(), keep, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    p->d_dbg_span = keep;
+    HIP_TRY(p, hipMemcpy(h.data(), p->d_dbg_span.get(), h.size() * sizeof(long long), hipMemcpyDeviceToHost));
     // the grid size is not known here: the launch of parity q used rows [q * grid, (q+1) * grid); find them by scanning non-zero pairs
     std::vector<long long> in[2], ex[2];
     std::vector<int> blk;
@@ -2235,22 +2179,19 @@ int vvhip_debug_step_spans(vvhip_plan* p, int nsteps, const void* site, double k
 #else
     if (nsteps < 2 || !site || !out || !p->hp.params.use_middle_scheme || vvhip_step_middle_phases(p) != 2) return VVHIP_ERR_INVALID;
     const size_t per = (size_t) 4096 * 8 * 2;
-    if (!p->d_dbg_span) HIP_TRY(p, hipMalloc((void**) &p->d_dbg_span, 6 * per * sizeof(long long)));
+    HIP_TRY(p, p->d_dbg_span.ensure(6 * per * sizeof(long long)));
     TRY(ensure_mass_table(p));
     for (int i = 0; i < nsteps - 2; i++) TRY(plan_step(p, site, k_tether, k_drude, false));      // warm: same launches, rows overwritten below
-    HIP_TRY(p, hipMemsetAsync(p->d_dbg_span, 0, 6 * per * sizeof(long long), p->stream));
-    long long* keep = p->d_dbg_span;
+    HIP_TRY(p, hipMemsetAsync(p->d_dbg_span.get(), 0, 6 * per * sizeof(long long), p->stream));
     p->dbg_seq = 0;
     int rc = VVHIP_OK;
     const long long fused_before = p->fused_launches;
     for (int i = 0; i < 2 && rc == VVHIP_OK; i++) rc = plan_step(p, site, k_tether, k_drude, false);
     p->dbg_seq = -1;
-    p->d_dbg_span = nullptr;
-    if (rc != VVHIP_OK) { p->d_dbg_span = keep; return rc; }
+    if (rc != VVHIP_OK) return rc;
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     std::vector<long long> h(6 * per);
-    HIP_TRY(p, hipMemcpy(h.data(), keep, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    p->d_dbg_span = keep;
+    HIP_TRY(p, hipMemcpy(h.data(), p->d_dbg_span.get(), h.size() * sizeof(long long), hipMemcpyDeviceToHost));
     long long t0 = 0;
     // (the one-launch step: provider + one kernel per step, four launches; rows 4 and 5 stay zero)
     const int nlaunch = p->fused_launches > fused_before ? 4 : 6;
@@ -2313,15 +2254,18 @@ int vvhip_peer_access(int device, int peer_device, int32_t* can_access) {
     return VVHIP_OK;
 }
 // ---- xGMI mailbox (include/vvhip.h): create -> exchange the 64-byte handles by any means -> connect
-static void mailbox_release(vvhip_plan* p) {
+// back to "created, not connected": the peers' mappings and the table of them go
+static void mailbox_disconnect(vvhip_plan* p) {
     p->mb_on = false;
-    p->mb_shared_device = false;
+    p->mb_shared_device = false;       // (a second connect must not count the first one's ranks again)
     p->mb_device_ranks = 1;
-    for (void* m : p->mb_opened) (void) hipIpcCloseMemHandle(m);
     p->mb_opened.clear();
-    if (p->d_mb_peers) { (void) hipFree(p->d_mb_peers); p->d_mb_peers = nullptr; }
-    if (p->d_mb_ctl) { (void) hipFree(p->d_mb_ctl); p->d_mb_ctl = nullptr; }
-    if (p->mb_local) { (void) hipFree(p->mb_local); p->mb_local = nullptr; }
+    p->d_mb_peers.reset();
+}
+static void mailbox_release(vvhip_plan* p) {
+    mailbox_disconnect(p);
+    p->d_mb_ctl.reset();
+    p->mb_local.reset();
     p->mb_ranks = 0;
 }
 int vvhip_mailbox_create(vvhip_plan* p, int nranks, int rank, void* handle64) {
@@ -2334,13 +2278,11 @@ int vvhip_mailbox_create(vvhip_plan* p, int nranks, int rank, void* handle64) {
     drop_graphs(p);
     const size_t bytes = (size_t) 2 * nranks * vv::MB_WORDS * sizeof(unsigned long long);
     // uncached: peers' stores land in this GPU's memory over xGMI and must be seen by loads that would otherwise hit in L2
-    HIP_TRY(p, hipExtMallocWithFlags((void**) &p->mb_local, std::max(bytes, (size_t) 4096), hipDeviceMallocUncached));
-    HIP_TRY(p, hipMemsetAsync(p->mb_local, 0, std::max(bytes, (size_t) 4096), p->stream));
-    HIP_TRY(p, hipMalloc((void**) &p->d_mb_ctl, 4 * sizeof(unsigned int)));
-    HIP_TRY(p, hipMemsetAsync(p->d_mb_ctl, 0, 4 * sizeof(unsigned int), p->stream));
+    HIP_TRY(p, vv::zeros(p->mb_local, std::max(bytes, (size_t) 4096), p->stream, true));
+    HIP_TRY(p, vv::zeros(p->d_mb_ctl, 4 * sizeof(unsigned int), p->stream));
     HIP_TRY(p, hipDeviceSynchronize());
     hipIpcMemHandle_t h;
-    HIP_TRY(p, hipIpcGetMemHandle(&h, p->mb_local));
+    HIP_TRY(p, hipIpcGetMemHandle(&h, p->mb_local.get()));
     std::memcpy(handle64, &h, 64);
     p->mb_ranks = nranks;
     p->mb_rank = rank;
@@ -2357,18 +2299,17 @@ int vvhip_mailbox_connect(vvhip_plan* p, const void* handles) {
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     drop_graphs(p);
     forget_fused_checks(p);
-    p->mb_shared_device = false;       // (a second connect must not count the first one's ranks again)
-    p->mb_device_ranks = 1;
-    for (void* m : p->mb_opened) (void) hipIpcCloseMemHandle(m);
-    p->mb_opened.clear();
-    if (p->d_mb_peers) { (void) hipFree(p->d_mb_peers); p->d_mb_peers = nullptr; }
+    mailbox_disconnect(p);
+    // (an error below leaves the mailbox as it is now: created, not connected)
+    auto give_up = [p](hipError_t e, const char* what) { mailbox_disconnect(p); return hip_fail(p, e, what); };
     for (int r = 0; r < p->mb_ranks; r++) {
-        if (r == p->mb_rank) { peers[r] = p->mb_local; continue; }
+        if (r == p->mb_rank) { peers[r] = p->mb_local.get(); continue; }
         hipIpcMemHandle_t h;
         std::memcpy(&h, (const char*) handles + (size_t) r * 64, 64);
-        void* m = nullptr;
-        HIP_TRY(p, hipIpcOpenMemHandle(&m, h, hipIpcMemLazyEnablePeerAccess));
-        p->mb_opened.push_back(m);
+        vv::IpcMapping box;
+        if (hipError_t e = box.open(h); e != hipSuccess) return give_up(e, "hipIpcOpenMemHandle");
+        void* m = box.get();
+        p->mb_opened.push_back(std::move(box));
         peers[r] = (unsigned long long*) m;
         // whose memory is it?  A box on this very device means that rank shares the GPU with this one
         hipPointerAttribute_t attr;
@@ -2376,8 +2317,7 @@ int vvhip_mailbox_connect(vvhip_plan* p, const void* handles) {
         if (hipGetDevice(&dev) == hipSuccess && hipPointerGetAttributes(&attr, m) == hipSuccess && attr.device == dev) { p->mb_shared_device = true; p->mb_device_ranks++; }
         else (void) hipGetLastError();
     }
-    HIP_TRY(p, hipMalloc((void**) &p->d_mb_peers, peers.size() * sizeof(void*)));
-    HIP_TRY(p, hipMemcpy(p->d_mb_peers, peers.data(), peers.size() * sizeof(void*), hipMemcpyHostToDevice));
+    if (hipError_t e = vv::upload(p->d_mb_peers, peers); e != hipSuccess) return give_up(e, "upload of the peer table");
     p->mb_on = true;
     return VVHIP_OK;
 }
@@ -2389,7 +2329,7 @@ int vvhip_mailbox_status(vvhip_plan* p, int32_t* active, int32_t* timed_out) {
         if (p->d_mb_ctl) {
             unsigned int ctl[4];
             HIP_TRY(p, hipStreamSynchronize(p->stream));
-            HIP_TRY(p, hipMemcpy(ctl, p->d_mb_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+            HIP_TRY(p, hipMemcpy(ctl, p->d_mb_ctl.get(), sizeof ctl, hipMemcpyDeviceToHost));
             *timed_out = (int32_t) ctl[0];
         }
     }
@@ -2518,26 +2458,32 @@ int vvhip_debug_read_accumulators(vvhip_plan* p, double out[4], int zero_after) 
     NEED_BOUND(p);
     static long long raw[vv::NUM_ACC * vv::ACC_SLOTS];
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(raw, p->d_acc + p->cur.parity * acc_stride(p), 4 * vv::ACC_SLOTS * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(p, hipMemcpy(raw, p->d_acc.get() + p->cur.parity * acc_stride(p), 4 * vv::ACC_SLOTS * sizeof(long long), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) {                 // the ABI hands out the three group sums and the bias moment
         long long s = 0;
         for (int j = 0; j < vv::ACC_SLOTS; j++) s += raw[i * vv::ACC_SLOTS + j];
         out[i] = (double) s * p->acc_inv_scale[i];
     }
-    if (zero_after) HIP_TRY(p, hipMemsetAsync(p->d_acc + p->cur.parity * acc_stride(p), 0, 4 * vv::ACC_SLOTS * sizeof(long long), p->stream));
+    if (zero_after) HIP_TRY(p, hipMemsetAsync(p->d_acc.get() + p->cur.parity * acc_stride(p), 0, 4 * vv::ACC_SLOTS * sizeof(long long), p->stream));
     return VVHIP_OK;
 }
 int vvhip_debug_set_scales(vvhip_plan* p, const double scales[4]) {
     NEED_BOUND(p);
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    HIP_TRY(p, hipMemcpy(p->d_nh[p->cur.parity].scales, scales, 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(p, hipMemcpy(p->d_nh.get()[p->cur.parity].scales, scales, 4 * sizeof(double), hipMemcpyHostToDevice));
     return VVHIP_OK;
 }
 
 int vvhip_debug_old_delta(vvhip_plan* p, void** device_ptr) {
     NEED_BOUND(p);
     if (!device_ptr) return VVHIP_ERR_INVALID;
-    *device_ptr = p->d_old_delta;
+    *device_ptr = p->d_old_delta.get();
+    return VVHIP_OK;
+}
+int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes) {
+    if (!count || !bytes) return VVHIP_ERR_INVALID;
+    *count = (int64_t) vv::live_buffers.load();
+    *bytes = (int64_t) vv::live_bytes.load();
     return VVHIP_OK;
 }
 
