@@ -401,6 +401,44 @@ int vvhip_remove_cm_motion(vvhip_plan* plan, double v_removed[3]);
 /* Synchronises and copies the schedule's record; VVHIP_ERR_OVERFLOW (record filled) if a scheduled removal was skipped.  The host-only
  * fields (frequency, total_mass) are filled on an unbound plan too. */
 int vvhip_cm_motion_read(vvhip_plan* plan, vvhip_cm_motion_record* out);
+/* ---------------------------------------------------------------- Maxwell-Boltzmann start velocities on the device
+ * What context.setVelocitiesToTemperature(T) gives a run inside OpenMM (examples/run-bulk.py:87): a stand-alone host has no such service.
+ * One kernel (csrc/vv_dev_thermalize.inc) writes velm.xyz of this plan's particles; velm.w, positions, forces, thermostat state,
+ * accumulators, rendezvous words, the four status words and the series / CM records are not touched.  The result is a pure function of
+ * (seed, global particle index, masses, T, T_D) -- not of the wave layout, the launch shape or the shard split, so every rank of a
+ * sharded run draws its own particles and the shards' arrays concatenate to the unsharded draw.  For particle g with mass m > 0
+ *     (w0 .. w3) = Philox4x32-10(counter {g, 0, 0, 0x5654}, key {seed & 0xffffffff, seed >> 32})
+ *     u0 = (w0 + 1) 2^-32, u1 = w1 2^-32, u2 = (w2 + 1) 2^-32, u3 = w3 2^-32,   r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2)
+ *     n(g) = (r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3)
+ * in float64, and with R = 8.31446261815324e-3 kJ/(mol K)
+ *     plain mode (drude_temperature < 0; OpenMM's documented behaviour):   v = sqrt(R T / m) n(g)
+ *     Drude-aware mode (drude_temperature >= 0), a pair (d, p) with both masses > 0:   M = m_d + m_p, mu = m_d m_p / M,
+ *         V = sqrt(R T / M) n(p), w = sqrt(R T_D / mu) n(d), v_d = V + (m_p / M) w, v_p = V - (m_d / M) w;   everybody else as in plain mode
+ * Massless particles (images, virtual sites, merged Drudes) get v = 0.  The store rounds to the mode's `mixed` type.  This is OpenMM's
+ * behaviour as documented, stated in float64, NOT pinned against OpenMM's bits or its random stream.
+ * The call works in the plan's stream behind whatever is queued: (1) the draw; (2) unless VVHIP_THERMALIZE_NO_CONSTRAINTS is set, on a plan
+ * that solves its constraints in-kernel (constraints_fused with constraint distances given), one launch of kernel A with exactly the
+ * plan's velocity-constraint stages on the bound positions at the current constraint tolerance (the bound arrays must already hold the
+ * positions and, in velm.w, the inverse masses: this launch reads them, and the plan's static mass tables are filled from velm.w by
+ * the first launch that uses them) -- OpenMM's applyVelocityConstraints
+ * after the draw (record.constrained = 1; otherwise 0, and a host with a solver of its own applies it); (3) with
+ * VVHIP_THERMALIZE_REMOVE_CM one removal as by the one-off call above (record.cm_removed = 1, v_removed = the V subtracted).  Then it
+ * blocks and fills the record.  The step counter, the thermostat state and the Langevin generator (its seed and epoch) are not touched;
+ * captured graphs stay valid (velocities are data, not arguments).
+ * Refused: temperature < 0 or not finite, drude_temperature NaN or infinite, unknown flag bits (VVHIP_ERR_INVALID); VVHIP_THERMALIZE_REMOVE_CM
+ * on a sharded plan (VVHIP_ERR_UNSUPPORTED, before anything is drawn); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID). */
+#define VVHIP_THERMALIZE_NO_CONSTRAINTS 1   /* leave the raw draw (tests; hosts with their own solver) */
+#define VVHIP_THERMALIZE_REMOVE_CM      2   /* then one removal of the centre-of-mass motion */
+typedef struct {
+    int64_t drawn;                  /* this plan's particles with mass > 0: every one got a fresh velocity */
+    int64_t pairs_split;            /* Drude pairs drawn as centre of mass + relative motion (0 in plain mode) */
+    int64_t zeroed;                 /* this plan's massless particles: velocity set to 0 */
+    int32_t constrained;            /* 1: the in-kernel velocity constraints ran on the draw */
+    int32_t cm_removed;             /* 1: the centre-of-mass velocity was removed */
+    double v_removed[3];            /* ... and what was subtracted, nm/ps (0 otherwise) */
+} vvhip_thermalize_record;
+int vvhip_set_velocities_to_temperature(vvhip_plan* plan, double temperature, double drude_temperature /* < 0: plain */,
+                                        uint64_t seed, uint32_t flags, vvhip_thermalize_record* out /* may be NULL */);
 
 /* Device pointer of the plan-owned forceExtra array (real3[n]); getForceExtra() of the reference
  * (CudaVVKernels.h:86-88). */

@@ -276,6 +276,8 @@ struct vvhip_plan {
         vv::DevBuf<vv::CmmDevRecord> d_rec;       // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
         vv::PinnedBuf<double> h_v;                // pinned: the V of a one-off call as copied back
     } cmm;
+    // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature): HostPlan::therm_laneless, uploaded by the first call
+    vv::DevBuf<int32_t> d_therm_laneless;
 };
 
 static void drop_graphs(vvhip_plan* p) {
@@ -1593,6 +1595,57 @@ int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
     *out = r;
     if (r.skipped > 0)
         return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: " + std::to_string((long long) r.skipped) + " scheduled removal(s) skipped: a momentum term was NaN or beyond the fixed-point range");
+    return VVHIP_OK;
+}
+// ------------------------------------------------------------------------------------------ Maxwell-Boltzmann start velocities
+int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, double drude_temperature, uint64_t seed, uint32_t flags,
+                                        vvhip_thermalize_record* out) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!(temperature >= 0) || !std::isfinite(temperature))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: the temperature must be finite and >= 0 K");
+    if (std::isnan(drude_temperature) || (drude_temperature >= 0 && !std::isfinite(drude_temperature)))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: the Drude temperature must be finite (>= 0 K), or negative for the plain draw");
+    if (flags & ~(uint32_t) (VVHIP_THERMALIZE_NO_CONSTRAINTS | VVHIP_THERMALIZE_REMOVE_CM))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: unknown flag bits");
+    const bool remove_cm = (flags & VVHIP_THERMALIZE_REMOVE_CM) != 0;
+    if (remove_cm && cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    // (the library's own captures, and a host that is capturing the plan's stream itself: the call has to block for its record)
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (p->capturing || (hipStreamIsCapturing(p->stream, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: not inside a graph capture");
+    TRY(settle_recovery(p));
+    const vv::HostPlan& hp = p->hp;
+    if (!p->d_therm_laneless) HIP_TRY(p, vv::upload(p->d_therm_laneless, hp.therm_laneless, 16));
+    if (remove_cm) TRY(cmm_ensure(p));
+    constexpr double R = 8.31446261815324e-3;
+    vv::ThermalizeArgs a{};
+    a.velm = p->buf.velm; a.slots = p->d_slots.get(); a.lane_mass = p->d_rep_lane_mass.get();
+    a.laneless = p->d_therm_laneless.get(); a.nwaves = hp.info.num_waves; a.nlaneless = (int32_t) hp.therm_laneless.size();
+    a.shard_begin = hp.shard_begin; a.drude_aware = drude_temperature >= 0 ? 1 : 0;
+    a.key[0] = (uint32_t) seed; a.key[1] = (uint32_t) (seed >> 32);
+    a.kt = R * temperature; a.kt_drude = a.drude_aware ? R * drude_temperature : 0.0;
+    HIP_TRY(p, vv::launch_thermalize(hp.precision, a, p->grid_cap_a, p->stream));
+    vvhip_thermalize_record r{};
+    r.drawn = hp.therm_massive; r.zeroed = hp.therm_massless; r.pairs_split = a.drude_aware ? hp.therm_pairs : 0;
+    // OpenMM's applyVelocityConstraints after the draw: kernel A with the plan's constraint stages and nothing else
+    if (!(flags & VVHIP_THERMALIZE_NO_CONSTRAINTS) && hp.info.constraints_fused && cons_a(p) != 0) {
+        TRY(run_a(p, cons_a(p), 0));
+        r.constrained = 1;
+    }
+    if (remove_cm) {
+        TRY(cmm_enqueue(p, 1));
+        HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    }
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (remove_cm) {
+        if (std::isnan(p->cmm.h_v[0]))
+            return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+        r.cm_removed = 1;
+        std::memcpy(r.v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
+    }
+    if (out) *out = r;
     return VVHIP_OK;
 }
 static void series_release(vvhip_plan* p) {

@@ -289,4 +289,19 @@ struct CmmArgs {
     double inv_total_mass;          // 1 / sum of the masses > 0, formed in double on the host (0 without massive particles)
 };
 
+// Maxwell-Boltzmann start velocities (vv_dev_thermalize.inc, vvhip_set_velocities_to_temperature): a pure function of the seed, the GLOBAL
+// particle index (shard_begin + the slot's index), the masses and the two temperatures -- nothing of the wave layout, the launch shape or
+// the shard split enters.  lane_mass is the report's table (ReportArgs); a Drude pair shares a wave (META_PARTNER_SHIFT), so the partner's
+// mass and index come from its lane.  Massless particles that have no lane (image particles, hosted virtual sites) are listed in `laneless`.
+struct ThermalizeArgs {
+    void* velm;
+    const int2* slots;
+    const double* lane_mass;        // [64*waves] mass, 0 where massless
+    const int32_t* laneless;        // [nlaneless] shard-relative indices of the massless particles without a lane: velm.xyz = 0
+    int32_t nwaves, nlaneless;
+    int32_t shard_begin, drude_aware;
+    uint32_t key[2];                // seed & 0xffffffff, seed >> 32
+    double kt, kt_drude;            // R T and R T_D, kJ/mol (the products formed in double on the host)
+};
+
 }  // namespace vv

@@ -14,3 +14,4 @@
 #include "vv_dev_misc.inc"
 #include "vv_dev_report.inc"
 #include "vv_dev_cmm.inc"
+#include "vv_dev_thermalize.inc"

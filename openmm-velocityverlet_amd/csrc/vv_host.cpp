@@ -990,6 +990,18 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
             hp.report_cross.insert(hp.report_cross.end(), rec, rec + 4);
             hp.report_cross_mu.push_back(reduced(d, c));
         }
+        // Maxwell-Boltzmann start velocities (vv_host.hpp: therm_*)
+        std::vector<char> has_lane((size_t) (se - sb), 0);
+        for (size_t k = 0; k < ns; k++) if (slots[2 * k] >= 0) has_lane[(size_t) slots[2 * k]] = 1;
+        for (int i = sb; i < se; i++) {
+            if (sys.masses[i] > 0) { hp.therm_massive++; continue; }
+            hp.therm_massless++;
+            if (!has_lane[(size_t) (i - sb)]) hp.therm_laneless.push_back(i - sb);
+        }
+        for (int k = 0; k < npairs_all; k++) {
+            const int d = sys.drude_pairs[2 * k], c = sys.drude_pairs[2 * k + 1];
+            if (in_shard(d) && in_shard(c) && reduced(d, c) > 0) hp.therm_pairs++;
+        }
     }
     return hp;
 }

@@ -93,6 +93,11 @@ struct HostPlan {
     // the sum of the masses > 0 of the WHOLE system, added up in particle order
     bool has_cm_motion_remover = false;
     double cm_total_mass = 0;
+    // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature; vv_dev_thermalize.inc), counts of THIS plan's particles:
+    // massive ones, massless ones, Drude pairs with two masses > 0 (what the Drude-aware mode splits); and the massless particles that
+    // have no lane (image particles, virtual sites placed from a parent's lane), shard-relative
+    int64_t therm_massive = 0, therm_massless = 0, therm_pairs = 0;
+    std::vector<int32_t> therm_laneless;
     // reference-style tables, kept for inspection / tests (global particle indices)
     std::vector<int32_t> particles_nh, molecules_nh, normal_nh, pairs_nh, normal_ld, pairs_ld;
 };

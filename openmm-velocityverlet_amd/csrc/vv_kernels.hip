@@ -501,6 +501,11 @@ hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, 
     VV_DISPATCH(vv_kernel_cmm_subtract, dim3((unsigned) g), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_cap, hipStream_t s) {
+    const int g = std::max(1, std::min(std::max((a.nwaves + 7) / 8, (a.nlaneless + 511) / 512), grid_cap));
+    VV_DISPATCH(vv_kernel_thermalize, dim3((unsigned) g), dim3(512), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

@@ -383,6 +383,23 @@ class Context:
         self.velm.upload(velm)
         self.forces_valid = False                               # VVIntegrator.h:447-449 stateChanged
 
+    def setVelocitiesToTemperature(self, temperature, randomSeed=None, drude_temperature=None, remove_cm=False,
+                                   constraints=True) -> H.ThermalizeRecord:
+        """Maxwell-Boltzmann velocities at `temperature` [K] for this context's particles, drawn on the device
+        (include/vvhip.h: vvhip_set_velocities_to_temperature): OpenMM's Context.setVelocitiesToTemperature(temperature, randomSeed).
+        randomSeed=None takes the integrator's getRandomNumberSeed().  drude_temperature=None is OpenMM's meaning (every massive particle
+        at `temperature`); a value >= 0 draws each Drude pair's centre of mass at `temperature` and its relative motion at
+        drude_temperature.  The plan's in-kernel velocity constraints are applied to the draw unless constraints=False; remove_cm=True
+        then removes the centre-of-mass velocity once.  A function of (seed, global particle index, masses, temperatures) alone, so the
+        shards of a sharded run draw their own particles.  Blocks; returns the record."""
+        seed = self.integrator.getRandomNumberSeed() if randomSeed is None else randomSeed
+        flags = (0 if constraints else H.THERMALIZE_NO_CONSTRAINTS) | (H.THERMALIZE_REMOVE_CM if remove_cm else 0)
+        out = H.ThermalizeRecord()
+        H.check(H.lib.vvhip_set_velocities_to_temperature(self.plan, float(temperature), -1.0 if drude_temperature is None else float(drude_temperature),
+                                                          int(seed) & 0xFFFFFFFFFFFFFFFF, flags, C.byref(out)), self.plan)
+        self.forces_valid = False                               # VVIntegrator.h:447-449 stateChanged
+        return out
+
     def getKineticEnergy(self) -> float:
         """1/2 sum m v^2 [kJ/mol] (what State.getKineticEnergy() returns through VVIntegrator::computeKineticEnergy)."""
         ke = C.c_double()

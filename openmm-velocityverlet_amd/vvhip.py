@@ -108,6 +108,15 @@ class CmMotionRecord(C.Structure):
                 ("last_v", C.c_double * 3), ("total_mass", C.c_double)]
 
 
+THERMALIZE_NO_CONSTRAINTS, THERMALIZE_REMOVE_CM = 1, 2
+
+
+class ThermalizeRecord(C.Structure):
+    """What one draw of Maxwell-Boltzmann start velocities did (include/vvhip.h: vvhip_thermalize_record)."""
+    _fields_ = [("drawn", C.c_int64), ("pairs_split", C.c_int64), ("zeroed", C.c_int64), ("constrained", C.c_int32),
+                ("cm_removed", C.c_int32), ("v_removed", C.c_double * 3)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -144,6 +153,7 @@ def _load():
         "vvhip_series_read": [vp, vp, i32, P(i32), P(C.c_int64), P(C.c_int64), i32], "vvhip_debug_series_guard": [vp, P(i32)],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
+        "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
         "vvhip_device_count": [P(C.c_int)], "vvhip_set_device": [C.c_int],
         "vvhip_malloc": [P(vp), C.c_size_t], "vvhip_free": [vp],
         "vvhip_memcpy_h2d": [vp, vp, C.c_size_t], "vvhip_memcpy_d2h": [vp, vp, C.c_size_t],
