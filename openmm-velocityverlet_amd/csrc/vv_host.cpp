@@ -464,8 +464,8 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
         // waves.  In between (round 4, tools/probes/layout_crossover.py, each layout with its own best launch shape, steps/s best-fit |
         // arithmetic): 222 k particles 66.0 | 57.7 k, 444 k 38.5 | 35.5 k, 666 k 26.8 | 25.0 k, 888 k 18.75 | 18.91 k, 1.33 M 13.6 | 14.1 k,
         // 2.7 M 7.1 | 7.5 k, 4.4 M 4.12 | 4.63 k.  (Round 2 had put the switch at 0.2 M lanes, +3 .. +7 % then: two blocks of 6-7 tile waves
-        // per CU, vv_api.cpp: pick_launch_shape, took the best-fit layout past it.)  With the chain kept inside kernel B up to 2.6 M particles
-        // (vv_api.cpp: split_chain_waves) the two meet a little higher: 888 k particles 20.8 | 20.6 k, 1.33 M 14.3 | 14.5 k, 1.78 M 11.2 | 11.4 k.
+        // per CU, vv_launch.cpp: pick_launch_shape, took the best-fit layout past it.)  With the chain kept inside kernel B up to 2.6 M particles
+        // (vv_plan.hpp: split_chain_waves) the two meet a little higher: 888 k particles 20.8 | 20.6 k, 1.33 M 14.3 | 14.5 k, 1.78 M 11.2 | 11.4 k.
         // So: from 1.1 M lanes, unless VVHIP_PERIODIC=1 / 0 says always / never.
         size_t lanes = 0;
         for (const Cluster& c : clusters) lanes += c.members.size();

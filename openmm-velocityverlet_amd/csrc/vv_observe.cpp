@@ -1,0 +1,334 @@
+// vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
+// the series of its rows, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.
+#include "vv_plan.hpp"
+
+// The steps i = 1 .. steps after step counter c0 that append a series row (empty without a series)
+std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps) {
+    std::vector<int> r;
+    if (!p->series.on) return r;
+    const long long k = p->series.interval;
+    for (long long i = k - c0 % k; i <= steps; i += k) r.push_back((int) i);
+    return r;
+}
+// The steps i = 0 .. steps - 1 after step counter c0 with a removal of the centre-of-mass motion in front (empty without a schedule)
+std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps) {
+    std::vector<int> r;
+    if (!p->cmm.on) return r;
+    const long long f = p->cmm.frequency;
+    for (long long i = (f - c0 % f) % f; i < steps; i += f) r.push_back((int) i);
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------ Drude temperature report
+// The two passes' arguments on `scratch` ([8] result words, then [6 per molecule] momentum words; zero on entry)
+static vv::ReportArgs report_args(const vvhip_plan* p, long long* scratch) {
+    const vv::HostPlan& hp = p->hp;
+    vv::ReportArgs a{};
+    a.velm = p->buf.velm; a.slots = p->d_slots.get();
+    a.lane_mol = p->d_rep_lane_mol.get(); a.lane_mass = p->d_rep_lane_mass.get(); a.lane_mu = p->d_rep_lane_mu.get();
+    a.mol_mass = p->d_rep_mol_mass.get(); a.cross = p->d_rep_cross.get(); a.cross_mu = p->d_rep_cross_mu.get();
+    a.out = scratch; a.mol_p = scratch ? scratch + 8 : nullptr;
+    a.nwaves = hp.info.num_waves; a.nmol = (int) hp.report_mol_mass.size(); a.ncross = (int) hp.report_cross_mu.size();
+    a.frac_bits = hp.report_frac_bits;
+    a.unit = std::ldexp(1.0, hp.report_unit_bits); a.frac_scale = std::ldexp(1.0, hp.report_frac_bits);
+    a.inv_unit = std::ldexp(1.0, -hp.report_unit_bits); a.inv_full = std::ldexp(1.0, -hp.report_unit_bits - hp.report_frac_bits);
+    a.limit = hp.report_limit;
+    return a;
+}
+
+// ------------------------------------------------------------------------------------------ series (vvhip_series_*)
+// One row behind the step just enqueued (or captured): the report's passes on the series' scratch, then the append kernel, which also
+// zeroes that scratch again.  Three kernel launches, no memset and no host synchronisation.
+static int series_row(vvhip_plan* p) {
+    vvhip_plan::Series& S = p->series;
+    vv::SeriesArgs a{};
+    if (S.mask & VVHIP_SERIES_DRUDE) {
+        HIP_TRY(p, vv::launch_report(p->hp.precision, report_args(p, S.d_scratch.get()), p->block_threads, p->grid_cap_a, p->stream));
+        a.rep_out = S.d_scratch.get(); a.rep_mol_p = S.d_scratch.get() + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
+    }
+    if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh.get()[p->cur.parity].s;
+    a.rows = S.d_rows.get(); a.cursor = S.d_cursor.get(); a.capacity = S.capacity;
+    for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
+    a.cos_acceleration = p->hp.params.cos_acceleration;
+    HIP_TRY(p, vv::launch_series_append(a, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// A full step has been enqueued (or captured): count it, and append a row when it is due.
+int step_done(vvhip_plan* p) {
+    p->cur.step_count++;
+    if (p->series.on && p->cur.step_count % p->series.interval == 0) return series_row(p);
+    return VVHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
+static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
+static int cmm_ensure(vvhip_plan* p) {
+    vvhip_plan::CmMotion& M = p->cmm;
+    if (M.d_words && M.d_rec && M.h_v) return VVHIP_OK;
+    HIP_TRY(p, vv::zeros(M.d_words, vv::CMM_WORDS * sizeof(long long), p->stream));
+    HIP_TRY(p, vv::zeros(M.d_rec, 2 * sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, M.h_v.alloc(3 * sizeof(double)));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    return VVHIP_OK;
+}
+// The pair of kernels behind what is queued (or captured); which = 0: a scheduled removal, 1: a one-off call (records of their own)
+static int cmm_enqueue(vvhip_plan* p, int which) {
+    TRY(settle_recovery(p));
+    vv::CmmArgs a{};
+    a.rep = report_args(p, nullptr);
+    a.words = p->cmm.d_words.get();
+    a.rec = p->cmm.d_rec.get() + which;
+    a.inv_total_mass = p->hp.cm_total_mass > 0 ? 1.0 / p->hp.cm_total_mass : 0.0;
+    HIP_TRY(p, vv::launch_cm_motion(p->hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// A full step is about to be enqueued (or captured): the removal in front of it when its index is due.  The one hook of every entry point
+// that starts a step (next to step_done, which ends it).
+int step_begin(vvhip_plan* p) {
+    if (p->cmm.on && p->cur.step_count % p->cmm.frequency == 0) return cmm_enqueue(p, 0);
+    return VVHIP_OK;
+}
+static void series_release(vvhip_plan* p) {
+    vvhip_plan::Series& S = p->series;
+    S.d_rows.reset(); S.d_cursor.reset(); S.d_scratch.reset();
+    S.on = false; S.interval = S.capacity = S.mask = 0; S.k0 = 0;
+}
+
+extern "C" {
+
+int vvhip_drude_report_dof(const vvhip_plan* p, double dof[3]) {
+    if (!p || !dof) return VVHIP_ERR_INVALID;
+    for (int g = 0; g < 3; g++) dof[g] = p->hp.report_dof[g];
+    return VVHIP_OK;
+}
+int vvhip_drude_report_raw(vvhip_plan* p, int64_t raw[6]) {
+    NEED_BOUND(p);
+    if (!raw) return VVHIP_ERR_INVALID;
+    const vv::HostPlan& hp = p->hp;
+    if (!hp.report_unsupported.empty()) return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + hp.report_unsupported);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "Drude temperature report: not inside a graph capture");
+    TRY(settle_recovery(p));
+    const int nmol = (int) hp.report_mol_mass.size();
+    HIP_TRY(p, hipMemsetAsync(p->d_rep.get(), 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
+    HIP_TRY(p, vv::launch_report(hp.precision, report_args(p, p->d_rep.get()), p->block_threads, p->grid_cap_a, p->stream));
+    HIP_TRY(p, hipMemcpyAsync(p->h_rep.get(), p->d_rep.get(), vv::REP_WORDS * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (p->h_rep[vv::REP_FLAG])
+        return fail(p, VVHIP_ERR_OVERFLOW, "Drude temperature report: a kinetic-energy or momentum term is NaN or beyond the fixed-point range; no numbers");
+    std::memcpy(raw, p->h_rep.get(), 6 * sizeof(int64_t));
+    return VVHIP_OK;
+}
+int vvhip_drude_report_combine(const vvhip_plan* p, const int64_t raw[6], double ke[3], double t[3]) {
+    if (!p || !raw) return VVHIP_ERR_INVALID;
+    const int F = p->hp.report_frac_bits, U = p->hp.report_unit_bits;
+    auto join = [F, U](int64_t hi, int64_t lo) {        // (hi + lo 2^-F) 2^-U with the carry of lo (of either sign) moved into hi first
+        const int64_t carry = lo >> F;                  // (arithmetic shift: floor)
+        return (double) (hi + carry) * std::ldexp(1.0, -U) + (double) (lo - carry * ((int64_t) 1 << F)) * std::ldexp(1.0, -U - F);
+    };
+    const int T = vv::REP_TOTAL, D = vv::REP_DRUDE, M = vv::REP_COM;
+    const double two_ke[3] = {join(raw[M], raw[M + 1]),
+                              join(raw[T] - raw[M] - raw[D], raw[T + 1] - raw[M + 1] - raw[D + 1]),      // KE_Atom = KE_total - KE_COM - KE_Drude
+                              join(raw[D], raw[D + 1])};
+    constexpr double R = 8.31446261815324e-3;
+    for (int g = 0; g < 3; g++) {
+        const double k = 0.5 * two_ke[g], dof = p->hp.report_dof[g];
+        if (ke) ke[g] = k;
+        if (t) t[g] = dof > 0 ? 2 * k / (dof * R) : 0.0;
+    }
+    return VVHIP_OK;
+}
+int vvhip_drude_temperatures(vvhip_plan* p, double ke[3], double t[3]) {
+    int64_t raw[6];
+    TRY(vvhip_drude_report_raw(p, raw));
+    return vvhip_drude_report_combine(p, raw, ke, t);
+}
+
+int vvhip_cm_motion_start(vvhip_plan* p, int32_t frequency) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (frequency < 1) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: frequency must be >= 1 step");
+    if (!p->hp.has_cm_motion_remover)
+        return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: the plan was described without a CMMotionRemover (has_cm_motion_remover = 0), so the thermostat's "
+                                          "degrees of freedom (DOF) still count the 3 of the centre of mass; describe the System with the remover to schedule removals");
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    TRY(settle_recovery(p));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (removals of a schedule before may still be in flight)
+    TRY(cmm_ensure(p));
+    HIP_TRY(p, hipMemsetAsync(p->cmm.d_rec.get(), 0, sizeof(vv::CmmDevRecord), p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    drop_graphs(p);
+    p->cmm.on = true; p->cmm.frequency = frequency;
+    return VVHIP_OK;
+}
+int vvhip_cm_motion_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    if (!p->cmm.on) return VVHIP_OK;
+    TRY(settle_recovery(p));
+    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    p->cmm.on = false; p->cmm.frequency = 0;
+    drop_graphs(p);
+    return VVHIP_OK;
+}
+int vvhip_remove_cm_motion(vvhip_plan* p, double v_removed[3]) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+    TRY(settle_recovery(p));
+    TRY(cmm_ensure(p));
+    TRY(cmm_enqueue(p, 1));
+    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (std::isnan(p->cmm.h_v[0]))      // (what the subtract kernel records for a removal it skipped)
+        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+    if (v_removed) std::memcpy(v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
+    return VVHIP_OK;
+}
+int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_cm_motion_record r{};
+    r.frequency = p->cmm.on ? p->cmm.frequency : 0;
+    r.total_mass = p->hp.cm_total_mass;
+    if (p->bound && p->cmm.d_rec) {
+        if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
+        TRY(settle_recovery(p));                        // (a repaired run redoes its removals first)
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        vv::CmmDevRecord d{};
+        HIP_TRY(p, hipMemcpy(&d, p->cmm.d_rec.get(), sizeof(d), hipMemcpyDeviceToHost));
+        r.removals = d.removals; r.skipped = d.skipped;
+        for (int k = 0; k < 3; k++) r.last_v[k] = d.last_v[k];
+    }
+    *out = r;
+    if (r.skipped > 0)
+        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: " + std::to_string((long long) r.skipped) + " scheduled removal(s) skipped: a momentum term was NaN or beyond the fixed-point range");
+    return VVHIP_OK;
+}
+// ------------------------------------------------------------------------------------------ Maxwell-Boltzmann start velocities
+int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, double drude_temperature, uint64_t seed, uint32_t flags,
+                                        vvhip_thermalize_record* out) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!(temperature >= 0) || !std::isfinite(temperature))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: the temperature must be finite and >= 0 K");
+    if (std::isnan(drude_temperature) || (drude_temperature >= 0 && !std::isfinite(drude_temperature)))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: the Drude temperature must be finite (>= 0 K), or negative for the plain draw");
+    if (flags & ~(uint32_t) (VVHIP_THERMALIZE_NO_CONSTRAINTS | VVHIP_THERMALIZE_REMOVE_CM))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: unknown flag bits");
+    const bool remove_cm = (flags & VVHIP_THERMALIZE_REMOVE_CM) != 0;
+    if (remove_cm && cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    NEED_BOUND(p);
+    // (the library's own captures, and a host that is capturing the plan's stream itself: the call has to block for its record)
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (p->capturing || (hipStreamIsCapturing(p->stream, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone))
+        return fail(p, VVHIP_ERR_INVALID, "start velocities: not inside a graph capture");
+    TRY(settle_recovery(p));
+    const vv::HostPlan& hp = p->hp;
+    if (!p->d_therm_laneless) HIP_TRY(p, vv::upload(p->d_therm_laneless, hp.therm_laneless, 16));
+    if (remove_cm) TRY(cmm_ensure(p));
+    constexpr double R = 8.31446261815324e-3;
+    vv::ThermalizeArgs a{};
+    a.velm = p->buf.velm; a.slots = p->d_slots.get(); a.lane_mass = p->d_rep_lane_mass.get();
+    a.laneless = p->d_therm_laneless.get(); a.nwaves = hp.info.num_waves; a.nlaneless = (int32_t) hp.therm_laneless.size();
+    a.shard_begin = hp.shard_begin; a.drude_aware = drude_temperature >= 0 ? 1 : 0;
+    a.key[0] = (uint32_t) seed; a.key[1] = (uint32_t) (seed >> 32);
+    a.kt = R * temperature; a.kt_drude = a.drude_aware ? R * drude_temperature : 0.0;
+    HIP_TRY(p, vv::launch_thermalize(hp.precision, a, p->grid_cap_a, p->stream));
+    vvhip_thermalize_record r{};
+    r.drawn = hp.therm_massive; r.zeroed = hp.therm_massless; r.pairs_split = a.drude_aware ? hp.therm_pairs : 0;
+    // OpenMM's applyVelocityConstraints after the draw: kernel A with the plan's constraint stages and nothing else
+    if (!(flags & VVHIP_THERMALIZE_NO_CONSTRAINTS) && hp.info.constraints_fused && cons_a(p) != 0) {
+        TRY(run_a(p, cons_a(p), 0));
+        r.constrained = 1;
+    }
+    if (remove_cm) {
+        TRY(cmm_enqueue(p, 1));
+        HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    }
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (remove_cm) {
+        if (std::isnan(p->cmm.h_v[0]))
+            return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+        r.cm_removed = 1;
+        std::memcpy(r.v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
+    }
+    if (out) *out = r;
+    return VVHIP_OK;
+}
+int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_t mask) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (interval < 1) return fail(p, VVHIP_ERR_INVALID, "series: interval must be >= 1 step");
+    if (capacity < 1) return fail(p, VVHIP_ERR_INVALID, "series: capacity must be >= 1 row");
+    if (mask == 0 || (mask & ~(VVHIP_SERIES_DRUDE | VVHIP_SERIES_THERMOSTAT)))
+        return fail(p, VVHIP_ERR_INVALID, "series: mask must be a non-empty set of VVHIP_SERIES_DRUDE / VVHIP_SERIES_THERMOSTAT");
+    if ((mask & VVHIP_SERIES_DRUDE) && !p->hp.report_unsupported.empty())
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + p->hp.report_unsupported);
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    TRY(settle_recovery(p));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (rows of a series before may still be in flight)
+    series_release(p);
+    drop_graphs(p);
+    vvhip_plan::Series& S = p->series;
+    const size_t row_bytes = sizeof(vvhip_series_row), scratch = (8 + 6 * p->hp.report_mol_mass.size()) * sizeof(long long);
+    HIP_TRY(p, vv::zeros(S.d_rows, ((size_t) capacity + 1) * row_bytes, p->stream));
+    HIP_TRY(p, hipMemsetAsync((char*) S.d_rows.get() + (size_t) capacity * row_bytes, kGuardByte, row_bytes, p->stream));
+    HIP_TRY(p, vv::zeros(S.d_cursor, 2 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, vv::zeros(S.d_scratch, scratch, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    S.on = true; S.interval = interval; S.capacity = capacity; S.mask = mask;
+    S.k0 = p->cur.step_count / interval + 1;               // the first multiple of interval after the current step
+    return VVHIP_OK;
+}
+int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_rows, int32_t* n_rows, int64_t* first_step, int64_t* dropped,
+                      int32_t reset) {
+    NEED_BOUND(p);
+    if (max_rows < 0 || (max_rows > 0 && !rows_out)) return VVHIP_ERR_INVALID;
+    vvhip_plan::Series& S = p->series;
+    if (!S.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    TRY(settle_recovery(p));                            // (a repaired run rewrites its rows first)
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    unsigned long long cur[2];
+    HIP_TRY(p, hipMemcpy(cur, S.d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost));
+    const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) S.capacity);
+    const long long copy = std::min<long long>(n, max_rows);
+    if (copy > 0) HIP_TRY(p, hipMemcpy(rows_out, S.d_rows.get(), (size_t) copy * sizeof(vvhip_series_row), hipMemcpyDeviceToHost));
+    if (n_rows) *n_rows = (int32_t) n;
+    if (first_step) *first_step = (int64_t) S.interval * S.k0;
+    if (dropped) *dropped = (int64_t) cur[1];
+    if (reset) {
+        HIP_TRY(p, hipMemsetAsync(S.d_cursor.get(), 0, 2 * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        S.k0 += (long long) cur[0];                     // (dropped rows included: their steps are gone)
+    }
+    return VVHIP_OK;
+}
+int vvhip_series_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
+    if (!p->series.on) return VVHIP_OK;
+    TRY(settle_recovery(p));
+    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    series_release(p);
+    drop_graphs(p);
+    return VVHIP_OK;
+}
+int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_series_layout r{};
+    r.row_bytes = (int32_t) sizeof(vvhip_series_row);
+    r.off_drude_raw = (int32_t) offsetof(vvhip_series_row, drude_raw);
+    r.off_nh = (int32_t) offsetof(vvhip_series_row, nh);
+    r.off_box = (int32_t) offsetof(vvhip_series_row, box);
+    r.active = p->series.on; r.interval = p->series.interval; r.capacity = p->series.capacity; r.mask = p->series.mask;
+    r.steps = p->cur.step_count;
+    r.graph_captures = p->graph_captures;
+    *out = r;
+    return VVHIP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,389 @@
+// vv_plan.hpp -- the one internal header of the C ABI (include/vvhip.h): the plan, and what more than one of its translation units calls.
+// "HOST" = platforms/cuda/src/CudaVVKernels.cpp, "API" = openmmapi/src/VVIntegrator.cpp of the reference.
+//
+//   vv_api.cpp       life cycle (create / tune / bind / parameters / destroy), the status words and vvhip_synchronize, the caller-owned
+//                    one-liners (vvhip_malloc ... vvhip_stream_*); fail, hip_fail, settle_recovery, check_exchange_health, drop_graphs
+//   vv_launch.cpp    fixed-point scales, launch shape, kernel arguments, ScopedTimer + roctx, run_a / run_b / run_chain / run_ke /
+//                    run_chain_and_b / run_fused and the checks in front of it, thermo_mode, the stage-bit helpers; vvhip_timing_*,
+//                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
+//   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
+//                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
+//   vv_observe.cpp   what rides beside the step: Drude report, series, removal of the centre-of-mass motion, start velocities;
+//                    step_begin / step_done and the schedules series_rows_in / cmm_steps_in
+//   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
+//                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
+//   vv_exchange.cpp  between the ranks: the RCCL loader and vvhip_comm_*, the xGMI mailbox, exchange_accumulators
+//   vv_debug.cpp     test hooks (vvhip_debug_* except vvhip_debug_tune), vvhip_time_kernel, the probes of the instrumented build
+//
+// Whatever one file alone uses is static (or in an anonymous namespace) there; what is declared here is hidden from the dynamic symbol
+// table, which holds the vvhip_* functions of include/vvhip.h and nothing else of these files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstddef>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <rccl/rccl.h>      // types and prototypes only: the library is resolved at run time (see rccl_api)
+
+#include "vv_devmem.hpp"
+#include "vv_host.hpp"
+#include "vv_kernels.hpp"
+#include "vv_rtc.hpp"
+
+#pragma GCC visibility push(hidden)
+
+// RCCL is looked up lazily so that single-GPU users never need it.  If the process already has a librccl (PyTorch
+// brings its own) that copy is used -- two RCCL builds in one process is asking for trouble.
+struct RcclApi {
+    void* handle = nullptr;
+    decltype(&ncclGetUniqueId) getUniqueId = nullptr;
+    decltype(&ncclCommInitRank) commInitRank = nullptr;
+    decltype(&ncclAllReduce) allReduce = nullptr;
+    decltype(&ncclCommDestroy) commDestroy = nullptr;
+    decltype(&ncclCommCount) commCount = nullptr;
+    decltype(&ncclGetErrorString) getErrorString = nullptr;
+    bool ok = false;
+};
+RcclApi& rccl_api();
+
+constexpr double kAvogadro = 6.02214076e23;
+constexpr double kBoltz = (1.380649e-23 * kAvogadro) / 1000.0;
+enum TimerClass { T_A = 0, T_B = 1, T_OTHER = 2 };
+constexpr int kAccN = vv::NUM_ACC * vv::ACC_SLOTS;
+constexpr int kRvCopy = 6 * kAccN;      // rendezvous words of one thermostat parity: up to 6 replicas (vv_device.inc: RV_REPLICAS) of [NUM_ACC][ACC_SLOTS]
+constexpr int kGuardByte = 0xA5;    // fills the guard row behind a series' last row (vvhip_series_start, vvhip_debug_series_guard)
+
+// How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
+// stands; thermo_mode is the one place that derives it.
+// COS_MOMENTS = the cos perturbation in two launches instead of three: kernel A accumulates the group sums as moments of the biased
+// velocities next to the bias moment itself, kernel B's inline chain finishes the algebra (vv_args.hpp: the moment bits).  Not with
+// molecules larger than a wave or the stand-alone chain launch (long chains, very large systems), which keep the bias -> KE -> scale
+// sequence of COS_THREE_LAUNCH (API:252-259).
+enum class ThermoMode { NO_NH, PLAIN, COS_MOMENTS, COS_THREE_LAUNCH };
+
+// The synthetic force provider of the plan-driven loops (vvhip_run_*: tether sites and the two spring constants; site = null: the host's forces)
+struct ForceProvider { const void* site; double kt, kd; };
+// What a captured graph depends on besides the thermostat parity of its slot
+struct GraphKey {
+    int steps = 0;
+    ForceProvider fp{};
+    std::vector<int> rows;                 // steps of the graph (1 .. steps) that append a series row
+    std::vector<int> cmm;                  // steps of the graph (0 .. steps - 1) with a removal of the centre-of-mass motion in front
+    bool operator==(const GraphKey& o) const {
+        return steps == o.steps && fp.site == o.fp.site && fp.kt == o.fp.kt && fp.kd == o.fp.kd && rows == o.rows && cmm == o.cmm;
+    }
+};
+
+struct vvhip_plan {
+    vv::HostPlan hp;
+    std::string err;
+    bool bound = false;
+    vvhip_buffers buf{};
+    hipStream_t stream = nullptr;
+    double box[3] = {1, 1, 1};
+    double acc_scale[vv::NUM_ACC], acc_inv_scale[vv::NUM_ACC];
+    int block_threads = 256;       // 64 x tile waves per block, the same for the force provider, kernel A and kernel B
+    int grid_cap_a = 2048, grid_cap_b = 1024;   // most blocks per launch (multiples of the CU count): see pick_launch_shape
+    int split_chain_waves = 44000;   // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
+                                     // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
+                                     // 1.33 M 14.5 | 14.0 k, 1.78 M 11.4 | 11.1 k, 2.66 M 7.38 | 7.37 k, 4.4 M 4.14 | 4.20 k, 8.9 M 2.16 | 2.21 k (round 2 had it at 12 288)
+    // The reference's kick kernels add forceExtra ALWAYS (K/middle.cu:11-21, K/velocityVerlet.cu:20-22) and the array is only reset in
+    // steps that have a source of extra forces (API:238-240, 316-318): once the cos acceleration is set to 0 in a run without Langevin
+    // particles or a field, the last cos force stays in forceExtra and every later kick keeps adding it.  The fused middle step computes
+    // extra forces on the fly and leaves the array alone; `cur.fextra_virtual` says the array SHOULD hold the cos force of the last fused
+    // step.  vvhip_set_params materialises it (kernel A from the cached cos(kz)) when the acceleration goes to 0, and a fused kick
+    // without sources loads the array whenever it is dirty -- the reference's behaviour to the bit, quirk included.
+    // The host's cursor through the steps: what a graph capture walks through its steps and puts back (prepare_slot) and what a recovery
+    // returns to its snapshot (Recovery::cur)
+    struct Cursor {
+        int parity = 0;                // which copy of the thermostat state / accumulators the next reduction/consumer pair uses
+        uint32_t random_pos = 0;       // prepareRandomNumbers cursor for the plan-driven loops (vvhip_run_*)
+        bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
+        bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
+        // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
+        // the series' rows (vvhip_series_*) and of the removals of the centre-of-mass motion
+        long long step_count = 0;
+    } cur;
+    bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
+    bool fextra_external = false;  // the host asked for the pointer (vvhip_force_extra) and may write to it: never assume zeros
+    bool no_moments = false;       // test hook "no_moments": keep the three-launch cos sequence (comparison runs)
+    // with an arithmetic work-item layout (HostPlan::per) the kernels compute particle indices instead of loading slot words (test hook "periodic_kernels" = 0:
+    // comparison runs).  Kernel A: no slot traffic (1.13 -> 1.0 x the algorithmic bytes) and the next tile's loads in flight during this tile's
+    // arithmetic: 133 vs 138 us in sequence at 8.9 M particles (round 2 without the second tile in flight: 113.6 vs 115.7 back to back);
+    // test hook "periodic_a" = 0 switches it off
+    bool periodic_kernels = true, periodic_a = true, periodic_b = true;
+    int shake_mode = 1;            // hydrogen-type constraint clusters: 1 = all constraints of a cluster at once (direct velocity solve, coupled Newton
+                                   // for positions), 0 = Gauss-Seidel sweeps by the central lane (OpenMM's iteration; generic kernels) -- VVHIP_SHAKE_MODE
+    // Race detection by timing (VVHIP_STALL=us[:period]): every period-th launch of this plan is preceded by a host sleep of `us` microseconds --
+    // the GPU drains, anything that was only ordered by the depth of the queue (a fill or copy on another stream, a host read without a
+    // synchronisation) lands differently, and the trajectory changes.  tests/test_gpu_stalls.py compares stalled and unstalled runs bit for bit.
+    long stall_us = 0, stall_period = 1, stall_count = 0;
+    bool acc_store = true;         // kernel A launches of <= 256 blocks store old + new into their accumulator slots instead of atomics (test hook "acc_store" = 0: atomics)
+    long long generic_launches[2] = {0, 0};   // kernel A / B launches of this plan (captured ones count once) that ran the generic kernel
+    uint32_t generic_flags[2] = {0, 0};       // ... and the last stage set that did (vvhip_generic_launches)
+    std::vector<uint32_t> generic_seen[2];    // every stage set that did (VVHIP_WARN_GENERIC prints each once)
+    bool rekick = true;            // fused middle step: kick repeated in kernel B instead of a velm store in kernel A (use_rekick)
+    // One launch per step (vv_device.inc: "fused step"): kernels A and B of the middle scheme as one launch of co-resident blocks around an
+    // in-kernel rendezvous.  `fused` = allowed (vvhip_debug_tune "fused": A/B comparisons and the bit-for-bit tests switch it off);
+    // d_rv = the rendezvous words, [2 thermostat parities][NUM_ACC][ACC_SLOTS], uncached; fused_checks = the pairs of stage sets / launch
+    // shapes whose kernel and occupancy were looked up and what came of it, fused_last = the entry the last attempt used (-1: none since the
+    // cache was emptied).
+    bool fused = true;
+    // the wait grows when more than blocks / 2^shift blocks needed a second round (test hook "fused_late_shift").  1/16 of the blocks (shift 4,
+    // the first choice) let the wait climb where the blocks finish their front unevenly (constraint clusters: 11 units against the best pinned 7);
+    // half of them: C3 + HBonds 80.2 -> 81.9 k steps/s, C4 83.1 -> 84.2 k, C5 + HBonds 96.0 -> 97.4 k, C2 150.4 -> 152.4 k, C3 / C5 + 0.4 %
+    // (profiles/r05s_late_shift_scan.txt)
+    int fused_late_shift = 1;
+    int fused_poll_delay = -1;     // >= 0: pins the wait between a block's publish and its first poll round, units of 256 clocks (test hook "fused_poll_delay"); -1: self-tuning
+    vv::DevBuf<unsigned long long> d_rv;
+    struct FusedCheck { uint32_t a = 0, b = 0; int threads = 0, waves = 0; bool ok = false; };
+    FusedCheck fused_checks[4];    // (the classic scheme alternates between the pairs of its two halves)
+    int fused_check_next = 0, fused_last = -1;
+    long long fused_launches = 0;
+    // Recovery from a missed rendezvous (round 6).  The one-launch step needs its blocks resident together; another process's kernel on the
+    // device can break that, the blocks' bounded wait then runs out (sticky word [2]) and the step -- and every step enqueued behind it -- has
+    // worked on incomplete sums.  The plan-driven loops (vvhip_run_graph / vvhip_run_eager) therefore keep a device-side copy of the physical
+    // state from the entry of the first run call that is not yet known to have ended well (positions, correction, velocities, forces, extra
+    // forces, both thermostat copies, the random generator's epoch: 116 B per particle in mixed precision, taken only for calls of at least
+    // `min_steps` steps) together with the run calls since; the next vvhip_synchronize that finds word [2] raised puts the copy back, pins
+    // the plan to two launches per step (bit for bit the same step), repeats the calls and says so once on stderr.  No multi-GPU exchange in
+    // between (the other ranks would have to repeat theirs).  `vvhip_debug_tune(plan, "recover", 0)` / VVHIP_RECOVER=0 switch it off.
+    struct Recovery {
+        bool enabled = true, valid = false, replaying = false, in_loop = false;
+        int min_steps = 64;
+        // the saved copies (vv_run.cpp: recovery_items pairs each with the live array it belongs to)
+        vv::DevBuf<void> posq, corr, velm, force, fextra, random, nh, epoch;
+        Cursor cur;                               // the host's cursor at the snapshot
+        struct Run { int kind, nsteps, spg; ForceProvider fp; };
+        std::vector<Run> runs;
+        long long recoveries = 0;
+        vv::DevBuf<void> series_cursor;               // the series' device-side row cursor (its schedule, the step counter, is in `cur`)
+        bool series_saved = false;
+        vv::DevBuf<void> cmm_rec;                 // the counters of the scheduled removals of the centre-of-mass motion
+        bool cmm_saved = false;
+    } rec;
+    // plan-owned device state: every buffer frees itself with the plan (vv_devmem.hpp)
+    vv::DevBuf<int2> d_slots;
+    vv::DevBuf<int32_t> d_slot_image;
+    vv::DevBuf<int32_t> d_slot_rand;
+    vv::DevBuf<int32_t> d_slot_big;
+    vv::DevBuf<int32_t> d_slot_shake;
+    vv::DevBuf<float4> d_slot_shake_param;
+    vv::DevBuf<int2> d_slot_vsite;
+    vv::DevBuf<double> d_vsite_params;
+    vv::DevBuf<int32_t> d_vsite_atom;
+    vv::DevBuf<unsigned long long> d_bigacc;
+    vv::DevBuf<int2> d_image_pairs;
+    vv::DevBuf<void> d_fextra;
+    vv::DevBuf<void> d_old_delta;
+    vv::DevBuf<void> d_pos_delta;  // used when the caller does not supply one
+    vv::DevBuf<void> d_comv;       // per-segment COM velocities handed from kernel A to kernel B
+    vv::DevBuf<double> d_slot_m;   // static per-lane RECIP(velm.w) (vv_args.hpp: A_MTAB), filled on the device from velm.w
+    vv::DevBuf<double> d_slot_f;   // static per-lane Drude-pair mass fraction (A_MTAB / B_MTAB)
+    bool mass_tab_a = false, mass_tab_b = true;   // kernel A / B launches read the tables (defaults follow the build; test hooks "mass_tab_a" / "mass_tab_b" override: comparison runs)
+    bool mass_tab_valid = false;   // tables match the bound velm.w (vvhip_bind / vvhip_masses_changed reset it)
+    vv::DevBuf<double> d_seg_mass; // static (mass, 1/mass) per COM segment
+    vv::DevBuf<int> d_seg_base;    // per wave: COM segments in the waves before it
+    vv::DevBuf<double> d_comw;     // per-segment mass-weighted mean of cos(kz) (moment form of the cos perturbation)
+    vv::DevBuf<double> d_cosz;     // per-lane cos(2 pi z / Lz) of the current step
+    vv::DevBuf<unsigned long long> d_acc;  // [2 parities][NUM_ACC][ACC_SLOTS]
+    vv::DevBuf<vv::NHDevState> d_nh;        // [2 parities]
+    vv::DevBuf<unsigned long long> d_epoch; // refill counter of the device Gaussian generator
+    uint64_t rng_seed = 0;
+    // HIP-event timing (eager launches only)
+    bool timing = false;
+    bool timing_kernels_only = false;   // vvhip_timing_enable(plan, 2): dispatch timestamps of kernels A and B only, nothing added to the stream
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> events[3];
+    std::vector<hipEvent_t> event_pool;  // events of earlier timing sessions, reused (hipEventCreate per launch would make the host the bottleneck)
+    // captured graph for vvhip_run_graph
+    // One executable per thermostat parity (the state is double-buffered by step parity, so a graph captured at parity q only
+    // replays correctly when the plan is at parity q again).  Captured by vvhip_graph_prepare / the first vvhip_run_graph that
+    // needs it, never re-captured while the key (steps, force provider) is unchanged: a run that alternates eager tails and
+    // replays keeps both.
+    struct GraphSlot {
+        hipGraphExec_t exec = nullptr;
+        GraphKey key;
+        uint32_t random_end = 0;               // prepareRandomNumbers cursor after the graph's last step
+    };
+    // (round 6: up to four graph lengths per parity -- a host that replays a short graph in front of a long one keeps both)
+    static constexpr int kGraphWays = 4;
+    GraphSlot graph[2][kGraphWays];
+    int graph_next[2] = {0, 0};
+    bool capturing = false;
+    // particle sharding over GPUs: RCCL communicator for the accumulator exchange (null = single GPU)
+    ncclComm_t comm = nullptr;
+    int comm_ranks = 1;
+    // ... or the xGMI mailbox (vv_args.hpp: Mailbox): no collective launch, works inside a captured graph
+    vv::DevBuf<unsigned long long> mb_local;      // uncached, exported through hipIpc
+    vv::DevBuf<unsigned long long*> d_mb_peers;   // device array of the peers' mappings
+    vv::DevBuf<unsigned int> d_mb_ctl;
+    std::vector<vv::IpcMapping> mb_opened;        // the peers' boxes as mapped here
+    int mb_ranks = 0, mb_rank = 0;
+    bool mb_on = false;
+    // A peer's box lives on THIS device (several ranks sharing one GPU: test set-ups): found out by vvhip_mailbox_connect.  Such ranks'
+    // kernels compete for the same CUs, and device-filling grids of polling thermostat waves keep the other process's kernels off
+    // the device until the bounded waits run out: every rank then launches on its share of the CUs (shared_device_cap).
+    bool mb_shared_device = false;
+    int dbg_seq = -1;              // instrumented build: >= 0 while vvhip_debug_step_spans numbers the launches of its steps
+    int mb_device_ranks = 1;       // ranks whose boxes live on this device (this one included)
+    // Sticky health word in pinned host memory, written by the kernels with system-scope stores when something goes wrong and
+    // read by the host without synchronising: [0] a mailbox wait on the peers ran out (the ranks have diverged), [1] a fixed-point
+    // accumulator left its range (|sum| x scale >= 2^62: the thermostat would see garbage).  Checked at the entry of the run loops
+    // and in vvhip_synchronize / vvhip_status.
+    vv::PinnedBuf<unsigned int> h_status;
+    unsigned int* d_status = nullptr;             // the same words as the device sees them
+    bool launch_shape_forced = false;             // a test hook fixed the launch shape ("block_threads", "grid_cap_a / b"): keep it at bind
+    int num_cus = 256;                            // hipDeviceProp_t::multiProcessorCount of the bound device
+    vv::DevBuf<vv::ChainLaneBlock> d_lane_const;  // [3] chain constants per temperature group (kernel B's thermostat wave)
+    vv::ChainLaneBlock lane_const_host[VVHIP_NUM_TG] = {};
+    bool lane_const_valid = false;
+    vv::DevBuf<long long> d_dbg_span;
+    int dbg_parity = 0;
+    vv::DevBuf<long long> d_dbg;                  // instrumented build only (vvhip_debug_timestamps)
+    int dbg_block = 0;
+    // Drude temperature report (vvhip_drude_temperatures): its tables (HostPlan::report_*) and its own scratch, nothing shared with the step
+    vv::DevBuf<int32_t> d_rep_lane_mol;
+    vv::DevBuf<double> d_rep_lane_mass;
+    vv::DevBuf<double> d_rep_lane_mu;
+    vv::DevBuf<double> d_rep_mol_mass;
+    vv::DevBuf<int4> d_rep_cross;
+    vv::DevBuf<double> d_rep_cross_mu;
+    vv::DevBuf<long long> d_rep;                  // [8] result words (vv_args.hpp: REP_*), then [6 per molecule] momentum words
+    vv::PinnedBuf<long long> h_rep;               // pinned: the result words as copied back
+    long long graph_captures = 0;
+    // Series (vvhip_series_*): the rows the steps append on the device, scheduled by cur.step_count
+    struct Series {
+        bool on = false;
+        int interval = 0, capacity = 0, mask = 0;
+        long long k0 = 0;                         // row 0 is step interval * k0
+        vv::DevBuf<vvhip_series_row> d_rows;      // [capacity + 1]: behind the last row a guard row (vvhip_debug_series_guard)
+        vv::DevBuf<unsigned long long> d_cursor;  // [2] rows appended (past capacity too), rows dropped
+        vv::DevBuf<long long> d_scratch;          // the report's scratch for the rows (as d_rep), zero between rows
+    } series;
+    // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
+    // allocated by the first call that needs them
+    struct CmMotion {
+        bool on = false;
+        int frequency = 0;
+        vv::DevBuf<long long> d_words;            // [CMM_WORDS] zero between removals
+        vv::DevBuf<vv::CmmDevRecord> d_rec;       // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
+        vv::PinnedBuf<double> h_v;                // pinned: the V of a one-off call as copied back
+    } cmm;
+    // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature): HostPlan::therm_laneless, uploaded by the first call
+    vv::DevBuf<int32_t> d_therm_laneless;
+};
+
+// ---- A thermostat application with the stages that ride on it, as data: what every step entry point launches, and what
+// vvhip_debug_fused_flags reports.  Phase k < phases - 1 is a launch of kernel A (through run_ke where it ends in the sums: molecules
+// larger than a wave split it), the last phase the chain and kernel B (run_chain_and_b), with the ranks' exchange between the phases;
+// without Nose-Hoover particles the one phase is kernel A, then kernel B, whichever has stages.
+struct ThermoApp {
+    ThermoMode mode = ThermoMode::NO_NH;
+    int phases = 1;
+    struct Launch { uint32_t flags = 0; bool sums = false; } a[2];
+    uint32_t b = 0;
+    bool with_bias = false;                     // the stand-alone chain launch also finishes the bias moment
+    bool one_launch = false;                    // (fused_a, fused_b) can be one launch (run_fused): the same sets without the hand-over bits
+    uint32_t fused_a = 0, fused_b = 0;
+    bool fe_virtual = false;                    // kernel A forms the cos force on the fly, and nothing else: see Cursor::fextra_virtual
+};
+
+struct ScopedTimer {
+    vvhip_plan* p;
+    int cls;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool on, ranged = false;
+    // dispatch = true: the launcher delivers the dispatch's own begin / end timestamps into e0 / e1 (kernels A and B: vv_launch);
+    // otherwise the events are recorded around the enqueued work (adds two barrier packets to the stream)
+    bool dispatch;
+    ScopedTimer(vvhip_plan* p_, int cls_, bool dispatch_ = false);
+    ~ScopedTimer();
+    ScopedTimer(const ScopedTimer&) = delete;
+};
+
+#define HIP_TRY(p, call)                                         \
+    do {                                                         \
+        hipError_t e_ = (call);                                  \
+        if (e_ != hipSuccess) return hip_fail(p, e_, #call);     \
+    } while (0)
+#define TRY(x)                       \
+    do {                             \
+        int rc_ = (x);               \
+        if (rc_ != VVHIP_OK) return rc_; \
+    } while (0)
+#define NEED_BOUND(p)                                                                  \
+    do {                                                                               \
+        if (!(p)) return VVHIP_ERR_INVALID;                                            \
+        if (!(p)->bound) return fail(p, VVHIP_ERR_INVALID, "vvhip_bind has not been called"); \
+    } while (0)
+#define NEED_FUSABLE(p)                                                                                                   \
+    do {                                                                                                                \
+        if (!(p)->hp.info.constraints_fused)                                                                            \
+            return fail(p, VVHIP_ERR_UNSUPPORTED, std::string("the System has constraints this backend cannot solve in-kernel") + ((p)->hp.unfused_reason.empty() ? "" : " (" + (p)->hp.unfused_reason + ")") + \
+                                                  ": use the split entry points around the host's constraint solver"); \
+    } while (0)
+
+inline size_t sizeof_real(int prec) { return prec == VVHIP_DOUBLE ? 8 : 4; }
+inline size_t sizeof_mixed(int prec) { return prec == VVHIP_SINGLE ? 4 : 8; }
+// one-line predicates and stage bits of the plan as it stands
+// distance between the two parity copies: only the rows in use (4 without the cos moments)
+inline int acc_stride(const vvhip_plan* p) { return (p->hp.params.cos_acceleration != 0 ? vv::NUM_ACC : 4) * vv::ACC_SLOTS; }
+inline bool periodic_b(const vvhip_plan* p) { return p->hp.per.enabled && p->periodic_kernels && p->periodic_b; }
+inline bool cos_on(const vvhip_plan* p) { return p->hp.params.cos_acceleration != 0; }
+// No source of extra forces in a step: its kick adds whatever forceExtra still holds (see Cursor::fextra_virtual)
+inline uint32_t stale_fextra(const vvhip_plan* p) { return (p->cur.fextra_dirty || p->fextra_external) ? vv::A_FE_LOAD : 0u; }
+inline bool shake_on(const vvhip_plan* p) { return !p->hp.slot_shake.empty(); }
+// stage bits of the in-kernel constraints the plan holds: hydrogen-type clusters and / or rigid three-site molecules
+inline uint32_t cons_a(const vvhip_plan* p) { return (p->hp.info.num_shake_clusters > 0 ? vv::A_SHAKE_V : 0u) | (p->hp.info.num_settle_clusters > 0 ? vv::A_SETTLE : 0u) | (p->hp.info.num_general_constraints > 0 ? vv::A_GCONS : 0u); }
+inline uint32_t cons_b(const vvhip_plan* p) { return (p->hp.info.num_shake_clusters > 0 ? vv::B_SHAKE : 0u) | (p->hp.info.num_settle_clusters > 0 ? vv::B_SETTLE : 0u) | (p->hp.info.num_general_constraints > 0 ? vv::B_GCONS : 0u); }
+
+// vv_api.cpp
+int fail(vvhip_plan* p, int code, const std::string& msg);
+int hip_fail(vvhip_plan* p, hipError_t e, const char* what);
+int settle_recovery(vvhip_plan* p);
+int check_exchange_health(vvhip_plan* p);
+void drop_graphs(vvhip_plan* p);
+// vv_launch.cpp
+void fill_scales(vvhip_plan* p);
+void pick_launch_shape(vvhip_plan* p);
+vv::KArgs make_args(vvhip_plan* p, uint32_t flags, uint32_t random_index);
+int upload_lane_const(vvhip_plan* p);
+int ensure_mass_table(vvhip_plan* p);
+int run_a(vvhip_plan* p, uint32_t flags, uint32_t random_index);
+int run_b(vvhip_plan* p, uint32_t flags);
+int run_chain(vvhip_plan* p, uint32_t flags);
+int run_ke(vvhip_plan* p, uint32_t flags, uint32_t random_index);
+int run_chain_and_b(vvhip_plan* p, uint32_t bflags, bool with_bias);
+int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_index, bool* taken);
+ThermoMode thermo_mode(const vvhip_plan* p);
+bool use_mailbox(const vvhip_plan* p);
+uint32_t chain_in_b(const vvhip_plan* p);
+bool fused_shape_ok(const vvhip_plan* p);
+bool fused_state_ok(const vvhip_plan* p);
+bool fused_active(const vvhip_plan* p);
+void forget_fused_checks(vvhip_plan* p);
+uint32_t extra_flags(const vvhip_plan* p);
+uint32_t after_positions(const vvhip_plan* p);
+uint32_t tail_flags(const vvhip_plan* p);
+// vv_steps.cpp
+ThermoApp middle_application(const vvhip_plan* p);
+int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_index, bool* taken);
+// vv_observe.cpp
+int step_begin(vvhip_plan* p);
+int step_done(vvhip_plan* p);
+std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps);
+std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps);
+// vv_run.cpp
+int recover_rendezvous(vvhip_plan* p);
+int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill);
+// vv_exchange.cpp
+int exchange_accumulators(vvhip_plan* p, int phase);
+void mailbox_release(vvhip_plan* p);
+
+#pragma GCC visibility pop

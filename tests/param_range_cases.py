@@ -1,7 +1,7 @@
 """Small Drude systems at the edges of the integrator's parameter range, for tests/test_param_range.py (CPU: the oracle alone reaches the
 regime each case claims and stays finite there) and tests/test_gpu_param_range.py (the fused step against the oracle).  Every other GPU
 test runs T = 300-333 K, T_Drude = 1 K, dt = 1-2 fs, thermostat frequencies 10 / 40 per ps, positions inside the box and the masses of
-systems.py; the cases here move one of those at a time: the temperatures (the fixed-point scales of the thermostat sums, csrc/vv_api.cpp:
+systems.py; the cases here move one of those at a time: the temperatures (the fixed-point scales of the thermostat sums, csrc/vv_launch.cpp:
 pick_scale, and the hard wall's sqrt(kB T_D)), dt and the couplings (the chain's masses kT / f^2), the masses (the mass tables), the
 start's kinetic energy (the headroom of the sums) and z (cos_kz's fallback to the library cosine beyond |x| = 1024 or next to a
 multiple of pi / 2, csrc/vv_dev_wave.inc).  Velocities are rescaled so that every case starts near its own targets.
@@ -219,7 +219,7 @@ def case(name) -> Case:
 
 
 def scale_exponent(nkbt):
-    """csrc/vv_api.cpp: pick_scale(total, 1024) of the three 2KE sums, restated: (exponent before the clamp, exponent used)."""
+    """csrc/vv_launch.cpp: pick_scale(total, 1024) of the three 2KE sums, restated: (exponent before the clamp, exponent used)."""
     top = 2.0 ** 62 / (max(float(sum(nkbt)), 1.0) * 1024.0)
     k = math.floor(math.log2(top))
     return k, max(0, min(k, 40))

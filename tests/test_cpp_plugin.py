@@ -241,7 +241,7 @@ def test_deferred_fusion_fuzz_under_the_reference_integrator(tmp_path, middle, c
             # the same algebra in another order of operations, so rounding-level differences (measured 3e-15 .. 6e-15 after 50 steps).
             # This case found a real one first (7e-4): the reference's kick kernels add forceExtra always and the array is only
             # reset in steps that have a source of extra forces, so after setCosAcceleration(0) the last cos force keeps acting
-            # (K/middle.cu:11-21, VVIntegrator.cpp:238-240) -- the fused path now does the same (vv_api.cpp: fextra_virtual).
+            # (K/middle.cu:11-21, VVIntegrator.cpp:238-240) -- the fused path now does the same (vv_plan.hpp: fextra_virtual).
             assert np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max() <= 1e-12 * max(1.0, np.abs(b[k]).max()), (k, np.abs(a[k] - b[k]).max())
     assert np.isfinite(a[7]).all() and np.isfinite(a[8]).all()
 

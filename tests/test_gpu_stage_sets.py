@@ -1,6 +1,6 @@
 """-m gpu: the stage sets vvhip_debug_fused_flags reports are the stage sets a step launches.
 
-The step entry points and the accessor read one composition of the thermostat application (csrc/vv_api.cpp: compose_application), in
+The step entry points and the accessor read one composition of the thermostat application (csrc/vv_steps.cpp: compose_application), in
 each of its modes: plain, the cos perturbation in moment form, and the cos perturbation as the bias -> sums -> scale sequence.  With
 run-time compilation off and the one-launch step off, a launch whose stage set has no compiled kernel runs the generic one and
 vvhip_generic_launches reports that set; it must be the accessor's, up to the bits that are named here:

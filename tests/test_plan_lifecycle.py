@@ -124,7 +124,7 @@ def test_restarts_replace_their_buffers_and_leave_the_run_alone():
         ctx.series_stop()
         ctx.remove_cm_motion_stop()
         ctx.mailbox_destroy()
-        # What the three calls keep, from csrc/vv_api.cpp: vvhip_series_stop frees the series' three buffers (series_release) and
+        # What the three calls keep, from csrc/vv_observe.cpp and vv_exchange.cpp: vvhip_series_stop frees the series' three buffers (series_release) and
         # vvhip_mailbox_destroy the box, the control words and the peer table (mailbox_release) -- nothing stays.  vvhip_cm_motion_stop only
         # switches the schedule off: the removal's scratch words ([CMM_WORDS = 8] int64), its two records (2 x CmmDevRecord = 2 x 40 bytes) and
         # the pinned 3 doubles of the one-off call stay for vvhip_remove_cm_motion and the next schedule (cmm_ensure allocates them once).

@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 SRC=$ROOT/openmm-velocityverlet_amd/csrc; OBJ=$ROOT/openmm-velocityverlet_amd/lib/obj; OUT=$ROOT/tools/probes/libs
 mkdir -p "$OUT/obj_$NAME"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -I/opt/rocm/include -mllvm -amdgpu-kernarg-preload-count=16"
-OBJS="$OBJ/vv_host.o $OBJ/vv_api.o $OBJ/vv_rtc.o"
+OBJS=$(for f in $(sed -n 's/^HOSTSRC *= *//p' "$SRC/Makefile"); do printf '%s ' "$OBJ/${f%.cpp}.o"; done)      # every host object of the product build (the Makefile's list)
 for part in 1 2; do
   if [[ " ${PART:-2} " == *" $part "* ]]; then
     /opt/rocm/bin/hipcc $FLAGS "$@" -DVV_KERNELS_PART=$part -c -o "$OUT/obj_$NAME/vv_kernels_$part.o" "$SRC/vv_kernels.hip" &
@@ -18,5 +18,5 @@ for part in 1 2; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc $FLAGS -shared -o "$OUT/libvvhip_$NAME.so" $OBJS -ldl
+/opt/rocm/bin/hipcc $FLAGS -shared -Wl,--version-script="$SRC/libvvhip.map" -o "$OUT/libvvhip_$NAME.so" $OBJS -ldl
 echo "$OUT/libvvhip_$NAME.so"
