@@ -440,6 +440,99 @@ typedef struct {
 int vvhip_set_velocities_to_temperature(vvhip_plan* plan, double temperature, double drude_temperature /* < 0: plain */,
                                         uint64_t seed, uint32_t flags, vvhip_thermalize_record* out /* may be NULL */);
 
+/* ---------------------------------------------------------------- checkpoint: a run's complete state, bit for bit
+ * What context.createCheckpoint() / loadCheckpoint() give a run inside OpenMM (examples/run-bulk.py: CheckpointReporter, --cpt): a
+ * stand-alone host has no such service.  The state is the list the plan's recovery snapshot keeps (vvhip_recovery_count), made durable:
+ * positions, correction, velocities, forces, forceExtra, the Langevin normals in use, BOTH parity copies of the device-resident
+ * thermostat state (with the exchange and rendezvous counters and the self-tuning wait), the generator's epoch, and the host's cursor
+ * (thermostat parity, random cursor, the two forceExtra flags, the step counter) with the generator's seed.  A run continued from a
+ * loaded blob gives the bits of the uninterrupted run on every path (step entry points, vvhip_run_eager, vvhip_run_graph; either
+ * scheme).  NOT carried: the rows of a series and the record of the scheduled removals (the host starts both again after a load; the
+ * step counter travels, so their schedules continue at the same steps), the parameters (read live from the host's setters, as in the
+ * reference; the header holds them as they stood, for inspection), the status words and the plan's tuning.  This is the project's own
+ * format, not OpenMM's.
+ *
+ * Digest.  View a section as 32-bit little-endian words w[j], j = 0 .. n - 1, with global word index g = base + j, g < 2^32; base =
+ * shard_begin x (words per particle) for the particle sections (posq, correction, velm, forceExtra), 0 for every other.  In uint64
+ * arithmetic mod 2^64
+ *     z = ((g << 32) | w[j]) + 0x9E3779B97F4A7C15;   z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;   z ^= z >> 27;  z *= 0x94D049BB133111EB;
+ *     z ^= z >> 31;   digest = sum of z over j                                                             (an empty section: 0)
+ * The wrapping sum is independent of order, launch shape and wave layout, and for the particle sections additive over shards.
+ * vvhip_digest_host computes it on the host (bytes a multiple of 4, base + bytes / 4 <= 2^32: VVHIP_ERR_INVALID otherwise),
+ * vvhip_state_digest on the device (csrc/vv_dev_digest.inc) for every section of the plan: 8 bytes copied back per section instead
+ * of the arrays.
+ *
+ * Blob (little-endian, version 1): the 272 bytes of vvhip_checkpoint_header, then `num_sections` vvhip_checkpoint_section entries (40 bytes
+ * each, ascending ids), then the payloads, each at a 16-byte aligned offset from the blob's start in the table's order, padding zero;
+ * total_bytes = the end of the last payload rounded up to 16.  header_digest = the digest of header bytes [0, 264) at base 0 plus the
+ * digest of the table at base 66.  The cursor section's payload is the 32 bytes of the header's vvhip_checkpoint_cursor and is always there. */
+enum {
+    VVHIP_CKPT_POSQ = 0, VVHIP_CKPT_CORRECTION = 1, VVHIP_CKPT_VELM = 2, VVHIP_CKPT_FORCE = 3, VVHIP_CKPT_FORCE_EXTRA = 4,
+    VVHIP_CKPT_RANDOM = 5,        /* the Langevin normals in use (float4 [random_size]; only with Langevin particles) */
+    VVHIP_CKPT_THERMOSTAT = 6,    /* both parity copies of the device-resident thermostat state */
+    VVHIP_CKPT_EPOCH = 7,         /* refill counter of the device Gaussian generator */
+    VVHIP_CKPT_CURSOR = 8,        /* vvhip_checkpoint_cursor */
+    VVHIP_CKPT_SECTIONS = 9
+};
+#define VVHIP_CKPT_MAGIC 0x504B435049485656ull      /* "VVHIPCKP" */
+#define VVHIP_CKPT_VERSION 1
+#define VVHIP_CKPT_ALL 0x1FFu                       /* mask of (1 << VVHIP_CKPT_*): every section in use */
+/* everything but posq, correction, velm and force: what an OpenMM adapter stores next to the Context's own checkpoint */
+#define VVHIP_CKPT_INTEGRATOR (VVHIP_CKPT_ALL & ~0xFu)
+typedef struct {
+    int32_t parity;                 /* which copy of the thermostat state the next application consumes */
+    uint32_t random_pos;            /* prepareRandomNumbers cursor of the plan-driven loops */
+    int32_t fextra_dirty, fextra_virtual;       /* forceExtra holds / should hold something since the last reset */
+    int64_t step_count;             /* full steps counted since vvhip_bind */
+    uint64_t rng_seed;              /* vvhip_set_random_seed */
+} vvhip_checkpoint_cursor;
+typedef struct {
+    uint64_t magic;                 /* VVHIP_CKPT_MAGIC */
+    uint32_t version;               /* VVHIP_CKPT_VERSION */
+    int32_t precision;              /* VVHIP_SINGLE / MIXED / DOUBLE */
+    int32_t num_atoms, shard_begin, shard_end, use_middle_scheme;
+    int32_t num_nh_chains;
+    uint32_t random_size;           /* float4 elements of the bound random buffer */
+    double box[3];
+    vvhip_params params;            /* as they stood at the save; NOT applied by a load */
+    vvhip_checkpoint_cursor cursor;
+    uint64_t host_words[4];         /* the host's own words (the stand-alone Context: its random index and "forces valid") */
+    uint32_t num_sections, reserved;
+    uint64_t total_bytes;
+    uint64_t header_digest;
+} vvhip_checkpoint_header;
+typedef struct {
+    uint32_t id, reserved;          /* VVHIP_CKPT_* */
+    uint64_t offset, bytes;         /* of the payload, from the blob's start */
+    uint64_t digest_base, digest;
+} vvhip_checkpoint_section;
+int vvhip_digest_host(const void* data, size_t bytes, uint64_t base, uint64_t* out);
+/* Settles a pending recovery, synchronises, digests every section on the device (the cursor on the host) and copies the words back;
+ * sections not in use (no correction outside mixed precision, no normals without Langevin particles) report 0.  Reads the state and
+ * writes scratch of its own: no accumulator, thermostat copy, status word or captured graph is touched.  Refused inside a graph capture. */
+int vvhip_state_digest(vvhip_plan* plan, uint64_t out[VVHIP_CKPT_SECTIONS]);
+/* Bytes of the blob vvhip_checkpoint_save writes for this mask of sections (the cursor section is always carried). */
+int vvhip_checkpoint_size(vvhip_plan* plan, uint32_t sections, size_t* bytes);
+/* Enters as vvhip_synchronize does (a missed rendezvous is repaired first); with a sticky status word up it returns that error and
+ * writes nothing: a void state is never saved.  Then: device digests, download, host digests of the downloaded bytes (a difference is
+ * VVHIP_ERR_HIP), table and header last.  host_words may be NULL (zeros). */
+int vvhip_checkpoint_save(vvhip_plan* plan, uint32_t sections, const uint64_t host_words[4], void* blob, size_t bytes);
+/* Host only, no plan, safe on arbitrary bytes: bounds, magic, version, the table's sanity and every digest.  Any failure is
+ * VVHIP_ERR_INVALID with a text that names the fault and the section (vvhip_checkpoint_error).  out may be NULL. */
+int vvhip_checkpoint_inspect(const void* blob, size_t bytes, vvhip_checkpoint_header* out);
+/* The text of this thread's last failed vvhip_checkpoint_inspect ("" if none). */
+const char* vvhip_checkpoint_error(void);
+/* Inspects the blob, compares its structure with the plan (precision, num_atoms, shard, scheme, chain length, random_size with Langevin
+ * particles, section sizes: VVHIP_ERR_INVALID saying which), then uploads the sections present into the live arrays, zeroes both
+ * accumulator copies and ALL rendezvous words (a plan may go BACK: words of later steps must not meet a restored tag), sets cursor, seed
+ * and box, invalidates mass tables, the recovery snapshot and the captured graphs, and verifies vvhip_state_digest against the table
+ * (VVHIP_ERR_HIP otherwise).  Refused: inside a graph capture; while a series is running (VVHIP_ERR_INVALID: stop it, load, start it
+ * again -- its first row belongs to the old step counter); on a sharded plan or one with a communicator / mailbox
+ * (VVHIP_ERR_UNSUPPORTED: the peers' exchange counters would have to move together).  A load that fails before its first upload leaves
+ * the device state untouched.  The status words and the plan's tuning are left alone: a host that returns to a checkpoint after an
+ * error calls vvhip_status_clear itself.  host_words_out may be NULL. */
+int vvhip_checkpoint_load(vvhip_plan* plan, const void* blob, size_t bytes, uint64_t host_words_out[4]);
+
 /* Device pointer of the plan-owned forceExtra array (real3[n]); getForceExtra() of the reference
  * (CudaVVKernels.h:86-88). */
 int vvhip_force_extra(vvhip_plan* plan, void** device_ptr);

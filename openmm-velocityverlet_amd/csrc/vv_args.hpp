@@ -304,4 +304,13 @@ struct ThermalizeArgs {
     double kt, kt_drude;            // R T and R T_D, kJ/mol (the products formed in double on the host)
 };
 
+// State digest (vv_dev_digest.inc, vvhip_state_digest): sum over the section's 32-bit words of mix((base + j) << 32 | w[j]), mod 2^64
+// (include/vvhip.h: "Digest").  `out` must be zero on entry; the launch adds to it.
+struct DigestArgs {
+    const unsigned int* words;      // the section, 4-byte aligned
+    unsigned long long nwords;      // base + nwords <= 2^32
+    unsigned long long base;
+    unsigned long long* out;
+};
+
 }  // namespace vv

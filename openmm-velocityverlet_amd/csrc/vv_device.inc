@@ -15,3 +15,4 @@
 #include "vv_dev_report.inc"
 #include "vv_dev_cmm.inc"
 #include "vv_dev_thermalize.inc"
+#include "vv_dev_digest.inc"

@@ -506,6 +506,14 @@ hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_ca
     VV_DISPATCH(vv_kernel_thermalize, dim3((unsigned) g), dim3(512), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    if (a.nwords == 0) return hipSuccess;
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    const unsigned long long want = (a.nwords / 4 + block_threads - 1) / block_threads;      // one 16-byte group per thread and pass
+    const unsigned g = (unsigned) std::max<unsigned long long>(1, std::min<unsigned long long>(want, (unsigned long long) std::max(1, grid_cap)));
+    hipLaunchKernelGGL(vv_kernel_digest, dim3(g), dim3((unsigned) block_threads), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

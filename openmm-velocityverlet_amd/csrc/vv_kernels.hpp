@@ -58,5 +58,8 @@ hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, 
 // Maxwell-Boltzmann start velocities (vv_dev_thermalize.inc): one kernel over a.nwaves waves and a.nlaneless listed particles in blocks of
 // 512 threads, at most grid_cap of them (the kernel strides beyond).
 hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_cap, hipStream_t s);
+// State digest (vv_dev_digest.inc): one streaming reduction over a.nwords words in blocks of block_threads (a multiple of 64, at most 512),
+// at most grid_cap of them (the kernel strides beyond), added to *a.out.
+hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -12,6 +12,8 @@
 //                    step_begin / step_done and the schedules series_rows_in / cmm_steps_in
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
 //                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
+//   vv_checkpoint.cpp  the state as a durable blob: vvhip_state_digest, vvhip_checkpoint_size / _save / _load, over the SAME list of items as
+//                    the recovery snapshot (recovery_items); the blob's format and parser are vv_ckpt_format.cpp (no HIP in it)
 //   vv_exchange.cpp  between the ranks: the RCCL loader and vvhip_comm_*, the xGMI mailbox, exchange_accumulators
 //   vv_debug.cpp     test hooks (vvhip_debug_* except vvhip_debug_tune), vvhip_time_kernel, the probes of the instrumented build
 //
@@ -277,6 +279,9 @@ struct vvhip_plan {
     } cmm;
     // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature): HostPlan::therm_laneless, uploaded by the first call
     vv::DevBuf<int32_t> d_therm_laneless;
+    // State digest (vvhip_state_digest): one word per section, scratch of its own, allocated by the first call
+    vv::DevBuf<unsigned long long> d_digest;
+    vv::PinnedBuf<unsigned long long> h_digest;   // pinned: the words as copied back
 };
 
 // ---- A thermostat application with the stages that ride on it, as data: what every step entry point launches, and what
@@ -380,6 +385,13 @@ int step_done(vvhip_plan* p);
 std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps);
 std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps);
 // vv_run.cpp
+// The plan's physical state, stated ONCE, as {live array, its saved copy of the recovery snapshot, bytes, ...}: the six state arrays (0
+// bytes: not in use), both thermostat copies, the random generator's epoch -- in this order the sections VVHIP_CKPT_POSQ ..
+// VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and on request the series' row cursor and the record of the scheduled removals
+// of the centre-of-mass motion (`late`: those two go back with the step counter, after the accumulators are zeroed; a checkpoint does not
+// carry them).  particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
+struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
+std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm);
 int recover_rendezvous(vvhip_plan* p);
 int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill);
 // vv_exchange.cpp

@@ -30,20 +30,17 @@ static int next_random_slice(vvhip_plan* p, uint32_t* index, bool force_refill) 
 }
 
 // ---- recovery from a missed rendezvous (vvhip_plan::Recovery)
-// What a snapshot holds, as {live array, its saved copy, bytes}: the six state arrays (0 bytes: not in use), both thermostat copies, the
-// random generator's epoch, and on request the series' row cursor and the record of the scheduled removals of the centre-of-mass motion
-// (`late`: those two go back with the step counter, after the accumulators are zeroed).
-struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; };
-static std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm) {
+// What a snapshot -- and a checkpoint (vv_checkpoint.cpp) -- holds: see RecItem in vv_plan.hpp.
+std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm) {
     vvhip_plan::Recovery& r = p->rec;
     const vv::HostPlan& hp = p->hp;
     const size_t nloc = (size_t) (hp.shard_end - hp.shard_begin), rs = sizeof_real(hp.precision), ms = sizeof_mixed(hp.precision);
     std::vector<RecItem> v = {
-        {p->buf.posq, &r.posq, nloc * 4 * rs, false},
-        {p->buf.posq_correction, &r.corr, p->buf.posq_correction ? nloc * 4 * rs : 0, false},
-        {p->buf.velm, &r.velm, nloc * 4 * ms, false},
+        {p->buf.posq, &r.posq, nloc * 4 * rs, false, (uint32_t) rs},
+        {p->buf.posq_correction, &r.corr, p->buf.posq_correction ? nloc * 4 * rs : 0, false, (uint32_t) rs},
+        {p->buf.velm, &r.velm, nloc * 4 * ms, false, (uint32_t) ms},
         {p->buf.force, &r.force, (size_t) hp.padded_num_atoms * 3 * 8, false},                                              // (planar int64)
-        {p->d_fextra.get(), &r.fextra, nloc * 3 * rs, false},
+        {p->d_fextra.get(), &r.fextra, nloc * 3 * rs, false, (uint32_t) (3 * rs / 4)},
         {const_cast<void*>(p->buf.random), &r.random, hp.has_ld ? (size_t) p->buf.random_size * sizeof(float4) : 0, false},      // the Langevin normals in use
         {p->d_nh.get(), &r.nh, 2 * sizeof(vv::NHDevState), false},
         {p->d_epoch.get(), &r.epoch, sizeof(unsigned long long), false}};

@@ -502,6 +502,37 @@ class Context:
         H.check(H.lib.vvhip_cm_motion_read(self.plan, C.byref(out)), self.plan)
         return out
 
+    # ---- checkpoint: the run's complete state as bytes (include/vvhip.h: vvhip_checkpoint_*)
+    def createCheckpoint(self, sections="all") -> bytes:
+        """The complete state of the run as a blob in the library's own format (not OpenMM's): particle arrays, forces, extra forces, the
+        Langevin normals in use, both thermostat copies, the generator's epoch and seed, the step counter and this context's random index.
+        sections="integrator" leaves out posq, correction, velm and force (what an OpenMM adapter stores next to the Context's own
+        checkpoint); an int is taken as a mask of H.CKPT_* bits.  A state with a sticky error raised is refused.  Blocks."""
+        mask = {"all": H.CKPT_ALL, "integrator": H.CKPT_INTEGRATOR}[sections] if isinstance(sections, str) else int(sections)
+        n = C.c_size_t(0)
+        H.check(H.lib.vvhip_checkpoint_size(self.plan, mask, C.byref(n)), self.plan)
+        buf = C.create_string_buffer(n.value)
+        words = (C.c_uint64 * 4)(int(self.random_index), int(bool(self.forces_valid)), 0, 0)
+        H.check(H.lib.vvhip_checkpoint_save(self.plan, mask, C.byref(words), buf, n.value), self.plan)
+        return buf.raw
+
+    def loadCheckpoint(self, blob):
+        """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
+        every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
+        integrator's parameters are NOT taken from the blob.  A running series must be stopped first and started again afterwards, as
+        must a removal schedule whose record is to start over; a sharded context refuses."""
+        blob = bytes(blob)
+        words = (C.c_uint64 * 4)()
+        H.check(H.lib.vvhip_checkpoint_load(self.plan, blob, len(blob), C.byref(words)), self.plan)
+        self.random_index, self.forces_valid = int(words[0]), bool(words[1])
+
+    def state_digest(self) -> dict:
+        """{section name: 64-bit digest} of the state as it stands, computed on the device (vvhip_state_digest): two states are the same
+        bits where their digests agree, at 8 bytes copied back per array.  Sections not in use report 0."""
+        out = (C.c_uint64 * H.CKPT_SECTIONS)()
+        H.check(H.lib.vvhip_state_digest(self.plan, C.byref(out)), self.plan)
+        return {name: int(out[k]) for k, name in enumerate(H.CKPT_SECTION_NAMES)}
+
     def getNHState(self) -> H.NHState:
         s = H.NHState()
         H.check(H.lib.vvhip_get_nh_state(self.plan, C.byref(s)), self.plan)

@@ -10,9 +10,14 @@ and looping over molecules and pairs on the host.  It asks OpenMM for no state a
 the same header and columns, one line per row, so that a long graph run keeps its sampled observables without stopping the GPU
 for every sample.
 
+``CheckpointReporter`` is examples/ommhelper/reporter/checkpointreporter.py on ``context.createCheckpoint()``: a file per report, the
+latest three kept.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
+
+import os
 
 HEADER = '#"Step"\t"T_COM"\t"T_Atom"\t"T_Drude"\t"KE_COM"\t"KE_Atom"\t"KE_Drude"'
 CM_MOTION_HEADER = '#"Step"\t"Removals"\t"Skipped"\t"Vx (nm/ps)"\t"Vy (nm/ps)"\t"Vz (nm/ps)"'
@@ -72,6 +77,38 @@ class DrudeTemperatureReporter:
             self.close()
         except Exception:
             pass
+
+
+class CheckpointReporter:
+    """Saves a checkpoint every `reportInterval` steps, as examples/ommhelper/reporter/checkpointreporter.py does: `file`_<step> holds
+    ``simulation.context.createCheckpoint()`` of that step, and only the latest three files are kept.  (The reference's optional State
+    XML next to it is not offered: there is no serializer here.)
+
+    Parameters
+    ----------
+    file : str
+        The file to write to; the step is appended to the name
+    reportInterval : int
+        The interval (in time steps) at which to write checkpoints
+    """
+
+    def __init__(self, file, reportInterval):
+        if type(file) is not str:
+            raise Exception("file should be str")
+        self._file = file
+        self._reportInterval = int(reportInterval)
+
+    def describeNextReport(self, simulation):
+        """(steps until the next report, positions?, velocities?, forces?, energies?): the checkpoint comes from the context itself."""
+        steps = self._reportInterval - simulation.currentStep % self._reportInterval
+        return (steps, False, False, False, False)
+
+    def report(self, simulation, state):
+        with open(self._file + "_%i" % simulation.currentStep, "wb") as out:
+            out.write(simulation.context.createCheckpoint())
+        prev3 = self._file + "_%i" % (simulation.currentStep - 3 * self._reportInterval)
+        if os.path.exists(prev3):
+            os.remove(prev3)
 
 
 def _open(file, append):

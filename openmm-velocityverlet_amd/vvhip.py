@@ -117,6 +117,32 @@ class ThermalizeRecord(C.Structure):
                 ("cm_removed", C.c_int32), ("v_removed", C.c_double * 3)]
 
 
+CKPT_SECTION_NAMES = ("posq", "correction", "velm", "force", "force_extra", "random", "thermostat", "epoch", "cursor")
+CKPT_SECTIONS = len(CKPT_SECTION_NAMES)
+CKPT_MAGIC, CKPT_VERSION = 0x504B435049485656, 1
+CKPT_ALL = (1 << CKPT_SECTIONS) - 1
+CKPT_INTEGRATOR = CKPT_ALL & ~0xF
+
+
+class CheckpointCursor(C.Structure):
+    _fields_ = [("parity", C.c_int32), ("random_pos", C.c_uint32), ("fextra_dirty", C.c_int32), ("fextra_virtual", C.c_int32),
+                ("step_count", C.c_int64), ("rng_seed", C.c_uint64)]
+
+
+class CheckpointHeader(C.Structure):
+    """The fixed header of a checkpoint blob (include/vvhip.h: vvhip_checkpoint_header)."""
+    _fields_ = [("magic", C.c_uint64), ("version", C.c_uint32), ("precision", C.c_int32), ("num_atoms", C.c_int32),
+                ("shard_begin", C.c_int32), ("shard_end", C.c_int32), ("use_middle_scheme", C.c_int32), ("num_nh_chains", C.c_int32),
+                ("random_size", C.c_uint32), ("box", C.c_double * 3), ("params", Params), ("cursor", CheckpointCursor),
+                ("host_words", C.c_uint64 * 4), ("num_sections", C.c_uint32), ("reserved", C.c_uint32), ("total_bytes", C.c_uint64),
+                ("header_digest", C.c_uint64)]
+
+
+class CheckpointSection(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("reserved", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64),
+                ("digest_base", C.c_uint64), ("digest", C.c_uint64)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -154,6 +180,9 @@ def _load():
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
+        "vvhip_digest_host": [vp, C.c_size_t, C.c_uint64, P(C.c_uint64)], "vvhip_state_digest": [vp, P(C.c_uint64 * CKPT_SECTIONS)],
+        "vvhip_checkpoint_size": [vp, u32, P(C.c_size_t)], "vvhip_checkpoint_save": [vp, u32, P(C.c_uint64 * 4), vp, C.c_size_t],
+        "vvhip_checkpoint_inspect": [vp, C.c_size_t, P(CheckpointHeader)], "vvhip_checkpoint_load": [vp, vp, C.c_size_t, P(C.c_uint64 * 4)],
         "vvhip_device_count": [P(C.c_int)], "vvhip_set_device": [C.c_int],
         "vvhip_malloc": [P(vp), C.c_size_t], "vvhip_free": [vp],
         "vvhip_memcpy_h2d": [vp, vp, C.c_size_t], "vvhip_memcpy_d2h": [vp, vp, C.c_size_t],
@@ -204,6 +233,9 @@ def _load():
     lib.vvhip_last_error.restype = C.c_char_p
     lib.vvhip_plan_unfused_reason.argtypes = [vp]
     lib.vvhip_plan_unfused_reason.restype = C.c_char_p
+    if hasattr(lib, "vvhip_checkpoint_error") or not os.environ.get("VVHIP_LIB"):      # (an older build named by VVHIP_LIB: see above)
+        lib.vvhip_checkpoint_error.argtypes = []
+        lib.vvhip_checkpoint_error.restype = C.c_char_p
     return lib
 
 
@@ -221,6 +253,35 @@ def check(rc: int, plan=None, what: str = ""):
     if rc != OK:
         msg = lib.vvhip_last_error(plan).decode() if plan else what
         raise VVHipError(rc, msg or what)
+
+
+def digest_host(data, base: int = 0) -> int:
+    """The digest of a buffer's 32-bit words at global word index `base` (include/vvhip.h: vvhip_digest_host)."""
+    a = np.ascontiguousarray(data).view(np.uint8).reshape(-1) if not isinstance(data, (bytes, bytearray)) else np.frombuffer(data, dtype=np.uint8)
+    out = C.c_uint64(0)
+    rc = lib.vvhip_digest_host(a.ctypes.data if a.size else None, a.size, int(base), C.byref(out))
+    if rc != OK:
+        raise VVHipError(rc, "vvhip_digest_host: the bytes are no multiple of 4, or a word index reaches 2^32")
+    return out.value
+
+
+def checkpoint_inspect(blob) -> CheckpointHeader:
+    """The header of a checkpoint blob after every check a load makes without a plan: bounds, magic, version, table, all digests
+    (vvhip_checkpoint_inspect).  Raises VVHipError(ERR_INVALID) with a text that names the fault."""
+    blob = bytes(blob)
+    h = CheckpointHeader()
+    rc = lib.vvhip_checkpoint_inspect(blob, len(blob), C.byref(h))
+    if rc != OK:
+        raise VVHipError(rc, lib.vvhip_checkpoint_error().decode())
+    return h
+
+
+def checkpoint_sections(blob) -> dict:
+    """{section name: CheckpointSection} of an inspected blob's table."""
+    blob = bytes(blob)
+    h = checkpoint_inspect(blob)
+    table = (CheckpointSection * h.num_sections).from_buffer_copy(blob, C.sizeof(CheckpointHeader))
+    return {CKPT_SECTION_NAMES[s.id]: s for s in table}
 
 
 class DeviceArray:
