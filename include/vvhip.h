@@ -359,6 +359,83 @@ int vvhip_series_stop(vvhip_plan* plan);
 int vvhip_series_info(const vvhip_plan* plan, vvhip_series_layout* out);
 /* Test hook: 1 if the guard row behind the buffer's last row still holds its fill pattern (nothing was written past capacity). */
 int vvhip_debug_series_guard(vvhip_plan* plan, int32_t* intact);
+/* ---------------------------------------------------------------- frames: the trajectory recorded on the device
+ * What DCDReporter / GroReporter(logarithm=True, subset=...) give a run inside OpenMM (examples/run-bulk.py, run-edl.py): a stand-alone
+ * host would have to end its run call, synchronise and download posq and posqCorrection of every particle for each frame.  A frame is a
+ * series row that is large: a device buffer of `capacity` frames, a device-side cursor, and after every full step that is due -- counted
+ * exactly as for the series, by the same entry points; the split per-KernelImpl entry points and vvhip_run_eager_unfused take none -- the
+ * step entry point enqueues one streaming kernel (csrc/vv_dev_frames.inc) and a one-thread kernel that writes the frame's header and
+ * advances the cursor.  Inside a captured graph both are part of the graph and the steps that take a frame are part of the graph-cache
+ * key.  A frame "after step k" is enqueued behind that step's series row and in front of the removal that precedes step k + 1.  The
+ * recorder reads posq, posqCorrection and velm and writes its own buffer and cursor, nothing else; a plan that never starts one launches
+ * what it launched before and allocates nothing.
+ * Schedule, after full step s (vvhip_frames_schedule is its one statement):
+ *     VVHIP_FRAMES_LINEAR   s mod interval = 0
+ *     VVHIP_FRAMES_LOG10    GroReporter's logarithmic rule: from step c the next frame is at c + base - (c mod base), base = interval
+ *                           while c < interval, else the largest power of ten <= c -- with interval 30: 30, 40, ..., 90, 100, 200, ...,
+ *                           900, 1000, 2000, ...  Equivalently s is due iff s = interval, or s > interval and s mod 10^floor(log10(s - 1))
+ *                           = 0: a function of s alone, wherever the recorder starts.
+ * Frame j (0-based, since the start or the last reset) belongs to the j-th due step after start_step (after the last frame counted
+ * before the reset); frames dropped for want of capacity count.
+ * Frame layout (vvhip_frames_info): the 64 bytes of vvhip_frame_header, then per quantity three component planes x | y | z of
+ * plane_stride elements each (what a DCD frame is on disk), positions first; elements past num_particles stay zero.  Values for recorded
+ * particle i, converted once:
+ *     mixed precision    float64: (double) posq.xyz + (double) posqCorrection.xyz      float32: that sum rounded once to nearest
+ *     single             float64: (double) posq.xyz                                    float32: the bits of posq.xyz
+ *     double             float64: posq.xyz                                             float32: (float) posq.xyz
+ * and velm.xyz the same way.  Positions are as stored: unwrapped, image particles and virtual sites included.  box is the plan's box when
+ * the frame was enqueued (a kernel argument: vvhip_set_box drops the captured graphs).
+ * A sharded plan records its own particles: subset intersected with [shard_begin, shard_end), named by vvhip_frames_particles. */
+#define VVHIP_FRAMES_POSITIONS  1
+#define VVHIP_FRAMES_VELOCITIES 2
+#define VVHIP_FRAMES_FLOAT64    4      /* components as double instead of float */
+enum { VVHIP_FRAMES_LINEAR = 0, VVHIP_FRAMES_LOG10 = 1 };
+typedef struct {
+    int32_t interval, schedule, capacity, mask;
+    int32_t num_subset;             /* 0 with subset = NULL: every particle of the plan */
+    const int32_t* subset;          /* global particle indices, strictly ascending */
+} vvhip_frames_desc;
+typedef struct {
+    int64_t ordinal;                /* the frame's index since the start or the last reset, from the device-side cursor */
+    int64_t reserved;               /* 0 */
+    double box[3];
+    double pad[3];                  /* 0 */
+} vvhip_frame_header;               /* 64 bytes, written on the device */
+typedef struct {
+    int32_t active, interval, schedule, capacity, mask;
+    int32_t num_particles;          /* particles this plan records: |subset intersected with [shard_begin, shard_end)| */
+    int32_t component_bytes;        /* 4 or 8 */
+    int32_t plane_stride;           /* elements per component plane: num_particles rounded up to a multiple of 16 */
+    int64_t frame_bytes;            /* 64 + planes * plane_stride * component_bytes */
+    int64_t off_positions, off_velocities;      /* byte offsets of the x plane inside a frame, -1 if absent; planes follow as x | y | z */
+    int64_t start_step;             /* the plan's step count at vvhip_frames_start */
+} vvhip_frames_layout;
+/* Starts (or restarts, dropping what was recorded) a recorder; synchronises and drops the captured graphs.  Refused, in this order:
+ * interval < 1, capacity < 1, a mask without VVHIP_FRAMES_POSITIONS / VVHIP_FRAMES_VELOCITIES or with unknown bits, an unknown schedule,
+ * a subset that is not strictly ascending or leaves [0, num_atoms) (VVHIP_ERR_INVALID naming the argument); an unbound plan; inside a
+ * graph capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP with the byte count).  A description that passes the argument
+ * checks is kept even where the start is then refused for an unbound plan (active = 0): vvhip_frames_info and vvhip_frames_particles
+ * answer for it, so a host can size its buffers before it binds. */
+int vvhip_frames_start(vvhip_plan* plan, const vvhip_frames_desc* desc);
+/* Synchronises, copies min(frames recorded, capacity, max_frames) frames of frame_bytes each to frames_out and their steps to steps_out
+ * (either may be null with max_frames = 0), and returns the frames recorded (n_frames: at most capacity) and the frames dropped for
+ * want of capacity.  A header whose ordinal is not its frame's index gives VVHIP_ERR_HIP.  reset != 0 empties the buffer: the next
+ * frame becomes frame 0 and continues the schedule without gap or repeat. */
+int vvhip_frames_read(vvhip_plan* plan, void* frames_out, int64_t* steps_out, int32_t max_frames, int32_t* n_frames, int64_t* dropped,
+                      int32_t reset);
+/* Stops the recorder: no more frames are enqueued, the buffers are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_frames_stop(vvhip_plan* plan);
+/* The layout of the recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_frames_info(const vvhip_plan* plan, vvhip_frames_layout* out);
+/* The global indices of the particles this plan records, in frame order: the first min(num_particles, capacity) of them
+ * (vvhip_frames_info gives num_particles); VVHIP_ERR_INVALID if no recorder was described; host only. */
+int vvhip_frames_particles(const vvhip_plan* plan, int32_t* global_indices, int32_t capacity);
+/* The first n due steps greater than after_step (>= 0) of a schedule; host only, no plan.  VVHIP_ERR_INVALID for interval < 1, an unknown
+ * schedule, after_step < 0, n < 0, or steps beyond 2^61 (the logarithmic schedule reaches them within a few hundred frames). */
+int vvhip_frames_schedule(int32_t interval, int32_t schedule, int64_t after_step, int32_t n, int64_t* steps_out);
+/* Test hook: 1 if the guard frame behind the buffer's last frame still holds its fill pattern (nothing was written past capacity). */
+int vvhip_debug_frames_guard(vvhip_plan* plan, int32_t* intact);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the
@@ -527,7 +604,7 @@ const char* vvhip_checkpoint_error(void);
  * accumulator copies and ALL rendezvous words (a plan may go BACK: words of later steps must not meet a restored tag), sets cursor, seed
  * and box, invalidates mass tables, the recovery snapshot and the captured graphs, and verifies vvhip_state_digest against the table
  * (VVHIP_ERR_HIP otherwise).  Refused: inside a graph capture; while a series is running (VVHIP_ERR_INVALID: stop it, load, start it
- * again -- its first row belongs to the old step counter); on a sharded plan or one with a communicator / mailbox
+ * again -- its first row belongs to the old step counter), and likewise while a frame recorder is running; on a sharded plan or one with a communicator / mailbox
  * (VVHIP_ERR_UNSUPPORTED: the peers' exchange counters would have to move together).  A load that fails before its first upload leaves
  * the device state untouched.  The status words and the plan's tuning are left alone: a host that returns to a checkpoint after an
  * error calls vvhip_status_clear itself.  host_words_out may be NULL. */

@@ -313,4 +313,20 @@ struct DigestArgs {
     unsigned long long* out;
 };
 
+// Trajectory frame (vv_dev_frames.inc, include/vvhip.h: vvhip_frames_*).  The frame index is read from the device-side cursor, so a
+// replayed graph (same arguments every time) records where the last frame ended.
+struct FrameArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const void* velm;               // mixed4
+    const int32_t* subset;          // [n] shard-relative indices of the recorded particles, ascending; null: particle i is index i
+    unsigned char* frames;          // [capacity] frames of frame_bytes each (+ the guard frame)
+    unsigned long long* cursor;     // [0] frames counted since the start / last reset (past capacity too), [1] frames dropped
+    int64_t frame_bytes;
+    int64_t off_positions, off_velocities;      // of the x plane inside a frame, -1: not recorded
+    int32_t n, plane_stride;        // recorded particles; elements per component plane
+    int32_t capacity, pad_;
+    double box[3];
+};
+
 }  // namespace vv

@@ -18,7 +18,7 @@ vvhip_checkpoint_cursor cursor_of(const vvhip_plan* p) {
 
 // The device sections of the plan as it stands: every item of the shared list, in its order (bytes 0: not in use)
 std::vector<Section> device_sections(vvhip_plan* p) {
-    const std::vector<RecItem> items = recovery_items(p, false, false);
+    const std::vector<RecItem> items = recovery_items(p, false, false, false);
     static_assert(VVHIP_CKPT_CURSOR == 8, "the list's items are sections 0 .. 7, the cursor follows");
     std::vector<Section> v;
     for (size_t k = 0; k < items.size() && k < (size_t) VVHIP_CKPT_CURSOR; k++)
@@ -130,6 +130,7 @@ int vvhip_checkpoint_load(vvhip_plan* p, const void* blob, size_t bytes, uint64_
     NEED_BOUND(p);
     if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "vvhip_checkpoint_load inside a graph capture");
     if (p->series.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: a series is running: stop it, load, start it again (its first row belongs to the old step counter)");
+    if (p->frames.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: a frame recorder is running: stop it, load, start it again (its first frame belongs to the old step counter)");
     if (sharded(p) || p->comm || p->mb_on || p->mb_local)
         return fail(p, VVHIP_ERR_UNSUPPORTED, "checkpoint: loading into a sharded plan or one with a communicator / mailbox is not supported (the peers' exchange counters would have to move together)");
     // ---- the blob's structure against the plan's

@@ -16,3 +16,4 @@
 #include "vv_dev_cmm.inc"
 #include "vv_dev_thermalize.inc"
 #include "vv_dev_digest.inc"
+#include "vv_dev_frames.inc"

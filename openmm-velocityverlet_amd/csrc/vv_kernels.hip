@@ -514,6 +514,23 @@ hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, h
     hipLaunchKernelGGL(vv_kernel_digest, dim3(g), dim3((unsigned) block_threads), 0, s, a);
     return hipGetLastError();
 }
+template <class out_t, bool SUBSET>
+static void frame_dispatch(int precision, const FrameArgs& a, dim3 g, hipStream_t s) {
+    switch (precision) {
+        case VVHIP_SINGLE: hipLaunchKernelGGL((vv_kernel_frame<float, float, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
+        case VVHIP_MIXED: hipLaunchKernelGGL((vv_kernel_frame<float, double, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
+        default: hipLaunchKernelGGL((vv_kernel_frame<double, double, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
+    }
+}
+hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int grid_cap, hipStream_t s) {
+    const dim3 g((unsigned) std::max(1, std::min((a.n + 511) / 512, std::max(1, grid_cap))));
+    if (a.subset) { if (float64) frame_dispatch<double, true>(precision, a, g, s); else frame_dispatch<float, true>(precision, a, g, s); }
+    else { if (float64) frame_dispatch<double, false>(precision, a, g, s); else frame_dispatch<float, false>(precision, a, g, s); }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_frame_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

@@ -61,5 +61,9 @@ hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_ca
 // State digest (vv_dev_digest.inc): one streaming reduction over a.nwords words in blocks of block_threads (a multiple of 64, at most 512),
 // at most grid_cap of them (the kernel strides beyond), added to *a.out.
 hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// One trajectory frame (vv_dev_frames.inc): the streaming kernel over a.n recorded particles in blocks of 512 threads, at most grid_cap of
+// them (the kernel strides beyond; one idle block where a.n = 0), then the one-thread kernel that writes the header and advances the
+// cursor.  float64: components as double instead of float.
+hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int grid_cap, hipStream_t s);
 
 }  // namespace vv

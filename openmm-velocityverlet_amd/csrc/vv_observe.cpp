@@ -1,6 +1,8 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.
+// the series of its rows, trajectory frames, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.
 #include "vv_plan.hpp"
+
+#include <algorithm>
 
 // The steps i = 1 .. steps after step counter c0 that append a series row (empty without a series)
 std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps) {
@@ -16,6 +18,24 @@ std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps) {
     if (!p->cmm.on) return r;
     const long long f = p->cmm.frequency;
     for (long long i = (f - c0 % f) % f; i < steps; i += f) r.push_back((int) i);
+    return r;
+}
+// The schedule of the trajectory frames, stated once (include/vvhip.h: vvhip_frames_schedule): the first due step after step c >= 0.
+// LOG10 is GroReporter(logarithm=True)'s recurrence -- base = interval while c < interval, else the largest power of ten <= c -- which
+// names the same steps wherever it starts; integers only.
+static long long frame_next_due(int interval, int schedule, long long c) {
+    long long base = interval;
+    if (schedule == VVHIP_FRAMES_LOG10 && c >= interval)
+        for (base = 1; base <= c / 10; base *= 10) {}
+    return c + base - c % base;
+}
+static bool frame_due(int interval, int schedule, long long s) { return s >= 1 && frame_next_due(interval, schedule, s - 1) == s; }
+// The steps i = 1 .. steps after step counter c0 that record a frame (empty without a recorder)
+std::vector<int> frames_in(const vvhip_plan* p, long long c0, int steps) {
+    std::vector<int> r;
+    if (!p->frames.on) return r;
+    const vvhip_plan::Frames& F = p->frames;
+    for (long long s = frame_next_due(F.interval, F.schedule, c0); s <= c0 + steps; s = frame_next_due(F.interval, F.schedule, s)) r.push_back((int) (s - c0));
     return r;
 }
 
@@ -53,10 +73,26 @@ static int series_row(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_series_append(a, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
-// A full step has been enqueued (or captured): count it, and append a row when it is due.
+// ------------------------------------------------------------------------------------------ frames (vvhip_frames_*)
+// One frame behind the step just enqueued (or captured), and behind its series row: the streaming kernel and the one-thread kernel that
+// writes the header and advances the cursor.  Two launches, no memset and no host synchronisation.
+static int frame_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Frames& F = p->frames;
+    vv::FrameArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.subset = F.has_subset ? F.d_subset.get() : nullptr;
+    a.frames = F.d_frames.get(); a.cursor = F.d_cursor.get();
+    a.frame_bytes = F.frame_bytes; a.off_positions = F.off_positions; a.off_velocities = F.off_velocities;
+    a.n = F.num_particles; a.plane_stride = F.plane_stride; a.capacity = F.capacity;
+    for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
+    HIP_TRY(p, vv::launch_frame(p->hp.precision, a, (F.mask & VVHIP_FRAMES_FLOAT64) != 0, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// A full step has been enqueued (or captured): count it, append a series row when it is due, then record a frame when one is due.
 int step_done(vvhip_plan* p) {
     p->cur.step_count++;
-    if (p->series.on && p->cur.step_count % p->series.interval == 0) return series_row(p);
+    if (p->series.on && p->cur.step_count % p->series.interval == 0) TRY(series_row(p));
+    if (p->frames.on && frame_due(p->frames.interval, p->frames.schedule, p->cur.step_count)) return frame_enqueue(p);
     return VVHIP_OK;
 }
 
@@ -93,6 +129,7 @@ static void series_release(vvhip_plan* p) {
     S.d_rows.reset(); S.d_cursor.reset(); S.d_scratch.reset();
     S.on = false; S.interval = S.capacity = S.mask = 0; S.k0 = 0;
 }
+static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
 
 extern "C" {
 
@@ -328,6 +365,154 @@ int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
     r.steps = p->cur.step_count;
     r.graph_captures = p->graph_captures;
     *out = r;
+    return VVHIP_OK;
+}
+
+int vvhip_frames_schedule(int32_t interval, int32_t schedule, int64_t after_step, int32_t n, int64_t* steps_out) {
+    if (interval < 1 || (schedule != VVHIP_FRAMES_LINEAR && schedule != VVHIP_FRAMES_LOG10) || after_step < 0 || n < 0 || (n > 0 && !steps_out))
+        return VVHIP_ERR_INVALID;
+    long long s = after_step;
+    for (int32_t j = 0; j < n; j++) {
+        if (s >= (1ll << 61)) return VVHIP_ERR_INVALID;      // (the logarithmic schedule grows tenfold every nine frames: no step beyond 2^62)
+        steps_out[j] = s = frame_next_due(interval, schedule, s);
+    }
+    return VVHIP_OK;
+}
+int vvhip_frames_start(vvhip_plan* p, const vvhip_frames_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "frames: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "frames: interval must be >= 1 step");
+    if (d->capacity < 1) return fail(p, VVHIP_ERR_INVALID, "frames: capacity must be >= 1 frame");
+    constexpr int kAll = VVHIP_FRAMES_POSITIONS | VVHIP_FRAMES_VELOCITIES | VVHIP_FRAMES_FLOAT64;
+    if (!(d->mask & (VVHIP_FRAMES_POSITIONS | VVHIP_FRAMES_VELOCITIES)) || (d->mask & ~kAll))
+        return fail(p, VVHIP_ERR_INVALID, "frames: mask must hold VVHIP_FRAMES_POSITIONS and / or VVHIP_FRAMES_VELOCITIES, and besides them VVHIP_FRAMES_FLOAT64 only");
+    if (d->schedule != VVHIP_FRAMES_LINEAR && d->schedule != VVHIP_FRAMES_LOG10)
+        return fail(p, VVHIP_ERR_INVALID, "frames: schedule must be VVHIP_FRAMES_LINEAR or VVHIP_FRAMES_LOG10");
+    const vv::HostPlan& hp = p->hp;
+    const bool has_subset = d->subset != nullptr || d->num_subset != 0;
+    if (d->num_subset < 0 || (d->num_subset > 0 && !d->subset) || (d->subset && d->num_subset == 0))
+        return fail(p, VVHIP_ERR_INVALID, "frames: subset and num_subset must both be given (or NULL / 0 for every particle)");
+    for (int32_t j = 0; j < d->num_subset; j++) {
+        if (d->subset[j] < 0 || d->subset[j] >= hp.num_atoms)
+            return fail(p, VVHIP_ERR_INVALID, "frames: subset[" + std::to_string(j) + "] = " + std::to_string(d->subset[j]) + " is outside [0, num_atoms = " + std::to_string(hp.num_atoms) + ")");
+        if (j > 0 && d->subset[j] <= d->subset[j - 1])
+            return fail(p, VVHIP_ERR_INVALID, "frames: subset must be strictly ascending (subset[" + std::to_string(j) + "] = " + std::to_string(d->subset[j]) + " follows " + std::to_string(d->subset[j - 1]) + ")");
+    }
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
+    // ---- a recorder that runs is settled and goes first (its frames may still be in flight); then the description, host only
+    if (p->frames.on) {
+        TRY(settle_recovery(p));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        drop_graphs(p);
+    }
+    frames_release(p);
+    vvhip_plan::Frames& F = p->frames;
+    F.interval = d->interval; F.schedule = d->schedule; F.capacity = d->capacity; F.mask = d->mask; F.has_subset = has_subset;
+    if (has_subset) {
+        const int32_t* lo = std::lower_bound(d->subset, d->subset + d->num_subset, hp.shard_begin);
+        const int32_t* hi = std::lower_bound(lo, d->subset + d->num_subset, hp.shard_end);
+        F.particles.assign(lo, hi);
+        F.num_particles = (int) F.particles.size();
+    } else {
+        F.num_particles = hp.shard_end - hp.shard_begin;
+    }
+    F.component_bytes = (d->mask & VVHIP_FRAMES_FLOAT64) ? 8 : 4;
+    F.plane_stride = (F.num_particles + 15) / 16 * 16;
+    const long long quantity = 3ll * F.plane_stride * F.component_bytes;
+    long long off = (long long) sizeof(vvhip_frame_header);
+    if (d->mask & VVHIP_FRAMES_POSITIONS) { F.off_positions = off; off += quantity; }
+    if (d->mask & VVHIP_FRAMES_VELOCITIES) { F.off_velocities = off; off += quantity; }
+    F.frame_bytes = off;
+    F.start_step = F.origin = p->cur.step_count;
+    F.described = true;
+    NEED_BOUND(p);
+    TRY(settle_recovery(p));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    drop_graphs(p);
+    const size_t fb = (size_t) F.frame_bytes, total = ((size_t) F.capacity + 1) * fb;
+    auto alloc_fail = [&](hipError_t e, size_t bytes) {
+        F.d_frames.reset(); F.d_cursor.reset(); F.d_subset.reset();
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string("frames: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
+    };
+    hipError_t e = vv::zeros(F.d_frames, total, p->stream);
+    if (e != hipSuccess) return alloc_fail(e, total);
+    HIP_TRY(p, hipMemsetAsync(F.d_frames.get() + (size_t) F.capacity * fb, kGuardByte, fb, p->stream));
+    e = vv::zeros(F.d_cursor, 2 * sizeof(unsigned long long), p->stream);
+    if (e != hipSuccess) return alloc_fail(e, 2 * sizeof(unsigned long long));
+    if (has_subset) {
+        std::vector<int32_t> local(F.particles);
+        for (int32_t& k : local) k -= hp.shard_begin;
+        e = vv::upload(F.d_subset, local, 16);
+        if (e != hipSuccess) return alloc_fail(e, std::max<size_t>(16, local.size() * sizeof(int32_t)));
+    }
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    F.start_step = F.origin = p->cur.step_count;            // (a settled recovery may have moved the counter)
+    F.on = true;
+    return VVHIP_OK;
+}
+int vvhip_frames_read(vvhip_plan* p, void* frames_out, int64_t* steps_out, int32_t max_frames, int32_t* n_frames, int64_t* dropped, int32_t reset) {
+    NEED_BOUND(p);
+    if (max_frames < 0 || (max_frames > 0 && (!frames_out || !steps_out))) return VVHIP_ERR_INVALID;
+    vvhip_plan::Frames& F = p->frames;
+    if (!F.on) return fail(p, VVHIP_ERR_INVALID, "frames: none started (vvhip_frames_start)");
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
+    TRY(settle_recovery(p));                            // (a repaired run rewrites its frames first)
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    unsigned long long cur[2];
+    HIP_TRY(p, hipMemcpy(cur, F.d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost));
+    const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) F.capacity);
+    const long long copy = std::min<long long>(n, max_frames);
+    if (copy > 0) HIP_TRY(p, hipMemcpy(frames_out, F.d_frames.get(), (size_t) copy * (size_t) F.frame_bytes, hipMemcpyDeviceToHost));
+    long long s = F.origin;
+    for (long long j = 0; j < (long long) cur[0]; j++) {    // (dropped frames included: their steps are gone)
+        s = frame_next_due(F.interval, F.schedule, s);
+        if (j >= copy) continue;
+        steps_out[j] = s;
+        vvhip_frame_header h;
+        std::memcpy(&h, (const char*) frames_out + (size_t) j * (size_t) F.frame_bytes, sizeof(h));
+        if (h.ordinal != j)
+            return fail(p, VVHIP_ERR_HIP, "frames: frame " + std::to_string(j) + " carries ordinal " + std::to_string((long long) h.ordinal) + " in its header: the device-side cursor and the buffer disagree");
+    }
+    if (n_frames) *n_frames = (int32_t) n;
+    if (dropped) *dropped = (int64_t) cur[1];
+    if (reset) {
+        HIP_TRY(p, hipMemsetAsync(F.d_cursor.get(), 0, 2 * sizeof(unsigned long long), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        F.origin = s;
+    }
+    return VVHIP_OK;
+}
+int vvhip_frames_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
+    if (!p->frames.on) { frames_release(p); return VVHIP_OK; }
+    TRY(settle_recovery(p));
+    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    frames_release(p);
+    drop_graphs(p);
+    return VVHIP_OK;
+}
+int vvhip_frames_info(const vvhip_plan* p, vvhip_frames_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    const vvhip_plan::Frames& F = p->frames;
+    vvhip_frames_layout r{};
+    r.off_positions = r.off_velocities = -1;
+    if (F.described) {
+        r.active = F.on; r.interval = F.interval; r.schedule = F.schedule; r.capacity = F.capacity; r.mask = F.mask;
+        r.num_particles = F.num_particles; r.component_bytes = F.component_bytes; r.plane_stride = F.plane_stride;
+        r.frame_bytes = F.frame_bytes; r.off_positions = F.off_positions; r.off_velocities = F.off_velocities;
+        r.start_step = F.start_step;
+    }
+    *out = r;
+    return VVHIP_OK;
+}
+int vvhip_frames_particles(const vvhip_plan* p, int32_t* global_indices, int32_t capacity) {
+    if (!p || capacity < 0 || (capacity > 0 && !global_indices)) return VVHIP_ERR_INVALID;
+    const vvhip_plan::Frames& F = p->frames;
+    if (!F.described) return VVHIP_ERR_INVALID;
+    const int32_t n = std::min<int32_t>(capacity, F.num_particles);
+    for (int32_t j = 0; j < n; j++) global_indices[j] = F.has_subset ? F.particles[j] : p->hp.shard_begin + j;
     return VVHIP_OK;
 }
 

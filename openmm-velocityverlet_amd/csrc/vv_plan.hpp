@@ -8,8 +8,8 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: Drude report, series, removal of the centre-of-mass motion, start velocities;
-//                    step_begin / step_done and the schedules series_rows_in / cmm_steps_in
+//   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, removal of the centre-of-mass motion, start
+//                    velocities; step_begin / step_done and the schedules series_rows_in / cmm_steps_in / frames_in
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
 //                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
 //   vv_checkpoint.cpp  the state as a durable blob: vvhip_state_digest, vvhip_checkpoint_size / _save / _load, over the SAME list of items as
@@ -77,8 +77,9 @@ struct GraphKey {
     ForceProvider fp{};
     std::vector<int> rows;                 // steps of the graph (1 .. steps) that append a series row
     std::vector<int> cmm;                  // steps of the graph (0 .. steps - 1) with a removal of the centre-of-mass motion in front
+    std::vector<int> frames;               // steps of the graph (1 .. steps) that record a trajectory frame
     bool operator==(const GraphKey& o) const {
-        return steps == o.steps && fp.site == o.fp.site && fp.kt == o.fp.kt && fp.kd == o.fp.kd && rows == o.rows && cmm == o.cmm;
+        return steps == o.steps && fp.site == o.fp.site && fp.kt == o.fp.kt && fp.kd == o.fp.kd && rows == o.rows && cmm == o.cmm && frames == o.frames;
     }
 };
 
@@ -169,6 +170,8 @@ struct vvhip_plan {
         bool series_saved = false;
         vv::DevBuf<void> cmm_rec;                 // the counters of the scheduled removals of the centre-of-mass motion
         bool cmm_saved = false;
+        vv::DevBuf<void> frames_cursor;           // the frame recorder's device-side cursor (as the series')
+        bool frames_saved = false;
     } rec;
     // plan-owned device state: every buffer frees itself with the plan (vv_devmem.hpp)
     vv::DevBuf<int2> d_slots;
@@ -268,6 +271,21 @@ struct vvhip_plan {
         vv::DevBuf<unsigned long long> d_cursor;  // [2] rows appended (past capacity too), rows dropped
         vv::DevBuf<long long> d_scratch;          // the report's scratch for the rows (as d_rep), zero between rows
     } series;
+    // Trajectory frames (vvhip_frames_*; vv_dev_frames.inc), scheduled by cur.step_count.  `described`: the layout below is that of the last
+    // description that passed vvhip_frames_start's argument checks (kept for an unbound plan too: vvhip_frames_info answers from it);
+    // `on`: the recorder runs and the device buffers exist
+    struct Frames {
+        bool on = false, described = false, has_subset = false;
+        int interval = 0, schedule = 0, capacity = 0, mask = 0;
+        int num_particles = 0, component_bytes = 0, plane_stride = 0;
+        long long frame_bytes = 0, off_positions = -1, off_velocities = -1;
+        long long start_step = 0;                 // the step count at the start
+        long long origin = 0;                     // frame j belongs to the j-th due step after this one (start_step, or the last frame counted before a reset)
+        std::vector<int32_t> particles;           // with a subset: the global indices this plan records (subset within the shard), ascending
+        vv::DevBuf<unsigned char> d_frames;       // [capacity + 1] frames: behind the last one a guard frame (vvhip_debug_frames_guard)
+        vv::DevBuf<unsigned long long> d_cursor;  // [2] frames counted (past capacity too), frames dropped
+        vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
+    } frames;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -384,14 +402,15 @@ int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps);
 std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps);
+std::vector<int> frames_in(const vvhip_plan* p, long long c0, int steps);
 // vv_run.cpp
 // The plan's physical state, stated ONCE, as {live array, its saved copy of the recovery snapshot, bytes, ...}: the six state arrays (0
 // bytes: not in use), both thermostat copies, the random generator's epoch -- in this order the sections VVHIP_CKPT_POSQ ..
-// VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and on request the series' row cursor and the record of the scheduled removals
-// of the centre-of-mass motion (`late`: those two go back with the step counter, after the accumulators are zeroed; a checkpoint does not
+// VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and on request the series' row cursor, the record of the scheduled removals
+// of the centre-of-mass motion and the frame recorder's cursor (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not
 // carry them).  particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
-std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm);
+std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm, bool frames);
 int recover_rendezvous(vvhip_plan* p);
 int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill);
 // vv_exchange.cpp

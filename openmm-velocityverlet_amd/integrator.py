@@ -264,6 +264,21 @@ class Series:
         return len(self.step)
 
 
+@dataclasses.dataclass
+class Frames:
+    """Trajectory frames of a device-side recorder (Context.frames_read; include/vvhip.h: vvhip_frames_*), one per recorded step, in nm and
+    nm/ps.  The arrays have the recorder's component type (float32, or float64 with frames_start(float64=True))."""
+    step: np.ndarray                       # int64 [n]: the step after which the frame was taken
+    box: np.ndarray                        # float64 [n, 3]: the periodic box the step ran with
+    particles: np.ndarray                  # int32 [m]: global indices of the recorded particles (of this context's shard), in frame order
+    positions: Optional[np.ndarray]        # [n, m, 3] as stored: unwrapped, image particles and virtual sites included; None if not recorded
+    velocities: Optional[np.ndarray]       # [n, m, 3], or None
+    dropped: int                           # frames not recorded for want of capacity (their steps follow the last frame)
+
+    def __len__(self):
+        return len(self.step)
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -478,6 +493,54 @@ class Context:
                                                               self.precision == "single")
         return out
 
+    # ---- frames: the trajectory recorded on the device inside the steps (include/vvhip.h: vvhip_frames_*)
+    def frames_start(self, interval: int, capacity: int = 64, logarithmic: bool = False, subset=None, velocities: bool = False,
+                     float64: bool = False, positions: bool = True):
+        """Record the positions (and velocities) of this context's particles, or of those of `subset` (global indices, strictly ascending),
+        after every step the schedule names -- steps counted as for the series; every `interval`-th one, or with logarithmic=True
+        GroReporter(logarithm=True)'s schedule (interval 30: 30, 40, ..., 100, 200, ..., 1000, 2000, ...) -- into a device buffer of
+        `capacity` frames.  No host synchronisation until frames_read.  Restarting drops what was recorded."""
+        sub = None if subset is None else np.ascontiguousarray(subset, dtype=np.int32).reshape(-1)
+        if sub is not None and sub.size == 0:
+            raise ValueError("an empty subset records nothing: pass None for every particle")
+        mask = (H.FRAMES_POSITIONS if positions else 0) | (H.FRAMES_VELOCITIES if velocities else 0) | (H.FRAMES_FLOAT64 if float64 else 0)
+        desc = H.FramesDesc(int(interval), H.FRAMES_LOG10 if logarithmic else H.FRAMES_LINEAR, int(capacity), mask,
+                            0 if sub is None else sub.size, None if sub is None else sub.ctypes.data)
+        H.check(H.lib.vvhip_frames_start(self.plan, C.byref(desc)), self.plan)
+
+    def frames_stop(self):
+        H.check(H.lib.vvhip_frames_stop(self.plan), self.plan)
+
+    def frames_info(self) -> H.FramesLayout:
+        out = H.FramesLayout()
+        H.check(H.lib.vvhip_frames_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def frames_read(self, reset: bool = False) -> Frames:
+        """The frames recorded so far (synchronises).  reset=True empties the buffer; the recorder then continues without gap or repeat."""
+        info = self.frames_info()
+        n, dropped = C.c_int32(0), C.c_int64(0)
+        H.check(H.lib.vvhip_frames_read(self.plan, None, None, 0, C.byref(n), C.byref(dropped), 0), self.plan)      # (how many there are)
+        count, m, fb = n.value, info.num_particles, info.frame_bytes
+        raw = np.zeros(max(count, 1) * fb, dtype=np.uint8)
+        step = np.zeros(max(count, 1), dtype=np.int64)
+        H.check(H.lib.vvhip_frames_read(self.plan, raw.ctypes.data, step.ctypes.data, count, C.byref(n), C.byref(dropped), int(bool(reset))), self.plan)
+        assert n.value == count, (n.value, count)       # (nothing runs between the two calls)
+        raw = raw[: count * fb].reshape(count, fb)
+        dtype = np.float64 if info.component_bytes == 8 else np.float32
+
+        def planes(off):
+            if off < 0:
+                return None
+            a = raw[:, off: off + 3 * info.plane_stride * info.component_bytes].copy().view(dtype).reshape(count, 3, info.plane_stride)
+            return np.ascontiguousarray(a[:, :, :m].transpose(0, 2, 1))
+
+        particles = np.zeros(m, dtype=np.int32)
+        H.check(H.lib.vvhip_frames_particles(self.plan, particles.ctypes.data if m else None, m), self.plan)
+        box = raw[:, 16:40].copy().view(np.float64).reshape(count, 3)
+        return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
+                      velocities=planes(info.off_velocities), dropped=int(dropped.value))
+
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
         """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
@@ -519,7 +582,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series or frame recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

@@ -13,11 +13,17 @@ for every sample.
 ``CheckpointReporter`` is examples/ommhelper/reporter/checkpointreporter.py on ``context.createCheckpoint()``: a file per report, the
 latest three kept.
 
+``write_dcd_frames`` writes the frames of a device-side recorder (``Context.frames_read``) as a DCD trajectory, what
+``DCDReporter('dump.dcd', 10000)`` leaves behind for the same steps.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
 
 import os
+import struct
+
+import numpy as np
 
 HEADER = '#"Step"\t"T_COM"\t"T_Atom"\t"T_Drude"\t"KE_COM"\t"KE_Atom"\t"KE_Drude"'
 CM_MOTION_HEADER = '#"Step"\t"Removals"\t"Skipped"\t"Vx (nm/ps)"\t"Vy (nm/ps)"\t"Vz (nm/ps)"'
@@ -166,3 +172,75 @@ def write_cm_motion_record(file, step, record, append=False, header=True):
     finally:
         if own:
             out.close()
+
+
+DCD_TITLE = (b"Created by openmm-velocityverlet_amd", b"")
+
+
+def _dcd_step_interval(first, count, interval, steps):
+    """The header's step interval after `steps` follow `count` frames that began at `first` with `interval`: their common distance, 0 when
+    the steps are not equidistant (or there is one frame only)."""
+    steps = [int(x) for x in steps]
+    if count == 0:
+        first, count, steps = steps[0], 1, steps[1:]
+        interval = steps[0] - first if steps else 0
+    elif count == 1:
+        interval = steps[0] - first if steps else 0
+    if interval <= 0:
+        return 0
+    return interval if all(x == first + interval * (count + j) for j, x in enumerate(steps)) else 0
+
+
+def write_dcd_frames(file, frames, dt, append=False):
+    """The frames of a device-side recorder (Context.frames_read) as a DCD trajectory at `file` (a path).  `dt`: the step size in ps.
+
+    Little-endian Fortran-unformatted records, each framed by its int32 byte count in front and behind:
+      * 84 bytes: ``CORD``; nine int32 -- number of frames, first step, step interval (0 when the steps are not equidistant, as on a
+        logarithmic schedule), six zeros; float32 dt; int32 1 (a unit cell per frame); eight int32 zeros; int32 24;
+      * 164 bytes: int32 2 and two title lines of 80 bytes;
+      * 4 bytes: the number of atoms;
+      * per frame 48 bytes of six float64 ``a, 0, b, 0, 0, c`` in Angstrom (the zeros: the cosines of the 90 degree angles), then three
+        records of m float32: x, y and z in Angstrom, nm x 10 multiplied in float32.
+    This is the layout OpenMM's DCDFile writes as far as it is documented and remembered; there is no OpenMM here to compare a file with,
+    so it is NOT pinned against one (OpenMM puts the date into the title, this writer does not: equal frames give equal bytes).
+    append=True adds the frames to a file this function wrote and rewrites the header's frame count (byte offset 8) and step interval
+    (byte offset 16): a file written in pieces equals the file written at once.  Positions are written as recorded: unwrapped."""
+    if frames.positions is None:
+        raise ValueError("the frames hold no positions (frames_start(positions=True))")
+    n, m = len(frames.step), len(frames.particles)
+    pos = np.asarray(frames.positions).astype(np.float32, copy=False) * np.float32(10)
+    cell = np.zeros((n, 6), dtype="<f8")
+    cell[:, 0], cell[:, 2], cell[:, 5] = frames.box[:, 0] * 10.0, frames.box[:, 1] * 10.0, frames.box[:, 2] * 10.0
+
+    def record(payload):
+        return struct.pack("<i", len(payload)) + payload + struct.pack("<i", len(payload))
+
+    body = bytearray()
+    for j in range(n):
+        body += record(cell[j].tobytes())
+        for k in range(3):
+            body += record(np.ascontiguousarray(pos[j, :, k], dtype="<f4").tobytes())
+    if append:
+        with open(file, "r+b") as out:
+            head = out.read(24)
+            if len(head) < 24 or head[:8] != struct.pack("<i", 84) + b"CORD":
+                raise ValueError(f"{file} is no DCD file of this writer")
+            count, first, interval = struct.unpack("<3i", head[8:20])
+            out.seek(4 + 84 + 4 + 4 + 164 + 4 + 4)
+            if struct.unpack("<i", out.read(4))[0] != m:
+                raise ValueError(f"{file} holds frames of another number of atoms")
+            if n:
+                new_first = first if count else int(frames.step[0])
+                new_interval = _dcd_step_interval(first, count, interval, frames.step)
+                out.seek(8)
+                out.write(struct.pack("<3i", count + n, new_first, new_interval))
+                out.seek(0, os.SEEK_END)
+                out.write(body)
+        return
+    first = int(frames.step[0]) if n else 0
+    interval = _dcd_step_interval(0, 0, 0, frames.step) if n else 0
+    head = b"CORD" + struct.pack("<9i", n, first, interval, *([0] * 6)) + struct.pack("<f", float(dt)) + struct.pack("<i", 1) + \
+        struct.pack("<8i", *([0] * 8)) + struct.pack("<i", 24)
+    title = struct.pack("<i", len(DCD_TITLE)) + b"".join(line.ljust(80)[:80] for line in DCD_TITLE)
+    with open(file, "wb") as out:
+        out.write(record(head) + record(title) + record(struct.pack("<i", m)) + bytes(body))

@@ -102,6 +102,27 @@ class SeriesLayout(C.Structure):
                 ("steps", C.c_int64), ("graph_captures", C.c_int64)]
 
 
+FRAMES_POSITIONS, FRAMES_VELOCITIES, FRAMES_FLOAT64 = 1, 2, 4
+FRAMES_LINEAR, FRAMES_LOG10 = 0, 1
+
+
+class FramesDesc(C.Structure):
+    """What a frame recorder is to record (include/vvhip.h: vvhip_frames_desc)."""
+    _fields_ = [("interval", C.c_int32), ("schedule", C.c_int32), ("capacity", C.c_int32), ("mask", C.c_int32),
+                ("num_subset", C.c_int32), ("subset", C.c_void_p)]
+
+
+class FrameHeader(C.Structure):
+    """The 64 bytes in front of every frame, written on the device (include/vvhip.h: vvhip_frame_header)."""
+    _fields_ = [("ordinal", C.c_int64), ("reserved", C.c_int64), ("box", C.c_double * 3), ("pad", C.c_double * 3)]
+
+
+class FramesLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("schedule", C.c_int32), ("capacity", C.c_int32), ("mask", C.c_int32),
+                ("num_particles", C.c_int32), ("component_bytes", C.c_int32), ("plane_stride", C.c_int32),
+                ("frame_bytes", C.c_int64), ("off_positions", C.c_int64), ("off_velocities", C.c_int64), ("start_step", C.c_int64)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -177,6 +198,9 @@ def _load():
         "vvhip_drude_report_raw": [vp, P(C.c_int64 * 6)], "vvhip_drude_report_combine": [vp, P(C.c_int64 * 6), P(dbl * 3), P(dbl * 3)],
         "vvhip_series_start": [vp, i32, i32, i32], "vvhip_series_stop": [vp], "vvhip_series_info": [vp, P(SeriesLayout)],
         "vvhip_series_read": [vp, vp, i32, P(i32), P(C.c_int64), P(C.c_int64), i32], "vvhip_debug_series_guard": [vp, P(i32)],
+        "vvhip_frames_start": [vp, P(FramesDesc)], "vvhip_frames_stop": [vp], "vvhip_frames_info": [vp, P(FramesLayout)],
+        "vvhip_frames_read": [vp, vp, vp, i32, P(i32), P(C.c_int64), i32], "vvhip_frames_particles": [vp, vp, i32],
+        "vvhip_frames_schedule": [i32, i32, C.c_int64, i32, vp], "vvhip_debug_frames_guard": [vp, P(i32)],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
@@ -253,6 +277,26 @@ def check(rc: int, plan=None, what: str = ""):
     if rc != OK:
         msg = lib.vvhip_last_error(plan).decode() if plan else what
         raise VVHipError(rc, msg or what)
+
+
+def frames_schedule(interval: int, after_step: int, n: int, logarithmic: bool = False) -> np.ndarray:
+    """The first n steps after `after_step` at which a frame recorder records (include/vvhip.h: vvhip_frames_schedule, the one statement
+    of the linear and the logarithmic schedule)."""
+    out = np.zeros(int(n), dtype=np.int64)
+    rc = lib.vvhip_frames_schedule(int(interval), FRAMES_LOG10 if logarithmic else FRAMES_LINEAR, int(after_step), int(n), out.ctypes.data)
+    if rc != OK:
+        raise VVHipError(rc, "vvhip_frames_schedule: interval must be >= 1, after_step >= 0 and the steps below 2^61")
+    return out
+
+
+def frames_steps(interval: int, after_step: int, last_step: int, logarithmic: bool = False) -> np.ndarray:
+    """The steps in (after_step, last_step] at which a frame recorder records."""
+    out, s = [], int(after_step)
+    while s <= last_step:
+        chunk = frames_schedule(interval, s, 64, logarithmic)
+        out.append(chunk[chunk <= last_step])
+        s = int(chunk[-1])
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
 
 
 def digest_host(data, base: int = 0) -> int:
