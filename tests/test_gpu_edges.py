@@ -42,7 +42,11 @@ def _assert_close(osys, ctx, tol=1e-9):
 @pytest.mark.parametrize("loops", [1, 3])
 @pytest.mark.parametrize("middle", [True, False])
 def test_chain_length_and_loops(chains, loops, middle):
-    spec = systems.drude_il(cells=(1, 1, 1), pairs_per_cell=12, seed=21)
+    """Ten steps from a zero chain state at 10 / 40 per ps against the oracle: every chain length and loop count takes its path and the
+    trajectories agree.  The exp arguments here are about 0.02 and the 1e-8 / 1e-7 below are a trajectory's tolerance, NOT the chain's
+    accuracy: tests/test_gpu_chain.py holds one application of the chain against an exact reference to a few ulps, at the arguments where
+    the device's exp changes its path."""
+    spec =systems.drude_il(cells=(1, 1, 1), pairs_per_cell=12, seed=21)
     osys, ctx, it = _run_pair(spec, 10, middle=middle, chains=chains, loops=loops)
     try:
         _assert_close(osys, ctx)
