@@ -166,7 +166,8 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
         const bool same = b->velm == o.velm && b->posq == o.posq && b->posq_correction == o.posq_correction && b->force == o.force &&
                           b->pos_delta == o.pos_delta && b->random == o.random && b->random_size == o.random_size;
         if (b->velm != o.velm) p->mass_tab_valid = false;
-        if (!same || p->series.on || p->cmm.on || p->frames.on) drop_graphs(p);      // (a series row, a scheduled removal and a frame read velm through their captured arguments too)
+        const Riders rd = riders(p);      // (a series row, a scheduled removal and a frame read velm through their captured arguments too)
+        if (!same || std::any_of(rd.begin(), rd.end(), [](const Rider& r) { return r.on; })) drop_graphs(p);
     }
     // a re-bind that moves the plan to another stream: whatever the plan still has in flight on the old one (fills, steps) must be
     // complete before work enqueued on the new one can touch the same buffers

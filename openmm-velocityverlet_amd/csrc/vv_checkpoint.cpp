@@ -18,7 +18,7 @@ vvhip_checkpoint_cursor cursor_of(const vvhip_plan* p) {
 
 // The device sections of the plan as it stands: every item of the shared list, in its order (bytes 0: not in use)
 std::vector<Section> device_sections(vvhip_plan* p) {
-    const std::vector<RecItem> items = recovery_items(p, false, false, false);
+    const std::vector<RecItem> items = recovery_items(p, nullptr);
     static_assert(VVHIP_CKPT_CURSOR == 8, "the list's items are sections 0 .. 7, the cursor follows");
     std::vector<Section> v;
     for (size_t k = 0; k < items.size() && k < (size_t) VVHIP_CKPT_CURSOR; k++)

@@ -244,22 +244,15 @@ int vvhip_debug_series_guard(vvhip_plan* p, int32_t* intact) {
     if (!intact) return VVHIP_ERR_INVALID;
     if (!p->series.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    unsigned char g[sizeof(vvhip_series_row)];
-    HIP_TRY(p, hipMemcpy(g, p->series.d_rows.get() + p->series.capacity, sizeof(g), hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (unsigned char c : g) if (c != kGuardByte) *intact = 0;
+    HIP_TRY(p, p->series.ring.guard_intact(intact));
     return VVHIP_OK;
 }
 int vvhip_debug_frames_guard(vvhip_plan* p, int32_t* intact) {
     NEED_BOUND(p);
     if (!intact) return VVHIP_ERR_INVALID;
-    const vvhip_plan::Frames& F = p->frames;
-    if (!F.on) return fail(p, VVHIP_ERR_INVALID, "frames: none started (vvhip_frames_start)");
+    if (!p->frames.on) return fail(p, VVHIP_ERR_INVALID, "frames: none started (vvhip_frames_start)");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    std::vector<unsigned char> g((size_t) F.frame_bytes);
-    HIP_TRY(p, hipMemcpy(g.data(), F.d_frames.get() + (size_t) F.capacity * g.size(), g.size(), hipMemcpyDeviceToHost));
-    *intact = 1;
-    for (unsigned char c : g) if (c != kGuardByte) *intact = 0;
+    HIP_TRY(p, p->frames.ring.guard_intact(intact));
     return VVHIP_OK;
 }
 

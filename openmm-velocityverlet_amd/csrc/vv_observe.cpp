@@ -1,42 +1,19 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.
+// the series of its rows, trajectory frames, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
+// ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
 #include "vv_plan.hpp"
 
 #include <algorithm>
 
-// The steps i = 1 .. steps after step counter c0 that append a series row (empty without a series)
-std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps) {
-    std::vector<int> r;
-    if (!p->series.on) return r;
-    const long long k = p->series.interval;
-    for (long long i = k - c0 % k; i <= steps; i += k) r.push_back((int) i);
-    return r;
-}
-// The steps i = 0 .. steps - 1 after step counter c0 with a removal of the centre-of-mass motion in front (empty without a schedule)
-std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps) {
-    std::vector<int> r;
-    if (!p->cmm.on) return r;
-    const long long f = p->cmm.frequency;
-    for (long long i = (f - c0 % f) % f; i < steps; i += f) r.push_back((int) i);
-    return r;
-}
-// The schedule of the trajectory frames, stated once (include/vvhip.h: vvhip_frames_schedule): the first due step after step c >= 0.
-// LOG10 is GroReporter(logarithm=True)'s recurrence -- base = interval while c < interval, else the largest power of ten <= c -- which
-// names the same steps wherever it starts; integers only.
-static long long frame_next_due(int interval, int schedule, long long c) {
-    long long base = interval;
-    if (schedule == VVHIP_FRAMES_LOG10 && c >= interval)
-        for (base = 1; base <= c / 10; base *= 10) {}
-    return c + base - c % base;
-}
-static bool frame_due(int interval, int schedule, long long s) { return s >= 1 && frame_next_due(interval, schedule, s - 1) == s; }
-// The steps i = 1 .. steps after step counter c0 that record a frame (empty without a recorder)
-std::vector<int> frames_in(const vvhip_plan* p, long long c0, int steps) {
-    std::vector<int> r;
-    if (!p->frames.on) return r;
-    const vvhip_plan::Frames& F = p->frames;
-    for (long long s = frame_next_due(F.interval, F.schedule, c0); s <= c0 + steps; s = frame_next_due(F.interval, F.schedule, s)) r.push_back((int) (s - c0));
-    return r;
+// The preamble of an entry point that works beside the steps: never inside a graph capture; the run calls since an unverified snapshot settled
+// (a repaired run redoes its rows, frames and removals first); `sync`: the stream drained; `drop`: the captured graphs, which hold the riders'
+// launches, gone.
+int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop) {
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, std::string(who) + ": not inside a graph capture");
+    TRY(settle_recovery(p));
+    if (sync && p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (drop) drop_graphs(p);
+    return VVHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------ Drude temperature report
@@ -67,7 +44,7 @@ static int series_row(vvhip_plan* p) {
         a.rep_out = S.d_scratch.get(); a.rep_mol_p = S.d_scratch.get() + 8; a.rep_mol_words = 6 * (int64_t) p->hp.report_mol_mass.size();
     }
     if (S.mask & VVHIP_SERIES_THERMOSTAT) a.nh = &p->d_nh.get()[p->cur.parity].s;
-    a.rows = S.d_rows.get(); a.cursor = S.d_cursor.get(); a.capacity = S.capacity;
+    a.rows = (vvhip_series_row*) S.ring.d_items.get(); a.cursor = S.ring.d_cursor.get(); a.capacity = S.ring.capacity;
     for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
     a.cos_acceleration = p->hp.params.cos_acceleration;
     HIP_TRY(p, vv::launch_series_append(a, p->grid_cap_a, p->stream));
@@ -81,23 +58,16 @@ static int frame_enqueue(vvhip_plan* p) {
     vv::FrameArgs a{};
     a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
     a.subset = F.has_subset ? F.d_subset.get() : nullptr;
-    a.frames = F.d_frames.get(); a.cursor = F.d_cursor.get();
+    a.frames = F.ring.d_items.get(); a.cursor = F.ring.d_cursor.get();
     a.frame_bytes = F.frame_bytes; a.off_positions = F.off_positions; a.off_velocities = F.off_velocities;
-    a.n = F.num_particles; a.plane_stride = F.plane_stride; a.capacity = F.capacity;
+    a.n = F.num_particles; a.plane_stride = F.plane_stride; a.capacity = F.ring.capacity;
     for (int k = 0; k < 3; k++) a.box[k] = p->box[k];
     HIP_TRY(p, vv::launch_frame(p->hp.precision, a, (F.mask & VVHIP_FRAMES_FLOAT64) != 0, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
-// A full step has been enqueued (or captured): count it, append a series row when it is due, then record a frame when one is due.
-int step_done(vvhip_plan* p) {
-    p->cur.step_count++;
-    if (p->series.on && p->cur.step_count % p->series.interval == 0) TRY(series_row(p));
-    if (p->frames.on && frame_due(p->frames.interval, p->frames.schedule, p->cur.step_count)) return frame_enqueue(p);
-    return VVHIP_OK;
-}
-
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
+static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
 static int cmm_ensure(vvhip_plan* p) {
     vvhip_plan::CmMotion& M = p->cmm;
     if (M.d_words && M.d_rec && M.h_v) return VVHIP_OK;
@@ -118,17 +88,38 @@ static int cmm_enqueue(vvhip_plan* p, int which) {
     HIP_TRY(p, vv::launch_cm_motion(p->hp.precision, a, p->block_threads, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
-// A full step is about to be enqueued (or captured): the removal in front of it when its index is due.  The one hook of every entry point
-// that starts a step (next to step_done, which ends it).
-int step_begin(vvhip_plan* p) {
-    if (p->cmm.on && p->cur.step_count % p->cmm.frequency == 0) return cmm_enqueue(p, 0);
+// A one-off removal behind what is queued, and its V: blocks (the call's one synchronisation).  NaN is what the subtract kernel records for
+// a removal it skipped.
+static int cmm_one_off(vvhip_plan* p, double v[3]) {
+    TRY(cmm_enqueue(p, 1));
+    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (std::isnan(p->cmm.h_v[0]))
+        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+    if (v) std::memcpy(v, p->cmm.h_v.get(), 3 * sizeof(double));
     return VVHIP_OK;
 }
-static void series_release(vvhip_plan* p) {
-    vvhip_plan::Series& S = p->series;
-    S.d_rows.reset(); S.d_cursor.reset(); S.d_scratch.reset();
-    S.on = false; S.interval = S.capacity = S.mask = 0; S.k0 = 0;
+// ------------------------------------------------------------------------------------------ the step's scheduled riders
+// In this order everywhere (item k of GraphKey::due, of Recovery::late): behind a step the series' row goes first, then the frame.  `late`: the
+// series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists (one-off calls allocate it too).
+Riders riders(vvhip_plan* p) {
+    return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
+             {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
+             {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue}}};
 }
+// A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
+// hooks of every entry point that starts / ends a step.
+static int enqueue_due(vvhip_plan* p, bool in_front) {
+    for (const Rider& r : riders(p))
+        if (r.on && r.in_front == in_front && due(r.when, p->cur.step_count)) TRY(r.enqueue(p));
+    return VVHIP_OK;
+}
+int step_begin(vvhip_plan* p) { return enqueue_due(p, true); }
+int step_done(vvhip_plan* p) {
+    p->cur.step_count++;
+    return enqueue_due(p, false);
+}
+static void series_release(vvhip_plan* p) { p->series = vvhip_plan::Series{}; }
 static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
 
 extern "C" {
@@ -143,8 +134,7 @@ int vvhip_drude_report_raw(vvhip_plan* p, int64_t raw[6]) {
     if (!raw) return VVHIP_ERR_INVALID;
     const vv::HostPlan& hp = p->hp;
     if (!hp.report_unsupported.empty()) return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + hp.report_unsupported);
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "Drude temperature report: not inside a graph capture");
-    TRY(settle_recovery(p));
+    TRY(quiesce(p, "Drude temperature report", false, false));
     const int nmol = (int) hp.report_mol_mass.size();
     HIP_TRY(p, hipMemsetAsync(p->d_rep.get(), 0, (8 + 6 * (size_t) nmol) * sizeof(long long), p->stream));
     HIP_TRY(p, vv::launch_report(hp.precision, report_args(p, p->d_rep.get()), p->block_threads, p->grid_cap_a, p->stream));
@@ -186,54 +176,36 @@ int vvhip_cm_motion_start(vvhip_plan* p, int32_t frequency) {
     if (!p->hp.has_cm_motion_remover)
         return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: the plan was described without a CMMotionRemover (has_cm_motion_remover = 0), so the thermostat's "
                                           "degrees of freedom (DOF) still count the 3 of the centre of mass; describe the System with the remover to schedule removals");
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    if (cmm_sharded(p)) return fail(p, VVHIP_ERR_UNSUPPORTED, kCmmSharded);
     NEED_BOUND(p);
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
-    TRY(settle_recovery(p));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (removals of a schedule before may still be in flight)
+    TRY(quiesce(p, "centre-of-mass motion", true, true));
     TRY(cmm_ensure(p));
     HIP_TRY(p, hipMemsetAsync(p->cmm.d_rec.get(), 0, sizeof(vv::CmmDevRecord), p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    drop_graphs(p);
-    p->cmm.on = true; p->cmm.frequency = frequency;
+    p->cmm.on = true; p->cmm.when = {frequency, SCHEDULE_LINEAR};
     return VVHIP_OK;
 }
 int vvhip_cm_motion_stop(vvhip_plan* p) {
     if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
-    if (!p->cmm.on) return VVHIP_OK;
-    TRY(settle_recovery(p));
-    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
-    p->cmm.on = false; p->cmm.frequency = 0;
-    drop_graphs(p);
+    if (p->capturing || p->cmm.on) TRY(quiesce(p, "centre-of-mass motion", true, true));      // (nothing to settle for a schedule that is off)
+    p->cmm.on = false; p->cmm.when = Schedule{};
     return VVHIP_OK;
 }
 int vvhip_remove_cm_motion(vvhip_plan* p, double v_removed[3]) {
     if (!p) return VVHIP_ERR_INVALID;
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    if (cmm_sharded(p)) return fail(p, VVHIP_ERR_UNSUPPORTED, kCmmSharded);
     NEED_BOUND(p);
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
-    TRY(settle_recovery(p));
+    TRY(quiesce(p, "centre-of-mass motion", false, false));
     TRY(cmm_ensure(p));
-    TRY(cmm_enqueue(p, 1));
-    HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    if (std::isnan(p->cmm.h_v[0]))      // (what the subtract kernel records for a removal it skipped)
-        return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
-    if (v_removed) std::memcpy(v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
-    return VVHIP_OK;
+    return cmm_one_off(p, v_removed);
 }
 int vvhip_cm_motion_read(vvhip_plan* p, vvhip_cm_motion_record* out) {
     if (!p || !out) return VVHIP_ERR_INVALID;
     vvhip_cm_motion_record r{};
-    r.frequency = p->cmm.on ? p->cmm.frequency : 0;
+    r.frequency = p->cmm.on ? p->cmm.when.interval : 0;
     r.total_mass = p->hp.cm_total_mass;
     if (p->bound && p->cmm.d_rec) {
-        if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "centre-of-mass motion: not inside a graph capture");
-        TRY(settle_recovery(p));                        // (a repaired run redoes its removals first)
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        TRY(quiesce(p, "centre-of-mass motion", true, false));
         vv::CmmDevRecord d{};
         HIP_TRY(p, hipMemcpy(&d, p->cmm.d_rec.get(), sizeof(d), hipMemcpyDeviceToHost));
         r.removals = d.removals; r.skipped = d.skipped;
@@ -255,8 +227,7 @@ int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, doubl
     if (flags & ~(uint32_t) (VVHIP_THERMALIZE_NO_CONSTRAINTS | VVHIP_THERMALIZE_REMOVE_CM))
         return fail(p, VVHIP_ERR_INVALID, "start velocities: unknown flag bits");
     const bool remove_cm = (flags & VVHIP_THERMALIZE_REMOVE_CM) != 0;
-    if (remove_cm && cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)");
+    if (remove_cm && cmm_sharded(p)) return fail(p, VVHIP_ERR_UNSUPPORTED, kCmmSharded);
     NEED_BOUND(p);
     // (the library's own captures, and a host that is capturing the plan's stream itself: the call has to block for its record)
     hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
@@ -281,17 +252,10 @@ int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, doubl
         TRY(run_a(p, cons_a(p), 0));
         r.constrained = 1;
     }
-    if (remove_cm) {
-        TRY(cmm_enqueue(p, 1));
-        HIP_TRY(p, hipMemcpyAsync(p->cmm.h_v.get(), p->cmm.d_rec.get()[1].last_v, 3 * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-    }
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    if (remove_cm) {
-        if (std::isnan(p->cmm.h_v[0]))
-            return fail(p, VVHIP_ERR_OVERFLOW, "centre-of-mass motion: a momentum term is NaN or beyond the fixed-point range; nothing was subtracted");
+    if (remove_cm) {      // (either way the call's one synchronisation)
+        TRY(cmm_one_off(p, r.v_removed));
         r.cm_removed = 1;
-        std::memcpy(r.v_removed, p->cmm.h_v.get(), 3 * sizeof(double));
-    }
+    } else HIP_TRY(p, hipStreamSynchronize(p->stream));
     if (out) *out = r;
     return VVHIP_OK;
 }
@@ -304,19 +268,14 @@ int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_
     if ((mask & VVHIP_SERIES_DRUDE) && !p->hp.report_unsupported.empty())
         return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + p->hp.report_unsupported);
     NEED_BOUND(p);
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
-    TRY(settle_recovery(p));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));      // (rows of a series before may still be in flight)
+    TRY(quiesce(p, "series", true, true));
     series_release(p);
-    drop_graphs(p);
     vvhip_plan::Series& S = p->series;
-    const size_t row_bytes = sizeof(vvhip_series_row), scratch = (8 + 6 * p->hp.report_mol_mass.size()) * sizeof(long long);
-    HIP_TRY(p, vv::zeros(S.d_rows, ((size_t) capacity + 1) * row_bytes, p->stream));
-    HIP_TRY(p, hipMemsetAsync((char*) S.d_rows.get() + (size_t) capacity * row_bytes, kGuardByte, row_bytes, p->stream));
-    HIP_TRY(p, vv::zeros(S.d_cursor, 2 * sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, vv::zeros(S.d_scratch, scratch, p->stream));
+    size_t asked = 0;
+    HIP_TRY(p, S.ring.alloc(sizeof(vvhip_series_row), capacity, p->stream, &asked));
+    HIP_TRY(p, vv::zeros(S.d_scratch, (8 + 6 * p->hp.report_mol_mass.size()) * sizeof(long long), p->stream));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
-    S.on = true; S.interval = interval; S.capacity = capacity; S.mask = mask;
+    S.on = true; S.when = {interval, SCHEDULE_LINEAR}; S.mask = mask;
     S.k0 = p->cur.step_count / interval + 1;               // the first multiple of interval after the current step
     return VVHIP_OK;
 }
@@ -326,32 +285,23 @@ int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_row
     if (max_rows < 0 || (max_rows > 0 && !rows_out)) return VVHIP_ERR_INVALID;
     vvhip_plan::Series& S = p->series;
     if (!S.on) return fail(p, VVHIP_ERR_INVALID, "series: none started (vvhip_series_start)");
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
-    TRY(settle_recovery(p));                            // (a repaired run rewrites its rows first)
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    unsigned long long cur[2];
-    HIP_TRY(p, hipMemcpy(cur, S.d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost));
-    const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) S.capacity);
-    const long long copy = std::min<long long>(n, max_rows);
-    if (copy > 0) HIP_TRY(p, hipMemcpy(rows_out, S.d_rows.get(), (size_t) copy * sizeof(vvhip_series_row), hipMemcpyDeviceToHost));
-    if (n_rows) *n_rows = (int32_t) n;
-    if (first_step) *first_step = (int64_t) S.interval * S.k0;
-    if (dropped) *dropped = (int64_t) cur[1];
+    TRY(quiesce(p, "series", true, false));
+    Ring::Count c;
+    HIP_TRY(p, S.ring.fetch(&c));
+    HIP_TRY(p, S.ring.copy_out(rows_out, std::min<long long>(c.stored, max_rows)));
+    if (n_rows) *n_rows = (int32_t) c.stored;
+    if (first_step) *first_step = (int64_t) S.when.interval * S.k0;
+    if (dropped) *dropped = (int64_t) c.dropped;
     if (reset) {
-        HIP_TRY(p, hipMemsetAsync(S.d_cursor.get(), 0, 2 * sizeof(unsigned long long), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-        S.k0 += (long long) cur[0];                     // (dropped rows included: their steps are gone)
+        HIP_TRY(p, S.ring.reset_cursor(p->stream));
+        S.k0 += c.counted;                              // (dropped rows included: their steps are gone)
     }
     return VVHIP_OK;
 }
 int vvhip_series_stop(vvhip_plan* p) {
     if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "series: not inside a graph capture");
-    if (!p->series.on) return VVHIP_OK;
-    TRY(settle_recovery(p));
-    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
+    if (p->capturing || p->series.on) TRY(quiesce(p, "series", true, true));
     series_release(p);
-    drop_graphs(p);
     return VVHIP_OK;
 }
 int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
@@ -361,7 +311,7 @@ int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
     r.off_drude_raw = (int32_t) offsetof(vvhip_series_row, drude_raw);
     r.off_nh = (int32_t) offsetof(vvhip_series_row, nh);
     r.off_box = (int32_t) offsetof(vvhip_series_row, box);
-    r.active = p->series.on; r.interval = p->series.interval; r.capacity = p->series.capacity; r.mask = p->series.mask;
+    r.active = p->series.on; r.interval = p->series.when.interval; r.capacity = p->series.ring.capacity; r.mask = p->series.mask;
     r.steps = p->cur.step_count;
     r.graph_captures = p->graph_captures;
     *out = r;
@@ -374,7 +324,7 @@ int vvhip_frames_schedule(int32_t interval, int32_t schedule, int64_t after_step
     long long s = after_step;
     for (int32_t j = 0; j < n; j++) {
         if (s >= (1ll << 61)) return VVHIP_ERR_INVALID;      // (the logarithmic schedule grows tenfold every nine frames: no step beyond 2^62)
-        steps_out[j] = s = frame_next_due(interval, schedule, s);
+        steps_out[j] = s = next_due({interval, schedule}, s);
     }
     return VVHIP_OK;
 }
@@ -398,16 +348,11 @@ int vvhip_frames_start(vvhip_plan* p, const vvhip_frames_desc* d) {
         if (j > 0 && d->subset[j] <= d->subset[j - 1])
             return fail(p, VVHIP_ERR_INVALID, "frames: subset must be strictly ascending (subset[" + std::to_string(j) + "] = " + std::to_string(d->subset[j]) + " follows " + std::to_string(d->subset[j - 1]) + ")");
     }
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
     // ---- a recorder that runs is settled and goes first (its frames may still be in flight); then the description, host only
-    if (p->frames.on) {
-        TRY(settle_recovery(p));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-        drop_graphs(p);
-    }
+    if (p->capturing || p->frames.on) TRY(quiesce(p, "frames", true, true));
     frames_release(p);
     vvhip_plan::Frames& F = p->frames;
-    F.interval = d->interval; F.schedule = d->schedule; F.capacity = d->capacity; F.mask = d->mask; F.has_subset = has_subset;
+    F.when = {d->interval, d->schedule}; F.capacity = d->capacity; F.mask = d->mask; F.has_subset = has_subset;
     if (has_subset) {
         const int32_t* lo = std::lower_bound(d->subset, d->subset + d->num_subset, hp.shard_begin);
         const int32_t* hi = std::lower_bound(lo, d->subset + d->num_subset, hp.shard_end);
@@ -426,20 +371,15 @@ int vvhip_frames_start(vvhip_plan* p, const vvhip_frames_desc* d) {
     F.start_step = F.origin = p->cur.step_count;
     F.described = true;
     NEED_BOUND(p);
-    TRY(settle_recovery(p));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    drop_graphs(p);
-    const size_t fb = (size_t) F.frame_bytes, total = ((size_t) F.capacity + 1) * fb;
+    TRY(quiesce(p, "frames", true, true));
     auto alloc_fail = [&](hipError_t e, size_t bytes) {
-        F.d_frames.reset(); F.d_cursor.reset(); F.d_subset.reset();
+        F.ring = Ring{}; F.d_subset.reset();
         (void) hipGetLastError();
         return fail(p, VVHIP_ERR_HIP, std::string("frames: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
     };
-    hipError_t e = vv::zeros(F.d_frames, total, p->stream);
-    if (e != hipSuccess) return alloc_fail(e, total);
-    HIP_TRY(p, hipMemsetAsync(F.d_frames.get() + (size_t) F.capacity * fb, kGuardByte, fb, p->stream));
-    e = vv::zeros(F.d_cursor, 2 * sizeof(unsigned long long), p->stream);
-    if (e != hipSuccess) return alloc_fail(e, 2 * sizeof(unsigned long long));
+    size_t asked = 0;
+    hipError_t e = F.ring.alloc((size_t) F.frame_bytes, F.capacity, p->stream, &asked);
+    if (e != hipSuccess) return alloc_fail(e, asked);
     if (has_subset) {
         std::vector<int32_t> local(F.particles);
         for (int32_t& k : local) k -= hp.shard_begin;
@@ -456,17 +396,14 @@ int vvhip_frames_read(vvhip_plan* p, void* frames_out, int64_t* steps_out, int32
     if (max_frames < 0 || (max_frames > 0 && (!frames_out || !steps_out))) return VVHIP_ERR_INVALID;
     vvhip_plan::Frames& F = p->frames;
     if (!F.on) return fail(p, VVHIP_ERR_INVALID, "frames: none started (vvhip_frames_start)");
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
-    TRY(settle_recovery(p));                            // (a repaired run rewrites its frames first)
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    unsigned long long cur[2];
-    HIP_TRY(p, hipMemcpy(cur, F.d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost));
-    const long long n = (long long) std::min<unsigned long long>(cur[0], (unsigned long long) F.capacity);
-    const long long copy = std::min<long long>(n, max_frames);
-    if (copy > 0) HIP_TRY(p, hipMemcpy(frames_out, F.d_frames.get(), (size_t) copy * (size_t) F.frame_bytes, hipMemcpyDeviceToHost));
+    TRY(quiesce(p, "frames", true, false));
+    Ring::Count c;
+    HIP_TRY(p, F.ring.fetch(&c));
+    const long long copy = std::min<long long>(c.stored, max_frames);
+    HIP_TRY(p, F.ring.copy_out(frames_out, copy));
     long long s = F.origin;
-    for (long long j = 0; j < (long long) cur[0]; j++) {    // (dropped frames included: their steps are gone)
-        s = frame_next_due(F.interval, F.schedule, s);
+    for (long long j = 0; j < c.counted; j++) {             // (dropped frames included: their steps are gone)
+        s = next_due(F.when, s);
         if (j >= copy) continue;
         steps_out[j] = s;
         vvhip_frame_header h;
@@ -474,23 +411,18 @@ int vvhip_frames_read(vvhip_plan* p, void* frames_out, int64_t* steps_out, int32
         if (h.ordinal != j)
             return fail(p, VVHIP_ERR_HIP, "frames: frame " + std::to_string(j) + " carries ordinal " + std::to_string((long long) h.ordinal) + " in its header: the device-side cursor and the buffer disagree");
     }
-    if (n_frames) *n_frames = (int32_t) n;
-    if (dropped) *dropped = (int64_t) cur[1];
+    if (n_frames) *n_frames = (int32_t) c.stored;
+    if (dropped) *dropped = (int64_t) c.dropped;
     if (reset) {
-        HIP_TRY(p, hipMemsetAsync(F.d_cursor.get(), 0, 2 * sizeof(unsigned long long), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
+        HIP_TRY(p, F.ring.reset_cursor(p->stream));
         F.origin = s;
     }
     return VVHIP_OK;
 }
 int vvhip_frames_stop(vvhip_plan* p) {
     if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "frames: not inside a graph capture");
-    if (!p->frames.on) { frames_release(p); return VVHIP_OK; }
-    TRY(settle_recovery(p));
-    if (p->bound) HIP_TRY(p, hipStreamSynchronize(p->stream));
-    frames_release(p);
-    drop_graphs(p);
+    if (p->capturing || p->frames.on) TRY(quiesce(p, "frames", true, true));
+    frames_release(p);                                  // (also the description an unbound plan kept)
     return VVHIP_OK;
 }
 int vvhip_frames_info(const vvhip_plan* p, vvhip_frames_layout* out) {
@@ -499,7 +431,7 @@ int vvhip_frames_info(const vvhip_plan* p, vvhip_frames_layout* out) {
     vvhip_frames_layout r{};
     r.off_positions = r.off_velocities = -1;
     if (F.described) {
-        r.active = F.on; r.interval = F.interval; r.schedule = F.schedule; r.capacity = F.capacity; r.mask = F.mask;
+        r.active = F.on; r.interval = F.when.interval; r.schedule = F.when.kind; r.capacity = F.capacity; r.mask = F.mask;
         r.num_particles = F.num_particles; r.component_bytes = F.component_bytes; r.plane_stride = F.plane_stride;
         r.frame_bytes = F.frame_bytes; r.off_positions = F.off_positions; r.off_velocities = F.off_velocities;
         r.start_step = F.start_step;

@@ -9,7 +9,8 @@
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
 //   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, removal of the centre-of-mass motion, start
-//                    velocities; step_begin / step_done and the schedules series_rows_in / cmm_steps_in / frames_in
+//                    velocities; the list of the step's scheduled riders (riders), step_begin / step_done, quiesce; their one schedule is
+//                    vv_schedule.hpp (integers only, no HIP in it)
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
 //                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
 //   vv_checkpoint.cpp  the state as a durable blob: vvhip_state_digest, vvhip_checkpoint_size / _save / _load, over the SAME list of items as
@@ -22,6 +23,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -37,6 +40,7 @@
 #include "vv_host.hpp"
 #include "vv_kernels.hpp"
 #include "vv_rtc.hpp"
+#include "vv_schedule.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -59,7 +63,9 @@ constexpr double kBoltz = (1.380649e-23 * kAvogadro) / 1000.0;
 enum TimerClass { T_A = 0, T_B = 1, T_OTHER = 2 };
 constexpr int kAccN = vv::NUM_ACC * vv::ACC_SLOTS;
 constexpr int kRvCopy = 6 * kAccN;      // rendezvous words of one thermostat parity: up to 6 replicas (vv_device.inc: RV_REPLICAS) of [NUM_ACC][ACC_SLOTS]
-constexpr int kGuardByte = 0xA5;    // fills the guard row behind a series' last row (vvhip_series_start, vvhip_debug_series_guard)
+constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
+static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
+constexpr int kRiders = 3;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -75,11 +81,44 @@ struct ForceProvider { const void* site; double kt, kd; };
 struct GraphKey {
     int steps = 0;
     ForceProvider fp{};
-    std::vector<int> rows;                 // steps of the graph (1 .. steps) that append a series row
-    std::vector<int> cmm;                  // steps of the graph (0 .. steps - 1) with a removal of the centre-of-mass motion in front
-    std::vector<int> frames;               // steps of the graph (1 .. steps) that record a trajectory frame
+    std::vector<int> due[kRiders];         // per rider the steps of the graph it rides on (Rider::window; empty while it is off)
     bool operator==(const GraphKey& o) const {
-        return steps == o.steps && fp.site == o.fp.site && fp.kt == o.fp.kt && fp.kd == o.fp.kd && rows == o.rows && cmm == o.cmm && frames == o.frames;
+        return steps == o.steps && fp.site == o.fp.site && fp.kt == o.fp.kt && fp.kd == o.fp.kd && std::equal(due, due + kRiders, o.due);
+    }
+};
+
+// What the series' rows and the recorder's frames both are: `capacity` items of item_bytes on the device with a guard item behind the last
+// (kGuardByte: vvhip_debug_*_guard) and a two-word cursor {items counted (past capacity too), items dropped} that the append kernels advance.
+// fetch, copy_out and guard_intact read what the device has written: the stream has drained.
+struct Ring {
+    size_t item_bytes = 0; int capacity = 0;
+    vv::DevBuf<unsigned char> d_items;
+    vv::DevBuf<unsigned long long> d_cursor;
+    struct Count { long long stored, counted, dropped; };
+    // zeroed items, guard and cursor, enqueued on `s`; a failed allocation leaves `*failed` = the bytes it asked for
+    hipError_t alloc(size_t item_bytes_, int capacity_, hipStream_t s, size_t* failed) {
+        hipError_t e = vv::zeros(d_items, *failed = ((size_t) capacity_ + 1) * item_bytes_, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_items.get() + (size_t) capacity_ * item_bytes_, kGuardByte, item_bytes_, s);
+        if (e == hipSuccess) e = vv::zeros(d_cursor, *failed = 2 * sizeof(unsigned long long), s);
+        if (e == hipSuccess) { item_bytes = item_bytes_; capacity = capacity_; }
+        return e;
+    }
+    hipError_t fetch(Count* c) const {
+        unsigned long long cur[2] = {0, 0};
+        const hipError_t e = hipMemcpy(cur, d_cursor.get(), sizeof(cur), hipMemcpyDeviceToHost);
+        *c = {(long long) (cur[0] < (unsigned long long) capacity ? cur[0] : capacity), (long long) cur[0], (long long) cur[1]};
+        return e;
+    }
+    hipError_t copy_out(void* out, long long n) const { return n > 0 ? hipMemcpy(out, d_items.get(), (size_t) n * item_bytes, hipMemcpyDeviceToHost) : hipSuccess; }
+    hipError_t guard_intact(int32_t* intact) const {
+        std::vector<unsigned char> g(item_bytes);
+        const hipError_t e = hipMemcpy(g.data(), d_items.get() + (size_t) capacity * item_bytes, item_bytes, hipMemcpyDeviceToHost);
+        *intact = std::all_of(g.begin(), g.end(), [](unsigned char c) { return c == kGuardByte; });
+        return e;
+    }
+    hipError_t reset_cursor(hipStream_t s) {      // complete on return
+        const hipError_t e = hipMemsetAsync(d_cursor.get(), 0, 2 * sizeof(unsigned long long), s);
+        return e == hipSuccess ? hipStreamSynchronize(s) : e;
     }
 };
 
@@ -166,12 +205,8 @@ struct vvhip_plan {
         struct Run { int kind, nsteps, spg; ForceProvider fp; };
         std::vector<Run> runs;
         long long recoveries = 0;
-        vv::DevBuf<void> series_cursor;               // the series' device-side row cursor (its schedule, the step counter, is in `cur`)
-        bool series_saved = false;
-        vv::DevBuf<void> cmm_rec;                 // the counters of the scheduled removals of the centre-of-mass motion
-        bool cmm_saved = false;
-        vv::DevBuf<void> frames_cursor;           // the frame recorder's device-side cursor (as the series')
-        bool frames_saved = false;
+        vv::DevBuf<void> late[kRiders];           // per rider its Rider::late words (its schedule, the step counter, is in `cur`) ...
+        bool saved[kRiders] = {};                 // ... where the snapshot took them
     } rec;
     // plan-owned device state: every buffer frees itself with the plan (vv_devmem.hpp)
     vv::DevBuf<int2> d_slots;
@@ -265,10 +300,10 @@ struct vvhip_plan {
     // Series (vvhip_series_*): the rows the steps append on the device, scheduled by cur.step_count
     struct Series {
         bool on = false;
-        int interval = 0, capacity = 0, mask = 0;
-        long long k0 = 0;                         // row 0 is step interval * k0
-        vv::DevBuf<vvhip_series_row> d_rows;      // [capacity + 1]: behind the last row a guard row (vvhip_debug_series_guard)
-        vv::DevBuf<unsigned long long> d_cursor;  // [2] rows appended (past capacity too), rows dropped
+        Schedule when;                            // (linear)
+        int mask = 0;
+        long long k0 = 0;                         // row 0 is step when.interval * k0
+        Ring ring;                                // of vvhip_series_row
         vv::DevBuf<long long> d_scratch;          // the report's scratch for the rows (as d_rep), zero between rows
     } series;
     // Trajectory frames (vvhip_frames_*; vv_dev_frames.inc), scheduled by cur.step_count.  `described`: the layout below is that of the last
@@ -276,21 +311,21 @@ struct vvhip_plan {
     // `on`: the recorder runs and the device buffers exist
     struct Frames {
         bool on = false, described = false, has_subset = false;
-        int interval = 0, schedule = 0, capacity = 0, mask = 0;
+        Schedule when;
+        int capacity = 0, mask = 0;               // (the capacity as described: the ring has it once the recorder runs)
         int num_particles = 0, component_bytes = 0, plane_stride = 0;
         long long frame_bytes = 0, off_positions = -1, off_velocities = -1;
         long long start_step = 0;                 // the step count at the start
         long long origin = 0;                     // frame j belongs to the j-th due step after this one (start_step, or the last frame counted before a reset)
         std::vector<int32_t> particles;           // with a subset: the global indices this plan records (subset within the shard), ascending
-        vv::DevBuf<unsigned char> d_frames;       // [capacity + 1] frames: behind the last one a guard frame (vvhip_debug_frames_guard)
-        vv::DevBuf<unsigned long long> d_cursor;  // [2] frames counted (past capacity too), frames dropped
+        Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
         bool on = false;
-        int frequency = 0;
+        Schedule when;                            // (linear: every when.interval-th step, step 0 included)
         vv::DevBuf<long long> d_words;            // [CMM_WORDS] zero between removals
         vv::DevBuf<vv::CmmDevRecord> d_rec;       // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
         vv::PinnedBuf<double> h_v;                // pinned: the V of a one-off call as copied back
@@ -400,17 +435,27 @@ int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_ind
 // vv_observe.cpp
 int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
-std::vector<int> series_rows_in(const vvhip_plan* p, long long c0, int steps);
-std::vector<int> cmm_steps_in(const vvhip_plan* p, long long c0, int steps);
-std::vector<int> frames_in(const vvhip_plan* p, long long c0, int steps);
+int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
+// One of the device work items that hang on the plan's step counter.  A new one is a descriptor in riders() with its enqueue function and its
+// entry points: the step hooks, the graph keys (vv_run.cpp) and the recovery (recovery_items) walk the list.
+struct Rider {
+    bool on; Schedule when;         // scheduled, and at which steps
+    bool in_front;                  // rides in front of the steps that are due (by their 0-based index) / behind them (by the count they complete)
+    void* late; size_t late_bytes;  // device words that a recovery puts back WITH the step counter (null: none to save as the plan stands)
+    int (*enqueue)(vvhip_plan*);
+    // the steps it rides on among the `steps` steps after step counter c0, counted from c0
+    std::vector<int> window(long long c0, int steps) const { return in_front ? due_in(when, c0, c0 + steps - 1, c0) : due_in(when, c0 + 1, c0 + steps, c0); }
+};
+using Riders = std::array<Rider, kRiders>;
+Riders riders(vvhip_plan* p);
 // vv_run.cpp
 // The plan's physical state, stated ONCE, as {live array, its saved copy of the recovery snapshot, bytes, ...}: the six state arrays (0
 // bytes: not in use), both thermostat copies, the random generator's epoch -- in this order the sections VVHIP_CKPT_POSQ ..
-// VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and on request the series' row cursor, the record of the scheduled removals
-// of the centre-of-mass motion and the frame recorder's cursor (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not
-// carry them).  particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
+// VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and behind them, for the riders `with` names (null: none), their Rider::late words
+// (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not carry them).
+// particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
-std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm, bool frames);
+std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);
 int recover_rendezvous(vvhip_plan* p);
 int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill);
 // vv_exchange.cpp

@@ -31,7 +31,7 @@ static int next_random_slice(vvhip_plan* p, uint32_t* index, bool force_refill) 
 
 // ---- recovery from a missed rendezvous (vvhip_plan::Recovery)
 // What a snapshot -- and a checkpoint (vv_checkpoint.cpp) -- holds: see RecItem in vv_plan.hpp.
-std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm, bool frames) {
+std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]) {
     vvhip_plan::Recovery& r = p->rec;
     const vv::HostPlan& hp = p->hp;
     const size_t nloc = (size_t) (hp.shard_end - hp.shard_begin), rs = sizeof_real(hp.precision), ms = sizeof_mixed(hp.precision);
@@ -44,17 +44,16 @@ std::vector<RecItem> recovery_items(vvhip_plan* p, bool series, bool cmm, bool f
         {const_cast<void*>(p->buf.random), &r.random, hp.has_ld ? (size_t) p->buf.random_size * sizeof(float4) : 0, false},      // the Langevin normals in use
         {p->d_nh.get(), &r.nh, 2 * sizeof(vv::NHDevState), false},
         {p->d_epoch.get(), &r.epoch, sizeof(unsigned long long), false}};
-    if (series) v.push_back({p->series.d_cursor.get(), &r.series_cursor, 2 * sizeof(unsigned long long), true});
-    if (cmm) v.push_back({p->cmm.d_rec.get(), &r.cmm_rec, sizeof(vv::CmmDevRecord), true});
-    if (frames) v.push_back({p->frames.d_cursor.get(), &r.frames_cursor, 2 * sizeof(unsigned long long), true});
+    const Riders rd = riders(p);
+    for (int k = 0; with && k < kRiders; k++)      // (words the plan no longer has, or not yet, are left out)
+        if (with[k] && rd[k].late) v.push_back({rd[k].late, &r.late[k], rd[k].late_bytes, true});
     return v;
 }
 static int recovery_snapshot(vvhip_plan* p) {
     vvhip_plan::Recovery& r = p->rec;
-    r.series_saved = p->series.on;                  // (a series cannot start or stop while the snapshot is unverified: both settle it first)
-    r.cmm_saved = (bool) p->cmm.d_rec;              // (a schedule cannot start or stop while the snapshot is unverified either)
-    r.frames_saved = p->frames.on;                  // (nor can a frame recorder)
-    for (const RecItem& it : recovery_items(p, r.series_saved, r.cmm_saved, r.frames_saved)) {
+    const Riders rd = riders(p);                    // (none of them can start or stop while the snapshot is unverified: both settle it first)
+    for (int k = 0; k < kRiders; k++) r.saved[k] = rd[k].late != nullptr;
+    for (const RecItem& it : recovery_items(p, r.saved)) {
         if (!it.bytes) continue;
         HIP_TRY(p, it.saved->ensure(it.bytes));      // (a re-bind may have brought a larger random buffer)
         HIP_TRY(p, hipMemcpyAsync(it.saved->get(), it.live, it.bytes, hipMemcpyDeviceToDevice, p->stream));
@@ -81,16 +80,15 @@ int recover_rendezvous(vvhip_plan* p) {
     for (const auto& run : r.runs) steps += run.nsteps;
     std::fprintf(stderr, "libvvhip: the one-launch step's blocks did not meet within 0.2 s (another process's kernels on the device?): the last %lld step(s) "
                          "are repeated from the plan's snapshot with two launches per step, and the plan keeps two launches from here on\n", steps);
-    const std::vector<RecItem> items = recovery_items(p, r.series_saved && p->series.on, r.cmm_saved && p->cmm.d_rec, r.frames_saved && p->frames.on);
+    const std::vector<RecItem> items = recovery_items(p, r.saved);      // (of the riders: what the snapshot took and the plan still has)
     for (const RecItem& it : items)
         if (!it.late && it.bytes && it.saved->get()) HIP_TRY(p, hipMemcpyAsync(it.live, it.saved->get(), it.bytes, hipMemcpyDeviceToDevice, p->stream));
     // both accumulator copies are zero between steps; whatever the failed steps left in them goes
     HIP_TRY(p, hipMemsetAsync(p->d_acc.get(), 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
     if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc.get(), 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
     HIP_TRY(p, hipMemsetAsync(p->d_rv.get() + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
-    // (with the step counter: the series' rows of the failed steps are written again, at the same places, by the repeat ... and so are the
-    // removals of the centre-of-mass motion, at the same steps -- the schedule follows the step counter: their counters go back with it, and
-    // the scratch words are zero between removals whatever the failed steps computed; the trajectory frames as the series' rows)
+    // (with the step counter: the riders' schedules follow it, so the repeat writes the failed steps' rows and frames again at the same places
+    // and redoes their removals at the same steps; the riders' scratch words are zero between steps whatever the failed steps computed)
     p->cur = r.cur;
     for (const RecItem& it : items)
         if (it.late) HIP_TRY(p, hipMemcpyAsync(it.live, it.saved->get(), it.bytes, hipMemcpyDeviceToDevice, p->stream));
@@ -129,11 +127,14 @@ int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill) {
 
 // Capture + instantiate + upload the graph of `steps_per_graph` steps for thermostat parity `q`, unless that slot already holds it.
 // Nothing is launched: the physical state is untouched.
-// The graph is captured at step counter c0 (where its replays start): its series rows sit at the steps series_rows_in(c0) names (its frames: frames_in).
+// The graph is captured at step counter c0 (where its replays start): every rider that is on sits at the steps its window at c0 names.
 static int prepare_slot(vvhip_plan* p, int q, int steps_per_graph, const ForceProvider& fp, long long c0, vvhip_plan::GraphSlot** out = nullptr) {
     hipStream_t s = p->stream;
     TRY(ensure_mass_table(p));                       // a one-off fill must not be recorded into the replayed graph
-    GraphKey key{steps_per_graph, fp, series_rows_in(p, c0, steps_per_graph), cmm_steps_in(p, c0, steps_per_graph), frames_in(p, c0, steps_per_graph)};
+    GraphKey key{steps_per_graph, fp};
+    const Riders rd = riders(p);
+    for (int k = 0; k < kRiders; k++)
+        if (rd[k].on) key.due[k] = rd[k].window(c0, steps_per_graph);
     vvhip_plan::GraphSlot& g = graph_slot(p, q, key);
     if (out) *out = &g;
     if (g.exec && g.key == key) return VVHIP_OK;
@@ -225,15 +226,15 @@ int vvhip_run_graph(vvhip_plan* p, int nsteps, int steps_per_graph, const void* 
     if (nsteps >= steps_per_graph) {
         vvhip_plan::GraphSlot* g = nullptr;
         TRY(prepare_slot(p, p->cur.parity, steps_per_graph, fp, p->cur.step_count, &g));     // no-op when the slot of this parity is ready
+        const Riders rd = riders(p);
         for (; done + steps_per_graph <= nsteps; done += steps_per_graph) {
-            // with a series the replays' rows fall on other steps of the graph as the counter moves on: the graph whose rows fit
-            // (at most two when the interval and the graph's length divide one another; otherwise the cache may capture again)
-            // (the same for the steps that carry a removal of the centre-of-mass motion, and for those that record a trajectory frame: on a
-            // logarithmic schedule most windows carry none and keep hitting the frame-less executable)
-            if (done > 0 && ((p->series.on && series_rows_in(p, p->cur.step_count, steps_per_graph) != g->key.rows) ||
-                             (p->cmm.on && cmm_steps_in(p, p->cur.step_count, steps_per_graph) != g->key.cmm) ||
-                             (p->frames.on && frames_in(p, p->cur.step_count, steps_per_graph) != g->key.frames)))
-                TRY(prepare_slot(p, p->cur.parity, steps_per_graph, fp, p->cur.step_count, &g));
+            // with a rider on, the replays' rows / removals / frames fall on other steps of the graph as the counter moves on: the graph whose
+            // windows fit (at most two per rider when its interval and the graph's length divide one another; otherwise the cache may capture
+            // again; on a logarithmic schedule most windows carry nothing and keep hitting the executable without)
+            bool fits = true;
+            for (int k = 0; k < kRiders && fits && done > 0; k++)
+                fits = !rd[k].on || rd[k].window(p->cur.step_count, steps_per_graph) == g->key.due[k];
+            if (!fits) TRY(prepare_slot(p, p->cur.parity, steps_per_graph, fp, p->cur.step_count, &g));
             HIP_TRY(p, hipGraphLaunch(g->exec, s));
             p->cur.step_count += steps_per_graph;
         }

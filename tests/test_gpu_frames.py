@@ -12,6 +12,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import checkpoint_cases as K     # noqa: E402
+
 pkg = importlib.import_module("openmm-velocityverlet_amd")
 S, I = pkg.systems, pkg.integrator
 H = I.H
@@ -335,6 +338,56 @@ def test_recorder_next_to_a_series_and_scheduled_removals():
     finally:
         for c in ctxs:
             c.close()
+
+
+def test_three_riders_with_windows_that_shift_between_replays():
+    """Series every 7, removals every 5, frames on the logarithmic schedule from 3, graphs of 20 steps: no interval divides the graph's
+    length, so the replays' windows differ and the cache has to pick (or capture) the graph that fits -- against a context driven one
+    vvhip_step_middle at a time."""
+    spec = spec_for("C3")
+    (it1, graph), (it2, single) = make("C3", spec), make("C3", spec)
+    try:
+        for c in (graph, single):
+            c.series_start(7, capacity=32)
+            c.remove_cm_motion_every(5)
+            c.frames_start(3, capacity=32, logarithmic=True, velocities=True, float64=True)
+        graph.run_graph(130, 20)
+        for _ in range(130):
+            it2.step(1)
+        rows = [[c.series_read(reset=True)] for c in (graph, single)]
+        frames = [[c.frames_read(reset=True)] for c in (graph, single)]
+        graph.run_eager(3)
+        graph.run_graph(47, 20)
+        for _ in range(50):
+            it2.step(1)
+        for k, c in enumerate((graph, single)):
+            rows[k].append(c.series_read())
+            frames[k].append(c.frames_read())
+            assert [r.dropped for r in rows[k]] == [0, 0] and [f.dropped for f in frames[k]] == [0, 0]
+            assert list(np.concatenate([r.step for r in rows[k]])) == list(range(7, 181, 7))
+            assert list(np.concatenate([f.step for f in frames[k]])) == list(H.frames_steps(3, 0, 180, True))
+            ok = C.c_int32(0)
+            H.check(H.lib.vvhip_debug_series_guard(c.plan, C.byref(ok)), c.plan)
+            assert ok.value == 1 and guard_intact(c)
+        assert len(frames[0][0]) == 17 and len(frames[0][1]) == 0          # 3 .. 10, 20 .. 100; the next one is step 200
+        for a, b in zip(rows[0], rows[1]):
+            for name in ("raw", "ke", "t", "box") + NH_FIELDS:
+                assert eq(getattr(a, name), getattr(b, name)), name
+        for a, b in zip(frames[0], frames[1]):
+            assert frames_equal(a, b)
+        ra, rb = graph.cm_motion_record(), single.cm_motion_record()
+        assert ra.removals == rb.removals == 36 and ra.skipped == rb.skipped == 0 and list(ra.last_v) == list(rb.last_v)
+        # every section's digest, the thermostat's over its copies without the rendezvous wait's self-tuning words (rv_delay / rv_calm follow
+        # the timing, not the trajectory: tests/checkpoint_cases.py), and the particle arrays as downloaded
+        K.assert_same(K.state(graph), K.state(single), "replays against single steps")
+        # The cache neither captures more nor keeps fewer than before the riders' schedules were stated once: 8 is what that commit's
+        # library counts for this exact sequence (the six windows of the first call all differ, and so do the two of the last, at the other
+        # thermostat parity).
+        print("graph_captures", graph.series_info().graph_captures)
+        assert graph.series_info().graph_captures == 8
+    finally:
+        graph.close()
+        single.close()
 
 
 def test_stop_leaves_the_run_as_if_there_never_was_a_recorder():
