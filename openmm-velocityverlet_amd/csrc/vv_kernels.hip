@@ -57,130 +57,178 @@ static inline hipError_t vv_launch_module(hipFunction_t f, dim3 g, dim3 b, unsig
     if (e0 || e1) return hipExtModuleLaunchKernel(f, g.x * b.x, 1, 1, b.x, 1, 1, lds, s, params, nullptr, e0, e1, 0);
     return hipModuleLaunchKernel(f, g.x, 1, 1, b.x, 1, 1, lds, s, params, nullptr);
 }
-#define VV_DISPATCH(KERNEL, ...)                                                                       \
-    switch (precision) {                                                                               \
-        case VVHIP_SINGLE: hipLaunchKernelGGL((KERNEL<float, float>), __VA_ARGS__); break;             \
-        case VVHIP_MIXED: hipLaunchKernelGGL((KERNEL<float, double>), __VA_ARGS__); break;             \
-        default: hipLaunchKernelGGL((KERNEL<double, double>), __VA_ARGS__); break;                     \
-    }
-#define VV_DISPATCH_SF(KERNEL, SFV, ...)                                                               \
-    switch (precision) {                                                                               \
-        case VVHIP_SINGLE: vv_launch((KERNEL<float, float, SFV>), __VA_ARGS__); break;                 \
-        case VVHIP_MIXED: vv_launch((KERNEL<float, double, SFV>), __VA_ARGS__); break;                 \
-        default: vv_launch((KERNEL<double, double, SFV>), __VA_ARGS__); break;                         \
-    }
+// The precision modes.  A kernel template's leading parameters are the mode's types (real, mixed) = (float, float) / (float, double) /
+// (double, double); every launcher of this file picks its instance here -- VV_PER_PRECISION names the three, PerPrecision chooses.
+template <class K> struct PerPrecision {
+    K single, mixed, dbl;
+    constexpr K operator()(int precision) const { return precision == VVHIP_SINGLE ? single : precision == VVHIP_MIXED ? mixed : dbl; }
+};
+#define VV_PER_PRECISION(KERNEL, ...) {&KERNEL<float, float, ##__VA_ARGS__>, &KERNEL<float, double, ##__VA_ARGS__>, &KERNEL<double, double, ##__VA_ARGS__>}
+#define VV_PICK(PRECISION, KERNEL, ...) (PerPrecision<decltype(&KERNEL<float, float, ##__VA_ARGS__>)> VV_PER_PRECISION(KERNEL, ##__VA_ARGS__)(PRECISION))
+// Kernels A and B have one signature each, whatever the precision mode and the stage sets (vv_dev_kernel_a.inc / vv_dev_kernel_b.inc)
+using KernelA = void (*)(const int2*, int, int, void*, const long long*, int, KArgs);
+using KernelB = void (*)(const int2*, int, int, const unsigned long long*, const NHDevState*, const ChainLaneBlock*, const int*, KArgs);
 
-// Stage-bit sets with their own compiled kernel: the fused middle step of a Drude system with / without hard wall
-// (BASELINE configs C3 / C2).  Everything else runs the generic kernel with run-time bits.
-constexpr uint32_t SF_A_MIDDLE = A_KICK_FULL | A_KE;
-constexpr uint32_t SF_A_COS1 = A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE;          // cos acceleration (BASELINE C4): kick + bias moment
-constexpr uint32_t SF_A_COS2 = A_KE | A_UNBIAS_ACC | A_CZ_LOAD;                     // ... kinetic energies of the bias-free velocities
-constexpr uint32_t SF_B_COS_HW = B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL;
-constexpr uint32_t SF_B_MIDDLE_HW = B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL;
-constexpr uint32_t SF_B_MIDDLE = B_CHAIN | B_SCALE | B_DRIFT_MIDDLE;
-constexpr uint32_t SF_A_EDL = A_KICK_FULL | A_LD | A_EF | A_KE;                                // electrode slab (BASELINE C5): Langevin subset + field
-constexpr uint32_t SF_B_EDL = SF_B_MIDDLE_HW | B_IMAGE;                                         // ... + image mirror
-constexpr uint32_t SF_A_COS_MOM = A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE | A_KE | A_KE_MOM;   // cos acceleration in one launch (moments)
-constexpr uint32_t SF_B_COS_HW_MOM = SF_B_COS_HW | B_KE_MOM;
-constexpr uint32_t SF_B_MIDDLE_HW_NC = B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL;                // large systems: the chain runs as its own 1-wave launch in front
-constexpr uint32_t SF_B_MIDDLE_HW_MB = SF_B_MIDDLE_HW | B_MAILBOX;
-constexpr uint32_t SF_A_MIDDLE_SHAKE = SF_A_MIDDLE | A_SHAKE_V;                         // HBonds constraints solved in-kernel
-constexpr uint32_t SF_B_MIDDLE_HW_SHAKE = SF_B_MIDDLE_HW | B_SHAKE;
-constexpr uint32_t SF_B_MIDDLE_SHAKE = SF_B_MIDDLE | B_SHAKE;
-constexpr uint32_t SF_A_MIDDLE_SETTLE = SF_A_MIDDLE | A_SETTLE;                       // rigid water (BASELINE C2 made physical): SETTLE only
-constexpr uint32_t SF_B_MIDDLE_SETTLE = SF_B_MIDDLE | B_SETTLE;
-
-// Further stage sets with their own compiled kernel (the generic kernel with run-time stage bits is 15-20 % slower: C5 went from
-// 74 k to 88 k steps/s when it got its own pair): the classic scheme's two halves and the stages of the un-fused entry points.
-constexpr uint32_t SF_A_KE = A_KE;                                              // vvhip_scale_velocity / classic first half: sums only
-constexpr uint32_t SF_A_VV2 = A_KICK_HALF | A_KE;                               // classic second half
-constexpr uint32_t SF_A_KICK = A_KICK_FULL;                                     // vvhip_middle_kick (forceExtra known to be zero)
-constexpr uint32_t SF_A_KICK_FE = A_FE_LOAD | A_KICK_FULL;                      // ... with extra forces
-constexpr uint32_t SF_A_POS1 = A_POS1;                                          // vvhip_middle_half_drift1
-constexpr uint32_t SF_B_SCALE = B_CHAIN | B_SCALE;                              // vvhip_scale_velocity / classic second half
-constexpr uint32_t SF_B_VV1_HW = B_CHAIN | B_SCALE | B_VV_KICK | B_HARDWALL;    // classic first half
-constexpr uint32_t SF_B_VV1 = B_CHAIN | B_SCALE | B_VV_KICK;
-constexpr uint32_t SF_B_POS2 = B_POS2;                                          // vvhip_middle_half_drift2
-constexpr uint32_t SF_B_POS3_HW = B_POS3 | B_HARDWALL;                          // vvhip_middle_finish
-constexpr uint32_t SF_B_POS3 = B_POS3;
-constexpr uint32_t SF_B_MIDDLE_MB = SF_B_MIDDLE | B_MAILBOX;                    // sharded runs of systems without Drude pairs
-
-// ... and the combinations the reference's example scripts actually run: HBonds constraints next to the cos perturbation
-// (run-bulk.py) and next to the electrode machinery (run-edl.py), and the sharded variants of the constrained / perturbed box
-constexpr uint32_t SF_A_COS_MOM_SHAKE = SF_A_COS_MOM | A_SHAKE_V;
-constexpr uint32_t SF_B_COS_HW_MOM_SHAKE = SF_B_COS_HW_MOM | B_SHAKE;
-constexpr uint32_t SF_A_EDL_SHAKE = SF_A_EDL | A_SHAKE_V;
-constexpr uint32_t SF_B_EDL_SHAKE = SF_B_EDL | B_SHAKE;
-constexpr uint32_t SF_A_LD = A_KICK_FULL | A_LD | A_KE;                     // a Langevin subset without the field (thermostatted wall)
-constexpr uint32_t SF_A_EF = A_KICK_FULL | A_EF | A_KE;                     // a field on the bulk without Langevin particles
-constexpr uint32_t SF_A_LD_SHAKE = SF_A_LD | A_SHAKE_V;
-constexpr uint32_t SF_A_EF_SHAKE = SF_A_EF | A_SHAKE_V;
-constexpr uint32_t SF_B_COS_HW_MOM_MB = SF_B_COS_HW_MOM | B_MAILBOX;
-constexpr uint32_t SF_B_MIDDLE_HW_SHAKE_MB = SF_B_MIDDLE_HW_SHAKE | B_MAILBOX;
-// the headline path without a velm round trip between the kernels (A_NOSTORE / B_KICK): plain, sharded, very large, without hard wall
-constexpr uint32_t SF_A_MIDDLE_NS = SF_A_MIDDLE | A_NOSTORE;
-constexpr uint32_t SF_B_MIDDLE_HW_K = SF_B_MIDDLE_HW | B_KICK;
-constexpr uint32_t SF_B_MIDDLE_K = SF_B_MIDDLE | B_KICK;
-constexpr uint32_t SF_B_MIDDLE_HW_NC_K = SF_B_MIDDLE_HW_NC | B_KICK;
-constexpr uint32_t SF_B_MIDDLE_HW_MB_K = SF_B_MIDDLE_HW_MB | B_KICK;
-constexpr uint32_t SF_B_MIDDLE_MB_K = SF_B_MIDDLE_MB | B_KICK;
-constexpr uint32_t SF_A_COS_MOM_NS = SF_A_COS_MOM | A_NOSTORE;                         // ... and with the cos perturbation (BASELINE C4)
-constexpr uint32_t SF_B_COS_HW_MOM_K = SF_B_COS_HW_MOM | B_KICK;
-constexpr uint32_t SF_B_COS_HW_MOM_MB_K = SF_B_COS_HW_MOM_MB | B_KICK;
-// ... with the arithmetic work-item layout (runs of identical molecules: every BASELINE bulk configuration)
-constexpr uint32_t SF_A_MIDDLE_NS_P = SF_A_MIDDLE_NS | A_PERIODIC;
-constexpr uint32_t SF_A_COS_MOM_NS_P = SF_A_COS_MOM_NS | A_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_HW_K_P = SF_B_MIDDLE_HW_K | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_K_P = SF_B_MIDDLE_K | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_HW_NC_K_P = SF_B_MIDDLE_HW_NC_K | B_PERIODIC;
-constexpr uint32_t SF_B_COS_HW_MOM_K_P = SF_B_COS_HW_MOM_K | B_PERIODIC;
-// ... next to the mailbox exchange of sharded runs (the chain stays in kernel B's head there, whatever the size)
-constexpr uint32_t SF_B_MIDDLE_HW_MB_K_P = SF_B_MIDDLE_HW_MB_K | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_MB_K_P = SF_B_MIDDLE_MB_K | B_PERIODIC;
-constexpr uint32_t SF_B_COS_HW_MOM_MB_K_P = SF_B_COS_HW_MOM_MB_K | B_PERIODIC;
-// large constrained boxes (the chain as its own launch): HBonds clusters solved in kernel B without the thermostat wave
-constexpr uint32_t SF_B_MIDDLE_HW_NC_SHAKE = SF_B_MIDDLE_HW_NC | B_SHAKE;
-constexpr uint32_t SF_B_MIDDLE_HW_NC_SHAKE_P = SF_B_MIDDLE_HW_NC_SHAKE | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_HW_SHAKE_P = SF_B_MIDDLE_HW_SHAKE | B_PERIODIC;
-constexpr uint32_t SF_A_MIDDLE_SHAKE_P = SF_A_MIDDLE_SHAKE | A_PERIODIC;
-// ... and the other stage sets large boxes produce (no thermostat wave in kernel B): without Drude pairs (water, plain ionic liquids), rigid
-// water, the cos perturbation in its three-launch form -- each with loaded and with computed slot words
-constexpr uint32_t SF_B_MIDDLE_NC_K = B_SCALE | B_DRIFT_MIDDLE | B_KICK;
-constexpr uint32_t SF_B_MIDDLE_NC_K_P = SF_B_MIDDLE_NC_K | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_NC_SHAKE = B_SCALE | B_DRIFT_MIDDLE | B_SHAKE;
-constexpr uint32_t SF_B_MIDDLE_NC_SHAKE_P = SF_B_MIDDLE_NC_SHAKE | B_PERIODIC;
-constexpr uint32_t SF_B_MIDDLE_NC_SETTLE = B_SCALE | B_DRIFT_MIDDLE | B_SETTLE;
-constexpr uint32_t SF_B_MIDDLE_NC_SETTLE_P = SF_B_MIDDLE_NC_SETTLE | B_PERIODIC;
-constexpr uint32_t SF_A_MIDDLE_SETTLE_P = SF_A_MIDDLE_SETTLE | A_PERIODIC;
-constexpr uint32_t SF_B_COS_HW_NC = B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL;
-constexpr uint32_t SF_B_COS_HW_NC_P = SF_B_COS_HW_NC | B_PERIODIC;
-// the classic scheme's two thermostat applications in large boxes: scale + half kick + positions (+ hard wall), and scale alone
-constexpr uint32_t SF_B_VV1_HW_NC = B_SCALE | B_VV_KICK | B_HARDWALL;
-constexpr uint32_t SF_B_VV1_HW_NC_P = SF_B_VV1_HW_NC | B_PERIODIC;
-constexpr uint32_t SF_B_VV1_HW_P = SF_B_VV1_HW | B_PERIODIC;                   // classic scheme, arithmetic layout, chain in the kernel (1.1 - 2.6 M particles)
-constexpr uint32_t SF_B_SCALE_P = SF_B_SCALE | B_PERIODIC;
-constexpr uint32_t SF_B_SCALE_NC = B_SCALE;
-constexpr uint32_t SF_B_SCALE_NC_P = SF_B_SCALE_NC | B_PERIODIC;
-
-// The classic scheme (two thermostat applications per step) of every BASELINE configuration with what the example scripts add to it:
-// second half = half kick (+ extra forces kept for the next first half) + sums, first half = scale + half kick + positions.
-constexpr uint32_t SF_A_KE_P = A_KE | A_PERIODIC;                                              // large boxes
-constexpr uint32_t SF_A_VV2_P = SF_A_VV2 | A_PERIODIC;
-constexpr uint32_t SF_A_VV2_SHAKE = SF_A_VV2 | A_SHAKE_V;                                      // + HBonds
-constexpr uint32_t SF_A_VV2_SETTLE = SF_A_VV2 | A_SETTLE;                                      // rigid water
-constexpr uint32_t SF_A_VV2_EDL = SF_A_VV2 | A_FE_STORE | A_LD | A_EF;                         // electrode slab
-constexpr uint32_t SF_A_VV2_EDL_SHAKE = SF_A_VV2_EDL | A_SHAKE_V;
-constexpr uint32_t SF_A_COS_MOM_VV1 = A_BIAS | A_KE | A_CZ_STORE | A_KE_MOM;                   // cos perturbation: sums of the first half
-constexpr uint32_t SF_A_COS_MOM_VV2 = SF_A_COS_MOM_VV1 | A_FE_STORE | A_COS | A_KICK_HALF;     // ... half kick + sums of the second half
-constexpr uint32_t SF_A_COS_MOM_VV2_SHAKE = SF_A_COS_MOM_VV2 | A_SHAKE_V;
-constexpr uint32_t SF_B_VV1_HW_SHAKE = SF_B_VV1_HW | B_SHAKE;
-constexpr uint32_t SF_B_VV1_SETTLE = SF_B_VV1 | B_SETTLE;
-constexpr uint32_t SF_B_VV1_EDL = SF_B_VV1_HW | B_IMAGE;
-constexpr uint32_t SF_B_VV1_EDL_SHAKE = SF_B_VV1_EDL | B_SHAKE;
-constexpr uint32_t SF_B_COS_SCALE_MOM = B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_KE_MOM;   // cos perturbation: second half's scaling
-constexpr uint32_t SF_B_COS_VV1_HW_MOM = SF_B_COS_SCALE_MOM | B_VV_KICK | B_HARDWALL;          // ... first half
-constexpr uint32_t SF_B_COS_VV1_HW_MOM_SHAKE = SF_B_COS_VV1_HW_MOM | B_SHAKE;
-constexpr uint32_t SF_B_MIDDLE_SETTLE_P = SF_B_MIDDLE_SETTLE | B_PERIODIC;                      // rigid water with the arithmetic layout and the chain in the kernel (forced layouts: automatic ones start where the chain is its own launch)
+// ================================================================================ the compiled stage sets
+// Stage-bit sets with their own compiled kernel, one list per kernel kind: VV_SF_A_LIST (kernel A), VV_SF_B_LIST (kernel B) and
+// VV_SF_FUSED_LIST (the one-launch step: B's set with A's).  A line X(name, bits) both defines the constant `name` and puts a kernel for
+// it, in the three precision modes, into the library: a new specialisation is one line here.  A launch whose stage set is in no list gets
+// a kernel compiled at run time (vv_rtc.cpp) or, failing that, the generic kernel with run-time stage bits, which is 15-20 % slower (C5
+// went from 74 k to 88 k steps/s when it got its own pair).  The lookup takes a list in order, so the headline sets stand first; a name may
+// be built from names above it.
+#define VV_SF_A_LIST(X) \
+    /* the headline path: the fused middle step without a velm round trip between the kernels (A_NOSTORE / B_KICK), with the arithmetic */ \
+    /* work-item layout (runs of identical molecules: every BASELINE bulk configuration) and without; these spell their bits in full */ \
+    X(SF_A_MIDDLE_NS_P, A_KICK_FULL | A_KE | A_NOSTORE | A_PERIODIC) \
+    X(SF_A_COS_MOM_NS_P, A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE | A_KE | A_KE_MOM | A_NOSTORE | A_PERIODIC) \
+    X(SF_A_MIDDLE_NS, A_KICK_FULL | A_KE | A_NOSTORE) \
+    X(SF_A_COS_MOM_NS, A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE | A_KE | A_KE_MOM | A_NOSTORE)         /* ... and with the cos perturbation (BASELINE C4) */ \
+    /* the fused middle step with the round trip (BASELINE configs C1 - C3), the cos perturbation (C4), the electrode slab (C5), constraints */ \
+    X(SF_A_MIDDLE, A_KICK_FULL | A_KE) \
+    X(SF_A_COS1, A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE)                                             /* cos acceleration (BASELINE C4): kick + bias moment */ \
+    X(SF_A_COS2, A_KE | A_UNBIAS_ACC | A_CZ_LOAD)                                                       /* ... kinetic energies of the bias-free velocities */ \
+    X(SF_A_COS_MOM, A_KICK_FULL | A_COS | A_BIAS | A_CZ_STORE | A_KE | A_KE_MOM)                        /* cos acceleration in one launch (moments) */ \
+    X(SF_A_EDL, A_KICK_FULL | A_LD | A_EF | A_KE)                                                       /* electrode slab (BASELINE C5): Langevin subset + field */ \
+    X(SF_A_MIDDLE_SHAKE, SF_A_MIDDLE | A_SHAKE_V)                                                       /* HBonds constraints solved in-kernel */ \
+    X(SF_A_MIDDLE_SHAKE_P, SF_A_MIDDLE_SHAKE | A_PERIODIC) \
+    X(SF_A_MIDDLE_SETTLE, SF_A_MIDDLE | A_SETTLE)                                                       /* rigid water (BASELINE C2 made physical): SETTLE only */ \
+    X(SF_A_MIDDLE_SETTLE_P, SF_A_MIDDLE_SETTLE | A_PERIODIC) \
+    /* ... and the combinations the reference's example scripts actually run: HBonds constraints next to the cos perturbation */ \
+    /* (run-bulk.py) and next to the electrode machinery (run-edl.py) */ \
+    X(SF_A_COS_MOM_SHAKE, SF_A_COS_MOM | A_SHAKE_V) \
+    X(SF_A_EDL_SHAKE, SF_A_EDL | A_SHAKE_V) \
+    X(SF_A_LD, A_KICK_FULL | A_LD | A_KE)                                                               /* a Langevin subset without the field (thermostatted wall) */ \
+    X(SF_A_EF, A_KICK_FULL | A_EF | A_KE)                                                               /* a field on the bulk without Langevin particles */ \
+    X(SF_A_LD_SHAKE, SF_A_LD | A_SHAKE_V) \
+    X(SF_A_EF_SHAKE, SF_A_EF | A_SHAKE_V) \
+    /* the classic scheme's two halves and the stages of the un-fused entry points */ \
+    X(SF_A_KE, A_KE)                                                                                    /* vvhip_scale_velocity / classic first half: sums only */ \
+    X(SF_A_VV2, A_KICK_HALF | A_KE)                                                                     /* classic second half */ \
+    X(SF_A_KICK, A_KICK_FULL)                                                                           /* vvhip_middle_kick (forceExtra known to be zero) */ \
+    X(SF_A_KICK_FE, A_FE_LOAD | A_KICK_FULL)                                                            /* ... with extra forces */ \
+    X(SF_A_POS1, A_POS1)                                                                                /* vvhip_middle_half_drift1 */ \
+    /* The classic scheme (two thermostat applications per step) of every BASELINE configuration with what the example scripts add to it: */ \
+    /* second half = half kick (+ extra forces kept for the next first half) + sums, first half = scale + half kick + positions. */ \
+    X(SF_A_KE_P, A_KE | A_PERIODIC)                                                                     /* large boxes */ \
+    X(SF_A_VV2_P, SF_A_VV2 | A_PERIODIC) \
+    X(SF_A_VV2_SHAKE, SF_A_VV2 | A_SHAKE_V)                                                             /* + HBonds */ \
+    X(SF_A_VV2_SETTLE, SF_A_VV2 | A_SETTLE)                                                             /* rigid water */ \
+    X(SF_A_VV2_EDL, SF_A_VV2 | A_FE_STORE | A_LD | A_EF)                                                /* electrode slab */ \
+    X(SF_A_VV2_EDL_SHAKE, SF_A_VV2_EDL | A_SHAKE_V) \
+    X(SF_A_COS_MOM_VV1, A_BIAS | A_KE | A_CZ_STORE | A_KE_MOM)                                          /* cos perturbation: sums of the first half */ \
+    X(SF_A_COS_MOM_VV2, SF_A_COS_MOM_VV1 | A_FE_STORE | A_COS | A_KICK_HALF)                            /* ... half kick + sums of the second half */ \
+    X(SF_A_COS_MOM_VV2_SHAKE, SF_A_COS_MOM_VV2 | A_SHAKE_V)
+#define VV_SF_B_LIST(X) \
+    /* the headline path (A_NOSTORE / B_KICK) with the arithmetic work-item layout: plain, without hard wall, very large (the chain as its */ \
+    /* own launch), cos perturbation, then next to the mailbox exchange of sharded runs (the chain stays in kernel B's head there, */ \
+    /* whatever the size); these spell their bits in full */ \
+    X(SF_B_MIDDLE_HW_K_P, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_KICK | B_PERIODIC) \
+    X(SF_B_MIDDLE_K_P, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_KICK | B_PERIODIC) \
+    X(SF_B_MIDDLE_HW_NC_K_P, B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_KICK | B_PERIODIC) \
+    X(SF_B_COS_HW_MOM_K_P, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM | B_KICK | B_PERIODIC) \
+    X(SF_B_MIDDLE_HW_MB_K_P, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_MAILBOX | B_KICK | B_PERIODIC) \
+    X(SF_B_MIDDLE_MB_K_P, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_MAILBOX | B_KICK | B_PERIODIC) \
+    X(SF_B_COS_HW_MOM_MB_K_P, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM | B_MAILBOX | B_KICK | B_PERIODIC) \
+    X(SF_B_VV1_HW_P, B_CHAIN | B_SCALE | B_VV_KICK | B_HARDWALL | B_PERIODIC)                           /* classic scheme, arithmetic layout, chain in the kernel (1.1 - 2.6 M particles) */ \
+    X(SF_B_SCALE_P, B_CHAIN | B_SCALE | B_PERIODIC) \
+    /* ... the same with loaded slot words */ \
+    X(SF_B_MIDDLE_HW_K, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_KICK) \
+    X(SF_B_MIDDLE_K, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_KICK) \
+    X(SF_B_MIDDLE_HW_NC_K, B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_KICK) \
+    X(SF_B_MIDDLE_HW_MB_K, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL | B_MAILBOX | B_KICK) \
+    X(SF_B_MIDDLE_MB_K, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_MAILBOX | B_KICK) \
+    X(SF_B_COS_HW_MOM_K, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM | B_KICK) \
+    X(SF_B_COS_HW_MOM_MB_K, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM | B_MAILBOX | B_KICK) \
+    /* the fused middle step of a Drude system with / without hard wall (BASELINE configs C3 / C1, C2), with the cos perturbation (C4) */ \
+    X(SF_B_MIDDLE_HW, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL) \
+    X(SF_B_MIDDLE, B_CHAIN | B_SCALE | B_DRIFT_MIDDLE) \
+    X(SF_B_COS_HW, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL) \
+    X(SF_B_COS_HW_MOM, SF_B_COS_HW | B_KE_MOM) \
+    X(SF_B_EDL, SF_B_MIDDLE_HW | B_IMAGE)                                                               /* ... + image mirror */ \
+    X(SF_B_MIDDLE_HW_NC, B_SCALE | B_DRIFT_MIDDLE | B_HARDWALL)                                         /* large systems: the chain runs as its own 1-wave launch in front */ \
+    X(SF_B_MIDDLE_HW_MB, SF_B_MIDDLE_HW | B_MAILBOX) \
+    X(SF_B_MIDDLE_MB, SF_B_MIDDLE | B_MAILBOX)                                                          /* sharded runs of systems without Drude pairs */ \
+    /* HBonds constraints solved in-kernel; large constrained boxes (the chain as its own launch): clusters solved without the thermostat wave */ \
+    X(SF_B_MIDDLE_HW_SHAKE, SF_B_MIDDLE_HW | B_SHAKE) \
+    X(SF_B_MIDDLE_HW_NC_SHAKE, SF_B_MIDDLE_HW_NC | B_SHAKE) \
+    /* ... and the other stage sets large boxes produce (no thermostat wave in kernel B): without Drude pairs (water, plain ionic liquids), */ \
+    /* rigid water, the cos perturbation in its three-launch form -- each with loaded and with computed slot words */ \
+    X(SF_B_MIDDLE_NC_K, B_SCALE | B_DRIFT_MIDDLE | B_KICK) \
+    X(SF_B_MIDDLE_NC_K_P, SF_B_MIDDLE_NC_K | B_PERIODIC) \
+    X(SF_B_MIDDLE_NC_SHAKE, B_SCALE | B_DRIFT_MIDDLE | B_SHAKE) \
+    X(SF_B_MIDDLE_NC_SHAKE_P, SF_B_MIDDLE_NC_SHAKE | B_PERIODIC) \
+    X(SF_B_MIDDLE_SETTLE, SF_B_MIDDLE | B_SETTLE) \
+    X(SF_B_MIDDLE_NC_SETTLE, B_SCALE | B_DRIFT_MIDDLE | B_SETTLE) \
+    X(SF_B_MIDDLE_NC_SETTLE_P, SF_B_MIDDLE_NC_SETTLE | B_PERIODIC) \
+    X(SF_B_COS_HW_NC, B_SCALE | B_UNBIAS | B_CZ_LOAD | B_DRIFT_MIDDLE | B_HARDWALL) \
+    X(SF_B_COS_HW_NC_P, SF_B_COS_HW_NC | B_PERIODIC) \
+    /* the classic scheme's two thermostat applications in large boxes: scale + half kick + positions (+ hard wall), and scale alone */ \
+    X(SF_B_VV1_HW_NC, B_SCALE | B_VV_KICK | B_HARDWALL) \
+    X(SF_B_VV1_HW_NC_P, SF_B_VV1_HW_NC | B_PERIODIC) \
+    X(SF_B_SCALE_NC, B_SCALE) \
+    X(SF_B_SCALE_NC_P, SF_B_SCALE_NC | B_PERIODIC) \
+    X(SF_B_MIDDLE_HW_NC_SHAKE_P, SF_B_MIDDLE_HW_NC_SHAKE | B_PERIODIC) \
+    X(SF_B_MIDDLE_HW_SHAKE_P, SF_B_MIDDLE_HW_SHAKE | B_PERIODIC) \
+    X(SF_B_MIDDLE_SHAKE, SF_B_MIDDLE | B_SHAKE) \
+    /* ... and the combinations the reference's example scripts actually run: HBonds constraints next to the cos perturbation */ \
+    /* (run-bulk.py) and next to the electrode machinery (run-edl.py), and the sharded variants of the constrained / perturbed box */ \
+    X(SF_B_COS_HW_MOM_SHAKE, SF_B_COS_HW_MOM | B_SHAKE) \
+    X(SF_B_EDL_SHAKE, SF_B_EDL | B_SHAKE) \
+    X(SF_B_COS_HW_MOM_MB, SF_B_COS_HW_MOM | B_MAILBOX) \
+    X(SF_B_MIDDLE_HW_SHAKE_MB, SF_B_MIDDLE_HW_SHAKE | B_MAILBOX) \
+    /* the classic scheme's two halves and the stages of the un-fused entry points */ \
+    X(SF_B_SCALE, B_CHAIN | B_SCALE)                                                                    /* vvhip_scale_velocity / classic second half */ \
+    X(SF_B_VV1_HW, B_CHAIN | B_SCALE | B_VV_KICK | B_HARDWALL)                                          /* classic first half */ \
+    X(SF_B_VV1, B_CHAIN | B_SCALE | B_VV_KICK) \
+    X(SF_B_POS2, B_POS2)                                                                                /* vvhip_middle_half_drift2 */ \
+    X(SF_B_POS3_HW, B_POS3 | B_HARDWALL)                                                                /* vvhip_middle_finish */ \
+    X(SF_B_POS3, B_POS3) \
+    /* the classic scheme of every BASELINE configuration with what the example scripts add to it: HBonds, rigid water, electrode slab, cos */ \
+    X(SF_B_VV1_HW_SHAKE, SF_B_VV1_HW | B_SHAKE) \
+    X(SF_B_VV1_SETTLE, SF_B_VV1 | B_SETTLE) \
+    X(SF_B_VV1_EDL, SF_B_VV1_HW | B_IMAGE) \
+    X(SF_B_VV1_EDL_SHAKE, SF_B_VV1_EDL | B_SHAKE) \
+    X(SF_B_COS_SCALE_MOM, B_CHAIN | B_SCALE | B_UNBIAS | B_CZ_LOAD | B_KE_MOM)                          /* cos perturbation: second half's scaling */ \
+    X(SF_B_COS_VV1_HW_MOM, SF_B_COS_SCALE_MOM | B_VV_KICK | B_HARDWALL)                                 /* ... first half */ \
+    X(SF_B_COS_VV1_HW_MOM_SHAKE, SF_B_COS_VV1_HW_MOM | B_SHAKE) \
+    X(SF_B_MIDDLE_SETTLE_P, SF_B_MIDDLE_SETTLE | B_PERIODIC)                                            /* rigid water with the arithmetic layout and the chain in the kernel (forced layouts: automatic ones start where the chain is its own launch) */
+#define VV_SF_NAME(NAME, BITS) constexpr uint32_t NAME = (BITS);
+VV_SF_A_LIST(VV_SF_NAME)
+VV_SF_B_LIST(VV_SF_NAME)
+#undef VV_SF_NAME
+// The one-launch step's kernel-B sets that no two-launch step uses: the cos perturbation keeps no cos(kz) cache between the halves
+constexpr uint32_t SF_B_COS_HW_MOM_F = B_CHAIN | B_SCALE | B_UNBIAS | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM;
+constexpr uint32_t SF_B_COS_SCALE_MOM_F = B_CHAIN | B_SCALE | B_UNBIAS | B_KE_MOM;                                  // classic scheme: second half / first half
+constexpr uint32_t SF_B_COS_VV1_HW_MOM_F = SF_B_COS_SCALE_MOM_F | B_VV_KICK | B_HARDWALL;
+#define VV_SF_FUSED_LIST(X) \
+    X(SF_B_MIDDLE_HW, SF_A_MIDDLE)                               /* BASELINE C3 */ \
+    X(SF_B_MIDDLE, SF_A_MIDDLE)                                  /* C1, C2 */ \
+    X(SF_B_EDL, SF_A_EDL)                                        /* C5 */ \
+    X(SF_B_COS_HW_MOM_F, SF_A_COS_MOM)                           /* C4 */ \
+    X(SF_B_MIDDLE_HW_SHAKE, SF_A_MIDDLE_SHAKE)                   /* ... with their HBonds / rigid water */ \
+    X(SF_B_MIDDLE_SETTLE, SF_A_MIDDLE_SETTLE) \
+    X(SF_B_EDL_SHAKE, SF_A_EDL_SHAKE) \
+    X(SF_B_COS_HW_MOM_F | B_SHAKE, SF_A_COS_MOM_SHAKE) \
+    X(SF_B_MIDDLE_HW_MB, SF_A_MIDDLE)                            /* sharded runs (xGMI mailbox behind the local rendezvous): C3, C4, water */ \
+    X(SF_B_COS_HW_MOM_F | B_MAILBOX, SF_A_COS_MOM) \
+    X(SF_B_MIDDLE_MB, SF_A_MIDDLE) \
+    X(SF_B_MIDDLE_HW_SHAKE_MB, SF_A_MIDDLE_SHAKE) \
+    X(SF_B_VV1_HW, SF_A_KE)                                      /* classic scheme, first half: sums + scaling + half kick + drift (C3) */ \
+    X(SF_B_VV1, SF_A_KE)                                         /* ... C1, C2 */ \
+    X(SF_B_SCALE, SF_A_VV2)                                      /* classic scheme, second half: half kick + sums + scaling */ \
+    X(SF_B_SCALE, SF_A_KE)                                       /* a thermostat application on its own (vvhip_scale_velocity) */ \
+    X(SF_B_VV1_HW_SHAKE, SF_A_KE)                                /* ... the classic scheme of the other BASELINE configurations and their constraints */ \
+    X(SF_B_SCALE, SF_A_VV2_SHAKE) \
+    X(SF_B_VV1_SETTLE, SF_A_KE) \
+    X(SF_B_SCALE, SF_A_VV2_SETTLE) \
+    X(SF_B_VV1_EDL, SF_A_KE) \
+    X(SF_B_SCALE, SF_A_VV2_EDL) \
+    X(SF_B_VV1_EDL_SHAKE, SF_A_KE) \
+    X(SF_B_SCALE, SF_A_VV2_EDL_SHAKE) \
+    X(SF_B_COS_VV1_HW_MOM_F, SF_A_COS_MOM_VV1) \
+    X(SF_B_COS_SCALE_MOM_F, SF_A_COS_MOM_VV2) \
+    X(SF_B_COS_VV1_HW_MOM_F | B_SHAKE, SF_A_COS_MOM_VV1) \
+    X(SF_B_COS_SCALE_MOM_F, SF_A_COS_MOM_VV2_SHAKE)
 
 // Which specialised kernels are compiled with the static mass tables; a launch whose flags disagree with the build falls through to
 // the generic kernel.  Measured on MI355X (gpurun_out/r02c-e): kernel B gains at every size (two IEEE fp64 divisions per pair lane
@@ -197,18 +245,67 @@ constexpr uint32_t SF_AM = VV_SF_MTAB_A ? A_MTAB : 0u, SF_BM = VV_SF_MTAB_B ? B_
 #if VV_KERNELS_PART != 2
 bool sf_kernels_use_mass_table(int kernel) { return kernel == 0 ? VV_SF_MTAB_A != 0 : VV_SF_MTAB_B != 0; }
 #endif
-#define VV_TRY_SF(KERNEL, SFV) if (a.flags == ((SFV) | XM)) { VV_DISPATCH_SF(KERNEL, ((SFV) | XM), g, b, lds, s, ev0, ev1, VV_PRE_ARGS, a); return hipGetLastError(); }
+
+// A list as a table: per row the stage set a launch must ask for (kernel B's and, in the one-launch step, kernel A's) and its kernels.
+template <class K> struct SfRow { uint32_t bits, bits_a; PerPrecision<K> kernel; };
+template <class K, size_t N>
+static K compiled_kernel(const SfRow<K> (&rows)[N], int precision, uint32_t bits, uint32_t bits_a = 0u) {
+    for (const SfRow<K>& r : rows)
+        if (r.bits == bits && r.bits_a == bits_a) return r.kernel(precision);
+    return nullptr;
+}
+template <class K, size_t N>
+constexpr bool rows_differ(const SfRow<K> (&rows)[N]) {
+    for (size_t i = 0; i < N; i++)
+        for (size_t j = 0; j < i; j++)
+            if (rows[i].bits == rows[j].bits && rows[i].bits_a == rows[j].bits_a) return false;
+    return true;
+}
+// The compiled kernels carry the three-link chain only
+static inline bool chain_is_compiled(const KArgs& a) { return !(a.flags & B_CHAIN) || a.chain.num_chains == 3; }
+// LDS of the in-kernel constraint / virtual-site solvers: one page per tile wave, 7 values of the mode's `mixed` type per lane
+static inline unsigned solver_lds(int precision, int block_threads, bool used) {
+    return used ? (unsigned) (block_threads / 64) * 64u * 7u * (precision == VVHIP_SINGLE ? 4u : 8u) : 0u;
+}
+// A kernel compiled at run time for exactly the launch's stage sets (vv_rtc.cpp), with the parameter list of kernel A's / kernel B's signature
+static hipError_t launch_module_a(hipFunction_t f, dim3 g, dim3 b, unsigned lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const KArgs& a, int* route) {
+    const int2* slots = a.slots; int nwaves = a.nwaves, wpb = (int) (b.x >> 6), padded = a.padded;
+    void* velm = a.velm; const long long* force = a.force;
+    void* params[] = {&slots, &nwaves, &wpb, &velm, &force, &padded, const_cast<KArgs*>(&a)};
+    vv_rtc_launches[0]++;
+    if (route) *route = ROUTE_RUNTIME;
+    return vv_launch_module(f, g, b, lds, s, ev0, ev1, params);
+}
+static hipError_t launch_module_b(hipFunction_t f, dim3 g, dim3 b, unsigned lds, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const unsigned long long* acc, const KArgs& a, int* route) {
+    const int2* slots = a.slots; int nwaves = a.nwaves, wpb = (int) (b.x >> 6);
+    const NHDevState* nh = a.nh; const ChainLaneBlock* lane_const = a.lane_const; const int* seg_base = a.seg_base;
+    void* params[] = {&slots, &nwaves, &wpb, &acc, &nh, &lane_const, &seg_base, const_cast<KArgs*>(&a)};
+    vv_rtc_launches[1]++;
+    if (route) *route = ROUTE_RUNTIME;
+    return vv_launch_module(f, g, b, lds, s, ev0, ev1, params);
+}
 
 #if VV_KERNELS_PART != 2
-// Launches that found no compiled specialisation of their stage set and ran the generic kernel with run-time stage bits (15-20 % slower):
-// counted per kernel with the last such stage set (vvhip_generic_launches reads them); VVHIP_WARN_GENERIC=1 also prints one line on
-// stderr per stage set.
-std::atomic<unsigned long long> vv_generic_count[2];
-static void note_generic(const char* kernel, int* route) {
-    vv_generic_count[kernel[0] == 'A' ? 0 : 1]++;
+// (a row names its set by NAME, which VV_SF_NAME has defined as BITS)
+#define VV_SF_ROW_A(NAME, BITS) {NAME | SF_AM, 0u, VV_PER_PRECISION(vv_kernel_a, NAME | SF_AM)},
+#define VV_SF_ROW_B(NAME, BITS) {NAME | SF_BM, 0u, VV_PER_PRECISION(vv_kernel_b, NAME | SF_BM)},
+// kernel A's table and generic kernel (the stage bits are read at run time), then kernel B's
+constexpr SfRow<KernelA> sf_rows_a[] = {VV_SF_A_LIST(VV_SF_ROW_A)};
+constexpr PerPrecision<KernelA> generic_kernel_a = VV_PER_PRECISION(vv_kernel_a, 0u);
+constexpr PerPrecision<KernelB> generic_kernel_b = VV_PER_PRECISION(vv_kernel_b, 0u);
+constexpr SfRow<KernelB> sf_rows_b[] = {VV_SF_B_LIST(VV_SF_ROW_B)};
+#undef VV_SF_ROW_A
+#undef VV_SF_ROW_B
+static_assert(rows_differ(sf_rows_a) && rows_differ(sf_rows_b), "a stage set is listed twice");
+
+// Launches that found no compiled specialisation of their stage set and ran the generic kernel: the caller counts them per plan
+// through `route` (vvhip_generic_launches reads the counts; VVHIP_WARN_GENERIC=1 also prints one line on stderr per stage set).
+static void note_generic(int* route) {
     if (route) *route = ROUTE_GENERIC;
 }
 
+// The routes of a launch, in this order: a kernel compiled at run time where VVHIP_RTC=2 asks for one always, the compiled list, a kernel
+// compiled at run time for a stage set the list has not (VVHIP_RTC=1, default), the generic kernel.
 hipError_t launch_a(int precision, const KArgs& a_in, int block_threads, int grid_cap, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int* route) {
     KArgs a = a_in;
     if (route) *route = ROUTE_COMPILED;
@@ -217,62 +314,14 @@ hipError_t launch_a(int precision, const KArgs& a_in, int block_threads, int gri
     vv_last_grid_value = g.x;
     if (g.x > (unsigned) ACC_SLOTS) a.acc_exclusive = 0;          // several blocks per accumulator slot: atomics (block_accumulate)
     const dim3 b(block_threads);
-    // per-wave LDS page of the in-kernel constraint solver (7 values of the mode's `mixed` type per lane)
-    const unsigned lds = (a.flags & A_CONS) ? (unsigned) (block_threads / 64) * 64u * 7u * (precision == VVHIP_SINGLE ? 4u : 8u) : 0u;
-    constexpr uint32_t XM = SF_AM;
-#define VV_PRE_ARGS a.slots, a.nwaves, (int) (b.x >> 6), a.velm, a.force, a.padded
-    // a kernel compiled at run time for exactly this stage set: where the list below has none (VVHIP_RTC=1, default), or always (=2)
-    hipError_t rtc_error = hipSuccess;
-    auto run_time_kernel = [&]() -> bool {
-        hipFunction_t f = rtc_kernel('A', precision, a.flags, 3);
-        if (!f) return false;
-        const int2* p_slots = a.slots; int p_nwaves = a.nwaves, p_wpb = (int) (b.x >> 6), p_padded = a.padded;
-        void* p_velm = a.velm; const long long* p_force = a.force;
-        void* params[] = {&p_slots, &p_nwaves, &p_wpb, &p_velm, &p_force, &p_padded, &a};
-        rtc_error = vv_launch_module(f, g, b, lds, s, ev0, ev1, params);
-        vv_rtc_launches[0]++;
-        if (route) *route = ROUTE_RUNTIME;
-        return true;
-    };
-    if (rtc_mode() >= 2 && run_time_kernel()) return rtc_error;
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_NS_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_NS_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_NS)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_NS)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS1)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS2)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM)
-    VV_TRY_SF(vv_kernel_a, SF_A_EDL)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_SHAKE_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_SETTLE)
-    VV_TRY_SF(vv_kernel_a, SF_A_MIDDLE_SETTLE_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_EDL_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_LD)
-    VV_TRY_SF(vv_kernel_a, SF_A_EF)
-    VV_TRY_SF(vv_kernel_a, SF_A_LD_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_EF_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_KE)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2)
-    VV_TRY_SF(vv_kernel_a, SF_A_KICK)
-    VV_TRY_SF(vv_kernel_a, SF_A_KICK_FE)
-    VV_TRY_SF(vv_kernel_a, SF_A_POS1)
-    VV_TRY_SF(vv_kernel_a, SF_A_KE_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2_P)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2_SETTLE)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2_EDL)
-    VV_TRY_SF(vv_kernel_a, SF_A_VV2_EDL_SHAKE)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_VV1)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_VV2)
-    VV_TRY_SF(vv_kernel_a, SF_A_COS_MOM_VV2_SHAKE)
-    if (rtc_mode() == 1 && run_time_kernel()) return rtc_error;
-    note_generic("A", route);
-    VV_DISPATCH_SF(vv_kernel_a, 0u, g, b, lds, s, ev0, ev1, VV_PRE_ARGS, a);
+    const unsigned lds = solver_lds(precision, block_threads, (a.flags & A_CONS) != 0);
+    hipFunction_t f = rtc_mode() >= 2 ? rtc_kernel('A', precision, a.flags, 3) : nullptr;
+    KernelA k = f ? nullptr : compiled_kernel(sf_rows_a, precision, a.flags);
+    if (!f && !k && rtc_mode() == 1) f = rtc_kernel('A', precision, a.flags, 3);
+    if (f) return launch_module_a(f, g, b, lds, s, ev0, ev1, a, route);
+    if (!k) { note_generic(route); k = generic_kernel_a(precision); }
+    vv_launch(k, g, b, lds, s, ev0, ev1, a.slots, a.nwaves, (int) (b.x >> 6), a.velm, a.force, a.padded, a);
     return hipGetLastError();
-#undef VV_PRE_ARGS
 }
 hipError_t launch_b(int precision, const KArgs& a, int block_threads, int grid_cap, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int* route) {
     if (route) *route = ROUTE_COMPILED;
@@ -282,94 +331,15 @@ hipError_t launch_b(int precision, const KArgs& a, int block_threads, int grid_c
     if ((int) g.x > grid_cap) g.x = (unsigned) grid_cap;
     vv_last_grid_value = g.x;
     const dim3 b(block_threads + ((a.flags & B_CHAIN) ? 64 : 0));
-    const unsigned lds = (a.flags & (B_CONS | B_VSITE)) ? (unsigned) (block_threads / 64) * 64u * 7u * (precision == VVHIP_SINGLE ? 4u : 8u) : 0u;      // one page per tile wave
-    constexpr uint32_t XM = SF_BM;
-#define VV_PRE_ARGS a.slots, a.nwaves, (int) (b.x >> 6), (const unsigned long long*) a.acc, a.nh, a.lane_const, a.seg_base
-    hipError_t rtc_error = hipSuccess;
-    auto run_time_kernel = [&]() -> bool {          // as in launch_a; the thermostat wave is built for the plan's chain length
-        hipFunction_t f = rtc_kernel('B', precision, a.flags, a.chain.num_chains);
-        if (!f) return false;
-        const int2* p_slots = a.slots; int p_nwaves = a.nwaves, p_wpb = (int) (b.x >> 6);
-        const unsigned long long* p_acc = a.acc; const NHDevState* p_nh = a.nh; const ChainLaneBlock* p_lc = a.lane_const; const int* p_sb = a.seg_base;
-        KArgs copy = a;
-        void* params[] = {&p_slots, &p_nwaves, &p_wpb, &p_acc, &p_nh, &p_lc, &p_sb, &copy};
-        rtc_error = vv_launch_module(f, g, b, lds, s, ev0, ev1, params);
-        vv_rtc_launches[1]++;
-        if (route) *route = ROUTE_RUNTIME;
-        return true;
-    };
-    if (rtc_mode() >= 2 && run_time_kernel()) return rtc_error;
-    if ((a.flags & B_CHAIN) && a.chain.num_chains != 3) {       // the compiled kernels carry the three-link chain only
-        if (rtc_mode() == 1 && run_time_kernel()) return rtc_error;
-        note_generic("B", route);
-        VV_DISPATCH_SF(vv_kernel_b, 0u, g, b, lds, s, ev0, ev1, VV_PRE_ARGS, a);
-        return hipGetLastError();
-    }
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_NC_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_MB_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_MB_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_MB_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_HW_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_SCALE_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_NC_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_MB_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_MB_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_MB_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM)
-    VV_TRY_SF(vv_kernel_b, SF_B_EDL)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_NC)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_MB)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_MB)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_NC_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_K)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_K_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_SHAKE_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_SETTLE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_SETTLE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_NC_SETTLE_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_NC)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_NC_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_HW_NC)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_HW_NC_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_SCALE_NC)
-    VV_TRY_SF(vv_kernel_b, SF_B_SCALE_NC_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_NC_SHAKE_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_SHAKE_P)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_EDL_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_HW_MOM_MB)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_HW_SHAKE_MB)
-    VV_TRY_SF(vv_kernel_b, SF_B_SCALE)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_HW)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1)
-    VV_TRY_SF(vv_kernel_b, SF_B_POS2)
-    VV_TRY_SF(vv_kernel_b, SF_B_POS3_HW)
-    VV_TRY_SF(vv_kernel_b, SF_B_POS3)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_HW_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_SETTLE)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_EDL)
-    VV_TRY_SF(vv_kernel_b, SF_B_VV1_EDL_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_SCALE_MOM)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_VV1_HW_MOM)
-    VV_TRY_SF(vv_kernel_b, SF_B_COS_VV1_HW_MOM_SHAKE)
-    VV_TRY_SF(vv_kernel_b, SF_B_MIDDLE_SETTLE_P)
-    if (rtc_mode() == 1 && run_time_kernel()) return rtc_error;
-    note_generic("B", route);
-    VV_DISPATCH_SF(vv_kernel_b, 0u, g, b, lds, s, ev0, ev1, VV_PRE_ARGS, a);
+    const unsigned lds = solver_lds(precision, block_threads, (a.flags & (B_CONS | B_VSITE)) != 0);
+    // (a run-time kernel's thermostat wave is built for the plan's chain length)
+    hipFunction_t f = rtc_mode() >= 2 ? rtc_kernel('B', precision, a.flags, a.chain.num_chains) : nullptr;
+    KernelB k = f || !chain_is_compiled(a) ? nullptr : compiled_kernel(sf_rows_b, precision, a.flags);
+    if (!f && !k && rtc_mode() == 1) f = rtc_kernel('B', precision, a.flags, a.chain.num_chains);
+    if (f) return launch_module_b(f, g, b, lds, s, ev0, ev1, a.acc, a, route);
+    if (!k) { note_generic(route); k = generic_kernel_b(precision); }
+    vv_launch(k, g, b, lds, s, ev0, ev1, a.slots, a.nwaves, (int) (b.x >> 6), (const unsigned long long*) a.acc, a.nh, a.lane_const, a.seg_base, a);
     return hipGetLastError();
-#undef VV_PRE_ARGS
 }
 #endif      // VV_KERNELS_PART != 2
 #if VV_KERNELS_PART != 1
@@ -377,72 +347,35 @@ hipError_t launch_b(int precision, const KArgs& a, int block_threads, int grid_c
 // wave of its own (it stays in registers across the rendezvous) and the blocks must be resident together: the caller (vv_api.cpp:
 // use_fused) has checked the launch shape; `blocks_per_cu` != nullptr only ASKS how many blocks of this kernel a CU holds and launches
 // nothing.  hipErrorNotSupported: no kernel for this pair of stage sets (the caller then takes the two-launch path).
-constexpr uint32_t SF_B_COS_HW_MOM_F = B_CHAIN | B_SCALE | B_UNBIAS | B_DRIFT_MIDDLE | B_HARDWALL | B_KE_MOM;      // (no cos(kz) cache between the halves)
-constexpr uint32_t SF_B_COS_SCALE_MOM_F = B_CHAIN | B_SCALE | B_UNBIAS | B_KE_MOM;                                  // classic scheme: second half / first half
-constexpr uint32_t SF_B_COS_VV1_HW_MOM_F = SF_B_COS_SCALE_MOM_F | B_VV_KICK | B_HARDWALL;
+#define VV_SF_ROW_FUSED(SFB, SFA) {(SFB) | SF_BM, SFA, VV_PER_PRECISION(vv_kernel_b, (SFB) | SF_BM, SFA)},
+constexpr SfRow<KernelB> sf_rows_fused[] = {VV_SF_FUSED_LIST(VV_SF_ROW_FUSED)};
+#undef VV_SF_ROW_FUSED
+template <size_t N>
+constexpr bool rows_are_pairs(const SfRow<KernelB> (&rows)[N]) {
+    for (const SfRow<KernelB>& r : rows)
+        if (!(r.bits & B_CHAIN) || r.bits_a == 0) return false;
+    return true;
+}
+static_assert(rows_differ(sf_rows_fused), "a pair of stage sets is listed twice");
+static_assert(rows_are_pairs(sf_rows_fused), "the one-launch step needs the thermostat wave (B_CHAIN) and a stage set of kernel A");
 hipError_t launch_fused(int precision, const KArgs& a, int block_threads, const unsigned long long* rendezvous, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int* route, int* blocks_per_cu) {
     if (route) *route = ROUTE_COMPILED;
     const dim3 g = grid_for(a.nwaves, block_threads);
     const dim3 b(block_threads + 64);                      // the tile waves + the block's thermostat wave
     if (!(a.flags & B_CHAIN) || a.flags_a == 0 || (int) g.x > ACC_SLOTS || b.x > 512) return hipErrorNotSupported;
-    const unsigned lds = ((a.flags & (B_CONS | B_VSITE)) || (a.flags_a & A_CONS)) ? (unsigned) (block_threads / 64) * 64u * 7u * (precision == VVHIP_SINGLE ? 4u : 8u) : 0u;      // one page per tile wave
+    const unsigned lds = solver_lds(precision, block_threads, (a.flags & (B_CONS | B_VSITE)) || (a.flags_a & A_CONS));
     vv_last_grid_value = g.x;
-    constexpr uint32_t XM = SF_BM;
-#define VV_PRE_ARGS a.slots, a.nwaves, (int) (b.x >> 6), rendezvous, a.nh, a.lane_const, a.seg_base
-#define VV_FUSED_ONE(REAL, MIXED, SFB, SFA) { \
-        if (blocks_per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, vv_kernel_b<REAL, MIXED, (SFB) | XM, SFA>, (int) b.x, lds); \
-        vv_launch((vv_kernel_b<REAL, MIXED, (SFB) | XM, SFA>), g, b, lds, s, ev0, ev1, VV_PRE_ARGS, a); return hipGetLastError(); }
-#define VV_TRY_FUSED(SFB, SFA) if (a.flags == ((SFB) | XM) && a.flags_a == (SFA) && a.chain.num_chains == 3) { \
-        switch (precision) { case VVHIP_SINGLE: VV_FUSED_ONE(float, float, SFB, SFA) case VVHIP_MIXED: VV_FUSED_ONE(float, double, SFB, SFA) default: VV_FUSED_ONE(double, double, SFB, SFA) } }
-    if (rtc_mode() < 2) {
-        VV_TRY_FUSED(SF_B_MIDDLE_HW, SF_A_MIDDLE)                    // BASELINE C3
-        VV_TRY_FUSED(SF_B_MIDDLE, SF_A_MIDDLE)                       // C1, C2
-        VV_TRY_FUSED(SF_B_EDL, SF_A_EDL)                             // C5
-        VV_TRY_FUSED(SF_B_COS_HW_MOM_F, SF_A_COS_MOM)                // C4
-        VV_TRY_FUSED(SF_B_MIDDLE_HW_SHAKE, SF_A_MIDDLE_SHAKE)        // ... with their HBonds / rigid water
-        VV_TRY_FUSED(SF_B_MIDDLE_SETTLE, SF_A_MIDDLE_SETTLE)
-        VV_TRY_FUSED(SF_B_EDL_SHAKE, SF_A_EDL_SHAKE)
-        VV_TRY_FUSED(SF_B_COS_HW_MOM_F | B_SHAKE, SF_A_COS_MOM_SHAKE)
-        VV_TRY_FUSED(SF_B_MIDDLE_HW_MB, SF_A_MIDDLE)                 // sharded runs (xGMI mailbox behind the local rendezvous): C3, C4, water
-        VV_TRY_FUSED(SF_B_COS_HW_MOM_F | B_MAILBOX, SF_A_COS_MOM)
-        VV_TRY_FUSED(SF_B_MIDDLE_MB, SF_A_MIDDLE)
-        VV_TRY_FUSED(SF_B_MIDDLE_HW_SHAKE_MB, SF_A_MIDDLE_SHAKE)
-        VV_TRY_FUSED(SF_B_VV1_HW, SF_A_KE)                           // classic scheme, first half: sums + scaling + half kick + drift (C3)
-        VV_TRY_FUSED(SF_B_VV1, SF_A_KE)                              // ... C1, C2
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_VV2)                           // classic scheme, second half: half kick + sums + scaling
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_KE)                            // a thermostat application on its own (vvhip_scale_velocity)
-        VV_TRY_FUSED(SF_B_VV1_HW_SHAKE, SF_A_KE)                     // ... the classic scheme of the other BASELINE configurations and their constraints
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_VV2_SHAKE)
-        VV_TRY_FUSED(SF_B_VV1_SETTLE, SF_A_KE)
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_VV2_SETTLE)
-        VV_TRY_FUSED(SF_B_VV1_EDL, SF_A_KE)
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_VV2_EDL)
-        VV_TRY_FUSED(SF_B_VV1_EDL_SHAKE, SF_A_KE)
-        VV_TRY_FUSED(SF_B_SCALE, SF_A_VV2_EDL_SHAKE)
-        VV_TRY_FUSED(SF_B_COS_VV1_HW_MOM_F, SF_A_COS_MOM_VV1)
-        VV_TRY_FUSED(SF_B_COS_SCALE_MOM_F, SF_A_COS_MOM_VV2)
-        VV_TRY_FUSED(SF_B_COS_VV1_HW_MOM_F | B_SHAKE, SF_A_COS_MOM_VV1)
-        VV_TRY_FUSED(SF_B_COS_SCALE_MOM_F, SF_A_COS_MOM_VV2_SHAKE)
+    if (KernelB k = (rtc_mode() < 2 && chain_is_compiled(a)) ? compiled_kernel(sf_rows_fused, precision, a.flags, a.flags_a) : nullptr) {
+        if (blocks_per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k, (int) b.x, lds);
+        vv_launch(k, g, b, lds, s, ev0, ev1, a.slots, a.nwaves, (int) (b.x >> 6), rendezvous, a.nh, a.lane_const, a.seg_base, a);
+        return hipGetLastError();
     }
-#undef VV_TRY_FUSED
-#undef VV_FUSED_ONE
     // any other pair of stage sets (and every pair with VVHIP_RTC=2): compiled at run time from the library's own source
-    if (rtc_mode() >= 1) {
-        hipFunction_t f = rtc_kernel('B', precision, a.flags, a.chain.num_chains, a.flags_a);
-        if (f) {
-            if (blocks_per_cu) return hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, (int) b.x, lds);
-            const int2* p_slots = a.slots; int p_nwaves = a.nwaves, p_wpb = (int) (b.x >> 6);
-            const unsigned long long* p_acc = rendezvous; const NHDevState* p_nh = a.nh; const ChainLaneBlock* p_lc = a.lane_const; const int* p_sb = a.seg_base;
-            KArgs copy = a;
-            void* params[] = {&p_slots, &p_nwaves, &p_wpb, &p_acc, &p_nh, &p_lc, &p_sb, &copy};
-            const hipError_t e = vv_launch_module(f, g, b, lds, s, ev0, ev1, params);
-            vv_rtc_launches[1]++;
-            if (route) *route = ROUTE_RUNTIME;
-            return e;
-        }
+    if (hipFunction_t f = rtc_mode() >= 1 ? rtc_kernel('B', precision, a.flags, a.chain.num_chains, a.flags_a) : nullptr) {
+        if (blocks_per_cu) return hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, (int) b.x, lds);
+        return launch_module_b(f, g, b, lds, s, ev0, ev1, rendezvous, a, route);
     }
     return hipErrorNotSupported;
-#undef VV_PRE_ARGS
 }
 #endif      // VV_KERNELS_PART != 1
 #if VV_KERNELS_PART != 2
@@ -451,16 +384,12 @@ hipError_t launch_chain(const NHConst& c, NHDevState* st, unsigned long long* ac
     return hipGetLastError();
 }
 hipError_t launch_tether(int precision, const TetherArgs& t, int block_threads, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-    switch (precision) {
-        case VVHIP_SINGLE: vv_launch((vv_kernel_tether<float, float>), grid_for(t.nwaves, block_threads), dim3(block_threads), 0, s, ev0, ev1, t.slots, t.nwaves, block_threads / 64, t); break;
-        case VVHIP_MIXED: vv_launch((vv_kernel_tether<float, double>), grid_for(t.nwaves, block_threads), dim3(block_threads), 0, s, ev0, ev1, t.slots, t.nwaves, block_threads / 64, t); break;
-        default: vv_launch((vv_kernel_tether<double, double>), grid_for(t.nwaves, block_threads), dim3(block_threads), 0, s, ev0, ev1, t.slots, t.nwaves, block_threads / 64, t); break;
-    }
+    vv_launch(VV_PICK(precision, vv_kernel_tether), grid_for(t.nwaves, block_threads), dim3(block_threads), 0, s, ev0, ev1, t.slots, t.nwaves, block_threads / 64, t);
     return hipGetLastError();
 }
 hipError_t launch_mass_table(int precision, const void* velm, const int2* slots, int nwaves, double* slot_m, double* slot_f, hipStream_t s) {
     if (nwaves <= 0) return hipSuccess;
-    VV_DISPATCH(vv_kernel_mass_table, dim3((unsigned) ((nwaves + 3) / 4)), dim3(256), 0, s, velm, slots, nwaves, slot_m, slot_f);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_mass_table), dim3((unsigned) ((nwaves + 3) / 4)), dim3(256), 0, s, velm, slots, nwaves, slot_m, slot_f);
     return hipGetLastError();
 }
 hipError_t launch_fill_normals(float4* out, uint32_t count, uint64_t seed, unsigned long long* epoch, hipStream_t s) {
@@ -473,18 +402,18 @@ hipError_t launch_fill_normals(float4* out, uint32_t count, uint64_t seed, unsig
 hipError_t launch_image_pairs(int precision, void* posq, void* corr, const int2* pairs, int npairs, double mirror, hipStream_t s) {
     if (npairs <= 0) return hipSuccess;
     const int blocks = (npairs + 255) / 256;
-    VV_DISPATCH(vv_kernel_images, dim3(blocks), dim3(256), 0, s, posq, corr, pairs, npairs, mirror);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_images), dim3(blocks), dim3(256), 0, s, posq, corr, pairs, npairs, mirror);
     return hipGetLastError();
 }
 hipError_t launch_report(int precision, const ReportArgs& a, int block_threads, int grid_cap, hipStream_t s) {
     const int wpb = block_threads / 64;
     const int g1 = std::max(1, std::min((a.nwaves + wpb - 1) / wpb, grid_cap));
-    VV_DISPATCH(vv_kernel_report_lanes, dim3((unsigned) g1), dim3(block_threads), 0, s, a);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_report_lanes), dim3((unsigned) g1), dim3(block_threads), 0, s, a);
     const hipError_t e = hipGetLastError();
     const int items = a.nmol + a.ncross;
     if (e != hipSuccess || items == 0) return e;
     const int g2 = std::max(1, std::min((items + block_threads - 1) / block_threads, grid_cap));
-    VV_DISPATCH(vv_kernel_report_molecules, dim3((unsigned) g2), dim3(block_threads), 0, s, a);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_report_molecules), dim3((unsigned) g2), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s) {
@@ -495,15 +424,15 @@ hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s
 hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, int grid_cap, hipStream_t s) {
     const int wpb = block_threads / 64;
     const int g = std::max(1, std::min((a.rep.nwaves + wpb - 1) / wpb, grid_cap));
-    VV_DISPATCH(vv_kernel_cmm_sum, dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_cmm_sum), dim3((unsigned) g), dim3(block_threads), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    VV_DISPATCH(vv_kernel_cmm_subtract, dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_cmm_subtract), dim3((unsigned) g), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_cap, hipStream_t s) {
     const int g = std::max(1, std::min(std::max((a.nwaves + 7) / 8, (a.nlaneless + 511) / 512), grid_cap));
-    VV_DISPATCH(vv_kernel_thermalize, dim3((unsigned) g), dim3(512), 0, s, a);
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_thermalize), dim3((unsigned) g), dim3(512), 0, s, a);
     return hipGetLastError();
 }
 hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, hipStream_t s) {
@@ -514,18 +443,11 @@ hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, h
     hipLaunchKernelGGL(vv_kernel_digest, dim3(g), dim3((unsigned) block_threads), 0, s, a);
     return hipGetLastError();
 }
-template <class out_t, bool SUBSET>
-static void frame_dispatch(int precision, const FrameArgs& a, dim3 g, hipStream_t s) {
-    switch (precision) {
-        case VVHIP_SINGLE: hipLaunchKernelGGL((vv_kernel_frame<float, float, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
-        case VVHIP_MIXED: hipLaunchKernelGGL((vv_kernel_frame<float, double, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
-        default: hipLaunchKernelGGL((vv_kernel_frame<double, double, out_t, SUBSET>), g, dim3(512), 0, s, a); break;
-    }
-}
 hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int grid_cap, hipStream_t s) {
     const dim3 g((unsigned) std::max(1, std::min((a.n + 511) / 512, std::max(1, grid_cap))));
-    if (a.subset) { if (float64) frame_dispatch<double, true>(precision, a, g, s); else frame_dispatch<float, true>(precision, a, g, s); }
-    else { if (float64) frame_dispatch<double, false>(precision, a, g, s); else frame_dispatch<float, false>(precision, a, g, s); }
+    const auto k = a.subset ? (float64 ? VV_PICK(precision, vv_kernel_frame, double, true) : VV_PICK(precision, vv_kernel_frame, float, true))
+                            : (float64 ? VV_PICK(precision, vv_kernel_frame, double, false) : VV_PICK(precision, vv_kernel_frame, float, false));
+    hipLaunchKernelGGL(k, g, dim3(512), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(vv_kernel_frame_advance, dim3(1), dim3(64), 0, s, a);

@@ -33,8 +33,6 @@ hipError_t launch_b(int precision, const KArgs& a, int block_threads, int grid_c
 // kernel's occupancy (blocks of this shape per CU).  hipErrorNotSupported: no kernel for the pair, or a shape the rendezvous cannot take.
 hipError_t launch_fused(int precision, const KArgs& a, int block_threads, const unsigned long long* rendezvous, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
                         int* route = nullptr, int* blocks_per_cu = nullptr);
-// launches of kernel A / B (index 0 / 1) that ran the generic kernel, process-wide (statistics only)
-extern std::atomic<unsigned long long> vv_generic_count[2];
 hipError_t launch_chain(const NHConst& c, NHDevState* st, unsigned long long* acc, hipStream_t s);
 hipError_t launch_tether(int precision, const TetherArgs& t, int block_threads, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // Fills the static per-lane mass tables from the inverse masses in velm.w (once per binding; see A_MTAB / B_MTAB).

@@ -121,3 +121,48 @@ def test_an_unlisted_stage_set_is_reported():
                 ctx.close()
     finally:
         I.Context.rtc_mode(old)
+
+
+def _timed_run(spec, chains, tune, timed):
+    it = I.VVIntegrator(333.0, 10.0, 1.0, 40.0, 0.001, numNHChains=chains)
+    it.setMaxDrudeDistance(0.02)
+    ctx = I.Context(spec, it, precision="mixed", force_provider="tether", tune=tune)
+    try:
+        if timed:
+            ctx.timing(2)
+        ctx.run_eager(4)
+        ctx.synchronize()
+        launches = ctx.timing_read()["launches"] if timed else None
+        state = (ctx.getVelm().tobytes(), ctx.getPosq().tobytes(), bytes(ctx.getNHState()))
+        return state, launches, ctx.fused_status()[0], ctx.generic_launches()[0]
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("chains,tune,mode", [(3, {"fused": 1}, 1), (3, {"fused": 0}, 1), (4, None, 1), (4, None, 0)],
+                         ids=["compiled-one-launch", "compiled-two-launches", "run-time", "generic"])
+def test_timed_launches_take_the_same_routes(chains, tune, mode):
+    """Launches with dispatch time stamps (ctx.timing(2): hipExtLaunchKernelGGL / hipExtModuleLaunchKernel instead of the plain launch)
+    go through the same lookup: a compiled kernel in one and in two launches, a kernel compiled at run time (four chain links: no
+    compiled kernel carries them) and the generic kernel.  Every launch is counted once, and the state after four steps is the
+    untimed run's, byte for byte."""
+    spec = S.drude_il(cells=(1, 1, 1), pairs_per_cell=20, seed=2)
+    old = I.Context.rtc_mode()
+    try:
+        I.Context.rtc_mode(mode)
+        plain, _, _, _ = _timed_run(spec, chains, tune, False)
+        before = I.Context.rtc_stats()
+        timed, launches, fused, generic = _timed_run(spec, chains, tune, True)
+        after = I.Context.rtc_stats()
+    finally:
+        I.Context.rtc_mode(old)
+    if tune is not None:      # this system's step fits one launch: "fused": 1 takes it (else the timed launch of launch_fused goes untested), 0 declines it
+        assert fused == bool(tune["fused"])
+    assert launches == ([0, 4, 0] if fused else [4, 4, 0])
+    assert timed == plain
+    if chains == 3:          # compiled: neither a run-time kernel nor the generic one
+        assert after[1:3] == before[1:3] and generic == (0, 0)
+    elif mode == 1:          # kernel B (alone or as the one-launch step) compiled at run time, kernel A from the list unless it is part of that step
+        assert after[2] - before[2] == 4 and after[1] == before[1] and generic == (0, 0)
+    else:
+        assert after[1:3] == before[1:3] and generic[1] == 4 and generic[0] == 0
