@@ -436,6 +436,94 @@ int vvhip_frames_particles(const vvhip_plan* plan, int32_t* global_indices, int3
 int vvhip_frames_schedule(int32_t interval, int32_t schedule, int64_t after_step, int32_t n, int64_t* steps_out);
 /* Test hook: 1 if the guard frame behind the buffer's last frame still holds its fill pattern (nothing was written past capacity). */
 int vvhip_debug_frames_guard(vvhip_plan* plan, int32_t* intact);
+/* ---------------------------------------------------------------- profiles: density and velocity profiles accumulated on the device
+ * What run-edl.py is run for (number and charge density along z between the electrodes) and what a --cos run of run-bulk.py is run for
+ * (the velocity profile v_x of z): sums over particles and samples per bin of one box axis.  A stand-alone host would get them from
+ * trajectory frames, 44 B per particle and sample, and bin on the host; a profile is a few KB however many samples it holds.  After every
+ * full step whose count is a multiple of `interval` -- counted exactly as for the series and the frames, by the same entry points; a
+ * sample "after step k" is enqueued behind that step's frame -- the step entry point enqueues one accumulating kernel
+ * (csrc/vv_dev_profile.inc) and a one-thread kernel that advances the sample count.  Inside a captured graph both are part of the graph and
+ * the steps that take a sample are part of the graph-cache key.  The recorder reads posq, posqCorrection and velm and writes its own table,
+ * nothing else; a plan that never starts one launches what it launched before and allocates nothing.
+ * Arithmetic, all float64 without contraction.  For recorded particle i with coordinate c along `axis` -- (double) posq + (double)
+ * posqCorrection in mixed precision, else (double) posq; positions are stored unwrapped --
+ *     t = c * inv_L,  inv_L = 1.0 / box[axis] (formed on the host from the plan's box when the sample is enqueued: vvhip_set_box drops the
+ *     captured graphs),  u = t - floor(t),  b = min((int) (u * (double) nbins), nbins - 1)
+ * which is the periodic wrap: c = -1e-20 gives u = 1.0 and lands in the last bin by the clamp.  With v = (double) velm.xyz and m the
+ * System's mass of the particle as the plan holds it, the terms per quantity are
+ *     COUNT     1
+ *     CHARGE    (double) posq.w, as it stands at the sample
+ *     MASS      m
+ *     MOMENTUM  m * v.x, m * v.y, m * v.z     (three rows)
+ *     KINETIC   m * ((v.x * v.x + v.y * v.y) + v.z * v.z)
+ * and a term x is added as the integer llrint(x * 2^frac_bits[quantity]), round-half-even (COUNT: the integer 1).  Integer adds commute:
+ * the table is the same bits for any launch shape, arrival order or shard split, and the shards' tables add to the unsharded table exactly.
+ * A particle any of whose enabled terms is NaN or has |x| >= limit[quantity] is left out of EVERY row for that sample and adds 1 to
+ * out_of_range instead.
+ * Table: int64 table[num_groups][rows][nbins], the rows being the enabled quantities in the order above (vvhip_profile_layout::row_of).
+ * Fraction bits: frac_bits[q] = min(40, 62 - ceil_log2(N + 1) - ceil_log2(max_samples + 1) - log2(limit[q])), so that no word can
+ * overflow within max_samples samples; past max_samples a sample adds nothing and counts as dropped.  N and the default limits are those of
+ * the description over the WHOLE System (N = num_particles on an unsharded plan): a sharded plan records the particles of its own shard,
+ * every shard scales its terms alike, and the shards' tables add as integers to the unsharded table.
+ * Unlike a series row or a frame, an accumulating table is not idempotent under the repeat of failed steps: a repaired rendezvous
+ * (vvhip_recovery_count) puts the WHOLE allocation, counts and table, back with the step counter before it repeats the steps. */
+#define VVHIP_PROFILE_COUNT    1       /* always on */
+#define VVHIP_PROFILE_CHARGE   2
+#define VVHIP_PROFILE_MASS     4
+#define VVHIP_PROFILE_MOMENTUM 8
+#define VVHIP_PROFILE_KINETIC  16
+enum { VVHIP_PROFILE_Q_COUNT = 0, VVHIP_PROFILE_Q_CHARGE = 1, VVHIP_PROFILE_Q_MASS = 2, VVHIP_PROFILE_Q_MOMENTUM = 3, VVHIP_PROFILE_Q_KINETIC = 4,
+       VVHIP_PROFILE_QUANTITIES = 5 };
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t axis;                   /* 0, 1, 2: the box axis the bins divide */
+    int32_t nbins;                  /* 1 .. 65536 */
+    int32_t mask;                   /* VVHIP_PROFILE_*; COUNT is on whether named or not */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t reserved;               /* 0 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: not recorded; NULL: everything in group 0 */
+    int64_t max_samples;            /* >= 1 */
+    double limit[4];                /* charge (e), mass (Da), momentum (Da nm/ps), kinetic (Da nm^2/ps^2): terms at or beyond it are out of
+                                       range; rounded up to a power of two.  0 takes the default: charge 16, mass the smallest power of two
+                                       above the largest recorded mass, momentum 64 x the mass limit, kinetic 4096 x the mass limit */
+} vvhip_profile_desc;
+typedef struct {
+    int64_t samples;                /* samples in the table since the start or the last reset (at most max_samples) */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added for them */
+    int64_t out_of_range;           /* particle-samples left out of every row */
+} vvhip_profile_counts;
+typedef struct {
+    int32_t active, interval, axis, nbins, mask, num_groups;
+    int32_t num_particles;          /* particles this plan records: group >= 0 within [shard_begin, shard_end) */
+    int32_t rows;                   /* rows per group: 1 .. 7 */
+    int64_t max_samples;
+    int64_t words;                  /* num_groups * rows * nbins */
+    int64_t start_step;             /* the plan's step count at vvhip_profile_start */
+    int32_t row_of[VVHIP_PROFILE_QUANTITIES];       /* first row of a quantity inside a group, -1: not recorded */
+    int32_t frac_bits[VVHIP_PROFILE_QUANTITIES];    /* value = word * 2^-frac_bits (COUNT: 0) */
+    double limit[VVHIP_PROFILE_QUANTITIES];         /* as applied (COUNT: 1) */
+} vvhip_profile_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order:
+ * interval < 1, axis outside 0 .. 2, nbins outside 1 .. 65536, unknown mask bits, num_groups outside 1 .. 16, max_samples < 1, a limit that
+ * is negative or not finite, a group entry outside -1 .. num_groups - 1, a quantity whose frac_bits would come out below 8
+ * (VVHIP_ERR_INVALID naming the argument or the quantity); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID); an allocation that
+ * fails (VVHIP_ERR_HIP).  A description that passes the argument checks is kept even where the start is then refused for an unbound plan
+ * (active = 0): vvhip_profile_info answers for it. */
+int vvhip_profile_start(vvhip_plan* plan, const vvhip_profile_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0;
+ * a capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts and table: the schedule continues without gap or
+ * repeat. */
+int vvhip_profile_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_profile_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, the table is released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_profile_stop(vvhip_plan* plan);
+/* The recorder as described (zeros, row_of = -1, with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_profile_info(const vvhip_plan* plan, vvhip_profile_layout* out);
+/* Test hook: with an unverified recovery snapshot in hand (a vvhip_run_graph / vvhip_run_eager call of at least 64 steps since the last
+ * vvhip_synchronize), drains the stream and repairs as after a missed rendezvous -- the snapshot goes back, step counter and riders' words
+ * included, the calls since are repeated with two launches per step -- without any rendezvous having failed.  VVHIP_ERR_INVALID without a
+ * snapshot. */
+int vvhip_debug_recover(vvhip_plan* plan);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

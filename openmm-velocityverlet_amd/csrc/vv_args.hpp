@@ -329,4 +329,23 @@ struct FrameArgs {
     double box[3];
 };
 
+// Profile sample (vv_dev_profile.inc, include/vvhip.h: vvhip_profile_* states the arithmetic).  The sample count is read from the
+// device-side words, so a replayed graph (same arguments every time) stops adding at max_samples.
+enum { PROFILE_SAMPLES = 0, PROFILE_DROPPED = 1, PROFILE_OUT_OF_RANGE = 2, PROFILE_HEAD = 3 };      // the words in front of the table
+struct ProfileArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const void* velm;               // mixed4 (read only with a velocity quantity on)
+    const int32_t* index;           // [n] shard-relative indices of the recorded particles, ascending; null: particle i is index i
+    const unsigned char* group;     // [n] group of recorded particle i, 255: not recorded (GROUPED kernels only)
+    const double* mass;             // [n] the System's mass of recorded particle i (read only with a mass-weighted quantity on)
+    long long* words;               // [PROFILE_HEAD + table_words]: samples, dropped, out_of_range, then table[group][row][nbins]
+    int64_t max_samples;
+    int32_t n, nbins;               // recorded particles; bins
+    int32_t axis, mask;             // VVHIP_PROFILE_* bits
+    int32_t rows, table_words;      // rows per group; num_groups * rows * nbins
+    double inv_L;                   // 1.0 / box[axis]
+    double scale[4], limit[4];      // 2^frac_bits and the limit of charge, mass, momentum, kinetic
+};
+
 }  // namespace vv

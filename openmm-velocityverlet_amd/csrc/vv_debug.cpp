@@ -255,5 +255,12 @@ int vvhip_debug_frames_guard(vvhip_plan* p, int32_t* intact) {
     HIP_TRY(p, p->frames.ring.guard_intact(intact));
     return VVHIP_OK;
 }
+int vvhip_debug_recover(vvhip_plan* p) {
+    NEED_BOUND(p);
+    if (p->capturing) return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_recover: not inside a graph capture");
+    if (!p->rec.valid || p->rec.replaying) return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_recover: no unverified snapshot (a run call of at least recover_min_steps steps since the last synchronisation)");
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    return recover_rendezvous(p, true);
+}
 
 }  // extern "C"

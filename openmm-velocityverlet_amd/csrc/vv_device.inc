@@ -17,3 +17,4 @@
 #include "vv_dev_thermalize.inc"
 #include "vv_dev_digest.inc"
 #include "vv_dev_frames.inc"
+#include "vv_dev_profile.inc"

@@ -190,6 +190,7 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
     if (sb == 0 && se == 0) se = n;
     if (sb < 0 || se > n || sb >= se) throw Error(VVHIP_ERR_INVALID, "bad particle shard range");
     hp.shard_begin = sb; hp.shard_end = se;
+    hp.masses.assign(sys.masses, sys.masses + n);
     auto in_shard = [&](int i) { return i >= sb && i < se; };
 
     // ---- Langevin random offsets (K/drudeLangevin.cu:20,30,51-52): normal i -> i, pair i -> Nn + 2 i

@@ -93,6 +93,7 @@ struct HostPlan {
     // the sum of the masses > 0 of the WHOLE system, added up in particle order
     bool has_cm_motion_remover = false;
     double cm_total_mass = 0;
+    std::vector<double> masses;                // [num_atoms] the System's masses (vvhip_profile_*: the mass-weighted rows and their limits)
     // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature; vv_dev_thermalize.inc), counts of THIS plan's particles:
     // massive ones, massless ones, Drude pairs with two masses > 0 (what the Drude-aware mode splits); and the massless particles that
     // have no lane (image particles, virtual sites placed from a parent's lane), shard-relative

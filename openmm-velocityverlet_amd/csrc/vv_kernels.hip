@@ -453,6 +453,18 @@ hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int gri
     hipLaunchKernelGGL(vv_kernel_frame_advance, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_profile(int precision, const ProfileArgs& a, int grid_cap, hipStream_t s) {
+    const dim3 g((unsigned) std::max(1, std::min((a.n + 511) / 512, std::max(1, grid_cap))));
+    const size_t table_bytes = (size_t) a.table_words * sizeof(long long);
+    const bool lds = table_bytes <= PROFILE_LDS_BYTES;
+    const auto k = a.group ? (lds ? VV_PICK(precision, vv_kernel_profile, true, true) : VV_PICK(precision, vv_kernel_profile, true, false))
+                           : (lds ? VV_PICK(precision, vv_kernel_profile, false, true) : VV_PICK(precision, vv_kernel_profile, false, false));
+    hipLaunchKernelGGL(k, g, dim3(512), lds ? (unsigned) table_bytes : 0u, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_profile_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

@@ -63,5 +63,10 @@ hipError_t launch_digest(const DigestArgs& a, int block_threads, int grid_cap, h
 // them (the kernel strides beyond; one idle block where a.n = 0), then the one-thread kernel that writes the header and advances the
 // cursor.  float64: components as double instead of float.
 hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int grid_cap, hipStream_t s);
+// One profile sample (vv_dev_profile.inc): the accumulating kernel over a.n recorded particles in blocks of 512 threads, at most grid_cap
+// of them (the kernel strides beyond; one idle block where a.n = 0), then the one-thread kernel that counts the sample.  A table of at
+// most PROFILE_LDS_BYTES is accumulated per block in LDS first, a larger one by global atomics directly; a.group selects the grouped kernels.
+constexpr size_t PROFILE_LDS_BYTES = 64 * 1024;
+hipError_t launch_profile(int precision, const ProfileArgs& a, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -1,5 +1,5 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
+// the series of its rows, trajectory frames, profiles, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
 // ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
 #include "vv_plan.hpp"
 
@@ -65,6 +65,22 @@ static int frame_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_frame(p->hp.precision, a, (F.mask & VVHIP_FRAMES_FLOAT64) != 0, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ profiles (vvhip_profile_*)
+// One sample behind the step just enqueued (or captured), and behind its frame: the accumulating kernel and the one-thread kernel that
+// counts the sample.  Two launches, no memset and no host synchronisation.
+static int profile_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Profile& P = p->profile;
+    const vvhip_profile_layout& L = P.lay;
+    vv::ProfileArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.index = P.index.empty() ? nullptr : P.d_index.get(); a.group = P.grouped ? P.d_group.get() : nullptr; a.mass = P.d_mass.get();
+    a.words = P.d_words.get(); a.max_samples = L.max_samples;
+    a.n = L.num_particles; a.nbins = L.nbins; a.axis = L.axis; a.mask = L.mask; a.rows = L.rows; a.table_words = (int32_t) L.words;
+    a.inv_L = 1.0 / p->box[L.axis];
+    for (int q = 0; q < 4; q++) { a.scale[q] = std::ldexp(1.0, L.frac_bits[q + 1]); a.limit[q] = L.limit[q + 1]; }
+    HIP_TRY(p, vv::launch_profile(p->hp.precision, a, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -100,12 +116,15 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
     return VVHIP_OK;
 }
 // ------------------------------------------------------------------------------------------ the step's scheduled riders
-// In this order everywhere (item k of GraphKey::due, of Recovery::late): behind a step the series' row goes first, then the frame.  `late`: the
-// series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists (one-off calls allocate it too).
+// In this order everywhere (item k of GraphKey::due, of Recovery::late): behind a step the series' row goes first, then the frame, then the
+// profile sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
+// (one-off calls allocate it too), and of a profile the WHOLE allocation, counts and table: a row or a frame written twice is the same row
+// or frame, a sample added twice is not the same table.
 Riders riders(vvhip_plan* p) {
     return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
-             {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue}}};
+             {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
+             {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue}}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -121,6 +140,11 @@ int step_done(vvhip_plan* p) {
 }
 static void series_release(vvhip_plan* p) { p->series = vvhip_plan::Series{}; }
 static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
+static void profile_release(vvhip_plan* p) { p->profile = vvhip_plan::Profile{}; }
+// frexp's view of a positive finite x: the smallest power of two >= x / > x, and the exponent of a power of two
+static double pow2_at_least(double x) { int e; const double f = std::frexp(x, &e); return f == 0.5 ? x : std::ldexp(1.0, e); }
+static double pow2_above(double x) { int e; (void) std::frexp(x, &e); return std::ldexp(1.0, e); }
+static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) k++; return k; }      // smallest k with 2^k >= n (1 <= n <= 2^62)
 
 extern "C" {
 
@@ -445,6 +469,121 @@ int vvhip_frames_particles(const vvhip_plan* p, int32_t* global_indices, int32_t
     if (!F.described) return VVHIP_ERR_INVALID;
     const int32_t n = std::min<int32_t>(capacity, F.num_particles);
     for (int32_t j = 0; j < n; j++) global_indices[j] = F.has_subset ? F.particles[j] : p->hp.shard_begin + j;
+    return VVHIP_OK;
+}
+
+int vvhip_profile_start(vvhip_plan* p, const vvhip_profile_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "profile: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "profile: interval must be >= 1 step");
+    if (d->axis < 0 || d->axis > 2) return fail(p, VVHIP_ERR_INVALID, "profile: axis must be 0, 1 or 2");
+    if (d->nbins < 1 || d->nbins > 65536) return fail(p, VVHIP_ERR_INVALID, "profile: nbins must be in [1, 65536]");
+    constexpr int kAll = VVHIP_PROFILE_COUNT | VVHIP_PROFILE_CHARGE | VVHIP_PROFILE_MASS | VVHIP_PROFILE_MOMENTUM | VVHIP_PROFILE_KINETIC;
+    if (d->mask & ~kAll) return fail(p, VVHIP_ERR_INVALID, "profile: mask holds bits besides VVHIP_PROFILE_COUNT / CHARGE / MASS / MOMENTUM / KINETIC");
+    if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "profile: num_groups must be in [1, 16]");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "profile: max_samples must be >= 1");
+    static const char* const kQuantity[VVHIP_PROFILE_QUANTITIES] = {"count", "charge", "mass", "momentum", "kinetic"};
+    for (int q = 0; q < 4; q++)
+        if (!(d->limit[q] >= 0) || !std::isfinite(d->limit[q]))
+            return fail(p, VVHIP_ERR_INVALID, std::string("profile: limit[") + std::to_string(q) + "] (" + kQuantity[q + 1] + ") must be finite and >= 0 (0: the default)");
+    const vv::HostPlan& hp = p->hp;
+    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
+        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
+            return fail(p, VVHIP_ERR_INVALID, "profile: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    // ---- the particles this plan records, the layout and the fixed point, host only
+    vvhip_plan::Profile N;
+    vvhip_profile_layout& L = N.lay;
+    N.grouped = d->group != nullptr;
+    // (the fixed point and the default limits follow the particles the DESCRIPTION records, of the whole System: every shard then scales
+    // its terms alike, and the shards' words add to the unsharded table)
+    double largest_mass = 0;
+    long long described = 0;
+    for (int32_t i = 0; i < hp.num_atoms; i++) {
+        if (d->group && d->group[i] < 0) continue;
+        described++;
+        largest_mass = std::max(largest_mass, hp.masses[(size_t) i]);
+        if (i < hp.shard_begin || i >= hp.shard_end) continue;
+        N.index.push_back(i - hp.shard_begin);
+        if (N.grouped) N.group.push_back((unsigned char) d->group[i]);
+        N.mass.push_back(hp.masses[(size_t) i]);
+    }
+    L.interval = d->interval; L.axis = d->axis; L.nbins = d->nbins; L.mask = d->mask | VVHIP_PROFILE_COUNT; L.num_groups = d->num_groups;
+    L.num_particles = (int32_t) N.index.size(); L.max_samples = d->max_samples;
+    if (L.num_particles == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard: the thread's own index)
+    const int rows_of[VVHIP_PROFILE_QUANTITIES] = {1, 1, 1, 3, 1};
+    for (int q = 0; q < VVHIP_PROFILE_QUANTITIES; q++) {
+        L.row_of[q] = (L.mask & (1 << q)) ? L.rows : -1;
+        if (L.mask & (1 << q)) L.rows += rows_of[q];
+    }
+    L.words = (int64_t) L.num_groups * L.rows * L.nbins;
+    const double mass_limit = d->limit[1] > 0 ? pow2_at_least(d->limit[1]) : (largest_mass > 0 ? pow2_above(largest_mass) : 1.0);
+    L.limit[VVHIP_PROFILE_Q_COUNT] = 1.0;
+    L.limit[VVHIP_PROFILE_Q_CHARGE] = d->limit[0] > 0 ? pow2_at_least(d->limit[0]) : 16.0;
+    L.limit[VVHIP_PROFILE_Q_MASS] = mass_limit;
+    L.limit[VVHIP_PROFILE_Q_MOMENTUM] = d->limit[2] > 0 ? pow2_at_least(d->limit[2]) : mass_limit * 64.0;
+    L.limit[VVHIP_PROFILE_Q_KINETIC] = d->limit[3] > 0 ? pow2_at_least(d->limit[3]) : mass_limit * 4096.0;
+    const int head = 62 - ceil_log2(described + 1) -ceil_log2(L.max_samples < (1ll << 62) ? L.max_samples + 1 : (1ll << 62));
+    for (int q = 1; q < VVHIP_PROFILE_QUANTITIES; q++) {
+        L.frac_bits[q] = std::min(40, head - std::ilogb(L.limit[q]));
+        if ((L.mask & (1 << q)) && L.frac_bits[q] < 8)
+            return fail(p, VVHIP_ERR_INVALID, std::string("profile: the ") + kQuantity[q] + " rows would keep " + std::to_string(L.frac_bits[q]) + " fraction bits (< 8) with " +
+                                              std::to_string(L.num_particles) + " particles, max_samples = " + std::to_string((long long) L.max_samples) + " and limit " +
+                                              std::to_string(L.limit[q]) + ": lower max_samples or the limit");
+    }
+    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
+    if (p->capturing || p->profile.on) TRY(quiesce(p, "profile", true, true));
+    profile_release(p);
+    vvhip_plan::Profile& P = p->profile;
+    P = std::move(N);
+    P.when = {d->interval, SCHEDULE_LINEAR};
+    P.lay.start_step = p->cur.step_count;
+    P.described = true;
+    NEED_BOUND(p);
+    TRY(quiesce(p, "profile", true, true));
+    auto alloc_fail = [&](hipError_t e, size_t bytes) {
+        P.d_words.reset(); P.d_index.reset(); P.d_group.reset(); P.d_mass.reset();
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string("profile: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
+    };
+    hipError_t e = vv::zeros(P.d_words, P.bytes(), p->stream);
+    if (e != hipSuccess) return alloc_fail(e, P.bytes());
+    if ((e = vv::upload(P.d_mass, P.mass, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.mass.size() * sizeof(double)));
+    if (!P.index.empty() && (e = vv::upload(P.d_index, P.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.index.size() * sizeof(int32_t)));
+    if (P.grouped && (e = vv::upload(P.d_group, P.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.group.size()));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    P.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
+    P.on = true;
+    return VVHIP_OK;
+}
+int vvhip_profile_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_profile_counts* out, int32_t reset) {
+    NEED_BOUND(p);
+    vvhip_plan::Profile& P = p->profile;
+    if (!P.on) return fail(p, VVHIP_ERR_INVALID, "profile: none started (vvhip_profile_start)");
+    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < P.lay.words))
+        return fail(p, VVHIP_ERR_INVALID, "profile: the table has " + std::to_string((long long) P.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
+    TRY(quiesce(p, "profile", true, false));
+    long long head[vv::PROFILE_HEAD];
+    HIP_TRY(p, hipMemcpy(head, P.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
+    if (words_out && P.lay.words > 0) HIP_TRY(p, hipMemcpy(words_out, P.d_words.get() + vv::PROFILE_HEAD, (size_t) P.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out) *out = {head[vv::PROFILE_SAMPLES], head[vv::PROFILE_DROPPED], head[vv::PROFILE_OUT_OF_RANGE]};
+    if (reset) {
+        HIP_TRY(p, hipMemsetAsync(P.d_words.get(), 0, P.bytes(), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+    }
+    return VVHIP_OK;
+}
+int vvhip_profile_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing || p->profile.on) TRY(quiesce(p, "profile", true, true));
+    profile_release(p);                                 // (also the description an unbound plan kept)
+    return VVHIP_OK;
+}
+int vvhip_profile_info(const vvhip_plan* p, vvhip_profile_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_profile_layout r{};
+    for (int q = 0; q < VVHIP_PROFILE_QUANTITIES; q++) r.row_of[q] = -1;
+    if (p->profile.described) { r = p->profile.lay; r.active = p->profile.on; }
+    *out = r;
     return VVHIP_OK;
 }
 

@@ -8,7 +8,7 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, removal of the centre-of-mass motion, start
+//   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, profiles, removal of the centre-of-mass motion, start
 //                    velocities; the list of the step's scheduled riders (riders), step_begin / step_done, quiesce; their one schedule is
 //                    vv_schedule.hpp (integers only, no HIP in it)
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -65,7 +65,7 @@ constexpr int kAccN = vv::NUM_ACC * vv::ACC_SLOTS;
 constexpr int kRvCopy = 6 * kAccN;      // rendezvous words of one thermostat parity: up to 6 replicas (vv_device.inc: RV_REPLICAS) of [NUM_ACC][ACC_SLOTS]
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
-constexpr int kRiders = 3;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame
+constexpr int kRiders = 4;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -132,7 +132,8 @@ struct vvhip_plan {
     double acc_scale[vv::NUM_ACC], acc_inv_scale[vv::NUM_ACC];
     int block_threads = 256;       // 64 x tile waves per block, the same for the force provider, kernel A and kernel B
     int grid_cap_a = 2048, grid_cap_b = 1024;   // most blocks per launch (multiples of the CU count): see pick_launch_shape
-    int split_chain_waves = 44000;   // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
+    int profile_grid_cap = 256;    // most blocks of a profile sample's accumulating kernel, besides grid_cap_a: every block flushes a table of its own (test hook "profile_grid_cap"; TUNING_LOG.md)
+    int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
                                      // 1.33 M 14.5 | 14.0 k, 1.78 M 11.4 | 11.1 k, 2.66 M 7.38 | 7.37 k, 4.4 M 4.14 | 4.20 k, 8.9 M 2.16 | 2.21 k (round 2 had it at 12 288)
     // The reference's kick kernels add forceExtra ALWAYS (K/middle.cu:11-21, K/velocityVerlet.cu:20-22) and the array is only reset in
@@ -321,6 +322,21 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
+    // Profiles (vvhip_profile_*; vv_dev_profile.inc), scheduled by cur.step_count.  `described` / `on` as for the frames: `lay` is the
+    // layout of the last description that passed vvhip_profile_start's checks, the device buffers exist while the recorder runs
+    struct Profile {
+        bool on = false, described = false, grouped = false;
+        Schedule when;                            // (linear)
+        vvhip_profile_layout lay{};
+        std::vector<int32_t> index;               // shard-relative indices of the recorded particles, ascending; empty: every particle of the shard
+        std::vector<unsigned char> group;         // [num_particles] their groups (grouped)
+        std::vector<double> mass;                 // [num_particles] their masses
+        vv::DevBuf<int32_t> d_index;
+        vv::DevBuf<unsigned char> d_group;
+        vv::DevBuf<double> d_mass;
+        vv::DevBuf<long long> d_words;            // [PROFILE_HEAD + lay.words]: counts, then the table -- ALL of it the rider's late words
+        size_t bytes() const { return (size_t) (vv::PROFILE_HEAD + lay.words) * sizeof(long long); }
+    } profile;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -452,11 +468,13 @@ Riders riders(vvhip_plan* p);
 // The plan's physical state, stated ONCE, as {live array, its saved copy of the recovery snapshot, bytes, ...}: the six state arrays (0
 // bytes: not in use), both thermostat copies, the random generator's epoch -- in this order the sections VVHIP_CKPT_POSQ ..
 // VVHIP_CKPT_EPOCH of a checkpoint (vv_checkpoint.cpp) -- and behind them, for the riders `with` names (null: none), their Rider::late words
-// (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not carry them).
+// (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not carry them).  For a series and a
+// frame recorder these are the cursors: the repeat writes the same rows and frames at the same places.  For a profile recorder they are the
+// whole allocation, counts and table: an accumulating table is not idempotent under the repeat, so it goes back as the snapshot took it.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);
-int recover_rendezvous(vvhip_plan* p);
+int recover_rendezvous(vvhip_plan* p, bool on_request = false);      // on_request: the test hook vvhip_debug_recover, nothing has failed
 int plan_step(vvhip_plan* p, const ForceProvider& fp, bool refill);
 // vv_exchange.cpp
 int exchange_accumulators(vvhip_plan* p, int phase);

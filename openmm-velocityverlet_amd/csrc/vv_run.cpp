@@ -74,11 +74,12 @@ static int recovery_note_run(vvhip_plan* p, int kind, int nsteps, int spg, const
     r.runs.push_back({kind, nsteps, spg, fp});
     return VVHIP_OK;
 }
-int recover_rendezvous(vvhip_plan* p) {
+int recover_rendezvous(vvhip_plan* p, bool on_request) {
     vvhip_plan::Recovery& r = p->rec;
     long long steps = 0;
     for (const auto& run : r.runs) steps += run.nsteps;
-    std::fprintf(stderr, "libvvhip: the one-launch step's blocks did not meet within 0.2 s (another process's kernels on the device?): the last %lld step(s) "
+    if (!on_request)
+        std::fprintf(stderr,"libvvhip: the one-launch step's blocks did not meet within 0.2 s (another process's kernels on the device?): the last %lld step(s) "
                          "are repeated from the plan's snapshot with two launches per step, and the plan keeps two launches from here on\n", steps);
     const std::vector<RecItem> items = recovery_items(p, r.saved);      // (of the riders: what the snapshot took and the plan still has)
     for (const RecItem& it : items)

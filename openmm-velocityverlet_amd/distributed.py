@@ -158,6 +158,21 @@ def drude_temperatures(ctx, group=None):
     return ctx.drude_report_combine(raw.numpy())
 
 
+def profile_sum(profiles):
+    """The profile of a sharded run from its shards' profiles (Context.profile_read of every shard, the same description and the same
+    steps behind each): the tables added as int64 words -- integer sums are associative, so the result is the unsharded table bit for
+    bit -- and out_of_range added; samples and dropped are the same on every shard."""
+    import dataclasses
+    from .integrator import profile_views
+    first = profiles[0]
+    for p in profiles[1:]:
+        if (p.words.shape, p.row_of, p.frac_bits, p.axis, p.samples, p.dropped) != (first.words.shape, first.row_of, first.frac_bits, first.axis, first.samples, first.dropped) \
+                or not np.array_equal(p.box, first.box):
+            raise ValueError("the profiles differ in layout, fixed point, box or number of samples: not shards of one run")
+    words = np.sum([p.words for p in profiles], axis=0, dtype=np.int64)
+    return dataclasses.replace(first, words=words, out_of_range=sum(p.out_of_range for p in profiles), **profile_views(words, first.row_of, first.frac_bits))
+
+
 def drude_temperature_series(ctx, group=None, reset=False):
     """A sharded run's series (Context.series_read): every rank's raw rows -- six fixed-point sums and the overflow flag per row, of its
     own particles -- summed over the process group in one all-reduce, then turned into KE / T with the whole system's DOFs.  Every rank

@@ -279,6 +279,73 @@ class Frames:
         return len(self.step)
 
 
+@dataclasses.dataclass
+class Profile:
+    """Sums per bin of one box axis, over the recorded particles and `samples` samples (Context.profile_read; include/vvhip.h:
+    vvhip_profile_* states the arithmetic).  `words` is the device's table as it stands, int64 [groups, rows, nbins]; the float64 views are
+    word * 2^-frac_bits, None for a quantity that was not recorded."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples: nothing was added for them
+    out_of_range: int                      # particle-samples left out of every row (a term NaN or at / beyond its limit)
+    axis: int
+    box: np.ndarray                        # float64 [3]: the periodic box at the read
+    edges: np.ndarray                      # float64 [nbins + 1]: the bins' edges along the axis, nm
+    words: np.ndarray                      # int64 [groups, rows, nbins]
+    row_of: tuple                          # first row of (count, charge, mass, momentum, kinetic), -1: not recorded
+    frac_bits: tuple
+    count: np.ndarray                      # [groups, nbins]
+    charge: Optional[np.ndarray] = None    # [groups, nbins] e
+    mass: Optional[np.ndarray] = None      # [groups, nbins] Da
+    momentum: Optional[np.ndarray] = None  # [groups, 3, nbins] Da nm/ps
+    kinetic: Optional[np.ndarray] = None   # [groups, nbins] sum m |v|^2, Da nm^2/ps^2
+
+    @property
+    def centres(self) -> np.ndarray:
+        return 0.5 * (self.edges[:-1] + self.edges[1:])
+
+    def bin_volume(self) -> float:
+        return float(self.box[0] * self.box[1] * self.box[2]) / (len(self.edges) - 1)
+
+    def number_density(self) -> np.ndarray:
+        """[groups, nbins] particles per nm^3, averaged over the samples."""
+        return self.count / (self.bin_volume() * max(self.samples, 1))
+
+    def charge_density(self) -> np.ndarray:
+        """[groups, nbins] e per nm^3, averaged over the samples."""
+        if self.charge is None:
+            raise ValueError("the charge was not recorded (profile_start(charge=True))")
+        return self.charge / (self.bin_volume() * max(self.samples, 1))
+
+    def velocity(self) -> np.ndarray:
+        """[groups, 3, nbins] momentum / mass, nm/ps, 0 where a bin holds no mass."""
+        if self.momentum is None or self.mass is None:
+            raise ValueError("momentum and mass were not both recorded (profile_start(mass=True, momentum=True))")
+        m = self.mass[:, None, :]
+        return np.where(m > 0, self.momentum / np.where(m > 0, m, 1.0), 0.0)
+
+
+def profile_from_words(words, layout, counts, box) -> Profile:
+    """A Profile from a table's int64 words [groups * rows * nbins], its layout (H.ProfileLayout) and counts."""
+    g, rows, nb = layout.num_groups, layout.rows, layout.nbins
+    words = np.ascontiguousarray(words, dtype=np.int64).reshape(g, rows, nb)
+    box = np.asarray(box, dtype=np.float64)
+    row_of, frac = tuple(layout.row_of), tuple(layout.frac_bits)
+    return Profile(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range), axis=int(layout.axis),
+                   box=box, edges=np.arange(nb + 1, dtype=np.float64) * (box[layout.axis] / nb), words=words, row_of=row_of, frac_bits=frac,
+                   **profile_views(words, row_of, frac))
+
+
+def profile_views(words, row_of, frac_bits) -> dict:
+    """The float64 views of a table: {quantity: word * 2^-frac_bits, or None where it was not recorded}."""
+    def view(q, n=1):
+        if row_of[q] < 0:
+            return None
+        a = words[:, row_of[q]: row_of[q] + n, :].astype(np.float64) * 2.0 ** -frac_bits[q]
+        return a[:, 0, :] if n == 1 else a
+
+    return dict(count=view(0), charge=view(1), mass=view(2), momentum=view(3, 3), kinetic=view(4))
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -372,6 +439,7 @@ class Context:
         H.check(H.lib.vvhip_bind(plan, C.byref(buf)), plan)
         box = (C.c_double * 3)(*[float(x) for x in system.box])
         H.check(H.lib.vvhip_set_box(plan, C.byref(box)), plan)
+        self._box = np.array(box, dtype=np.float64)
         self.forces_valid = False
         integrator._context = self
 
@@ -541,6 +609,46 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
+    # ---- profiles: density and velocity profiles accumulated on the device inside the steps (include/vvhip.h: vvhip_profile_*)
+    def profile_start(self, interval: int, nbins: int, axis: int = 2, groups=None, charge: bool = True, mass: bool = False,
+                      momentum: bool = False, kinetic: bool = False, max_samples: int = 1 << 20, limits=None):
+        """Add, after every step whose number is a multiple of `interval` (steps counted as for the series), every recorded particle to
+        its bin of `nbins` along box axis `axis`: its count and, as asked, charge, mass, momentum (three rows) and m |v|^2, as fixed-point
+        integers, so that the table is the same bits for any launch shape or shard split.  `groups`: one int per particle of the System
+        (-1: not recorded), each group a table of its own; None: everything in group 0.  `limits`: {"charge" | "mass" | "momentum" |
+        "kinetic": largest |term|}; a particle beyond one is left out of every row and counted in out_of_range.  At most `max_samples`
+        samples are added (the fixed point is sized for them).  No host synchronisation until profile_read."""
+        grp = None
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+            if grp.size != self.system.num_atoms:
+                raise ValueError("groups must have one entry per particle of the System")
+        unknown = set(limits or {}) - set(H.PROFILE_QUANTITIES[1:])
+        if unknown:
+            raise ValueError(f"limits: unknown quantity {sorted(unknown)}")
+        mask = (H.PROFILE_COUNT | (H.PROFILE_CHARGE if charge else 0) | (H.PROFILE_MASS if mass else 0) | (H.PROFILE_MOMENTUM if momentum else 0)
+                | (H.PROFILE_KINETIC if kinetic else 0))
+        desc = H.ProfileDesc(int(interval), int(axis), int(nbins), mask, 1 if grp is None else max(int(grp.max()) + 1, 1), 0,
+                             None if grp is None else grp.ctypes.data, int(max_samples),
+                             (C.c_double * 4)(*[float((limits or {}).get(q, 0.0)) for q in H.PROFILE_QUANTITIES[1:]]))
+        H.check(H.lib.vvhip_profile_start(self.plan, C.byref(desc)), self.plan)
+
+    def profile_stop(self):
+        H.check(H.lib.vvhip_profile_stop(self.plan), self.plan)
+
+    def profile_info(self) -> H.ProfileLayout:
+        out = H.ProfileLayout()
+        H.check(H.lib.vvhip_profile_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def profile_read(self, reset: bool = False) -> Profile:
+        """The table accumulated so far (synchronises).  reset=True zeroes it; the schedule continues without gap or repeat."""
+        info = self.profile_info()
+        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
+        counts = H.ProfileCounts()
+        H.check(H.lib.vvhip_profile_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
+        return profile_from_words(words[: info.words], info, counts, self._box)
+
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
         """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
@@ -582,7 +690,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series or frame recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame or profile recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()
@@ -609,6 +717,7 @@ class Context:
         """A barostat move as the plugin sees it: cu.getPeriodicBoxSize() is read live by the cos kernels (HOST:1057, 1129)."""
         box = (C.c_double * 3)(float(lx), float(ly), float(lz))
         H.check(H.lib.vvhip_set_box(self.plan, C.byref(box)), self.plan)
+        self._box = np.array(box, dtype=np.float64)
 
     def _set_params(self):
         H.check(H.lib.vvhip_set_params(self.plan, C.byref(self.integrator._params())), self.plan)

@@ -16,6 +16,8 @@ latest three kept.
 ``write_dcd_frames`` writes the frames of a device-side recorder (``Context.frames_read``) as a DCD trajectory, what
 ``DCDReporter('dump.dcd', 10000)`` leaves behind for the same steps.
 
+``write_profile`` writes a device-side density / velocity profile (``Context.profile_read``) as text columns, one line per bin.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -168,6 +170,41 @@ def write_cm_motion_record(file, step, record, append=False, header=True):
         if header:
             print(CM_MOTION_HEADER, file=out)
         print(int(step), int(record.removals), int(record.skipped), *[float(x) for x in record.last_v], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def profile_columns(profile):
+    """[(name, values per bin)] of a profile's text file: the bin centre, then per group the recorded quantities as sums over the samples."""
+    cols = [("%s (nm)" % "xyz"[profile.axis], profile.centres)]
+    for g in range(profile.words.shape[0]):
+        cols.append(("count[%d]" % g, profile.count[g]))
+        if profile.charge is not None:
+            cols.append(("charge[%d] (e)" % g, profile.charge[g]))
+        if profile.mass is not None:
+            cols.append(("mass[%d] (Da)" % g, profile.mass[g]))
+        if profile.momentum is not None:
+            cols += [("p%s[%d] (Da nm/ps)" % ("xyz"[k], g), profile.momentum[g, k]) for k in range(3)]
+        if profile.kinetic is not None:
+            cols.append(("mv2[%d] (Da nm^2/ps^2)" % g, profile.kinetic[g]))
+    return cols
+
+
+def write_profile(file, profile, append=False, header=True):
+    """A profile (Context.profile_read, distributed.profile_sum) as text: two comment lines (samples, dropped, out of range; the column
+    names) unless header=False, then one tab-separated line per bin -- the bin centre, then per group the recorded quantities as summed
+    over the samples (divide by `samples` and the bin volume for densities: Profile.number_density).  Floats are written with repr, so
+    np.loadtxt reads back the bits.  `file`: a path or an open text stream."""
+    cols = profile_columns(profile)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d' % (profile.samples, profile.dropped, profile.out_of_range), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for b in range(len(profile.edges) - 1):
+            print(*[repr(float(v[b])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:
         if own:

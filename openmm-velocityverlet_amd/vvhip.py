@@ -123,6 +123,27 @@ class FramesLayout(C.Structure):
                 ("frame_bytes", C.c_int64), ("off_positions", C.c_int64), ("off_velocities", C.c_int64), ("start_step", C.c_int64)]
 
 
+PROFILE_COUNT, PROFILE_CHARGE, PROFILE_MASS, PROFILE_MOMENTUM, PROFILE_KINETIC = 1, 2, 4, 8, 16
+PROFILE_QUANTITIES = ("count", "charge", "mass", "momentum", "kinetic")      # quantity q has mask bit 1 << q
+
+
+class ProfileDesc(C.Structure):
+    """What a profile recorder is to accumulate (include/vvhip.h: vvhip_profile_desc)."""
+    _fields_ = [("interval", C.c_int32), ("axis", C.c_int32), ("nbins", C.c_int32), ("mask", C.c_int32), ("num_groups", C.c_int32),
+                ("reserved", C.c_int32), ("group", C.c_void_p), ("max_samples", C.c_int64), ("limit", C.c_double * 4)]
+
+
+class ProfileCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64)]
+
+
+class ProfileLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("axis", C.c_int32), ("nbins", C.c_int32), ("mask", C.c_int32),
+                ("num_groups", C.c_int32), ("num_particles", C.c_int32), ("rows", C.c_int32), ("max_samples", C.c_int64),
+                ("words", C.c_int64), ("start_step", C.c_int64), ("row_of", C.c_int32 * 5), ("frac_bits", C.c_int32 * 5),
+                ("limit", C.c_double * 5)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -201,6 +222,8 @@ def _load():
         "vvhip_frames_start": [vp, P(FramesDesc)], "vvhip_frames_stop": [vp], "vvhip_frames_info": [vp, P(FramesLayout)],
         "vvhip_frames_read": [vp, vp, vp, i32, P(i32), P(C.c_int64), i32], "vvhip_frames_particles": [vp, vp, i32],
         "vvhip_frames_schedule": [i32, i32, C.c_int64, i32, vp], "vvhip_debug_frames_guard": [vp, P(i32)],
+        "vvhip_profile_start": [vp, P(ProfileDesc)], "vvhip_profile_stop": [vp], "vvhip_profile_info": [vp, P(ProfileLayout)],
+        "vvhip_profile_read": [vp, vp, C.c_int64, P(ProfileCounts), i32], "vvhip_debug_recover": [vp],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
