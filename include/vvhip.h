@@ -604,6 +604,57 @@ typedef struct {
 } vvhip_thermalize_record;
 int vvhip_set_velocities_to_temperature(vvhip_plan* plan, double temperature, double drude_temperature /* < 0: plain */,
                                         uint64_t seed, uint32_t flags, vvhip_thermalize_record* out /* may be NULL */);
+/* ---------------------------------------------------------------- Monte Carlo barostat: molecule-wise box scaling on the device
+ * The device half of an attempt of OpenMM's MonteCarloBarostat / MonteCarloAnisotropicBarostat (examples/run-bulk.py: --barostat, the
+ * default ensemble of the bulk example): a stand-alone host has no such service.  The Monte Carlo decision is a few host scalars per
+ * attempt and needs the host's potential energy, which this library does not own (openmm-velocityverlet_amd/barostat.py holds the
+ * driver); what is done here: every molecule is moved rigidly so that its centre scales with the box, the proposal can be undone bit
+ * for bit, and the plan's box is kept in step.  A plain operation on the bound arrays between run calls -- host-driven, never captured,
+ * not scheduled by the step counter: the box is a kernel argument baked into the captured graphs, so graphs run between attempts as
+ * they do between two vvhip_set_box calls.  Inside OpenMM the platform's own barostat runs and this stays off.
+ * Arithmetic.  Let particle i of this plan have stored position X_i, component-wise in float64: (double) posq + (double) posqCorrection
+ * in mixed precision, (double) posq in single, posq in double.  Let mol(i) be its molecule from vvhip_system_desc.mol_id -- ALL particles,
+ * massless images and virtual sites included; molecules need not be contiguous in index.  Let n_max be the largest molecule of the whole
+ * System (not of the shard) and F = 40 - ceil(log2(n_max)).
+ *     Q_i = llrint(X_i 2^F), to nearest even; valid only for finite |X_i| < 2^22 nm, anything else raises a "bad" word
+ *     S_m = sum of Q_i over i in m, exact in int64 (|S_m| < 2^62 by construction): integer atomics, any order, the same bits
+ *     c_m = ((double) S_m 2^-F) / (double) n_m                the geometric centre
+ *     e_a = s_a - 1.0                                         formed once per axis by the host, in double
+ *     d_(m,a) = c_(m,a) e_a                                   one multiply (the library is built with contraction off, as everywhere)
+ *     X'_i = X_i + d_mol(i)                                   one add
+ * Store: mixed precision posq' = (float) X', then corr' = (float) (X' - (double) posq') -- the split of the step's own position store
+ * (kernel B's B_POS3 stage; csrc/vv_dev_wave.inc: PosIO) --; single (float) X'; double X'.  posq.w and corr.w keep their bits.  An axis
+ * with e_a == 0 keeps the stored bits of that component, posq and correction alike: it is not re-split.  The geometric centre is
+ * OpenMM's choice for its barostat as remembered; this is that behaviour stated in float64, NOT pinned against OpenMM.
+ * Two kernels (sum, shift) in the plan's stream with only the kernel boundary between them (csrc/vv_dev_barostat.inc); neither touches
+ * velocities, velm.w, forces, forceExtra, thermostat copies, accumulators, rendezvous words or status words.  With the bad word up the
+ * shift kernel stores nothing at all.  The bits do not depend on the launch shape, the wave layout or the shard split: a sharded plan
+ * scales its own molecules (a shard must not cut a molecule: VVHIP_ERR_UNSUPPORTED otherwise), F comes from the whole System, and the
+ * shards' arrays concatenate to the unsharded result bit for bit; sending the same scale to every rank is the host's business.
+ * Checkpoints carry the box: one taken while a scale is pending records the scaled state, and the backup does not travel -- after a
+ * load there is nothing to restore. */
+typedef struct {
+    int64_t molecules;              /* shard-local molecules moved by a scale */
+    int64_t scales, restores;       /* calls done since bind */
+    int32_t pending;                /* 1: a scale can still be undone */
+    int32_t frac_bits;              /* F */
+    double box_before[3], box_after[3];   /* of the last scale */
+} vvhip_barostat_record;
+/* Enters as vvhip_synchronize does (a pending rendezvous repair is settled first; a sticky status word returns its error).  Copies posq
+ * (and the correction) of this plan's particles device-to-device into plan-owned backup buffers (allocated by the first call), runs the
+ * two kernels and blocks.  With the bad word raised: VVHIP_ERR_OVERFLOW for this call only, positions and box untouched, nothing pending.
+ * Otherwise box[a] *= scale[a] as by vvhip_set_box (the captured graphs go), the recovery snapshot is invalidated as by a checkpoint
+ * load, and the scale is pending.  A second scale while one is pending overwrites the backup: the implicit accept.
+ * Refused, in this order: a scale component that is not finite or <= 0 (VVHIP_ERR_INVALID, naming it); image pairs with scale[2] != 1
+ * (VVHIP_ERR_UNSUPPORTED: the mirror plane would have to move); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID). */
+int vvhip_barostat_scale(vvhip_plan* plan, const double scale[3]);
+/* Copies the backup back, puts the old box back and clears the pending mark: the state is bit for bit the state before the scale, every
+ * vvhip_state_digest word equal.  VVHIP_ERR_INVALID when no scale is pending, or when after the scale the plan's step counter moved or
+ * vvhip_set_box, vvhip_bind or vvhip_checkpoint_load was called.  The split per-KernelImpl entry points do not count steps: steps
+ * taken through them are NOT detected. */
+int vvhip_barostat_restore(vvhip_plan* plan);
+/* The record; the host-only fields (molecules, frac_bits) are filled on an unbound plan too. */
+int vvhip_barostat_read(vvhip_plan* plan, vvhip_barostat_record* out);
 
 /* ---------------------------------------------------------------- checkpoint: a run's complete state, bit for bit
  * What context.createCheckpoint() / loadCheckpoint() give a run inside OpenMM (examples/run-bulk.py: CheckpointReporter, --cpt): a

@@ -159,6 +159,7 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
     if (e != hipSuccess || ndev == 0)
         return fail(p, VVHIP_ERR_NO_DEVICE, "no HIP device: libvvhip has no CPU path");
     if (p->bound) TRY(settle_recovery(p));
+    p->baro.pending = false;       // (the backup of a barostat scale belongs to the arrays bound when it was taken)
     if (p->bound) {
         // The captured graphs bake EVERY caller-owned pointer (make_args): a re-bind that swaps any of them must drop both
         // executables, or vvhip_run_graph would replay kernels on the old arrays without a word.  The stream is not part of a
@@ -283,6 +284,7 @@ int vvhip_set_params(vvhip_plan* p, const vvhip_params* q) {
 
 int vvhip_set_box(vvhip_plan* p, const double box[3]) {
     if (!p || !box) return VVHIP_ERR_INVALID;
+    p->baro.pending = false;                         // (the host has taken the box into its own hands: vvhip_barostat_restore refuses)
     if (p->box[0] == box[0] && p->box[1] == box[1] && p->box[2] == box[2]) return VVHIP_OK;      // hosts re-send it every step
     for (int i = 0; i < 3; i++) p->box[i] = box[i];
     drop_graphs(p);                                  // the box is baked into the captured kernel arguments

@@ -289,6 +289,25 @@ struct CmmArgs {
     double inv_total_mass;          // 1 / sum of the masses > 0, formed in double on the host (0 without massive particles)
 };
 
+// Monte Carlo barostat (vv_dev_barostat.inc, vvhip_barostat_scale): every molecule moved rigidly so that its geometric centre scales with the
+// box.  A component X of a stored position becomes Q = llrint(X 2^frac_bits); a molecule's Q are summed as integers (exact, in any order,
+// the same bits whatever the launch shape, the wave layout or the shard split) into words[BARO_HEAD + 3 m + component].  frac_bits = 40 -
+// ceil(log2(largest molecule of the whole System)) and |X| < 2^22 nm keep |sum| < 2^62; a position beyond that (or not finite) raises
+// words[BARO_BAD] and nothing is stored.  Resolution of a centre: 2^-frac_bits nm (< 1e-9 nm for molecules of up to 1024 particles).
+enum { BARO_BAD = 0, BARO_HEAD = 1 };
+struct BarostatArgs {
+    void* posq;                     // real4 [shard particles]
+    void* corr;                     // real4, mixed precision only (else null)
+    const int2* slots;
+    const int32_t* lane_mol;        // [64*waves] shard-local molecule of the lane's particle, -1: idle lane
+    const int2* laneless;           // [nlaneless] (shard-relative index, shard-local molecule) of the particles without a lane
+    const double* mol_count;        // [nmol] particles per molecule n_m, as double
+    unsigned long long* words;      // [BARO_HEAD + 3 nmol], zero on entry of the sum kernel
+    int32_t nwaves, nlaneless, nmol, frac_bits;
+    double scale, inv_scale;        // 2^frac_bits, 2^-frac_bits
+    double e[3];                    // scale[a] - 1.0 per axis, formed in double on the host; 0: the axis keeps its stored bits
+};
+
 // Maxwell-Boltzmann start velocities (vv_dev_thermalize.inc, vvhip_set_velocities_to_temperature): a pure function of the seed, the GLOBAL
 // particle index (shard_begin + the slot's index), the masses and the two temperatures -- nothing of the wave layout, the launch shape or
 // the shard split enters.  lane_mass is the report's table (ReportArgs); a Drude pair shares a wave (META_PARTNER_SHIFT), so the partner's

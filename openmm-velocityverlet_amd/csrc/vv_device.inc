@@ -14,6 +14,7 @@
 #include "vv_dev_misc.inc"
 #include "vv_dev_report.inc"
 #include "vv_dev_cmm.inc"
+#include "vv_dev_barostat.inc"
 #include "vv_dev_thermalize.inc"
 #include "vv_dev_digest.inc"
 #include "vv_dev_frames.inc"

@@ -1003,6 +1003,31 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
             const int d = sys.drude_pairs[2 * k], c = sys.drude_pairs[2 * k + 1];
             if (in_shard(d) && in_shard(c) && reduced(d, c) > 0) hp.therm_pairs++;
         }
+        // Monte Carlo barostat (vv_host.hpp: baro_*): EVERY particle of the shard belongs to a molecule, massless ones included, so the
+        // report's lane table (-1 on massless lanes) does not serve.  The fixed point follows the largest molecule of the WHOLE System:
+        // |Q| < 2^(22 + F) and n_max <= 2^(40 - F) terms keep a molecule's sum below 2^62 on every shard alike.
+        std::vector<int32_t> mol_count(nmol, 0);
+        for (int i = 0; i < n; i++) mol_count[sys.mol_id[i]]++;
+        int32_t n_max = 1;
+        for (int m = 0; m < nmol; m++) n_max = std::max(n_max, mol_count[m]);
+        int lg = 0;
+        while (((int64_t) 1 << lg) < (int64_t) n_max) lg++;
+        hp.baro_frac_bits = 40 - lg;
+        hp.baro_num_molecules = nmol;
+        std::vector<int32_t> blocal(nmol, -1), here(nmol, 0);
+        for (int i = sb; i < se; i++) here[sys.mol_id[i]]++;
+        for (int m = 0; m < nmol; m++) {
+            if (here[m] == 0) continue;
+            if (here[m] != mol_count[m] && hp.baro_unsupported.empty())
+                hp.baro_unsupported = "the particle shard cuts a molecule: its centre needs particles of another shard";
+            blocal[m] = (int32_t) hp.baro_mol_count.size();
+            hp.baro_mol_count.push_back((double) mol_count[m]);
+        }
+        hp.baro_lane_mol.assign(ns, -1);
+        for (size_t k = 0; k < ns; k++)
+            if (slots[2 * k] >= 0) hp.baro_lane_mol[k] = blocal[sys.mol_id[slots[2 * k] + sb]];
+        for (int i = sb; i < se; i++)
+            if (!has_lane[(size_t) (i - sb)]) { hp.baro_laneless.push_back(i - sb); hp.baro_laneless.push_back(blocal[sys.mol_id[i]]); }
     }
     return hp;
 }

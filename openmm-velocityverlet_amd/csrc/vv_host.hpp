@@ -99,6 +99,14 @@ struct HostPlan {
     // have no lane (image particles, virtual sites placed from a parent's lane), shard-relative
     int64_t therm_massive = 0, therm_massless = 0, therm_pairs = 0;
     std::vector<int32_t> therm_laneless;
+    // Monte Carlo barostat (vvhip_barostat_*; vv_dev_barostat.inc): molecules as vvhip_system_desc.mol_id states them, over ALL particles of
+    // the shard (massless images and virtual sites included: report_lane_mol does not serve), numbered by ascending molecule id
+    int32_t baro_frac_bits = 40;               // F = 40 - ceil(log2(largest molecule of the WHOLE System)), the same on every shard
+    int32_t baro_num_molecules = 0;            // molecules of the WHOLE System
+    std::vector<int32_t> baro_lane_mol;        // [64*waves] shard-local molecule of the lane's particle; -1: idle lane
+    std::vector<int32_t> baro_laneless;        // 2 per particle of the shard without a lane: shard-relative index, shard-local molecule
+    std::vector<double> baro_mol_count;        // [shard molecules] particles of the molecule, as the divisor n_m
+    std::string baro_unsupported;              // why this plan cannot scale (a shard that cuts a molecule); empty otherwise
     // reference-style tables, kept for inspection / tests (global particle indices)
     std::vector<int32_t> particles_nh, molecules_nh, normal_nh, pairs_nh, normal_ld, pairs_ld;
 };

@@ -430,6 +430,15 @@ hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, 
     hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_cmm_subtract), dim3((unsigned) g), dim3(block_threads), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_barostat(int precision, const BarostatArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    const int wpb = block_threads / 64;
+    const int g = std::max(1, std::min(std::max((a.nwaves + wpb - 1) / wpb, (a.nlaneless + block_threads - 1) / block_threads), grid_cap));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_barostat_sum), dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_barostat_shift), dim3((unsigned) g), dim3(block_threads), 0, s, a);
+    return hipGetLastError();
+}
 hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_cap, hipStream_t s) {
     const int g = std::max(1, std::min(std::max((a.nwaves + 7) / 8, (a.nlaneless + 511) / 512), grid_cap));
     hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_thermalize), dim3((unsigned) g), dim3(512), 0, s, a);

@@ -53,6 +53,9 @@ hipError_t launch_series_append(const SeriesArgs& a, int grid_cap, hipStream_t s
 // Removal of the centre-of-mass velocity (vv_dev_cmm.inc): the sum kernel, then the subtract kernel, over a.rep.nwaves waves in blocks of
 // block_threads, at most grid_cap of them (the kernels stride beyond).  a.words must be zero on entry and is zero again afterwards.
 hipError_t launch_cm_motion(int precision, const CmmArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// Monte Carlo barostat (vv_dev_barostat.inc): the sum kernel, then the shift kernel, over a.nwaves waves and a.nlaneless listed particles in
+// blocks of block_threads, at most grid_cap of them (the kernels stride beyond).  a.words must be zero on entry.
+hipError_t launch_barostat(int precision, const BarostatArgs& a, int block_threads, int grid_cap, hipStream_t s);
 // Maxwell-Boltzmann start velocities (vv_dev_thermalize.inc): one kernel over a.nwaves waves and a.nlaneless listed particles in blocks of
 // 512 threads, at most grid_cap of them (the kernel strides beyond).
 hipError_t launch_thermalize(int precision, const ThermalizeArgs& a, int grid_cap, hipStream_t s);

@@ -11,6 +11,7 @@
 //   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, profiles, removal of the centre-of-mass motion, start
 //                    velocities; the list of the step's scheduled riders (riders), step_begin / step_done, quiesce; their one schedule is
 //                    vv_schedule.hpp (integers only, no HIP in it)
+//   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
 //                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
 //   vv_checkpoint.cpp  the state as a durable blob: vvhip_state_digest, vvhip_checkpoint_size / _save / _load, over the SAME list of items as
@@ -346,6 +347,21 @@ struct vvhip_plan {
         vv::DevBuf<vv::CmmDevRecord> d_rec;       // [2] the schedule's record; the record of vvhip_remove_cm_motion's one-off calls
         vv::PinnedBuf<double> h_v;                // pinned: the V of a one-off call as copied back
     } cmm;
+    // Monte Carlo barostat (vvhip_barostat_*; vv_barostat.cpp, vv_dev_barostat.inc): tables, scratch and the backup of the last scale, all
+    // allocated by the first scale.  `pending`: the backup and box_before still describe the state in front of the last scale -- cleared by
+    // vvhip_set_box, vvhip_bind and (through vvhip_set_box) vvhip_checkpoint_load; a moved step counter is seen at the restore itself
+    struct Barostat {
+        bool pending = false;
+        long long scales = 0, restores = 0;
+        long long step_at_scale = 0;
+        double box_before[3] = {0, 0, 0}, box_after[3] = {0, 0, 0};
+        vv::DevBuf<int32_t> d_lane_mol;
+        vv::DevBuf<int2> d_laneless;
+        vv::DevBuf<double> d_mol_count;
+        vv::DevBuf<unsigned long long> d_words;   // [BARO_HEAD + 3 per shard-local molecule]
+        vv::PinnedBuf<unsigned long long> h_bad;  // pinned: the bad word as copied back
+        vv::DevBuf<void> posq, corr;              // the positions in front of the last scale
+    } baro;
     // Maxwell-Boltzmann start velocities (vvhip_set_velocities_to_temperature): HostPlan::therm_laneless, uploaded by the first call
     vv::DevBuf<int32_t> d_therm_laneless;
     // State digest (vvhip_state_digest): one word per section, scratch of its own, allocated by the first call

@@ -673,6 +673,37 @@ class Context:
         H.check(H.lib.vvhip_cm_motion_read(self.plan, C.byref(out)), self.plan)
         return out
 
+    # ---- Monte Carlo barostat: the device half of an attempt (include/vvhip.h: vvhip_barostat_*); the driver is barostat.MonteCarloBarostat
+    @property
+    def num_molecules(self) -> int:
+        """Molecules of the whole System (the N of the barostat's acceptance rule)."""
+        return int(self.system.num_molecules)
+
+    def getPeriodicBoxSize(self) -> np.ndarray:
+        """The box edges [nm] as the plan holds them."""
+        return self._box.copy()
+
+    def scale_box(self, scale):
+        """Scale the box edges by scale[0..2] and move every molecule of this context rigidly so that its geometric centre scales with
+        them, on the device.  The positions in front of the call are kept on the device until the next scale: restore_box() undoes the
+        proposal bit for bit.  Blocks; a position that is not finite or beyond 2^22 nm raises ERR_OVERFLOW and changes nothing."""
+        s = (C.c_double * 3)(*[float(x) for x in scale])
+        H.check(H.lib.vvhip_barostat_scale(self.plan, C.byref(s)), self.plan)
+        self._box = np.array(self.barostat_record().box_after, dtype=np.float64)
+        self.forces_valid = False
+
+    def restore_box(self):
+        """Undo the last scale_box: positions and box are bit for bit what they were.  Refused (ERR_INVALID) when nothing is pending, or
+        when steps were taken, the box was set or a checkpoint was loaded since."""
+        H.check(H.lib.vvhip_barostat_restore(self.plan), self.plan)
+        self._box = np.array(self.barostat_record().box_before, dtype=np.float64)
+        self.forces_valid = False
+
+    def barostat_record(self) -> H.BarostatRecord:
+        out = H.BarostatRecord()
+        H.check(H.lib.vvhip_barostat_read(self.plan, C.byref(out)), self.plan)
+        return out
+
     # ---- checkpoint: the run's complete state as bytes (include/vvhip.h: vvhip_checkpoint_*)
     def createCheckpoint(self, sections="all") -> bytes:
         """The complete state of the run as a blob in the library's own format (not OpenMM's): particle arrays, forces, extra forces, the
@@ -696,6 +727,9 @@ class Context:
         words = (C.c_uint64 * 4)()
         H.check(H.lib.vvhip_checkpoint_load(self.plan, blob, len(blob), C.byref(words)), self.plan)
         self.random_index, self.forces_valid = int(words[0]), bool(words[1])
+        hdr = H.CheckpointHeader()
+        H.check(H.lib.vvhip_checkpoint_inspect(blob, len(blob), C.byref(hdr)), what="checkpoint header")
+        self._box = np.array(hdr.box, dtype=np.float64)                   # (the plan has taken the blob's box)
 
     def state_digest(self) -> dict:
         """{section name: 64-bit digest} of the state as it stands, computed on the device (vvhip_state_digest): two states are the same

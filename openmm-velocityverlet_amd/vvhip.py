@@ -159,6 +159,12 @@ class ThermalizeRecord(C.Structure):
                 ("cm_removed", C.c_int32), ("v_removed", C.c_double * 3)]
 
 
+class BarostatRecord(C.Structure):
+    """What the plan knows of its barostat scales (include/vvhip.h: vvhip_barostat_record)."""
+    _fields_ = [("molecules", C.c_int64), ("scales", C.c_int64), ("restores", C.c_int64), ("pending", C.c_int32),
+                ("frac_bits", C.c_int32), ("box_before", C.c_double * 3), ("box_after", C.c_double * 3)]
+
+
 CKPT_SECTION_NAMES = ("posq", "correction", "velm", "force", "force_extra", "random", "thermostat", "epoch", "cursor")
 CKPT_SECTIONS = len(CKPT_SECTION_NAMES)
 CKPT_MAGIC, CKPT_VERSION = 0x504B435049485656, 1
@@ -227,6 +233,7 @@ def _load():
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
+        "vvhip_barostat_scale": [vp, P(dbl * 3)], "vvhip_barostat_restore": [vp], "vvhip_barostat_read": [vp, P(BarostatRecord)],
         "vvhip_digest_host": [vp, C.c_size_t, C.c_uint64, P(C.c_uint64)], "vvhip_state_digest": [vp, P(C.c_uint64 * CKPT_SECTIONS)],
         "vvhip_checkpoint_size": [vp, u32, P(C.c_size_t)], "vvhip_checkpoint_save": [vp, u32, P(C.c_uint64 * 4), vp, C.c_size_t],
         "vvhip_checkpoint_inspect": [vp, C.c_size_t, P(CheckpointHeader)], "vvhip_checkpoint_load": [vp, vp, C.c_size_t, P(C.c_uint64 * 4)],
