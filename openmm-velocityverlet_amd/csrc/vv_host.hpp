@@ -22,6 +22,9 @@ struct Error : std::runtime_error {
     Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 
+// SimTKOpenMMRealType.h of OpenMM 8.1.2 (not vendored by the reference): BOLTZ = RGAS / KILO
+constexpr double kAvogadro = 6.02214076e23;
+constexpr double kBoltz = (1.380649e-23 * kAvogadro) / 1000.0;
 
 struct ResolvedParams : vvhip_params {};
 

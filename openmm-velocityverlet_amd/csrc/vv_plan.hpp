@@ -59,8 +59,8 @@ struct RcclApi {
 };
 RcclApi& rccl_api();
 
-constexpr double kAvogadro = 6.02214076e23;
-constexpr double kBoltz = (1.380649e-23 * kAvogadro) / 1000.0;
+using vv::kAvogadro;      // vv_host.hpp
+using vv::kBoltz;
 enum TimerClass { T_A = 0, T_B = 1, T_OTHER = 2 };
 constexpr int kAccN = vv::NUM_ACC * vv::ACC_SLOTS;
 constexpr int kRvCopy = 6 * kAccN;      // rendezvous words of one thermostat parity: up to 6 replicas (vv_device.inc: RV_REPLICAS) of [NUM_ACC][ACC_SLOTS]
