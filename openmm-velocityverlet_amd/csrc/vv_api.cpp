@@ -216,8 +216,8 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
     HIP_TRY(p, vv::zeros(p->d_acc, 2 * kAccN * sizeof(unsigned long long), p->stream));
     // rendezvous words of the fused step: uncached (every block's thermostat wave polls what the other blocks -- on other XCDs, behind other
     // L2s -- have just stored); zero = "no step's word" (tags run from 1)
-    // (+ ACC_SLOTS words: the two rows of "polled twice" flags; + 8: the "a rendezvous has failed" word behind them, vv_device.inc: rv_dead_word)
-    HIP_TRY(p, vv::zeros(p->d_rv, (size_t) (2 * kRvCopy + vv::ACC_SLOTS + 8) * sizeof(unsigned long long), p->stream, true));
+    // (the layout: vv_plan.hpp, kRvWords)
+    HIP_TRY(p, vv::zeros(p->d_rv, (size_t) kRvWords * sizeof(unsigned long long), p->stream, true));
     std::vector<vv::NHDevState> init(2);
     for (int c = 0; c < 2; c++)
         for (int g = 0; g < 3; g++) { init[c].s.vscale[g] = 1.0; init[c].scales[g] = 1.0; }
@@ -383,7 +383,7 @@ int vvhip_status_clear(vvhip_plan* p) {
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     std::memset(p->h_status.get(), 0, 4 * sizeof(unsigned int));
     if (p->d_mb_ctl) HIP_TRY(p, hipMemsetAsync(p->d_mb_ctl.get(), 0, 4 * sizeof(unsigned int), p->stream));
-    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(p->d_rv.get() + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));      // "a rendezvous has failed" (vv_device.inc: rv_dead_word)
+    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(rv_dead_tail(p->d_rv.get()), 0, kRvDeadTail * sizeof(unsigned long long), p->stream));      // "a rendezvous has failed" (vv_device.inc: rv_dead_word)
     p->rec.valid = false;          // (a snapshot from before the failure the caller has just acknowledged is nobody's to restore)
     p->rec.runs.clear();
     return VVHIP_OK;

@@ -83,6 +83,9 @@ constexpr int ACC_SLOTS = 256; // each quantity is spread over 256 int64 slots (
                                // thousands of blocks adding into ONE word serialise at ~10 ns per atomic on MI355X
                                // (measured: 17 us for kernel A at 1000 blocks); integer sums stay exact and
                                // order-independent, the chain wave folds the slots.  Layout acc[quantity][slot].
+constexpr int RV_REPLICAS = 4; // one-launch step: copies of the rendezvous words [NUM_ACC][ACC_SLOTS] a block publishes -- lane k + NUM_ACC r of
+                               // the thermostat wave stores quantity k into copy r, ONE store instruction --, each polled by its share of the blocks
+static_assert(RV_REPLICAS * NUM_ACC <= 64, "one lane of the thermostat wave per quantity and replica");
 
 // Multi-GPU accumulator exchange without a collective launch ("mailbox", one node over xGMI).  Every rank owns an UNCACHED
 // device allocation box[2 parities][ranks][MB_WORDS] of 8-byte words {sequence number : 32 | payload : 32} that all peers

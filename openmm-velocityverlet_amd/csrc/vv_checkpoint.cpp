@@ -165,7 +165,7 @@ int vvhip_checkpoint_load(vvhip_plan* p, const void* blob, size_t bytes, uint64_
     // dead word): a plan that goes back would otherwise meet the words of later steps under a restored tag
     HIP_TRY(p, hipMemsetAsync(p->d_acc.get(), 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
     if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc.get(), 0, p->d_bigacc.bytes(), p->stream));
-    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(p->d_rv.get(), 0, p->d_rv.bytes(), p->stream));
+    if (p->d_rv) HIP_TRY(p, hipMemsetAsync(p->d_rv.get(), 0, (size_t) kRvWords * sizeof(unsigned long long), p->stream));
     p->cur.parity = h.cursor.parity; p->cur.random_pos = h.cursor.random_pos;
     p->cur.fextra_dirty = h.cursor.fextra_dirty != 0; p->cur.fextra_virtual = h.cursor.fextra_virtual != 0;
     p->cur.step_count = h.cursor.step_count;

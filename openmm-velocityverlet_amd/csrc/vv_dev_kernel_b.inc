@@ -9,7 +9,7 @@ __device__ __forceinline__ int rv_index(int k, int slot) { return k * ACC_SLOTS 
 // WRAPPING sum of the 256 raw words: 256 (tag << 58) = tag << 66 and 256 << 57 = 2^65 vanish modulo 2^64, and |sum of q| < 2^62 by the
 // accumulators' headroom -- no decoding, no masking.  Round 5 decoded and masked every word behind the poll: with the tag test ~85 instructions
 // of one wave, at ~5 clocks per instruction of a single wave (tools/probes/icache_probe.cpp) 0.18 us on the critical path of every step.
-// "a rendezvous of this plan has failed" (uncached device word behind the two rows of "polled twice" words): raised by the wave whose wait ran
+// "a rendezvous of this plan has failed" (uncached device word behind the two rows of "polled twice" words -- the host's kRvDeadWord, vv_plan.hpp): raised by the wave whose wait ran
 // out, next to the sticky word in host memory; every later poll round that is incomplete gives up at once instead of waiting its own 0.2 s --
 // a 100-step graph behind the failure drains in microseconds, and the host (which restores its snapshot and goes on with two launches per
 // step, vv_api.cpp: recovery) gets the GPU back.
@@ -52,40 +52,27 @@ __device__ __forceinline__ void lane_swap16(unsigned long long& x, unsigned long
     const auto hi = __builtin_amdgcn_permlane16_swap((unsigned) (x >> 32), (unsigned) (y >> 32), false, false);
     x = ((unsigned long long) hi[0] << 32) | lo[0]; y = ((unsigned long long) hi[1] << 32) | lo[1];
 }
-#ifndef VV_RV_REPLICAS
-#define VV_RV_REPLICAS 4
-#endif
-constexpr int RV_REPLICAS = VV_RV_REPLICAS, RV_REPLICA_WORDS = NUM_ACC * ACC_SLOTS;      // copies of the words (<= 64 / NUM_ACC), each polled by its share of the blocks
+// copies of the words (RV_REPLICAS, vv_args.hpp), each polled by its share of the blocks
+constexpr int RV_REPLICA_WORDS = NUM_ACC * ACC_SLOTS;
 // SFA != 0: the FUSED step -- this launch also executes kernel A's stage set SFA on its tiles, in front of an in-kernel rendezvous of the
 // (co-resident) blocks that takes the place of the A -> B kernel boundary (see "fused step" below); pre_acc is then the rendezvous buffer.
-#ifndef VV_CORR_LATE
-#define VV_CORR_LATE 1
-#endif
-#ifndef VV_THERMO_HEAD_SLEEP
-#define VV_THERMO_HEAD_SLEEP 8      // x 64 clocks
-#endif
-// Probe builds only (tools/probes/ablate_tail.sh; wrong physics, never shipped): where on the thermostat wave's serial path does the one-launch step's time go?
-// 1: the tiles are released with factor 1 as soon as all words are held (fold, 2KE and the chain leave the critical path); 2: ... right behind the publish
-// (the wait and the poll leave it too); 3: as 1, and the publish stores a zero word right behind barrier 1 (the block sum leaves it).
-#ifndef VV_ABLATE
-#define VV_ABLATE 0
-#endif
+constexpr int THERMO_HEAD_SLEEP = 8;      // x 64 clocks: how long the one-launch step's thermostat wave steps aside at the kernel's head (HEAD_ASIDE)
 // MAP OF THIS KERNEL, in the order of its timeline (the body is ONE function on purpose: round 6 split it into forced-inline stage functions over
 // register structs -- same operations, 125 bit-for-bit tests green -- and the compiled instances came out 1-6.5 % SLOWER (other selects, other schedule:
 // C3 100.0 -> 96.2 k steps/s, C5 116 -> 108.6 k, C2 149 -> 142.9 k, profiles/r06m_split_ab.txt); the stages are lambdas and labelled sections instead):
-//   preamble          instance facts (FUSED, RV_SPLIT, ...), the block's LDS, `rendezvous_poll` (a wave's share of the rendezvous rows), pattern rows
+//   preamble          instance facts (FUSED, FA_KICK, ...), the block's LDS, pattern rows
 //   THERMOSTAT WAVE   (wave 0 of a block with B_CHAIN; returns at its end)
 //     head            priority / stepping aside; which lane advances which temperature group (LANE_LOCAL)
 //     load_batch      state, chain constants, accumulator slots [two launches: + chain_head]
 //     thermostat_tail one-launch step: hoists -> BARRIER 1 -> block sums -> publish -> [idle accumulators, chain_head in the wait's shadow]
-//                     -> poll (all rows, or its share + BARRIER 2a) | fold -> [mailbox] -> 2KE -> chain with release_tiles (BARRIER 2) in its middle
+//                     -> poll (all rows in use) | fold -> [mailbox] -> 2KE -> chain with release_tiles (BARRIER 2) in its middle
 //     record          block 0 stores the advanced thermostat and the wait's controller
 //   TILE WAVES        (grid-stride loop; one pass in the one-launch step)
 //     fetch           slot word, the tile's loads in one batch (positions behind the kick where kernel A's stages do not read them), role, masks
 //     [B_KICK]        two launches: kernel A's kick again from the same bits
 //     kernel A stages one-launch step: extra forces, kick, velocity constraints, Koenig-form sums -> LDS -> BARRIER 1
 //     scale_prep      the factor-independent half of the scaling (early unless a bias must be removed first)
-//     scales          [share of the rendezvous rows + BARRIER 2a] BARRIER 2: the scale factors from LDS
+//     scales          BARRIER 2: the scale factors from LDS
 //     kernel B stages bias removal, scaling, restore | classic first half | positions (+ constraints) | hard wall | virtual sites | stores | image mirror
 template <class real, class mixed, uint32_t SF, uint32_t SFA = 0u>
 __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_slots, const int pre_nwaves, const int pre_wpb, const unsigned long long* __restrict__ pre_acc,
@@ -116,18 +103,10 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
     constexpr bool FA_KICK = FUSED && (SFA & (A_KICK_FULL | A_KICK_HALF)) != 0;
     constexpr bool VV1_EARLY = FUSED && (SF & B_VV_KICK) != 0;      // classic first half in one launch: the VV kick's force and forceExtra come with the tile's batch
     __shared__ double sh_red[FUSED ? 8 : 1][NUM_ACC];       // the tile waves' partial sums (fused step)
-    // ... and what the block's waves share around the rendezvous: the step's tag and the wait (set by the thermostat wave in front of barrier 1),
-    // the row totals the polling waves deliver, whether one of them needed a second round
-    __shared__ unsigned long long sh_rv_tag;
-    __shared__ int sh_rv_wait;
-    __shared__ unsigned int sh_rv_late;
-    __shared__ long long sh_rv_tot[NUM_ACC];
-    // Collecting all blocks' words is shared out among the block's waves: the thermostat wave (poller 0) and the tile waves (pollers 1 ..), which
-    // have nothing to do until the scale factors arrive, take the rows in use in turn -- row k goes to poller k mod (waves of the block) -- and
-    // each polls its row(s) in one batch of 4 loads per row per lane, folds what it holds (lane sums, one DPP reduction) and leaves the total
-    // in LDS.  One wave polling every row was 12 loads per round for the three kinetic-energy rows and 40 with the cos moments, and folded
-    // them alone, on the kernel's critical path (tools/probes/rendezvous_probe.cpp, "split": last publish -> totals held 1.89 -> 1.68 us
-    // with three rows, 3.57 -> 2.48 us with ten, 251 blocks).
+    // The rendezvous' poll (thermostat_tail): every block's thermostat wave collects ALL rows in use itself, one batch of 4 loads per row per lane
+    // and round, and folds them.  (Round 5 shared the rows out among the block's waves -- the tile waves have nothing to do until the scale factors
+    // arrive -- behind a second barrier and a hand-over of the totals through LDS; since the rows add up without decoding (rv_word) round 6 measured
+    // that a wash on the full boxes and a loss on a rank's share of a sharded run, and removed it.  TUNING_LOG.md has the numbers.)
     // Bounded: after ~0.2 s without the other blocks' words (they are not resident: the launch shape was wrong for this device, or another
     // process holds CUs) the wave raises the sticky flag and carries on -- the host reports the run as void, nothing hangs.
     // The first round is sent a little BEHIND the block's publish.  The blocks publish over ~0.4 us and a word is ~0.6 us on its way: a round
@@ -135,80 +114,8 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
     // whole grid then leaves a round late.  Measured on one box, steps/s against the wait in units of 256 clocks (tools/probes/fused_delay.py,
     // one polling wave): C3 90.0 / 93.4 / 96.3 / 96.5 / 97.4 / 96.5 / 96.1 k at 0 / 3 / 4 / 5 / 6 / 7 / 8 (two launches 86.7 k), C5 104.5 -> 114.1 k
     // at 6, C2 132.5 -> 150.3 k at 5, C1 143.8 -> 159.1 k at 5, with HBonds (more skew between the blocks) best beyond 8.  The wait tunes
-    // itself (rv_delay in the device-resident state): every block reports whether one of its waves needed a second round; many late blocks,
+    // itself (rv_delay in the device-resident state): every block reports whether its thermostat wave needed a second round; many late blocks,
     // and the step after next waits one unit longer; 64 steps without a late block, one unit shorter.  a.fused_poll_delay >= 0 pins it.
-    // Shared out only with the ten rows of the cos moments: with three rows the second barrier and the totals' trip through LDS cost more than the
-    // parallel fold saves (one box, steps/s shared | alone: C4 83.3 | 80.9 k, but C3 95.5 | 97.5 k, C5 111.3 | 115.0 k, C2 137.4 | 145.5 k, C1 142.7 |
-    // 150.8 k; profiles/r05g_split_poll_ab.txt) -- there the thermostat wave polls all rows itself.
-// Round 6: OFF.  Since the rows add up without decoding (rv_word) one wave polls and folds ten rows as fast as eight waves share them -- the full C4
-// box 87.4 against 87.1 k steps/s -- and a rank's share of a sharded C4 run is faster without the extra barrier and the LDS hand-over: C4 / 8 10.40 ->
-// 9.92 us per step, 9.70 with one tile wave per block (profiles/r06w_c4_shard_shapes.txt).  -DVV_RV_SPLIT=1 builds round 5's sharing.
-#ifndef VV_RV_SPLIT
-#define VV_RV_SPLIT 0
-#endif
-#ifndef VV_SETTLE_PREP
-#define VV_SETTLE_PREP 1
-#endif
-#ifndef VV_VEL_EARLY
-#define VV_VEL_EARLY 1
-#endif
-#ifndef VV_GEOM_SHARED      // (0: the tail gathers the clusters' old bonds from the page again, as before round 6's last change -- for comparisons)
-#define VV_GEOM_SHARED 1
-#endif
-    constexpr bool RV_SPLIT = VV_RV_SPLIT && FUSED && (FA & A_KE_MOM) != 0;
-    auto rendezvous_poll = [&](const int poller) {
-        constexpr int NR = (FA & A_KE_MOM) ? NUM_ACC : ((FA & A_BIAS) ? 4 : 3);      // rows in use: 0 .. NR - 1
-        constexpr int MAXR = (NR + 1) / 2;                                           // (at least two pollers: a thermostat wave and a tile wave)
-        if (poller >= NR) return;
-        const int np = pre_wpb;
-        const unsigned long long tag = sh_rv_tag;
-        const unsigned tag_lo = (unsigned) (tag >> 32), tag_hi = tag_lo | 0x03FFFFFFu;
-        const int wait_units = sh_rv_wait;
-        const unsigned long long* rvp = pre_acc + ((int) blockIdx.x % RV_REPLICAS) * RV_REPLICA_WORDS;
-        for (int d = 0; d < wait_units; d++) __builtin_amdgcn_s_sleep(4);
-        unsigned long long word[MAXR][ACC_SLOTS / 64];
-        long long t0 = 0;
-        int rounds = 0;
-        for (;;) {
-            rounds++;
-            // (Two rows of a slot side by side and ONE 16-byte load for both was built and measured: C3 90.4 k against 97.3 k steps/s, C4 58.7 k
-            // against 81.5 k, profiles/r05d_paired_vs_unpaired.txt.  16-byte accesses of the uncached allocation are the slower ones.)
-            // (a poller without a second row holds the bare tag in its place: the tag test then needs no case distinction)
-#pragma unroll
-            for (int i = 0; i < MAXR; i++) {
-                const int k = poller + i * np;
-#pragma unroll
-                for (int j = 0; j < ACC_SLOTS / 64; j++) word[i][j] = k < NR ? __hip_atomic_load(&rvp[rv_index(k < NR ? k : 0, lane + 64 * j)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : tag;
-            }
-            // (every eighth round, with the round's batch -- a block that is merely late needs two or three: in EVERY round 251 blocks asking for this ONE word
-            // cost the small and mid configurations 1-3 %, profiles/r06n_dead_word_ab.txt)
-            const unsigned int dead = (rounds & 7) == 0 ? __hip_atomic_load(rv_dead_word(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-            unsigned lo = 0xFFFFFFFFu, hi = 0u;
-#pragma unroll
-            for (int i = 0; i < MAXR; i++) rv_tag_range(word[i], lo, hi);
-            if (!__any(lo < tag_lo || hi > tag_hi)) break;
-            if (__any(dead != 0u)) break;
-            if (t0 == 0) t0 = wall_clock64();
-            if (wall_clock64() - t0 > 20000000LL) {                                  // 100 MHz counter
-                if (a.status) __hip_atomic_store(&a.status[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __hip_atomic_store(rv_dead_word(a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (rounds > 1 && lane == 0) sh_rv_late = 1u;
-#pragma unroll
-        for (int i = 0; i < MAXR; i++) {
-            const int k = poller + i * np;
-            if (k < NR) {
-                unsigned long long part = 0;
-#pragma unroll
-                for (int j = 0; j < ACC_SLOTS / 64; j++) part += word[i][j];
-                const long long total = (long long) wrap_reduce_lane_sum(part);          // (see rv_word: the wrapping sum of all slots IS the total)
-                if (lane == 0) sh_rv_tot[k] = total;
-            }
-        }
-    };
     // Block layout.  With B_CHAIN the FIRST wave of every block is the block's thermostat wave: it folds the
     // accumulators and advances the NH chain (a ~2 us serial fp64 dependency chain) while the other waves of the
     // block load their particles and do the scale-independent preparation; one barrier joins them.  Without this,
@@ -255,19 +162,18 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         // against C3 99.2 -> 100.2 k, C2 150.0 -> 151.4 k; profiles/r05p_thermostat_head_ab.txt) and the wave keeps its priority from the start.
         constexpr bool HEAD_ASIDE = FUSED && (FA & (A_CONS | A_COS | A_BIAS)) == 0;
         if constexpr (HEAD_ASIDE) {
-            __builtin_amdgcn_s_sleep(VV_THERMO_HEAD_SLEEP);
+            __builtin_amdgcn_s_sleep(THERMO_HEAD_SLEEP);
         } else {
             __builtin_amdgcn_s_setprio(3);        // the block waits for this wave: let it win the issue arbitration on its SIMD
         }
         VV_STAMP(7, 0);
-        // Which lane advances which temperature group.  Two-launch kernel B (and the one-launch step next to the mailbox or with the rows shared
-        // out): lane g, group g; the totals arrive in scalar registers.  One-launch step otherwise (round 6): the fold leaves the total of row g in
+        // Which lane advances which temperature group.  Two-launch kernel B (and the one-launch step next to the mailbox): lane g, group g; the totals arrive in scalar registers.  One-launch step otherwise (round 6): the fold leaves the total of row g in
         // lane 16 g + 15, and THAT lane runs group g's chain -- six v_readlane, the per-lane selects and the copies back into vector registers
         // (~20 instructions of one wave between "words held" and the release) are gone.  The other lanes of a row run the same instructions on the
         // row's partial sums and are ignored (no store, no vote in the chain's range test).
         // (With the cos moments the rows are grouped so that group g's three totals -- rows g, 4 + g, 7 + g -- meet in lane 16 g + 15 too; the bias
         // moment, row 3, is fetched from lane 63 for all of them.)
-        constexpr bool LANE_LOCAL = FUSED && !RV_SPLIT && (SF & B_MAILBOX) == 0;
+        constexpr bool LANE_LOCAL = FUSED && (SF & B_MAILBOX) == 0;
         const int cg = LANE_LOCAL ? ((lane >> 4) < VVHIP_NUM_TG ? (lane >> 4) : VVHIP_NUM_TG - 1) : (lane < VVHIP_NUM_TG ? lane : VVHIP_NUM_TG - 1);
         const bool group_lane = LANE_LOCAL ? ((lane & 15) == 15 && lane < 16 * VVHIP_NUM_TG) : lane < VVHIP_NUM_TG;
         constexpr int BIAS_LANE = LANE_LOCAL ? 63 : 3;
@@ -285,10 +191,6 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         unsigned chain_max_hi = 0;
         ChainExpK ek = chain_exp_k();
         double ke2 = 0, bias = 0, factor = 1.0;
-#if VV_ABLATE
-        bool ablate_released = false;
-        auto ablate_release = [&]() { if (lane < VVHIP_NUM_TG) sh_scales[lane] = 1.0; if (lane == 3) sh_scales[3] = 0.0; __syncthreads(); ablate_released = true; };
-#endif
         // every load of this wave -- thermostat state, chain constants, the accumulator slots of all rows in use -- is issued here, in
         // front of a scheduling barrier: left to itself the backend sank part of the state loads BEHIND the first row's reduction
         // (register pressure), i.e. behind a wait for the cold accumulator loads, and the chain started a second memory round trip late
@@ -346,8 +248,7 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
             cr_loaded = cr;
             if constexpr (!FUSED) chain_head();
         };
-        // (`live` = true in every call that is left: a false one ran the tail without publishing anything, see below)
-        auto thermostat_tail = [&](const bool live) {
+        auto thermostat_tail = [&]() {
         if constexpr (FUSED) {
             // ---- rendezvous.  The tile waves have laid their partial sums into sh_red (barrier 1); lane k adds quantity k over the block's
             // tile waves -- kernel A's tail, operation for operation -- and publishes it; then all blocks' words are collected.
@@ -359,10 +260,8 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
             // double -- is fetched HERE, while the wave waits for the tiles anyway: behind the barrier those scalar loads were ~0.2 us of the
             // 0.37 us between barrier 1 and the publish, on the kernel's critical path; in-kernel stamps, round 5)
             const double my_scale = block_quantity_scale<NUM_ACC>(en, a.acc_scale, lane % NUM_ACC);
-            unsigned int* const status_live = live ? a.status : nullptr;
             const double block_limit = (double) (nblocks > 32 ? nblocks : 32);
             const int wait_units = a.fused_poll_delay >= 0 ? a.fused_poll_delay : (int) rv_delay;
-            if constexpr (RV_SPLIT) { if (lane == 0) { sh_rv_tag = tag; sh_rv_wait = wait_units; sh_rv_late = 0u; } }
             // (rows of tile waves this block does not have: zero, so that the sum behind barrier 1 needs no selects -- block_fixed_point_sum_padded)
             if (lane < NUM_ACC)
                 for (int i = nwb - 1; i < 8; i++) sh_red[i][lane] = 0.0;
@@ -372,101 +271,71 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
             unsigned long long* const my_slot = rv + my_rep * RV_REPLICA_WORDS + rv_index(my_q, (int) blockIdx.x);
             const double* const my_partials = &sh_red[0][my_q];
             const unsigned long long word0 = rv_word(tag, 0);
-            asm volatile("" :: "v"(my_scale), "s"(status_live), "v"(block_limit), "s"(wait_units), "v"(my_slot), "v"(my_partials), "s"(word0));
+            asm volatile("" :: "v"(my_scale), "s"(a.status), "v"(block_limit), "s"(wait_units), "v"(my_slot), "v"(my_partials), "s"(word0));
             __builtin_amdgcn_sched_barrier(0);
             VV_STAMP_NOWAIT(7, 6);
             __builtin_amdgcn_s_setprio(3);
-            if (live) __syncthreads();
+            __syncthreads();
             VV_STAMP_NOWAIT(7, 7);
             if (my_rep < RV_REPLICAS && block_quantity_enabled<NUM_ACC>(en, my_q)) {
                 // (a block may contribute 2^62 / blocks and must fit the 58-bit payload: 2^57 at most)
-#if VV_ABLATE == 3
-                const long long q = 0;
-#else
-                const long long q = block_fixed_point_sum_padded<NUM_ACC>(sh_red, my_q, my_scale, status_live, block_limit);
-#endif
-                if (live) __hip_atomic_store(my_slot, word0 + (unsigned long long) q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                const long long q = block_fixed_point_sum_padded<NUM_ACC>(sh_red, my_q, my_scale, a.status, block_limit);
+                __hip_atomic_store(my_slot, word0 + (unsigned long long) q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 // the slots beyond the grid: the neutral word, from the first blocks (behind the block's own word; a grid of 251 blocks has five of them)
-                if (live)
-                    for (int sl = nblocks + (int) blockIdx.x; sl < ACC_SLOTS; sl += nblocks)
-                        __hip_atomic_store(my_slot + (sl - (int) blockIdx.x), word0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                for (int sl = nblocks + (int) blockIdx.x; sl < ACC_SLOTS; sl += nblocks)
+                    __hip_atomic_store(my_slot + (sl - (int) blockIdx.x), word0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             VV_STAMP_NOWAIT(7, 8);      // "published"
-            if (live) clear_idle_accumulators();
+            clear_idle_accumulators();
             chain_head();
-            if constexpr (RV_SPLIT) {
-                rendezvous_poll(0);              // this wave's share of the rows; the tile waves collect the others meanwhile
-                __syncthreads();                 // barrier 2a: every row's total is in LDS
-                // (this block's report to the wait's controller of the step after next: a word of its own -- 251 blocks flagging ONE word serialise
-                // at the memory side for microseconds, first version of this)
-                // (this block's report to the wait's controller of the step after next: a word of its own -- 251 blocks flagging ONE word serialise
-                // at the memory side for microseconds, first version of this.  HERE, not behind the release where nothing would wait for it: there it cost
-                // the small configurations 4-5 % (C2 150 against 158 k steps/s, profiles/r06e_ek_late_ab.txt; unexplained))
-                if (live && lane == 0) __hip_atomic_store(&a.rv_late_cur[blockIdx.x], sh_rv_late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                VV_STAMP_NOWAIT(7, 9);
-            } else {
-                const unsigned long long* rvp = rv + ((int) blockIdx.x % RV_REPLICAS) * RV_REPLICA_WORDS;
-#if VV_ABLATE == 2
-                ablate_release();
-#endif
-                // (three or four rows: this wave polls them all itself, one batch of 4 loads per row per lane and round, and folds them below)
-                for (int d = 0; d < wait_units; d++) __builtin_amdgcn_s_sleep(4);
-                unsigned long long word[NUM_ACC][ACC_SLOTS / 64];
-                long long t0 = 0;
-                int rounds = 0;
-                const unsigned tag_lo = (unsigned) (tag >> 32), tag_hi = tag_lo | 0x03FFFFFFu;
-                for (;;) {
-                    rounds++;
-                    // (Two rows of a slot side by side and ONE 16-byte load for both -- 8 / 20 loads per round instead of 12 / 40 -- was built and measured:
-                    // C3 90.4 k against 97.3 k steps/s, C4 58.7 k against 81.5 k, C5 108.1 against 114.7 k, two rotations on one box,
-                    // profiles/r05d_paired_vs_unpaired.txt.  16-byte accesses of the uncached allocation are the slower ones; 8-byte loads stay.)
-#pragma unroll
-                    for (int k = 0; k < NUM_ACC; k++)
-#pragma unroll
-                        for (int j = 0; j < ACC_SLOTS / 64; j++) word[k][j] = en[k] ? __hip_atomic_load(&rvp[rv_index(k, lane + 64 * j)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : tag;
-                    // complete: every slot of every row in use carries this step's tag (rv_word) -- smallest and largest high word inside the tag's range
-                    // (every eighth round, with the round's batch -- a block that is merely late needs two or three: in EVERY round 251 blocks asking for this ONE word
-                    // cost the small and mid configurations 1-3 %, profiles/r06n_dead_word_ab.txt)
-                    const unsigned int dead = (rounds & 7) == 0 ? __hip_atomic_load(rv_dead_word(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-                    unsigned lo = 0xFFFFFFFFu, hi = 0u;
-#pragma unroll
-                    for (int k = 0; k < NUM_ACC; k++) if (en[k]) rv_tag_range(word[k], lo, hi);
-                    if (!live || !__any(lo < tag_lo || hi > tag_hi)) break;
-                    if (__any(dead != 0u)) break;
-                    if (t0 == 0) t0 = wall_clock64();
-                    if (wall_clock64() - t0 > 20000000LL) {                                  // 100 MHz counter
-                        if (a.status) __hip_atomic_store(&a.status[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        __hip_atomic_store(rv_dead_word(a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                // (no decoding, no mask: the wrapping sum of a row's 256 raw words is the row's total, see rv_word)
+            // ---- the poll: this wave collects every row in use itself, one batch of 4 loads per row per lane and round, and folds them below
+            const unsigned long long* rvp = rv + ((int) blockIdx.x % RV_REPLICAS) * RV_REPLICA_WORDS;
+            for (int d = 0; d < wait_units; d++) __builtin_amdgcn_s_sleep(4);
+            unsigned long long word[NUM_ACC][ACC_SLOTS / 64];
+            long long t0 = 0;
+            int rounds = 0;
+            const unsigned tag_lo = (unsigned) (tag >> 32), tag_hi = tag_lo | 0x03FFFFFFu;
+            for (;;) {
+                rounds++;
+                // (Two rows of a slot side by side and ONE 16-byte load for both -- 8 / 20 loads per round instead of 12 / 40 -- was built and measured:
+                // C3 90.4 k against 97.3 k steps/s, C4 58.7 k against 81.5 k, C5 108.1 against 114.7 k, two rotations on one box,
+                // profiles/r05d_paired_vs_unpaired.txt.  16-byte accesses of the uncached allocation are the slower ones; 8-byte loads stay.)
 #pragma unroll
                 for (int k = 0; k < NUM_ACC; k++)
 #pragma unroll
-                    for (int j = 0; j < ACC_SLOTS / 64; j++) raw[k][j] = en[k] ? (long long) word[k][j] : 0ll;
-                // (this block's report to the wait's controller of the step after next: a word of its own -- 251 blocks flagging ONE word serialise at the
-                // memory side for microseconds, first version of this)
-                if (live && lane == 0) __hip_atomic_store(&a.rv_late_cur[blockIdx.x], rounds > 1 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#if VV_ABLATE == 1 || VV_ABLATE == 3
-                asm volatile("" :: "v"(raw[0][0]), "v"(raw[1][3]), "v"(raw[2][3]));
-                ablate_release();
-#endif
-                VV_STAMP_AFTER(7, 9, raw[0][0]);
-                VV_STAMP_VALUE(7, 10, rounds);
+                    for (int j = 0; j < ACC_SLOTS / 64; j++) word[k][j] = en[k] ? __hip_atomic_load(&rvp[rv_index(k, lane + 64 * j)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : tag;
+                // complete: every slot of every row in use carries this step's tag (rv_word) -- smallest and largest high word inside the tag's range
+                // (every eighth round, with the round's batch -- a block that is merely late needs two or three: in EVERY round 251 blocks asking for this ONE word
+                // cost the small and mid configurations 1-3 %, profiles/r06n_dead_word_ab.txt)
+                const unsigned int dead = (rounds & 7) == 0 ? __hip_atomic_load(rv_dead_word(a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+                unsigned lo = 0xFFFFFFFFu, hi = 0u;
+#pragma unroll
+                for (int k = 0; k < NUM_ACC; k++) if (en[k]) rv_tag_range(word[k], lo, hi);
+                if (!__any(lo < tag_lo || hi > tag_hi)) break;
+                if (__any(dead != 0u)) break;
+                if (t0 == 0) t0 = wall_clock64();
+                if (wall_clock64() - t0 > 20000000LL) {                                  // 100 MHz counter
+                    if (a.status) __hip_atomic_store(&a.status[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(rv_dead_word(a), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
             }
+            // (no decoding, no mask: the wrapping sum of a row's 256 raw words is the row's total, see rv_word)
+#pragma unroll
+            for (int k = 0; k < NUM_ACC; k++)
+#pragma unroll
+                for (int j = 0; j < ACC_SLOTS / 64; j++) raw[k][j] = en[k] ? (long long) word[k][j] : 0ll;
+            // (this block's report to the wait's controller of the step after next: a word of its own -- 251 blocks flagging ONE word serialise
+            // at the memory side for microseconds, first version of this.  HERE, not behind the release where nothing would wait for it: there it cost
+            // the small configurations 4-5 % (C2 150 against 158 k steps/s, profiles/r06e_ek_late_ab.txt; unexplained))
+            if (lane == 0) __hip_atomic_store(&a.rv_late_cur[blockIdx.x], rounds > 1 ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            VV_STAMP_AFTER(7, 9, raw[0][0]);
+            VV_STAMP_VALUE(7, 10, rounds);
         }
         long long tot[NUM_ACC] = {};
         unsigned long long row_total_here = 0;      // LANE_LOCAL: the total of row (lane >> 4) in the row's last lane ...
         unsigned long long row_total_ab = 0, row_total_bb = 0;      // ... and, with the cos moments, of rows 4 + (lane >> 4) and 7 + (lane >> 4)
-        if constexpr (FUSED && RV_SPLIT) {
-#pragma unroll
-            for (int k = 0; k < NUM_ACC; k++) {
-                const bool wanted = (k < 3 || (k == 3 && (F & B_UNBIAS)) || (k > 3 && (F & B_KE_MOM)));
-                tot[k] = wanted ? sh_rv_tot[k] : 0ll;
-            }
-        } else {
         // totals of the rows in use, four per wave reduction and the (up to three) groups of four step by step side by side, as kernel A's
         // tail does (wave_reduce4_groups): with the cos moments the fold is three rounds, and one after the other they kept this wave --
         // the block's critical path -- 0.3 us longer than C3's single round (in-kernel stamps, round 4).  Every total ends in a scalar register.
@@ -515,15 +384,12 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
                              : (long long) (((unsigned long long) (unsigned) __builtin_amdgcn_readlane((int) (ft[g] >> 32), 16 * i + 15) << 32) |
                                             (unsigned) __builtin_amdgcn_readlane((int) (unsigned) ft[g], 16 * i + 15));
         }
-        }
         if (F & B_MAILBOX) {                      // multi-GPU: block 0 publishes this rank's totals, every block collects all ranks'
             __shared__ unsigned int mb_words[MB_MAX_RANKS * MB_WORDS];
             __shared__ unsigned long long mb_peer_boxes[MB_MAX_RANKS];
-            if (live) {
-                if (lane < a.mb.ranks) mb_peer_boxes[lane] = mb_peer_box;
-                VV_WAVE_LDS_FENCE();
-                mailbox_exchange(a, lane, mb_seq + 1u, mb_dead != 0, mb_peer_boxes, mb_words, tot);
-            }
+            if (lane < a.mb.ranks) mb_peer_boxes[lane] = mb_peer_box;
+            VV_WAVE_LDS_FENCE();
+            mailbox_exchange(a, lane, mb_seq + 1u, mb_dead != 0, mb_peer_boxes, mb_words, tot);
         }
         VV_STAMP_AFTER(7, 1, row_total_here);      // "folded" (not VV_STAMP: that one waits for the wave's outstanding stores -- the "polled twice" word -- as well)
         ke2 = 0;
@@ -553,29 +419,19 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         // Hands the scale factors to the block's tile waves the moment they are final -- in the MIDDLE of the chain update (see
         // propagate_preloaded): this wave's only barrier.  The second half of the chain runs while the tile waves scale and drift.
         auto release_tiles = [&](double f) {
-#if VV_ABLATE
-            if (ablate_released) return;
-#endif
-            if (live) {
-                if (group_lane) sh_scales[cg] = f;
-                if (lane == BIAS_LANE) sh_scales[3] = bias;
-                VV_STAMP_AFTER(7, 5, f);
-                __syncthreads();
-            }
+            if (group_lane) sh_scales[cg] = f;
+            if (lane == BIAS_LANE) sh_scales[3] = bias;
+            VV_STAMP_AFTER(7, 5, f);
+            __syncthreads();
         };
         factor = propagate_group_small<NCT>(a.chain, lc, ke2, cr, cr_loaded, cpre, chain_max_hi, !LANE_LOCAL || group_lane, ek, release_tiles);
         };
-        if constexpr (!FUSED) {
-            load_batch();
-            thermostat_tail(true);
-        } else {
-            // (A warm-up pass of the tail on zeros in the shadow of the tiles' loads -- the fold, 2KE and the chain up to the scale factor are
-            // ~1.1 us of serial work behind the rendezvous where their arithmetic is ~0.3 us, and a cold instruction cache was the suspect --
-            // was built and measured in round 5: the real pass was no faster (publish 0.28 / fold 0.26 / chain 0.49 us against 0.37 / 0.24 /
-            // 0.54), and the wave reached barrier 1 0.3 us AFTER the tiles: C2 -11 %, C1 -5 %, C3 +-0.  Not the instruction cache; dropped.)
-            load_batch();
-            thermostat_tail(true);
-        }
+        // (One-launch step: a warm-up pass of the tail on zeros in the shadow of the tiles' loads -- the fold, 2KE and the chain up to the scale factor are
+        // ~1.1 us of serial work behind the rendezvous where their arithmetic is ~0.3 us, and a cold instruction cache was the suspect --
+        // was built and measured in round 5: the real pass was no faster (publish 0.28 / fold 0.26 / chain 0.49 us against 0.37 / 0.24 /
+        // 0.54), and the wave reached barrier 1 0.3 us AFTER the tiles: C2 -11 %, C1 -5 %, C3 +-0.  Not the instruction cache; dropped.)
+        load_batch();
+        thermostat_tail();
         VV_STAMP_AFTER(7, 2, factor);
         // Every block clears ITS share of the idle accumulator copy (slots b, b + grid, ... of the rows in use): one store instruction
         // per thermostat wave.  Block 0 used to clear all of it -- 16 store instructions per lane, 40 with the cos moments -- behind its
@@ -675,7 +531,7 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         // C3 + HBonds 78.4 -> 79.8 k; the electrode slab and the cos perturbation lose 0.3-1 % with it and keep their single batch)
         constexpr bool TABF_LATE = POS_LATE || (FUSED && (FA & A_CONS) != 0 && (FA & (A_EF | A_COS | A_BIAS)) == 0);
         // (field / cos perturbation without constraints: kernel A's stages read posq alone -- the charge, z --, the correction follows behind the kick)
-        constexpr bool CORR_LATE = VV_CORR_LATE && FUSED && !POS_LATE && (FA & A_CONS) == 0;
+        constexpr bool CORR_LATE = FUSED && !POS_LATE && (FA & A_CONS) == 0;
         real4 p1 = {0, 0, 0, 0}, p2 = {0, 0, 0, 0};
         if (touches_pos && !POS_LATE) {
             p1 = ((const real4*) a.posq)[ai];
@@ -706,7 +562,7 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         if ((F & B_MTAB) && (F & B_SCALE) && !TABF_LATE) tab_f = (F & B_PERIODIC) ? (mixed) sh_pat_f[pw.region][lane] : (mixed) a.slot_f[li];      // (one-launch step: requested behind the kick, like the positions)
         // cluster word and parameters of the in-kernel constraints
         // (one-launch step: the hydrogen-type clusters' old bonds are formed ONCE per launch, by the velocity constraints of the front; vv_dev_constraints.inc: ClusterGeom)
-        constexpr bool GEOM_SHARED = VV_GEOM_SHARED && FUSED && (FA & A_SHAKE_V) != 0 && (FA & (A_GCONS | A_SHAKE_GS)) == 0 && (F & B_SHAKE) != 0 && (F & (B_GCONS | B_SHAKE_GS)) == 0;
+        constexpr bool GEOM_SHARED = FUSED && (FA & A_SHAKE_V) != 0 && (FA & (A_GCONS | A_SHAKE_GS)) == 0 && (F & B_SHAKE) != 0 && (F & (B_GCONS | B_SHAKE_GS)) == 0;
         ClusterGeom<mixed> geom;      // (written and read by cluster members only)
         unsigned shake_word = 0;
         float4 shake_prm = make_float4(0, 0, 0, 0);
@@ -949,7 +805,7 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         VV_STAMP(wib, 1);
         if (prep_early) scale_prep();
         // (rigid triangles: what their position solve needs from the OLD positions alone -- vv_dev_constraints.inc: settle_prepare -- while the wave waits anyway)
-        constexpr bool SETTLE_PREP = VV_SETTLE_PREP && FUSED && (FA & A_CONS) != 0 && (F & B_SETTLE) != 0 && (F & (B_SHAKE_GS | B_GCONS)) == 0;
+        constexpr bool SETTLE_PREP = FUSED && (FA & A_CONS) != 0 && (F & B_SETTLE) != 0 && (F & (B_SHAKE_GS | B_GCONS)) == 0;
         SettleFrame<mixed> sframe;
         if constexpr (SETTLE_PREP) settle_prepare<mixed>(lane, shake_word, shake_prm, x, y, z, v.w, shake_page_b, sframe);
         VV_STAMP(wib, 2);
@@ -957,10 +813,6 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
         if (need_scales) {
             need_scales = false;
             if (has_cw) {
-                if constexpr (FUSED && RV_SPLIT) {
-                    rendezvous_poll(wib + 1);      // this wave's share of the rendezvous rows (it has nothing else to do until the release)
-                    __syncthreads();                 // barrier 2a: the thermostat wave takes the totals from LDS
-                }
                 __syncthreads();
                 sc0 = sh_scales[0]; sc1 = sh_scales[1]; sc2 = sh_scales[2]; scb = sh_scales[3];
                 VV_STAMP(wib, 3);
@@ -1052,7 +904,7 @@ __global__ void __launch_bounds__(512) vv_kernel_b(const int2* __restrict__ pre_
             }
             // (one-launch step without constraints: the velocity is final here unless the hard wall is hit -- its 32 bytes per lane leave now, in front of the wall's
             // and the position's arithmetic, instead of in one burst with the position's at the wave's end; a lane the wall does hit stores again below)
-            if constexpr (VV_VEL_EARLY && FUSED && (F & B_CONS) == 0) {
+            if constexpr (FUSED && (F & B_CONS) == 0) {
                 if (act && vel_dirty) store_vec(velm, atom, v);
                 vel_dirty = false;
             }

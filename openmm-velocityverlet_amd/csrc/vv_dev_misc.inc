@@ -87,17 +87,7 @@ __global__ void __launch_bounds__(512) vv_kernel_tether(const int2* __restrict__
         const long long sx = (long long) (-kd * dxx * scale), sy = (long long) (-kd * dyy * scale), sz = (long long) (-kd * dzz * scale);
         if (isd) { ix += sx; iy += sy; iz += sz; } else { ix -= sx; iy -= sy; iz -= sz; }
     }
-#if VV_STORE_POLICY == 1
-    if (act) { __builtin_nontemporal_store(ix, &t.force[atom]); __builtin_nontemporal_store(iy, &t.force[atom + t.padded]); __builtin_nontemporal_store(iz, &t.force[atom + 2 * t.padded]); }
-#elif VV_STORE_POLICY == 2
-    if (act) {
-        asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" :: "v"(&t.force[atom]), "v"(ix) : "memory");
-        asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" :: "v"(&t.force[atom + t.padded]), "v"(iy) : "memory");
-        asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" :: "v"(&t.force[atom + 2 * t.padded]), "v"(iz) : "memory");
-    }
-#else
     if (act) { t.force[atom] = ix; t.force[atom + t.padded] = iy; t.force[atom + 2 * t.padded] = iz; }
-#endif
     VV_SPAN_END;
 }
 

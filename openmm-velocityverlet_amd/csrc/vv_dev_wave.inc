@@ -40,26 +40,7 @@ __device__ __forceinline__ double sqrt_nr(double x) { return x > 0 ? x * rsqrt_n
 __device__ __forceinline__ float sqrt_nr(float x) { return sqrtf(x); }
 template <class V>
 __device__ __forceinline__ void store_vec(V* base, int index, const V& val) {
-#ifndef VV_STORE_POLICY
-#define VV_STORE_POLICY 0      // comparison builds: 1 = non-temporal stores, 2 = system-scope (write-through) stores for the state the step leaves behind
-#endif
-#if VV_STORE_POLICY == 0
     base[index] = val;
-#else
-    using chunk = __attribute__((ext_vector_type(4))) unsigned;
-    static_assert(sizeof(V) % 16 == 0, "whole 16-byte chunks");
-    const V tmp = val;
-    const chunk* src = (const chunk*) &tmp;
-    chunk* dst = (chunk*) (base + index);
-#pragma unroll
-    for (int i = 0; i < (int) (sizeof(V) / 16); i++) {
-#if VV_STORE_POLICY == 1
-        __builtin_nontemporal_store(src[i], dst + i);
-#else
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst + i), "v"(src[i]) : "memory");
-#endif
-    }
-#endif
 }
 
 __device__ __forceinline__ float shfl(float x, int src) { return __shfl(x, src, 64); }

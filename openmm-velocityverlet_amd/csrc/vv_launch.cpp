@@ -439,10 +439,10 @@ int run_fused(vvhip_plan* p, uint32_t aflags, uint32_t bflags, uint32_t random_i
     q.flags_a = aflags;
     q.fused_poll_delay = p->fused_poll_delay;
     // the "a block polled twice" words of this step and of the one before (by thermostat parity), behind the two copies of the rendezvous words
-    q.rv_late_cur = (unsigned int*) (p->d_rv.get() + 2 * kRvCopy) + vv::ACC_SLOTS * p->cur.parity;
-    q.rv_late_prev = (const unsigned int*) (p->d_rv.get() + 2 * kRvCopy) + vv::ACC_SLOTS * (p->cur.parity ^ 1);
+    q.rv_late_cur = rv_late_row(p->d_rv.get(), p->cur.parity);
+    q.rv_late_prev = rv_late_row(p->d_rv.get(), p->cur.parity ^ 1);
     q.fused_late_shift = p->fused_late_shift;
-    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, p->d_rv.get() + p->cur.parity * kRvCopy, p->stream, t.e0, t.e1, &route, nullptr));
+    HIP_TRY(p, vv::launch_fused(p->hp.precision, q, p->block_threads, rv_words(p->d_rv.get(), p->cur.parity), p->stream, t.e0, t.e1, &route, nullptr));
     p->cur.parity ^= 1;            // the advanced thermostat state now lives in the other copy
     p->fused_launches++;
     *taken = true;

@@ -63,7 +63,21 @@ using vv::kAvogadro;      // vv_host.hpp
 using vv::kBoltz;
 enum TimerClass { T_A = 0, T_B = 1, T_OTHER = 2 };
 constexpr int kAccN = vv::NUM_ACC * vv::ACC_SLOTS;
-constexpr int kRvCopy = 6 * kAccN;      // rendezvous words of one thermostat parity: up to 6 replicas (vv_device.inc: RV_REPLICAS) of [NUM_ACC][ACC_SLOTS]
+// The one-launch step's rendezvous buffer (d_rv), in 8-byte words -- the one statement of its layout on the host:
+//   [2 thermostat parities][kRvRoom replicas][NUM_ACC][ACC_SLOTS]   the blocks' words; vv::RV_REPLICAS of the kRvRoom copies are in use, the rest is slack
+//   [2 parities][ACC_SLOTS] 4-byte words                            "this block polled twice", read by the wait's controller of the step after next
+//   [kRvDeadTail] words                                             the first one = "a rendezvous of this plan has failed" (vv_device.inc: rv_dead_word)
+constexpr int kRvRoom = 6;
+static_assert(vv::RV_REPLICAS <= kRvRoom, "the replicas in use must fit the room of a parity");
+constexpr int kRvCopy = kRvRoom * kAccN;
+constexpr int kRvLateWord = 2 * kRvCopy;
+constexpr int kRvDeadWord = kRvLateWord + 2 * vv::ACC_SLOTS * (int) sizeof(unsigned int) / (int) sizeof(unsigned long long);
+constexpr int kRvDeadTail = 8;
+constexpr int kRvWords = kRvDeadWord + kRvDeadTail;
+static_assert(kRvCopy == 15360 && kRvLateWord == 30720 && kRvDeadWord == 30976 && kRvWords == 30984, "the addresses the compiled kernels see");
+inline unsigned long long* rv_words(unsigned long long* rv, int parity) { return rv + parity * kRvCopy; }
+inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (unsigned int*) (rv + kRvLateWord) + vv::ACC_SLOTS * parity; }
+inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 constexpr int kRiders = 4;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample
@@ -175,7 +189,7 @@ struct vvhip_plan {
     bool rekick = true;            // fused middle step: kick repeated in kernel B instead of a velm store in kernel A (use_rekick)
     // One launch per step (vv_device.inc: "fused step"): kernels A and B of the middle scheme as one launch of co-resident blocks around an
     // in-kernel rendezvous.  `fused` = allowed (vvhip_debug_tune "fused": A/B comparisons and the bit-for-bit tests switch it off);
-    // d_rv = the rendezvous words, [2 thermostat parities][NUM_ACC][ACC_SLOTS], uncached; fused_checks = the pairs of stage sets / launch
+    // d_rv = the rendezvous buffer, uncached (its layout: kRvWords above); fused_checks = the pairs of stage sets / launch
     // shapes whose kernel and occupancy were looked up and what came of it, fused_last = the entry the last attempt used (-1: none since the
     // cache was emptied).
     bool fused = true;

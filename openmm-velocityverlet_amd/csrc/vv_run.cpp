@@ -87,7 +87,7 @@ int recover_rendezvous(vvhip_plan* p, bool on_request) {
     // both accumulator copies are zero between steps; whatever the failed steps left in them goes
     HIP_TRY(p, hipMemsetAsync(p->d_acc.get(), 0, 2 * kAccN * sizeof(unsigned long long), p->stream));
     if (p->d_bigacc) HIP_TRY(p, hipMemsetAsync(p->d_bigacc.get(), 0, (size_t) p->hp.num_big * 4 * sizeof(unsigned long long), p->stream));
-    HIP_TRY(p, hipMemsetAsync(p->d_rv.get() + 2 * kRvCopy + vv::ACC_SLOTS, 0, 8 * sizeof(unsigned long long), p->stream));
+    HIP_TRY(p, hipMemsetAsync(rv_dead_tail(p->d_rv.get()), 0, kRvDeadTail * sizeof(unsigned long long), p->stream));
     // (with the step counter: the riders' schedules follow it, so the repeat writes the failed steps' rows and frames again at the same places
     // and redoes their removals at the same steps; the riders' scratch words are zero between steps whatever the failed steps computed)
     p->cur = r.cur;

@@ -4,8 +4,7 @@ set -u
 R=$GRAFT_REPO_ROOT; T=${1:-r06x}; O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
 # instrumented build (in-kernel stamps) for the timeline / anatomy probes: built here, where the sources are the ones under test
-( cd openmm-velocityverlet_amd/csrc && mkdir -p ../../tools/probes/libs && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function -I/opt/rocm/include \
-    -mllvm -amdgpu-kernarg-preload-count=16 -DVV_KERNEL_TIMESTAMPS -shared -Wl,--version-script=libvvhip.map -o ../../tools/probes/libs/libvvhip_ts.so vv_host.cpp vv_api.cpp vv_launch.cpp vv_steps.cpp vv_observe.cpp vv_run.cpp vv_exchange.cpp vv_debug.cpp vv_rtc.cpp vv_kernels.hip -ldl > $O/ts_build.log 2>&1 ) &
+make -C openmm-velocityverlet_amd/csrc instrumented > $O/ts_build.log 2>&1 &
 TS=$!
 timeout 900 python tools/probes/fused_ab.py C3,C4,C5,C2,C1,C3hb,C5hb,C2hb 3 > $O/fused_ab_all_configs.txt 2>&1
 # this round's kernels against the previous round's on this very box (tools/probes/build_round_lib.sh e195552 r05, in the build container)
