@@ -524,6 +524,95 @@ int vvhip_profile_info(const vvhip_plan* plan, vvhip_profile_layout* out);
  * included, the calls since are repeated with two launches per step -- without any rendezvous having failed.  VVHIP_ERR_INVALID without a
  * snapshot. */
 int vvhip_debug_recover(vvhip_plan* plan);
+/* ---------------------------------------------------------------- mean-squared displacements accumulated on the device
+ * What run-bulk.py and run-edl.py add GroReporter('dump.gro', 1000, logarithm=True, ...) for: the mean-squared displacement over many
+ * decades of lag time, whose slope gives the ions' diffusion coefficients.  A stand-alone host would get it from trajectory frames, 24 B
+ * per particle and sample, and O(samples^2 N) work on the host, the frame ring's capacity bounding the statistics; an accumulating table is
+ * a few KB however long the run.  After every full step whose count is a multiple of `interval` -- counted exactly as for the series, the
+ * frames and the profiles, by the same entry points (the split per-KernelImpl entry points take none); a sample "after step k" is enqueued
+ * behind that step's profile sample -- the step entry point enqueues one accumulating kernel (csrc/vv_dev_msd.inc) and a one-thread kernel
+ * that advances the sample ordinal: two launches, no memset, no host work.  Inside a captured graph both are part of the graph and the steps
+ * that take a sample are part of the graph-cache key.  The recorder reads posq and posqCorrection and writes its own words, nothing else; a
+ * plan that never starts one launches what it launched before and allocates nothing.
+ * Units.
+ *   VVHIP_MSD_PARTICLES  every recorded particle is a unit.  Its position is X_i in float64, exactly as a float64 frame defines it:
+ *                        (double) posq + (double) posqCorrection in mixed precision, (double) posq otherwise; positions are stored unwrapped.
+ *   VVHIP_MSD_MOLECULES  a unit is a molecule of vvhip_system_desc.mol_id, restricted to its particles with mass > 0.  Its position is the
+ *                        centre of mass in float64 without contraction:  s = 0; for i in ascending particle index: s = s + m_i * X_i;
+ *                        c = s / M,  M summed on the host in the same order.  The order of this sum is part of the definition (the
+ *                        parallelisation over units is free, the order inside one is not).  The group of a molecule is the group of its
+ *                        massive particles; mixed groups inside one molecule are refused; a molecule with group -1, or without mass, is not
+ *                        recorded.  A shard that holds some but not all massive particles of a molecule gives VVHIP_ERR_UNSUPPORTED, as the
+ *                        barostat and the Drude report do.
+ * Schedule.  Sample ordinal j = 0, 1, ... counts the due steps since the start or the last reset.  Every sample whose ordinal is a multiple
+ * of origin_every (E) is also stored as an origin, in slot (j / E) mod num_origins of a device ring; num_origins = ceil(num_lags / E) is
+ * derived, not chosen.  Row l (0 <= l < num_lags) is the lag of (l + 1) * interval steps.  At sample j every origin k E contributes to row
+ * l = j - k E - 1 provided  origin_floor <= k E < j,  j - k E <= num_lags,  and the unit was not out of range.  Accumulation comes first,
+ * the store second: when num_origins * E == num_lags the slot that is overwritten was read in the same sample.
+ * Terms.  Delta_a = c_a(now) - c_a(origin) in float64, a = x, y, z.  Each of Delta_x^2, Delta_y^2, Delta_z^2 is added as the integer
+ * llrint(Delta_a * Delta_a * 2^frac_bits), round-half-even; the pair count as the integer 1.  A unit with any Delta_a that is NaN or has
+ * |Delta_a| >= limit is left out of all four words for that pair and adds 1 to out_of_range.  limit is in nm, rounded up to a power of two;
+ * 0 takes the default of 64.
+ * Table: int64 table[num_groups][num_lags][4], the four words being pairs, sum Delta_x^2, sum Delta_y^2, sum Delta_z^2.
+ * frac_bits = min(40, 62 - ceil_log2(U + 1) - ceil_log2(ceil(max_samples / E) + 1) - 2 log2(limit)), so that no word can overflow within
+ * max_samples samples; U is the number of recorded units of the WHOLE System in that mode (on an unsharded plan: num_units): a sharded plan
+ * records the units of its own shard, every shard scales alike, and the shards' tables add as integers to the unsharded table.  Past
+ * max_samples a sample adds nothing, stores no origin and counts as dropped.  Integer adds commute: the table is the same bits for any
+ * grid, block size, unit order or shard split.
+ * What rewrites positions outside the steps.  vvhip_barostat_scale and vvhip_barostat_restore, with a recorder running, set origin_floor to
+ * the current sample ordinal (one one-thread kernel in the stream): older origins are dead, the table is kept.  vvhip_checkpoint_load is
+ * refused while a recorder runs.  Host uploads into the bound arrays (vvhip_memcpy_h2d into posq, a re-bind to other arrays) are NOT
+ * detected: the next samples measure against origins of the positions that were there before; stop the recorder and start it again.
+ * Recovery.  Neither the table nor the ring is idempotent under the repeat of failed steps -- an origin overwritten inside the failed
+ * window is needed again by the repeat -- so the rider's recovery words are the WHOLE allocation: counts, floor, table and origin ring,
+ * (4 + words) * 8 B + ring_bytes with ring_bytes = num_origins x 3 x stride x 8 B, stride = num_units rounded up to 16. */
+#define VVHIP_MSD_PARTICLES 0
+#define VVHIP_MSD_MOLECULES 1
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096: row l is the lag of (l + 1) * interval steps */
+    int32_t origin_every;           /* E, 1 .. num_lags: every E-th sample is stored as an origin */
+    int32_t mode;                   /* VVHIP_MSD_PARTICLES, VVHIP_MSD_MOLECULES */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t reserved;               /* 0 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: not recorded; NULL: everything in group 0 */
+    int64_t max_samples;            /* >= 1 */
+    double limit;                   /* nm: a displacement component at or beyond it is out of range; rounded up to a power of two; 0: 64 */
+} vvhip_msd_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset (at most max_samples): the next sample's ordinal */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added or stored for them */
+    int64_t out_of_range;           /* unit-pairs left out of all four words */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+} vvhip_msd_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, mode, num_groups;
+    int32_t num_units;              /* units this plan records (particles: group >= 0 within [shard_begin, shard_end)) */
+    int32_t num_origins;            /* ceil(num_lags / origin_every) */
+    int32_t frac_bits, reserved;    /* value = word * 2^-frac_bits (pairs: the word itself) */
+    int64_t max_samples;
+    int64_t words;                  /* num_groups * num_lags * 4 */
+    int64_t ring_bytes;             /* num_origins * 3 * stride * 8 */
+    int64_t start_step;             /* the plan's step count at vvhip_msd_start */
+    double limit;                   /* as applied */
+} vvhip_msd_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order:
+ * interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, an unknown mode, num_groups outside 1 .. 16, max_samples
+ * < 1, a limit that is negative or not finite, a group entry outside -1 .. num_groups - 1 (VVHIP_ERR_INVALID naming the argument); in
+ * molecule mode a molecule whose massive particles lie in different groups (VVHIP_ERR_INVALID naming it); frac_bits below 8; num_origins
+ * above 1024 (VVHIP_ERR_INVALID); in molecule mode a shard that cuts a molecule (VVHIP_ERR_UNSUPPORTED); an unbound plan; inside a graph
+ * capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes the checks in
+ * front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_msd_info answers for it, for sizing. */
+int vvhip_msd_start(vvhip_plan* plan, const vvhip_msd_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the ordinal at 0 with no
+ * live origin: the step schedule continues without gap or repeat. */
+int vvhip_msd_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_msd_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and ring are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_msd_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_msd_info(const vvhip_plan* plan, vvhip_msd_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

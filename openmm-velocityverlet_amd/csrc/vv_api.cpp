@@ -109,6 +109,8 @@ int vvhip_debug_tune(vvhip_plan* p, const char* key, int value) {
     else if (k == "grid_cap_a") { if (value < 1) return VVHIP_ERR_INVALID; p->grid_cap_a = value; p->launch_shape_forced = true; }
     else if (k == "grid_cap_b") { if (value < 1) return VVHIP_ERR_INVALID; p->grid_cap_b = value; p->launch_shape_forced = true; }
     else if (k == "profile_grid_cap") { if (value < 1) return VVHIP_ERR_INVALID; p->profile_grid_cap = value; }      // (no launch shape of the step: nothing forced)
+    else if (k == "msd_block_threads") { if (value != 0 && (value < 64 || value > 512 || value % 64)) return VVHIP_ERR_INVALID; p->msd_block_threads = value; }
+    else if (k == "msd_wave_reduce") { if (value < 0 || value > 1) return VVHIP_ERR_INVALID; p->msd_wave_reduce = value; }
     else return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_tune: unknown key " + k);
     if (k == "mass_tab_a" || k == "mass_tab_b") p->mass_tab_valid = false;
     drop_graphs(p);

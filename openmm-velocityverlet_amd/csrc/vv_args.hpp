@@ -370,4 +370,26 @@ struct ProfileArgs {
     double scale[4], limit[4];      // 2^frac_bits and the limit of charge, mass, momentum, kinetic
 };
 
+// MSD sample (vv_dev_msd.inc, include/vvhip.h: vvhip_msd_* states the units, the schedule and the terms).  The sample ordinal and the
+// origin floor are read from the device-side words, so a replayed graph (same arguments every time) finds the origins where the last
+// sample left them and stops adding at max_samples.
+enum { MSD_SAMPLES = 0, MSD_DROPPED = 1, MSD_OUT_OF_RANGE = 2, MSD_FLOOR = 3, MSD_HEAD = 4 };      // the words in front of the table
+struct MsdArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // particles: [n] shard-relative index of unit u, null: unit u is particle u.  Molecules: the member lists
+    const int32_t* first;           // molecules: [n + 1] unit u's members are index[first[u]] .. index[first[u + 1] - 1], ascending
+    const double* weight;           // molecules: the mass of every member, beside index
+    const double* total;            // molecules: [n] M, the members' masses summed in their order
+    const unsigned char* group;     // [n] group of unit u (GROUPED kernels only)
+    long long* words;               // [MSD_HEAD + table_words]: samples, dropped, out_of_range, origin floor, then table[group][lag][4]
+    double* ring;                   // [num_origins][3][stride] the origins' positions, behind the table in the same allocation
+    int64_t max_samples;
+    int32_t n, stride;              // recorded units; n rounded up to 16
+    int32_t num_lags, origin_every;
+    int32_t num_origins, table_words;      // ceil(num_lags / origin_every); num_groups * num_lags * 4
+    int32_t wave_reduce, pad_;      // 1: a wave whose lanes share a group adds its four sums once
+    double scale, limit;            // 2^frac_bits; |delta| at or beyond it is out of range
+};
+
 }  // namespace vv

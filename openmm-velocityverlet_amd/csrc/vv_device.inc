@@ -19,3 +19,4 @@
 #include "vv_dev_digest.inc"
 #include "vv_dev_frames.inc"
 #include "vv_dev_profile.inc"
+#include "vv_dev_msd.inc"

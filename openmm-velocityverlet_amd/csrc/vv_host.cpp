@@ -1141,6 +1141,7 @@ HostPlan analyze(const vvhip_system_desc& sys, const vvhip_params& params_in, in
     if (shard.begin < 0 || shard.end > sys.num_atoms || shard.begin >= shard.end) throw Error(VVHIP_ERR_INVALID, "bad particle shard range");
     hp.shard_begin = shard.begin; hp.shard_end = shard.end;
     hp.masses.assign(sys.masses, sys.masses + sys.num_atoms);
+    hp.mol_id.assign(sys.mol_id, sys.mol_id + sys.num_atoms);
     const ConstraintPlan cons = classify_constraints(sys);
     const SitePlan sites = plan_sites(sys, top);
     const Model model{sys, top, cons, sites};

@@ -112,6 +112,7 @@ struct HostPlan {
     std::string baro_unsupported;              // why this plan cannot scale (a shard that cuts a molecule); empty otherwise
     // reference-style tables, kept for inspection / tests (global particle indices)
     std::vector<int32_t> particles_nh, molecules_nh, normal_nh, pairs_nh, normal_ld, pairs_ld;
+    std::vector<int32_t> mol_id;               // [num_atoms] the System's molecule of every particle (vvhip_msd_*: the molecule units are built at the start)
 };
 
 // Throws vv::Error.  `sys` pointers are only read during the call.

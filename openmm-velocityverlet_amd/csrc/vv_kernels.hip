@@ -474,6 +474,27 @@ hipError_t launch_profile(int precision, const ProfileArgs& a, int grid_cap, hip
     hipLaunchKernelGGL(vv_kernel_profile_advance, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
+template <bool MOLECULES, bool GROUPED>
+static auto pick_msd(int precision, bool lds) {
+    return lds ? VV_PICK(precision, vv_kernel_msd, MOLECULES, GROUPED, true) : VV_PICK(precision, vv_kernel_msd, MOLECULES, GROUPED, false);
+}
+hipError_t launch_msd(int precision, const MsdArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    const dim3 g((unsigned) std::max(1, std::min((a.n + block_threads - 1) / block_threads, std::max(1, grid_cap))));
+    const size_t table_bytes = (size_t) a.table_words * sizeof(long long);
+    const bool lds = table_bytes <= PROFILE_LDS_BYTES;
+    const auto k = a.first ? (a.group ? pick_msd<true, true>(precision, lds) : pick_msd<true, false>(precision, lds))
+                           : (a.group ? pick_msd<false, true>(precision, lds) : pick_msd<false, false>(precision, lds));
+    hipLaunchKernelGGL(k, g, dim3((unsigned) block_threads), lds ? (unsigned) table_bytes : 0u, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_msd_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_msd_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_msd_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

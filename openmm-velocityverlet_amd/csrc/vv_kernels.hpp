@@ -71,5 +71,11 @@ hipError_t launch_frame(int precision, const FrameArgs& a, bool float64, int gri
 // most PROFILE_LDS_BYTES is accumulated per block in LDS first, a larger one by global atomics directly; a.group selects the grouped kernels.
 constexpr size_t PROFILE_LDS_BYTES = 64 * 1024;
 hipError_t launch_profile(int precision, const ProfileArgs& a, int grid_cap, hipStream_t s);
+// One MSD sample (vv_dev_msd.inc): the accumulating kernel over a.n units in blocks of block_threads threads (64 .. 512, a multiple of
+// 64), at most grid_cap of them (the kernel strides beyond; one idle block where a.n = 0), then the one-thread kernel that counts the sample.  A table of at most PROFILE_LDS_BYTES is
+// accumulated per block in LDS first, a larger one by global atomics directly; a.first selects the molecule kernels, a.group the grouped ones.
+hipError_t launch_msd(int precision, const MsdArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as MsdArgs::words.
+hipError_t launch_msd_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

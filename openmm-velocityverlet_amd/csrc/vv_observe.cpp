@@ -1,5 +1,5 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, profiles, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
+// the series of its rows, trajectory frames, profiles, mean-squared displacements, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
 // ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
 #include "vv_plan.hpp"
 
@@ -81,6 +81,37 @@ static int profile_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_profile(p->hp.precision, a, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ mean-squared displacements (vvhip_msd_*)
+// One sample behind the step just enqueued (or captured), and behind its profile sample: the accumulating kernel and the one-thread kernel
+// that advances the ordinal.  Two launches, no memset and no host synchronisation.
+static int msd_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Msd& M = p->msd;
+    const vvhip_msd_layout& L = M.lay;
+    vv::MsdArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    const bool molecules = L.mode == VVHIP_MSD_MOLECULES;
+    a.index = M.index.empty() ? nullptr : M.d_index.get();
+    a.first = molecules ? M.d_first.get() : nullptr; a.weight = molecules ? M.d_weight.get() : nullptr; a.total = molecules ? M.d_total.get() : nullptr;
+    a.group = M.grouped ? M.d_group.get() : nullptr;
+    a.words = M.d_words.get(); a.ring = (double*) (M.d_words.get() + vv::MSD_HEAD + L.words);
+    a.max_samples = L.max_samples;
+    a.n = L.num_units; a.stride = M.stride(); a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
+    a.table_words = (int32_t) L.words; a.wave_reduce = p->msd_wave_reduce;
+    a.scale = std::ldexp(1.0, L.frac_bits); a.limit = L.limit;
+    // blocks of 512 threads where they still make 128 blocks, else the largest of 256, 128, 64 that does (64 at the least): few units in
+    // few blocks leave their gathers to a handful of CUs (TUNING_LOG.md)
+    int threads = p->msd_block_threads;
+    if (threads == 0)
+        for (threads = 512; threads > 64 && (a.n + threads - 1) / threads < 128; threads /= 2) {}
+    HIP_TRY(p, vv::launch_msd(p->hp.precision, a, threads, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    return VVHIP_OK;
+}
+// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
+int msd_positions_rewritten(vvhip_plan* p) {
+    if (!p->msd.on) return VVHIP_OK;
+    HIP_TRY(p, vv::launch_msd_floor(p->msd.d_words.get(), p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -117,14 +148,15 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 }
 // ------------------------------------------------------------------------------------------ the step's scheduled riders
 // In this order everywhere (item k of GraphKey::due, of Recovery::late): behind a step the series' row goes first, then the frame, then the
-// profile sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
+// profile sample, then the MSD sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
 // (one-off calls allocate it too), and of a profile the WHOLE allocation, counts and table: a row or a frame written twice is the same row
-// or frame, a sample added twice is not the same table.
+// or frame, a sample added twice is not the same table.  Of an MSD recorder likewise the whole allocation, the ring of origins included.
 Riders riders(vvhip_plan* p) {
     return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
-             {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue}}};
+             {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue},
+             {p->msd.on, p->msd.when, false, p->msd.on ? p->msd.d_words.get() : nullptr, p->msd.bytes(), msd_enqueue}}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -141,6 +173,7 @@ int step_done(vvhip_plan* p) {
 static void series_release(vvhip_plan* p) { p->series = vvhip_plan::Series{}; }
 static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
 static void profile_release(vvhip_plan* p) { p->profile = vvhip_plan::Profile{}; }
+static void msd_release(vvhip_plan* p) { p->msd = vvhip_plan::Msd{}; }
 // frexp's view of a positive finite x: the smallest power of two >= x / > x, and the exponent of a power of two
 static double pow2_at_least(double x) { int e; const double f = std::frexp(x, &e); return f == 0.5 ? x : std::ldexp(1.0, e); }
 static double pow2_above(double x) { int e; (void) std::frexp(x, &e); return std::ldexp(1.0, e); }
@@ -583,6 +616,151 @@ int vvhip_profile_info(const vvhip_plan* p, vvhip_profile_layout* out) {
     vvhip_profile_layout r{};
     for (int q = 0; q < VVHIP_PROFILE_QUANTITIES; q++) r.row_of[q] = -1;
     if (p->profile.described) { r = p->profile.lay; r.active = p->profile.on; }
+    *out = r;
+    return VVHIP_OK;
+}
+
+int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "msd: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "msd: interval must be >= 1 step");
+    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "msd: num_lags must be in [1, 4096]");
+    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "msd: origin_every must be in [1, num_lags]");
+    if (d->mode != VVHIP_MSD_PARTICLES && d->mode != VVHIP_MSD_MOLECULES) return fail(p, VVHIP_ERR_INVALID, "msd: mode must be VVHIP_MSD_PARTICLES or VVHIP_MSD_MOLECULES");
+    if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "msd: num_groups must be in [1, 16]");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "msd: max_samples must be >= 1");
+    if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "msd: limit must be finite and >= 0 (0: the default of 64 nm)");
+    const vv::HostPlan& hp = p->hp;
+    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
+        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
+            return fail(p, VVHIP_ERR_INVALID, "msd: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    // ---- the units this plan records, the layout and the fixed point, host only
+    vvhip_plan::Msd N;
+    vvhip_msd_layout& L = N.lay;
+    N.grouped = d->group != nullptr;
+    const bool molecules = d->mode == VVHIP_MSD_MOLECULES;
+    auto group_of = [&](int32_t i) { return d->group ? (int) d->group[i] : 0; };
+    auto in_shard = [&](int32_t i) { return i >= hp.shard_begin && i < hp.shard_end; };
+    struct Unit { int group; int32_t id; };      // id: the particle, or the molecule
+    std::vector<Unit> units;                      // of this plan
+    long long described = 0;                      // U: the units the DESCRIPTION records, of the whole System
+    std::vector<std::vector<int32_t>> members;    // molecules: per molecule id its massive particles, ascending
+    bool cut = false;
+    if (!molecules) {
+        for (int32_t i = 0; i < hp.num_atoms; i++) {
+            if (group_of(i) < 0) continue;
+            described++;
+            if (in_shard(i)) units.push_back({group_of(i), i});
+        }
+    } else {
+        int32_t nmol = 0;
+        for (int32_t i = 0; i < hp.num_atoms; i++) nmol = std::max(nmol, hp.mol_id[(size_t) i] + 1);
+        members.resize((size_t) nmol);
+        for (int32_t i = 0; i < hp.num_atoms; i++)
+            if (hp.masses[(size_t) i] > 0) members[(size_t) hp.mol_id[(size_t) i]].push_back(i);
+        for (int32_t m = 0; m < nmol; m++) {
+            const std::vector<int32_t>& mem = members[(size_t) m];
+            if (mem.empty()) continue;
+            int here = 0;
+            for (int32_t i : mem) {
+                here += in_shard(i);
+                if (group_of(i) != group_of(mem[0]))
+                    return fail(p, VVHIP_ERR_INVALID, "msd: molecule " + std::to_string(m) + " has massive particles in different groups (particle " + std::to_string(mem[0]) + ": " +
+                                                      std::to_string(group_of(mem[0])) + ", particle " + std::to_string(i) + ": " + std::to_string(group_of(i)) + ")");
+            }
+            cut = cut || (here != 0 && here != (int) mem.size());
+            if (group_of(mem[0]) < 0) continue;
+            described++;
+            if (here == (int) mem.size()) units.push_back({group_of(mem[0]), m});
+        }
+    }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.mode = d->mode; L.num_groups = d->num_groups;
+    L.max_samples = d->max_samples;
+    L.num_units = (int32_t) units.size();
+    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.words = (int64_t) L.num_groups * L.num_lags * 4;
+    L.limit = d->limit > 0 ? pow2_at_least(d->limit) : 64.0;
+    L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
+    const long long max_origins = (L.max_samples < (1ll << 62) ? L.max_samples + L.origin_every - 1 : (1ll << 62)) / L.origin_every;
+    L.frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(L.limit));
+    if (L.frac_bits < 8)
+        return fail(p, VVHIP_ERR_INVALID, "msd: the sums would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
+                                          std::to_string((long long) L.max_samples) + ", origin_every = " + std::to_string(L.origin_every) + " and limit " + std::to_string(L.limit) +
+                                          ": lower max_samples or the limit");
+    if (L.num_origins > 1024)
+        return fail(p, VVHIP_ERR_INVALID, "msd: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
+    if (molecules && cut)
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "msd: the particle shard cuts a molecule: its centre of mass needs particles of another shard");
+    for (const Unit& u : units) {
+        if (N.grouped) N.group.push_back((unsigned char) u.group);
+        if (!molecules) { N.index.push_back(u.id - hp.shard_begin); continue; }
+        N.first.push_back((int32_t) N.index.size());
+        double M = 0;
+        for (int32_t i : members[(size_t) u.id]) {
+            N.index.push_back(i - hp.shard_begin); N.weight.push_back(hp.masses[(size_t) i]);
+            M = M + hp.masses[(size_t) i];
+        }
+        N.total.push_back(M);
+    }
+    if (molecules) N.first.push_back((int32_t) N.index.size());
+    if (!molecules && !N.grouped && L.num_units == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
+    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
+    if (p->capturing || p->msd.on) TRY(quiesce(p, "msd", true, true));
+    msd_release(p);
+    vvhip_plan::Msd& M = p->msd;
+    M = std::move(N);
+    M.when = {d->interval, SCHEDULE_LINEAR};
+    M.lay.start_step = p->cur.step_count;
+    M.described = true;
+    NEED_BOUND(p);
+    TRY(quiesce(p, "msd", true, true));
+    auto alloc_fail = [&](hipError_t e, size_t bytes) {
+        M.d_words.reset(); M.d_index.reset(); M.d_first.reset(); M.d_weight.reset(); M.d_total.reset(); M.d_group.reset();
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string("msd: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
+    };
+    hipError_t e = vv::zeros(M.d_words, M.bytes(), p->stream);
+    if (e != hipSuccess) return alloc_fail(e, M.bytes());
+    if (!M.index.empty() && (e = vv::upload(M.d_index, M.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.index.size() * sizeof(int32_t)));
+    if (molecules) {
+        if ((e = vv::upload(M.d_first, M.first, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.first.size() * sizeof(int32_t)));
+        if ((e = vv::upload(M.d_weight, M.weight, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.weight.size() * sizeof(double)));
+        if ((e = vv::upload(M.d_total, M.total, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.total.size() * sizeof(double)));
+    }
+    if (M.grouped && (e = vv::upload(M.d_group, M.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.group.size()));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    M.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
+    M.on = true;
+    return VVHIP_OK;
+}
+int vvhip_msd_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_msd_counts* out, int32_t reset) {
+    NEED_BOUND(p);
+    vvhip_plan::Msd& M = p->msd;
+    if (!M.on) return fail(p, VVHIP_ERR_INVALID, "msd: none started (vvhip_msd_start)");
+    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < M.lay.words))
+        return fail(p, VVHIP_ERR_INVALID, "msd: the table has " + std::to_string((long long) M.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
+    TRY(quiesce(p, "msd", true, false));
+    long long head[vv::MSD_HEAD];
+    HIP_TRY(p, hipMemcpy(head, M.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
+    if (words_out) HIP_TRY(p, hipMemcpy(words_out, M.d_words.get() + vv::MSD_HEAD, (size_t) M.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out) *out = {head[vv::MSD_SAMPLES], head[vv::MSD_DROPPED], head[vv::MSD_OUT_OF_RANGE], head[vv::MSD_FLOOR]};
+    if (reset) {      // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
+        HIP_TRY(p, hipMemsetAsync(M.d_words.get(), 0, (size_t) (vv::MSD_HEAD + M.lay.words) * sizeof(long long), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+    }
+    return VVHIP_OK;
+}
+int vvhip_msd_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing || p->msd.on) TRY(quiesce(p, "msd", true, true));
+    msd_release(p);                                     // (also the description an unbound plan kept)
+    return VVHIP_OK;
+}
+int vvhip_msd_info(const vvhip_plan* p, vvhip_msd_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_msd_layout r{};
+    if (p->msd.described) { r = p->msd.lay; r.active = p->msd.on; }
     *out = r;
     return VVHIP_OK;
 }

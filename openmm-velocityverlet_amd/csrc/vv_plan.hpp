@@ -80,7 +80,7 @@ inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (u
 inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
-constexpr int kRiders = 4;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample
+constexpr int kRiders = 5;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -148,6 +148,8 @@ struct vvhip_plan {
     int block_threads = 256;       // 64 x tile waves per block, the same for the force provider, kernel A and kernel B
     int grid_cap_a = 2048, grid_cap_b = 1024;   // most blocks per launch (multiples of the CU count): see pick_launch_shape
     int profile_grid_cap = 256;    // most blocks of a profile sample's accumulating kernel, besides grid_cap_a: every block flushes a table of its own (test hook "profile_grid_cap"; TUNING_LOG.md)
+    int msd_block_threads = 0;     // threads per block of an MSD sample's accumulating kernel, 0: by the number of units (msd_enqueue; test hook "msd_block_threads")
+    int msd_wave_reduce = 1;       // an MSD sample's waves whose units share a group add their four sums once (test hook "msd_wave_reduce": 0 = every lane adds; same bits)
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
                                      // 1.33 M 14.5 | 14.0 k, 1.78 M 11.4 | 11.1 k, 2.66 M 7.38 | 7.37 k, 4.4 M 4.14 | 4.20 k, 8.9 M 2.16 | 2.21 k (round 2 had it at 12 288)
@@ -352,6 +354,23 @@ struct vvhip_plan {
         vv::DevBuf<long long> d_words;            // [PROFILE_HEAD + lay.words]: counts, then the table -- ALL of it the rider's late words
         size_t bytes() const { return (size_t) (vv::PROFILE_HEAD + lay.words) * sizeof(long long); }
     } profile;
+    // Mean-squared displacements (vvhip_msd_*; vv_dev_msd.inc), scheduled by cur.step_count.  `described` / `on` as for the profiles.  The
+    // unit tables are built from the plan's molecules when the recorder starts: units ordered by group, then by particle / molecule index
+    struct Msd {
+        bool on = false, described = false, grouped = false;
+        Schedule when;                            // (linear)
+        vvhip_msd_layout lay{};
+        std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending
+        std::vector<int32_t> first;               // molecules: [num_units + 1] offsets into index / weight
+        std::vector<double> weight, total;        // molecules: the members' masses; [num_units] their sums M in the members' order
+        std::vector<unsigned char> group;         // [num_units] (grouped)
+        vv::DevBuf<int32_t> d_index, d_first;
+        vv::DevBuf<double> d_weight, d_total;
+        vv::DevBuf<unsigned char> d_group;
+        vv::DevBuf<long long> d_words;            // [MSD_HEAD + lay.words] counts, floor and table, then the ring -- ALL of it the rider's late words
+        int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
+        size_t bytes() const { return (size_t) (vv::MSD_HEAD + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
+    } msd;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -482,6 +501,7 @@ int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_ind
 int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
+int msd_positions_rewritten(vvhip_plan* p);      // vvhip_barostat_scale / _restore: an MSD recorder's origins so far are dead
 // One of the device work items that hang on the plan's step counter.  A new one is a descriptor in riders() with its enqueue function and its
 // entry points: the step hooks, the graph keys (vv_run.cpp) and the recovery (recovery_items) walk the list.
 struct Rider {
@@ -501,6 +521,7 @@ Riders riders(vvhip_plan* p);
 // (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not carry them).  For a series and a
 // frame recorder these are the cursors: the repeat writes the same rows and frames at the same places.  For a profile recorder they are the
 // whole allocation, counts and table: an accumulating table is not idempotent under the repeat, so it goes back as the snapshot took it.
+// For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

@@ -173,6 +173,19 @@ def profile_sum(profiles):
     return dataclasses.replace(first, words=words, out_of_range=sum(p.out_of_range for p in profiles), **profile_views(words, first.row_of, first.frac_bits))
 
 
+def msd_sum(msds):
+    """The MSD table of a sharded run from its shards' tables (Context.msd_read of every shard, the same description and the same steps
+    behind each): the words added as int64 -- integer sums are associative, so the result is the unsharded table bit for bit -- and
+    out_of_range added; samples, dropped and the origin floor are the same on every shard."""
+    import dataclasses
+    first = msds[0]
+    key = lambda m: (m.words.shape, m.frac_bits, m.interval, m.origin_every, m.molecules, m.samples, m.dropped, m.origin_floor)
+    for m in msds[1:]:
+        if key(m) != key(first):
+            raise ValueError("the MSD tables differ in layout, fixed point, schedule or number of samples: not shards of one run")
+    return dataclasses.replace(first, words=np.sum([m.words for m in msds], axis=0, dtype=np.int64), out_of_range=sum(m.out_of_range for m in msds))
+
+
 def drude_temperature_series(ctx, group=None, reset=False):
     """A sharded run's series (Context.series_read): every rank's raw rows -- six fixed-point sums and the overflow flag per row, of its
     own particles -- summed over the process group in one all-reduce, then turned into KE / T with the whole system's DOFs.  Every rank

@@ -346,6 +346,65 @@ def profile_views(words, row_of, frac_bits) -> dict:
     return dict(count=view(0), charge=view(1), mass=view(2), momentum=view(3, 3), kinetic=view(4))
 
 
+@dataclasses.dataclass
+class Msd:
+    """Mean-squared displacements per group and lag (Context.msd_read; include/vvhip.h: vvhip_msd_* states the units, the schedule and the
+    terms).  `words` is the device's table as it stands, int64 [groups, lags, 4]: pairs, then the sums of dx^2, dy^2, dz^2 scaled by
+    2^frac_bits."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples: nothing was added or stored for them
+    out_of_range: int                      # unit-pairs left out (a displacement component NaN or at / beyond the limit)
+    origin_floor: int                      # origins with an ordinal below it are dead (a barostat move rewrote the positions)
+    interval: int
+    origin_every: int
+    frac_bits: int
+    molecules: bool
+    words: np.ndarray                      # int64 [groups, lags, 4]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [lags]: row l is the lag of (l + 1) * interval steps."""
+        return (np.arange(self.words.shape[1], dtype=np.int64) + 1) * self.interval
+
+    @property
+    def pairs(self) -> np.ndarray:
+        """int64 [groups, lags]: unit-pairs behind every row."""
+        return self.words[:, :, 0]
+
+    @property
+    def msd(self) -> np.ndarray:
+        """float64 [groups, lags, 3]: <dx^2>, <dy^2>, <dz^2> in nm^2 = word * 2^-frac_bits / pairs, NaN where a row has no pairs."""
+        n = self.pairs[:, :, None]
+        sums = self.words[:, :, 1:].astype(np.float64) * 2.0 ** -self.frac_bits
+        return np.where(n > 0, sums / np.where(n > 0, n, 1), np.nan)
+
+    @property
+    def total(self) -> np.ndarray:
+        """float64 [groups, lags]: <|dr|^2> in nm^2."""
+        return self.msd.sum(axis=2)
+
+    def diffusion(self, dt: float, first_lag: int, last_lag: int, axes=(0, 1, 2)) -> np.ndarray:
+        """float64 [groups]: the diffusion coefficient in nm^2/ps from rows first_lag .. last_lag (inclusive): the least-squares slope of
+        the MSD summed over `axes` against the lag time (lag_steps * dt, dt in ps), divided by 2 * len(axes)."""
+        axes = tuple(axes)
+        rows = slice(int(first_lag), int(last_lag) + 1)
+        t = self.lag_steps[rows].astype(np.float64) * float(dt)
+        if t.size < 2:
+            raise ValueError("a slope needs at least two lags")
+        y = self.msd[:, rows, :][:, :, list(axes)].sum(axis=2)
+        tc = t - t.mean()
+        slope = ((y - y.mean(axis=1, keepdims=True)) * tc).sum(axis=1) / (tc * tc).sum()
+        return slope / (2.0 * len(axes))
+
+
+def msd_from_words(words, layout, counts) -> Msd:
+    """An Msd from a table's int64 words [groups * lags * 4], its layout (H.MsdLayout) and counts (H.MsdCounts)."""
+    words = np.ascontiguousarray(words, dtype=np.int64).reshape(layout.num_groups, layout.num_lags, 4)
+    return Msd(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range),
+               origin_floor=int(counts.origin_floor), interval=int(layout.interval), origin_every=int(layout.origin_every),
+               frac_bits=int(layout.frac_bits), molecules=layout.mode == H.MSD_MOLECULES, words=words)
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -649,6 +708,43 @@ class Context:
         H.check(H.lib.vvhip_profile_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
         return profile_from_words(words[: info.words], info, counts, self._box)
 
+    # ---- mean-squared displacements accumulated on the device inside the steps (include/vvhip.h: vvhip_msd_*)
+    def msd_start(self, interval: int, num_lags: int, origin_every: int = 1, molecules: bool = False, groups=None,
+                  max_samples: int = 1 << 20, limit: float = 0.0):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), measure every recorded unit -- a
+        particle, or with molecules=True a molecule's centre of mass -- against the stored origins and add, per group and lag of 1 ..
+        `num_lags` samples, the pair count and dx^2, dy^2, dz^2 as fixed-point integers, so that the table is the same bits for any launch
+        shape or shard split.  Every `origin_every`-th sample is stored as an origin.  `groups`: one int per particle of the System (-1:
+        not recorded), each group a table of its own; None: everything in group 0.  `limit` (nm, 0: 64): a displacement component at or
+        beyond it leaves the pair out and counts in out_of_range.  At most `max_samples` samples are taken (the fixed point is sized for
+        them).  No host synchronisation until msd_read."""
+        grp = None
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+            if grp.size != self.system.num_atoms:
+                raise ValueError("groups must have one entry per particle of the System")
+        desc = H.MsdDesc(int(interval), int(num_lags), int(origin_every), H.MSD_MOLECULES if molecules else H.MSD_PARTICLES,
+                         1 if grp is None else max(int(grp.max()) + 1, 1), 0, None if grp is None else grp.ctypes.data, int(max_samples),
+                         float(limit))
+        H.check(H.lib.vvhip_msd_start(self.plan, C.byref(desc)), self.plan)
+
+    def msd_stop(self):
+        H.check(H.lib.vvhip_msd_stop(self.plan), self.plan)
+
+    def msd_info(self) -> H.MsdLayout:
+        out = H.MsdLayout()
+        H.check(H.lib.vvhip_msd_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def msd_read(self, reset: bool = False) -> Msd:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        info = self.msd_info()
+        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
+        counts = H.MsdCounts()
+        H.check(H.lib.vvhip_msd_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
+        return msd_from_words(words[: info.words], info, counts)
+
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
         """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
@@ -721,7 +817,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame or profile recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile or MSD recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

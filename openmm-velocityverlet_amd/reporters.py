@@ -18,6 +18,8 @@ latest three kept.
 
 ``write_profile`` writes a device-side density / velocity profile (``Context.profile_read``) as text columns, one line per bin.
 
+``write_msd`` writes a device-side mean-squared displacement table (``Context.msd_read``) as text columns, one line per lag.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -205,6 +207,36 @@ def write_profile(file, profile, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for b in range(len(profile.edges) - 1):
             print(*[repr(float(v[b])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def msd_columns(msd, dt):
+    """[(name, values per lag)] of an MSD's text file: the lag in ps, then per group the pairs, the total and x | y | z in nm^2."""
+    cols = [("lag (ps)", msd.lag_steps.astype(np.float64) * float(dt))]
+    values, total = msd.msd, msd.total
+    for g in range(msd.words.shape[0]):
+        cols.append(("pairs[%d]" % g, msd.pairs[g].astype(np.float64)))
+        cols.append(("msd[%d] (nm^2)" % g, total[g]))
+        cols += [("msd_%s[%d] (nm^2)" % ("xyz"[k], g), values[g, :, k]) for k in range(3)]
+    return cols
+
+
+def write_msd(file, msd, dt, append=False, header=True):
+    """A mean-squared displacement table (Context.msd_read, distributed.msd_sum) as text: two comment lines (samples, dropped, out of
+    range, origin floor; the column names) unless header=False, then one tab-separated line per lag -- the lag in ps (lag steps x `dt`),
+    then per group the pairs, <|dr|^2> and <dx^2> | <dy^2> | <dz^2> in nm^2 (nan where a lag has no pairs).  Floats are written with repr,
+    so np.loadtxt reads back the bits.  `file`: a path or an open text stream."""
+    cols = msd_columns(msd, dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"OriginFloor"\t%d' % (msd.samples, msd.dropped, msd.out_of_range, msd.origin_floor), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for l in range(msd.words.shape[1]):
+            print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:
         if own:

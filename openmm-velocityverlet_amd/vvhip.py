@@ -144,6 +144,26 @@ class ProfileLayout(C.Structure):
                 ("limit", C.c_double * 5)]
 
 
+MSD_PARTICLES, MSD_MOLECULES = 0, 1
+
+
+class MsdDesc(C.Structure):
+    """What an MSD recorder is to accumulate (include/vvhip.h: vvhip_msd_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32), ("num_groups", C.c_int32),
+                ("reserved", C.c_int32), ("group", C.c_void_p), ("max_samples", C.c_int64), ("limit", C.c_double)]
+
+
+class MsdCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64), ("origin_floor", C.c_int64)]
+
+
+class MsdLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32),
+                ("num_groups", C.c_int32), ("num_units", C.c_int32), ("num_origins", C.c_int32), ("frac_bits", C.c_int32),
+                ("reserved", C.c_int32), ("max_samples", C.c_int64), ("words", C.c_int64), ("ring_bytes", C.c_int64),
+                ("start_step", C.c_int64), ("limit", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -230,6 +250,8 @@ def _load():
         "vvhip_frames_schedule": [i32, i32, C.c_int64, i32, vp], "vvhip_debug_frames_guard": [vp, P(i32)],
         "vvhip_profile_start": [vp, P(ProfileDesc)], "vvhip_profile_stop": [vp], "vvhip_profile_info": [vp, P(ProfileLayout)],
         "vvhip_profile_read": [vp, vp, C.c_int64, P(ProfileCounts), i32], "vvhip_debug_recover": [vp],
+        "vvhip_msd_start": [vp, P(MsdDesc)], "vvhip_msd_stop": [vp], "vvhip_msd_info": [vp, P(MsdLayout)],
+        "vvhip_msd_read": [vp, vp, C.c_int64, P(MsdCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
