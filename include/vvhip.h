@@ -613,6 +613,97 @@ int vvhip_msd_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words,
 int vvhip_msd_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_msd_info(const vvhip_plan* plan, vvhip_msd_layout* out);
+/* ---------------------------------------------------------------- radial distribution functions accumulated on the device
+ * The pair structure g(r) between chosen sites (cation - anion, cation - cation, ion - electrode atom): the first thing plotted from a
+ * bulk or slab trajectory, and the one analysis a host cannot afford during a run: a pair histogram is O(N_a N_b) per sample, about 1 s
+ * for 3 000 x 3 000 sites in NumPy, against 24 B per particle and sample through the frame ring.  An accumulating histogram is a few KB
+ * however long the run.  After every full step whose count is a multiple of `interval` -- counted exactly as for the series, the frames,
+ * the profiles and the MSD, by the same entry points (the split per-KernelImpl entry points take none); a sample "after step k" is
+ * enqueued behind that step's MSD sample -- the step entry point enqueues three kernels (csrc/vv_dev_rdf.inc): a gather of the sites'
+ * float64 positions into a planar scratch, the pair kernel, and a one-thread kernel that counts the sample: no memset, no host work.
+ * Inside a captured graph all three are graph nodes and the steps that take a sample are part of the graph-cache key.  The recorder reads
+ * posq and posqCorrection and writes its own words and scratch, nothing else; a plan that never starts one launches what it launched
+ * before and allocates nothing.
+ * Sites.  The particles with group[i] >= 0, each in the one group it names; `group` covers the whole System, NULL puts every particle
+ * into group 0; num_groups is 1 .. 16.
+ * Classes.  num_classes (1 .. 32) unordered pairs of groups, classes[c] = {ga, gb}, both in [0, num_groups).  A class with ga != gb counts
+ * every pair (i in ga, j in gb); a class with ga == gb counts every unordered pair {i, j} of the group once and no particle with itself.
+ * With exclude_same_molecule != 0 pairs whose particles have equal vvhip_system_desc.mol_id are left out of every class (counted nowhere).
+ * Position.  X_i in float64, exactly as a float64 frame defines it: (double) posq + (double) posqCorrection in mixed precision, (double)
+ * posq otherwise; positions are stored unwrapped, in any periodic image.
+ * Arithmetic.  All float64, no contraction.  Per axis a = x, y, z, with L the plan's box when the sample is enqueued and inv_L_a =
+ * 1.0 / L_a formed once per sample:
+ *     d = X_i,a - X_j,a;   n = rint(d * inv_L_a)  (round-half-even);   d = d - L_a * n
+ * and then  r2 = (dx * dx + dy * dy) + dz * dz.  Every operation is odd or even in d, so a pair gives the same r2 in either orientation.
+ * Bins.  Uniform in r: dr = r_max / nbins in float64 and edges e(k) = ((double) k * dr) * ((double) k * dr), k = 0 .. nbins.  A pair adds
+ * the integer 1 to the bin b of its class with  e(b) <= r2 < e(b + 1),  0 <= b < nbins (where edges coincide: the largest such b); a pair
+ * with r2 >= e(nbins) adds nothing; a pair whose r2 is NaN adds 1 to `invalid` and to no bin.  The comparisons define the bin, not a
+ * square root; the host's views (vvhip_rdf_layout.dr, Python's Rdf.edges) use the same e.  nbins is 1 .. 8192.
+ * Table: int64 table[num_classes][nbins].  Integer adds commute: the table is the same bits for any grid, tile shape or order.
+ * Range.  r_max must be finite, > 0 and <= min(Lx, Ly, Lz) / 2 of the plan's box at the start (one image per pair).  A sample that is
+ * enqueued while the plan's box no longer satisfies this (vvhip_set_box, the barostat's moves) adds nothing and counts as dropped; back in
+ * range the samples count again.  The box is a kernel argument: what changes it drops the captured graphs.
+ * Counts.  samples; dropped (due past max_samples, or in a box too small for r_max); invalid; and inv_volume_sum, float64: every counted
+ * sample adds, in sample order,  s = s + 1.0 / ((Lx * Ly) * Lz)  -- sequential, so reproducible; under a barostat the normalisation of
+ * g(r) needs this sum:  g_c(b) = table[c][b] / (P_c * shell(b) * inv_volume_sum),  P_c = pairs_per_sample[c] = N_a N_b, or N_a (N_a - 1)
+ * / 2 for ga == gb (exclusion does not lower it), shell(b) = 4 pi / 3 (e(b + 1)^(3/2) - e(b)^(3/2)).
+ * Overflow.  Refused at the start where the largest P_c times max_samples reaches 2^62.
+ * Sharded plans.  A shard holds its own particles' arrays only, so pairs across shards exist on no device: a plan with a real shard is
+ * refused (VVHIP_ERR_UNSUPPORTED) rather than given a partial histogram.
+ * Recovery.  An accumulating table is not idempotent under the repeat of failed steps, so the rider's recovery words are the whole
+ * allocation, counts and table, (4 + words) * 8 B; the scratch is rewritten by every sample and is not saved.  vvhip_checkpoint_load is
+ * refused while a recorder runs, a re-bind drops the captured graphs, as for a profile recorder. */
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t nbins;                  /* 1 .. 8192 */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t num_classes;            /* 1 .. 32 */
+    int32_t exclude_same_molecule;  /* != 0: pairs inside one molecule (mol_id) are left out */
+    int32_t reserved;               /* 0 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: no site; NULL: everything in group 0 */
+    const int32_t* classes;         /* [num_classes][2] the groups ga, gb of every class */
+    int64_t max_samples;            /* >= 1 */
+    double r_max;                   /* nm */
+} vvhip_rdf_desc;
+typedef struct {
+    int64_t samples;                /* samples counted since the start or the last reset (at most max_samples) */
+    int64_t dropped;                /* samples that were due past max_samples or in a box with min(L) / 2 < r_max: nothing was added */
+    int64_t invalid;                /* pairs whose r2 was NaN */
+    double inv_volume_sum;          /* the counted samples' 1 / V, summed in sample order */
+} vvhip_rdf_counts;
+typedef struct {
+    int32_t active, interval, nbins, num_groups, num_classes, exclude_same_molecule;
+    int32_t tile;                   /* sites per tile of the pair kernel (a site count of tile + 1 is the first with a second tile) */
+    int32_t num_items;              /* blocks of the pair kernel per sample */
+    int32_t num_sites[16];          /* per group */
+    int32_t classes[32][2];
+    int64_t pairs_per_sample[32];   /* per class: N_a N_b, or N_a (N_a - 1) / 2 */
+    int64_t max_samples;
+    int64_t words;                  /* num_classes * nbins */
+    int64_t scratch_bytes;          /* the gather's planes: 3 x stride x 8 B, stride = the sites rounded up to 16 */
+    int64_t start_step;             /* the plan's step count at vvhip_rdf_start */
+    double r_max, dr;               /* dr = r_max / nbins */
+} vvhip_rdf_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, r_max not finite or <= 0, nbins outside 1 .. 8192, num_groups outside 1 .. 16, num_classes outside 1 ..
+ * 32, classes NULL, max_samples < 1, a group entry outside -1 .. num_groups - 1, a class entry outside 0 .. num_groups - 1
+ * (VVHIP_ERR_INVALID naming the argument); the largest class's pairs per sample times max_samples at or above 2^62; r_max above half the
+ * shortest edge of the plan's box (VVHIP_ERR_INVALID); a sharded plan (VVHIP_ERR_UNSUPPORTED); an unbound plan; inside a graph capture
+ * (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes the checks in front of
+ * "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_rdf_info answers for it, for sizing. */
+int vvhip_rdf_start(vvhip_plan* plan, const vvhip_rdf_desc* desc);
+/* Enqueues one sample now, behind what is queued, whatever the schedule says; it counts as a sample like a scheduled one (a host that
+ * analyses a configuration it has uploaded).  VVHIP_ERR_INVALID without a running recorder or inside a graph capture. */
+int vvhip_rdf_sample(vvhip_plan* plan);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts and table: the step schedule continues without gap or
+ * repeat. */
+int vvhip_rdf_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_rdf_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and scratch are released, the description is forgotten; synchronises and drops
+ * the captured graphs. */
+int vvhip_rdf_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_rdf_info(const vvhip_plan* plan, vvhip_rdf_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

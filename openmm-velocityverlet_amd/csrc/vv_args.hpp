@@ -392,4 +392,34 @@ struct MsdArgs {
     double scale, limit;            // 2^frac_bits; |delta| at or beyond it is out of range
 };
 
+// RDF sample (vv_dev_rdf.inc, include/vvhip.h: vvhip_rdf_* states the sites, the classes, the arithmetic and the bins).  The sample count is
+// read from the device-side words, so a replayed graph (same arguments every time) stops adding at max_samples; whether the box still
+// holds r_max is the host's decision at enqueue (`live`): the box is an argument, and a box that changes drops the captured graphs.
+enum { RDF_SAMPLES = 0, RDF_DROPPED = 1, RDF_INVALID = 2, RDF_INV_VOLUME = 3, RDF_HEAD = 4 };      // the words in front of the table ([3]: the bits of a double)
+constexpr int RDF_TILE = 256;       // sites per tile = threads per block of the pair kernel
+constexpr int RDF_MAX_CLASSES = 32, RDF_MAX_GROUPS = 16;      // (the arrays of vvhip_rdf_layout)
+// A block's work: the sites i0 .. i0 + ni - 1 (one per thread, 1 <= ni <= RDF_TILE) of class cls's group a against the sites b0 + j0 ..
+// b0 + j1 - 1 of its group b, which starts at site b0; same != 0: ga == gb, and a pair counts where the i-site's index is below the
+// j-site's (the host lists no j-site below i0)
+struct RdfItem { int32_t cls, same, i0, ni, b0, j0, j1, pad_; };
+struct RdfArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // [n] particle of site s; the sites are ordered by group, inside a group ascending by particle
+    const int32_t* mol;             // [n] molecule of site s (exclusion on, else null)
+    const RdfItem* items;           // [num_items]
+    double* scratch;                // [3][stride] the sites' x, y, z planes, rewritten by every sample's gather
+    long long* words;               // [RDF_HEAD + num_classes * nbins]: samples, dropped, invalid, inv_volume_sum, then table[class][nbins]
+    int64_t max_samples;
+    int32_t n, stride;              // sites; n rounded up to 16
+    int32_t nbins, num_items;
+    int32_t copies, live;           // private histograms per block (1, or one per wave); 0: the box no longer holds r_max, the sample is dropped
+    int32_t max_jsites, pad_;       // no item has more j-sites: RDF_TILE * max_jsites pairs fit a private histogram's 32-bit words
+    double L[3], inv_L[3];          // the plan's box at enqueue and 1.0 / L[a], formed on the host
+    double dr, cut2;                // r_max / nbins; e(nbins)
+    float inv_dr;                   // 1 / dr, for the guess of the bin only
+    float pad2_;
+    double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
+};
+
 }  // namespace vv

@@ -20,3 +20,4 @@
 #include "vv_dev_frames.inc"
 #include "vv_dev_profile.inc"
 #include "vv_dev_msd.inc"
+#include "vv_dev_rdf.inc"

@@ -495,6 +495,24 @@ hipError_t launch_msd_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_msd_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+size_t rdf_lds_bytes(int nbins, int copies) { return (size_t) RDF_TILE * (3 * sizeof(double) + sizeof(int)) + (size_t) copies * (size_t) nbins * sizeof(unsigned int); }
+hipError_t launch_rdf(int precision, const RdfArgs& a, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: a private word cannot wrap, the histograms fit the block's LDS, the planes hold the sites
+    if (a.max_jsites < 1 || (long long) a.max_jsites * RDF_TILE >= (1ll << 32)) return hipErrorInvalidValue;
+    if (a.nbins < 1 || a.copies < 1 || a.copies > RDF_TILE / 64 || rdf_lds_bytes(a.nbins, a.copies) > PROFILE_LDS_BYTES) return hipErrorInvalidValue;
+    if (a.n < 0 || a.stride < a.n || a.num_items < 0) return hipErrorInvalidValue;
+    const dim3 gg((unsigned) std::max(1, std::min((a.n + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_rdf_gather), gg, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 gp((unsigned) std::max(1, a.num_items));
+    const unsigned lds = (unsigned) rdf_lds_bytes(a.nbins, a.copies);
+    if (a.mol) hipLaunchKernelGGL(vv_kernel_rdf_pairs<true>, gp, dim3(RDF_TILE), lds, s, a);
+    else hipLaunchKernelGGL(vv_kernel_rdf_pairs<false>, gp, dim3(RDF_TILE), lds, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_rdf_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

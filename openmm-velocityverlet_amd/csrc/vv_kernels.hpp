@@ -77,5 +77,12 @@ hipError_t launch_profile(int precision, const ProfileArgs& a, int grid_cap, hip
 hipError_t launch_msd(int precision, const MsdArgs& a, int block_threads, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as MsdArgs::words.
 hipError_t launch_msd_floor(long long* words, hipStream_t s);
+// One RDF sample (vv_dev_rdf.inc): the gather over a.n sites in blocks of 256 threads, at most grid_cap of them (the kernel strides
+// beyond), the pair kernel with one block of RDF_TILE threads per work item (one idle block where there is none) and dynamic LDS of
+// rdf_lds_bytes (the staged j-tile and a.copies private histograms, 1 .. RDF_TILE / 64, within PROFILE_LDS_BYTES), then the one-thread
+// kernel that counts the sample.  a.mol selects the kernel that leaves out pairs of one molecule.  hipErrorInvalidValue where
+// a.max_jsites * RDF_TILE >= 2^32: a block's private 32-bit words could wrap.
+size_t rdf_lds_bytes(int nbins, int copies);
+hipError_t launch_rdf(int precision, const RdfArgs& a, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -1,5 +1,5 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, profiles, mean-squared displacements, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
+// the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
 // ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
 #include "vv_plan.hpp"
 
@@ -112,6 +112,31 @@ int msd_positions_rewritten(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_msd_floor(p->msd.d_words.get(), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ radial distribution functions (vvhip_rdf_*)
+// r_max against the box: one image per pair
+static bool rdf_box_holds(const double box[3], double r_max) { return r_max <= std::min(box[0], std::min(box[1], box[2])) / 2; }
+// One sample behind the step just enqueued (or captured), and behind its MSD sample -- or behind what is queued (vvhip_rdf_sample): the
+// gather, the pair kernel and the one-thread kernel that counts the sample.  Three launches, no memset and no host synchronisation.  The
+// box and whether it still holds r_max are arguments: what changes the box drops the captured graphs.
+static int rdf_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Rdf& R = p->rdf;
+    const vvhip_rdf_layout& L = R.lay;
+    vv::RdfArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.index = R.d_index.get(); a.mol = L.exclude_same_molecule ? R.d_mol.get() : nullptr; a.items = R.d_items.get();
+    a.scratch = R.d_scratch.get(); a.words = R.d_words.get();
+    a.max_samples = L.max_samples;
+    a.n = (int32_t) R.index.size(); a.stride = R.stride(); a.nbins = L.nbins; a.num_items = (int32_t) R.items.size();
+    // (one histogram per wave only where all of them fit beside the staged tile)
+    a.copies = p->rdf_hist_copies > 1 && vv::rdf_lds_bytes(L.nbins, vv::RDF_TILE / 64) <= vv::PROFILE_LDS_BYTES ? vv::RDF_TILE / 64 : 1;
+    a.live = rdf_box_holds(p->box, L.r_max) ? 1 : 0;
+    a.max_jsites = R.max_jsites;
+    for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
+    a.dr = L.dr; a.cut2 = ((double) L.nbins * L.dr) * ((double) L.nbins * L.dr); a.inv_dr = (float) (1.0 / L.dr);
+    a.inv_volume = 1.0 / ((p->box[0] * p->box[1]) * p->box[2]);
+    HIP_TRY(p, vv::launch_rdf(p->hp.precision, a, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -151,12 +176,14 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 // profile sample, then the MSD sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
 // (one-off calls allocate it too), and of a profile the WHOLE allocation, counts and table: a row or a frame written twice is the same row
 // or frame, a sample added twice is not the same table.  Of an MSD recorder likewise the whole allocation, the ring of origins included.
+// The RDF sample goes last, behind the MSD sample; its late words are counts and table (its gather scratch is rewritten by every sample).
 Riders riders(vvhip_plan* p) {
     return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue},
-             {p->msd.on, p->msd.when, false, p->msd.on ? p->msd.d_words.get() : nullptr, p->msd.bytes(), msd_enqueue}}};
+             {p->msd.on, p->msd.when, false, p->msd.on ? p->msd.d_words.get() : nullptr, p->msd.bytes(), msd_enqueue},
+             {p->rdf.on, p->rdf.when, false, p->rdf.on ? p->rdf.d_words.get() : nullptr, p->rdf.bytes(), rdf_enqueue}}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -174,6 +201,7 @@ static void series_release(vvhip_plan* p) { p->series = vvhip_plan::Series{}; }
 static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
 static void profile_release(vvhip_plan* p) { p->profile = vvhip_plan::Profile{}; }
 static void msd_release(vvhip_plan* p) { p->msd = vvhip_plan::Msd{}; }
+static void rdf_release(vvhip_plan* p) { p->rdf = vvhip_plan::Rdf{}; }
 // frexp's view of a positive finite x: the smallest power of two >= x / > x, and the exponent of a power of two
 static double pow2_at_least(double x) { int e; const double f = std::frexp(x, &e); return f == 0.5 ? x : std::ldexp(1.0, e); }
 static double pow2_above(double x) { int e; (void) std::frexp(x, &e); return std::ldexp(1.0, e); }
@@ -761,6 +789,157 @@ int vvhip_msd_info(const vvhip_plan* p, vvhip_msd_layout* out) {
     if (!p || !out) return VVHIP_ERR_INVALID;
     vvhip_msd_layout r{};
     if (p->msd.described) { r = p->msd.lay; r.active = p->msd.on; }
+    *out = r;
+    return VVHIP_OK;
+}
+
+int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "rdf: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "rdf: interval must be >= 1 step");
+    if (!(d->r_max > 0) || !std::isfinite(d->r_max)) return fail(p, VVHIP_ERR_INVALID, "rdf: r_max must be finite and > 0");
+    if (d->nbins < 1 || d->nbins > 8192) return fail(p, VVHIP_ERR_INVALID, "rdf: nbins must be in [1, 8192]");
+    if (d->num_groups < 1 || d->num_groups > vv::RDF_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "rdf: num_groups must be in [1, 16]");
+    if (d->num_classes < 1 || d->num_classes > vv::RDF_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "rdf: num_classes must be in [1, 32]");
+    if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "rdf: classes must not be NULL");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "rdf: max_samples must be >= 1");
+    const vv::HostPlan& hp = p->hp;
+    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
+        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
+            return fail(p, VVHIP_ERR_INVALID, "rdf: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    for (int32_t c = 0; c < d->num_classes; c++)
+        for (int q = 0; q < 2; q++)
+            if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= d->num_groups)
+                return fail(p, VVHIP_ERR_INVALID, "rdf: classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(d->classes[2 * c + q]) + " is outside [0, num_groups = " + std::to_string(d->num_groups) + ")");
+    // ---- the sites, the layout and the pair kernel's work list, host only
+    vvhip_plan::Rdf N;
+    vvhip_rdf_layout& L = N.lay;
+    L.interval = d->interval; L.nbins = d->nbins; L.num_groups = d->num_groups; L.num_classes = d->num_classes;
+    L.exclude_same_molecule = d->exclude_same_molecule != 0; L.tile = vv::RDF_TILE;
+    L.max_samples = d->max_samples; L.words = (int64_t) d->num_classes * d->nbins;
+    L.r_max = d->r_max; L.dr = d->r_max / (double) d->nbins;
+    for (int32_t i = 0; i < hp.num_atoms; i++) {
+        const int g = d->group ? (int) d->group[i] : 0;
+        if (g >= 0) L.num_sites[g]++;
+    }
+    int32_t first[vv::RDF_MAX_GROUPS + 1] = {0};
+    for (int g = 0; g < d->num_groups; g++) first[g + 1] = first[g] + L.num_sites[g];
+    int64_t largest = 0;
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int ga = d->classes[2 * c], gb = d->classes[2 * c + 1];
+        const int64_t na = L.num_sites[ga], nb = L.num_sites[gb];
+        L.classes[c][0] = ga; L.classes[c][1] = gb;
+        L.pairs_per_sample[c] = ga == gb ? na * (na - 1) / 2 : na * nb;
+        largest = std::max(largest, L.pairs_per_sample[c]);
+    }
+    if ((unsigned __int128) largest * (unsigned __int128) d->max_samples >= ((unsigned __int128) 1 << 62))
+        return fail(p, VVHIP_ERR_INVALID, "rdf: " + std::to_string((long long) largest) + " pairs per sample times max_samples = " + std::to_string((long long) d->max_samples) +
+                                          " reaches 2^62: a bin could overflow; lower max_samples");
+    if (!rdf_box_holds(p->box, d->r_max))
+        return fail(p, VVHIP_ERR_INVALID, "rdf: r_max = " + std::to_string(d->r_max) + " nm is above half the shortest edge of the box (" +
+                                          std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm): a pair would have more than one image in range");
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "rdf: a sharded plan holds its own particles' positions only, so the pairs across shards exist on no device; "
+                                              "a partial histogram is not recorded (run the analysis on an unsharded plan)");
+    N.index.resize((size_t) first[d->num_groups]);
+    if (L.exclude_same_molecule) N.mol.resize(N.index.size());
+    {
+        int32_t next[vv::RDF_MAX_GROUPS];
+        std::copy(first, first + vv::RDF_MAX_GROUPS, next);
+        for (int32_t i = 0; i < hp.num_atoms; i++) {      // ascending by particle inside every group
+            const int g = d->group ? (int) d->group[i] : 0;
+            if (g < 0) continue;
+            N.index[(size_t) next[g]] = i;
+            if (L.exclude_same_molecule) N.mol[(size_t) next[g]] = hp.mol_id[(size_t) i];
+            next[g]++;
+        }
+    }
+    // the work list: per class and i-tile the j-sites in runs of `max_jsites`, a multiple of 64; a class of one group with itself from
+    // the i-tile's first site on.  A small workload gets runs of 64, so that its blocks fill the device; beyond rdf_items_target blocks
+    // a run grows, so that the flush of a block's histogram and its launch are shared (at most 2^18 sites: 2^26 pairs, far inside what
+    // a private 32-bit word holds)
+    constexpr int T = vv::RDF_TILE;
+    long long runs = 0;                                     // of 64 j-sites, over all i-tiles
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int64_t na = L.num_sites[L.classes[c][0]], nb = L.num_sites[L.classes[c][1]];
+        for (int64_t i0 = 0; i0 < na; i0 += T) runs += (nb - (L.classes[c][0] == L.classes[c][1] ? i0 : 0) + 63) / 64;
+    }
+    const int target = std::max(1, p->rdf_items_target);
+    N.max_jsites = 64 * (int) std::max<long long>(1, std::min<long long>(4096, (runs + target - 1) / target));
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int ga = L.classes[c][0], gb = L.classes[c][1];
+        const int32_t na = L.num_sites[ga], nb = L.num_sites[gb];
+        if (ga == gb && na < 2) continue;                  // (no pair)
+        for (int32_t i0 = 0; i0 < na; i0 += T)
+            for (int32_t j0 = ga == gb ? i0 : 0; j0 < nb; j0 += N.max_jsites)
+                N.items.push_back({c, ga == gb ? 1 : 0, first[ga] + i0, std::min(T, na - i0), first[gb], j0, std::min(nb, j0 + N.max_jsites), 0});
+    }
+    L.num_items = (int32_t) N.items.size();
+    L.scratch_bytes = (int64_t) 3 * N.stride() * (int64_t) sizeof(double);
+    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
+    if (p->capturing || p->rdf.on) TRY(quiesce(p, "rdf", true, true));
+    rdf_release(p);
+    vvhip_plan::Rdf& R = p->rdf;
+    R = std::move(N);
+    R.when = {d->interval, SCHEDULE_LINEAR};
+    R.lay.start_step = p->cur.step_count;
+    R.described = true;
+    NEED_BOUND(p);
+    TRY(quiesce(p, "rdf", true, true));
+    auto alloc_fail = [&](hipError_t e, size_t bytes) {
+        R.d_words.reset(); R.d_index.reset(); R.d_mol.reset(); R.d_items.reset(); R.d_scratch.reset();
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string("rdf: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
+    };
+    hipError_t e = vv::zeros(R.d_words, R.bytes(), p->stream);
+    if (e != hipSuccess) return alloc_fail(e, R.bytes());
+    const size_t scratch = std::max<size_t>(16, (size_t) R.lay.scratch_bytes);
+    if ((e = vv::zeros(R.d_scratch, scratch, p->stream)) != hipSuccess) return alloc_fail(e, scratch);
+    if ((e = vv::upload(R.d_index, R.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, R.index.size() * sizeof(int32_t)));
+    if (R.lay.exclude_same_molecule && (e = vv::upload(R.d_mol, R.mol, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, R.mol.size() * sizeof(int32_t)));
+    if ((e = vv::upload(R.d_items, R.items, 32)) != hipSuccess) return alloc_fail(e, std::max<size_t>(32, R.items.size() * sizeof(vv::RdfItem)));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    R.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
+    R.on = true;
+    return VVHIP_OK;
+}
+int vvhip_rdf_sample(vvhip_plan* p) {
+    NEED_BOUND(p);
+    if (!p->rdf.on) return fail(p, VVHIP_ERR_INVALID, "rdf: none started (vvhip_rdf_start)");
+    TRY(quiesce(p, "rdf", false, false));
+    return rdf_enqueue(p);
+}
+int vvhip_rdf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_rdf_counts* out, int32_t reset) {
+    NEED_BOUND(p);
+    vvhip_plan::Rdf& R = p->rdf;
+    if (!R.on) return fail(p, VVHIP_ERR_INVALID, "rdf: none started (vvhip_rdf_start)");
+    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < R.lay.words))
+        return fail(p, VVHIP_ERR_INVALID, "rdf: the table has " + std::to_string((long long) R.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
+    TRY(quiesce(p, "rdf", true, false));
+    long long head[vv::RDF_HEAD];
+    HIP_TRY(p, hipMemcpy(head, R.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
+    if (words_out) HIP_TRY(p, hipMemcpy(words_out, R.d_words.get() + vv::RDF_HEAD, (size_t) R.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out) {
+        double s;
+        std::memcpy(&s, &head[vv::RDF_INV_VOLUME], sizeof s);
+        *out = {head[vv::RDF_SAMPLES], head[vv::RDF_DROPPED], head[vv::RDF_INVALID], s};
+    }
+    if (reset) {
+        HIP_TRY(p, hipMemsetAsync(R.d_words.get(), 0, R.bytes(), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+    }
+    return VVHIP_OK;
+}
+int vvhip_rdf_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing || p->rdf.on) TRY(quiesce(p, "rdf", true, true));
+    rdf_release(p);                                     // (also the description an unbound plan kept)
+    return VVHIP_OK;
+}
+int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_rdf_layout r{};
+    if (p->rdf.described) { r = p->rdf.lay; r.active = p->rdf.on; }
     *out = r;
     return VVHIP_OK;
 }

@@ -80,7 +80,7 @@ inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (u
 inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
-constexpr int kRiders = 5;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample
+constexpr int kRiders = 6;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample, RDF sample
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -150,6 +150,8 @@ struct vvhip_plan {
     int profile_grid_cap = 256;    // most blocks of a profile sample's accumulating kernel, besides grid_cap_a: every block flushes a table of its own (test hook "profile_grid_cap"; TUNING_LOG.md)
     int msd_block_threads = 0;     // threads per block of an MSD sample's accumulating kernel, 0: by the number of units (msd_enqueue; test hook "msd_block_threads")
     int msd_wave_reduce = 1;       // an MSD sample's waves whose units share a group add their four sums once (test hook "msd_wave_reduce": 0 = every lane adds; same bits)
+    int rdf_hist_copies = 1;       // private histograms per block of an RDF sample's pair kernel: 1, or 4 = one per wave where they fit the LDS budget (test hook "rdf_hist_copies"; same bits; TUNING_LOG.md)
+    int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
                                      // 1.33 M 14.5 | 14.0 k, 1.78 M 11.4 | 11.1 k, 2.66 M 7.38 | 7.37 k, 4.4 M 4.14 | 4.20 k, 8.9 M 2.16 | 2.21 k (round 2 had it at 12 288)
@@ -371,6 +373,23 @@ struct vvhip_plan {
         int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
         size_t bytes() const { return (size_t) (vv::MSD_HEAD + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
     } msd;
+    // Radial distribution functions (vvhip_rdf_*; vv_dev_rdf.inc), scheduled by cur.step_count.  `described` / `on` as for the profiles.  The
+    // site list (ordered by group, inside a group ascending by particle), the sites' molecules and the pair kernel's work items are built
+    // when the recorder starts
+    struct Rdf {
+        bool on = false, described = false;
+        Schedule when;                            // (linear)
+        vvhip_rdf_layout lay{};
+        std::vector<int32_t> index, mol;          // [sites] particle and molecule of every site (mol: with the exclusion on)
+        std::vector<vv::RdfItem> items;
+        int max_jsites = 64;                      // no item has more j-sites
+        vv::DevBuf<int32_t> d_index, d_mol;
+        vv::DevBuf<vv::RdfItem> d_items;
+        vv::DevBuf<double> d_scratch;             // [3][stride()] rewritten by every sample, not saved
+        vv::DevBuf<long long> d_words;            // [RDF_HEAD + lay.words]: counts, then the table -- ALL of it the rider's late words
+        int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
+        size_t bytes() const { return (size_t) (vv::RDF_HEAD + lay.words) * sizeof(long long); }
+    } rdf;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -521,7 +540,8 @@ Riders riders(vvhip_plan* p);
 // (`late`: those go back with the step counter, after the accumulators are zeroed; a checkpoint does not carry them).  For a series and a
 // frame recorder these are the cursors: the repeat writes the same rows and frames at the same places.  For a profile recorder they are the
 // whole allocation, counts and table: an accumulating table is not idempotent under the repeat, so it goes back as the snapshot took it.
-// For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.
+// For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.  For an RDF
+// recorder counts and table; its gather scratch is rewritten by every sample and is not saved.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

@@ -405,6 +405,77 @@ def msd_from_words(words, layout, counts) -> Msd:
                frac_bits=int(layout.frac_bits), molecules=layout.mode == H.MSD_MOLECULES, words=words)
 
 
+def rdf_edges(r_max: float, nbins: int) -> np.ndarray:
+    """float64 [nbins + 1]: the SQUARED bin edges e(k) = ((double) k * dr)^2 with dr = r_max / nbins, as include/vvhip.h defines them."""
+    t = np.arange(int(nbins) + 1, dtype=np.float64) * (np.float64(r_max) / np.float64(nbins))
+    return t * t
+
+
+@dataclasses.dataclass
+class Rdf:
+    """Pair histograms per class and bin (Context.rdf_read; include/vvhip.h: vvhip_rdf_* states the sites, the classes, the arithmetic and
+    the bins).  `counts` is the device's table as it stands, int64 [classes, bins]."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples or in a box too small for r_max: nothing was added
+    invalid: int                           # pairs whose squared distance was NaN
+    inv_volume_sum: float                  # the counted samples' 1 / V in nm^-3, summed in sample order
+    interval: int
+    r_max: float
+    dr: float
+    classes: np.ndarray                    # int32 [classes, 2] the groups of every class
+    num_sites: np.ndarray                  # int64 [groups]
+    pairs_per_sample: np.ndarray           # int64 [classes]: N_a N_b, or N_a (N_a - 1) / 2 for a class of one group with itself
+    counts: np.ndarray                     # int64 [classes, bins]
+
+    @property
+    def edges2(self) -> np.ndarray:
+        """float64 [bins + 1]: the squared edges e(k) the device compares against."""
+        return rdf_edges(self.r_max, self.counts.shape[1])
+
+    @property
+    def edges(self) -> np.ndarray:
+        """float64 [bins + 1]: the bin edges in nm, sqrt(e(k))."""
+        return np.sqrt(self.edges2)
+
+    @property
+    def r(self) -> np.ndarray:
+        """float64 [bins]: the bin centres in nm."""
+        e = self.edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    @property
+    def shell_volumes(self) -> np.ndarray:
+        """float64 [bins]: 4 pi / 3 (e+^3 - e-^3) in nm^3, exact for the edges as they are."""
+        e3 = self.edges ** 3
+        return 4.0 * np.pi / 3.0 * (e3[1:] - e3[:-1])
+
+    def g(self) -> np.ndarray:
+        """float64 [classes, bins]: counts / pairs_per_sample / shell volume / inv_volume_sum -- an ideal gas gives 1; NaN where a class
+        has no pair or no sample was counted."""
+        pairs = self.pairs_per_sample.astype(np.float64)[:, None]
+        norm = pairs * self.shell_volumes[None, :] * self.inv_volume_sum
+        return np.where(norm > 0, self.counts / np.where(norm > 0, norm, 1.0), np.nan)
+
+    def coordination(self) -> np.ndarray:
+        """float64 [classes, bins]: the running integral up to every bin's outer edge: sites of group b within that distance of a site of
+        group a, averaged over the samples and the sites of a (a class of one group with itself counts every pair for both its sites)."""
+        na = self.num_sites[self.classes[:, 0]].astype(np.float64)[:, None]
+        both = np.where(self.classes[:, 0] == self.classes[:, 1], 2.0, 1.0)[:, None]
+        denom = na * float(self.samples)
+        return np.where(denom > 0, both * np.cumsum(self.counts, axis=1) / np.where(denom > 0, denom, 1.0), np.nan)
+
+
+def rdf_from_words(words, layout, counts) -> Rdf:
+    """An Rdf from a table's int64 words [classes * bins], its layout (H.RdfLayout) and counts (H.RdfCounts)."""
+    nc, ng = int(layout.num_classes), int(layout.num_groups)
+    table = np.ascontiguousarray(words, dtype=np.int64).reshape(nc, int(layout.nbins))
+    return Rdf(samples=int(counts.samples), dropped=int(counts.dropped), invalid=int(counts.invalid), inv_volume_sum=float(counts.inv_volume_sum),
+               interval=int(layout.interval), r_max=float(layout.r_max), dr=float(layout.dr),
+               classes=np.array([[layout.classes[c][0], layout.classes[c][1]] for c in range(nc)], dtype=np.int32).reshape(nc, 2),
+               num_sites=np.array(layout.num_sites[:ng], dtype=np.int64), pairs_per_sample=np.array(layout.pairs_per_sample[:nc], dtype=np.int64),
+               counts=table)
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -745,6 +816,48 @@ class Context:
         H.check(H.lib.vvhip_msd_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
         return msd_from_words(words[: info.words], info, counts)
 
+    # ---- radial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_rdf_*)
+    def rdf_start(self, interval: int, r_max: float, nbins: int, classes, groups=None, exclude_same_molecule: bool = False,
+                  max_samples: int = 1 << 20):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), histogram the minimum-image
+        distances of every pair of sites of every class into `nbins` bins of width r_max / nbins (nm), as integers, so that the table is
+        the same bits for any launch shape.  `groups`: one int per particle of the System (-1: no site); None: everything in group 0.
+        `classes`: pairs of groups (ga, gb); ga == gb counts every unordered pair of the group once.  exclude_same_molecule leaves out the
+        pairs inside one molecule.  r_max must not exceed half the shortest box edge.  At most `max_samples` samples are taken.  A sharded
+        context raises ERR_UNSUPPORTED.  No host synchronisation until rdf_read."""
+        grp = None
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+            if grp.size != self.system.num_atoms:
+                raise ValueError("groups must have one entry per particle of the System")
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1, 2)
+        num_groups = max(1, 0 if grp is None else int(grp.max()) + 1, int(cls.max()) + 1 if cls.size else 1)      # (a class may name a group without sites)
+        desc = H.RdfDesc(int(interval), int(nbins), num_groups, int(cls.shape[0]),
+                         int(bool(exclude_same_molecule)), 0, None if grp is None else grp.ctypes.data, cls.ctypes.data, int(max_samples),
+                         float(r_max))
+        H.check(H.lib.vvhip_rdf_start(self.plan, C.byref(desc)), self.plan)
+
+    def rdf_sample(self):
+        """One sample now, behind what is queued, whatever the schedule says (a configuration the host has just uploaded)."""
+        H.check(H.lib.vvhip_rdf_sample(self.plan), self.plan)
+
+    def rdf_stop(self):
+        H.check(H.lib.vvhip_rdf_stop(self.plan), self.plan)
+
+    def rdf_info(self) -> H.RdfLayout:
+        out = H.RdfLayout()
+        H.check(H.lib.vvhip_rdf_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def rdf_read(self, reset: bool = False) -> Rdf:
+        """The histograms accumulated so far (synchronises).  reset=True zeroes counts and table; the step schedule continues without gap
+        or repeat."""
+        info = self.rdf_info()
+        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
+        counts = H.RdfCounts()
+        H.check(H.lib.vvhip_rdf_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
+        return rdf_from_words(words[: info.words], info, counts)
+
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
         """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
@@ -817,7 +930,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile or MSD recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD or RDF recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

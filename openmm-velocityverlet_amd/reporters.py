@@ -20,6 +20,8 @@ latest three kept.
 
 ``write_msd`` writes a device-side mean-squared displacement table (``Context.msd_read``) as text columns, one line per lag.
 
+``write_rdf`` writes device-side radial distribution functions (``Context.rdf_read``) as text columns, one line per bin.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -237,6 +239,35 @@ def write_msd(file, msd, dt, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for l in range(msd.words.shape[1]):
             print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def rdf_columns(rdf):
+    """[(name, values per bin)] of an RDF's text file: the bin centre in nm, then per class the count, g(r) and the coordination number."""
+    cols = [("r (nm)", rdf.r)]
+    g, n = rdf.g(), rdf.coordination()
+    for c in range(rdf.counts.shape[0]):
+        tag = "%d-%d" % (int(rdf.classes[c, 0]), int(rdf.classes[c, 1]))
+        cols += [("count[%s]" % tag, rdf.counts[c].astype(np.float64)), ("g[%s]" % tag, g[c]), ("n[%s]" % tag, n[c])]
+    return cols
+
+
+def write_rdf(file, rdf, append=False, header=True):
+    """Radial distribution functions (Context.rdf_read) as text: two comment lines (samples, dropped, invalid, the sum of 1 / V; the
+    column names) unless header=False, then one tab-separated line per bin -- the bin centre in nm, then per class the pair count, g(r)
+    and the running coordination number.  Floats are written with repr, so np.loadtxt reads back the bits.  `file`: a path or an open
+    text stream."""
+    cols = rdf_columns(rdf)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"Invalid"\t%d\t"InvVolumeSum"\t%r' % (rdf.samples, rdf.dropped, rdf.invalid, float(rdf.inv_volume_sum)), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for b in range(rdf.counts.shape[1]):
+            print(*[repr(float(v[b])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:
         if own:

@@ -164,6 +164,24 @@ class MsdLayout(C.Structure):
                 ("start_step", C.c_int64), ("limit", C.c_double)]
 
 
+class RdfDesc(C.Structure):
+    """What an RDF recorder is to accumulate (include/vvhip.h: vvhip_rdf_desc)."""
+    _fields_ = [("interval", C.c_int32), ("nbins", C.c_int32), ("num_groups", C.c_int32), ("num_classes", C.c_int32),
+                ("exclude_same_molecule", C.c_int32), ("reserved", C.c_int32), ("group", C.c_void_p), ("classes", C.c_void_p),
+                ("max_samples", C.c_int64), ("r_max", C.c_double)]
+
+
+class RdfCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("invalid", C.c_int64), ("inv_volume_sum", C.c_double)]
+
+
+class RdfLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("nbins", C.c_int32), ("num_groups", C.c_int32), ("num_classes", C.c_int32),
+                ("exclude_same_molecule", C.c_int32), ("tile", C.c_int32), ("num_items", C.c_int32), ("num_sites", C.c_int32 * 16),
+                ("classes", (C.c_int32 * 2) * 32), ("pairs_per_sample", C.c_int64 * 32), ("max_samples", C.c_int64), ("words", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("start_step", C.c_int64), ("r_max", C.c_double), ("dr", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -252,6 +270,8 @@ def _load():
         "vvhip_profile_read": [vp, vp, C.c_int64, P(ProfileCounts), i32], "vvhip_debug_recover": [vp],
         "vvhip_msd_start": [vp, P(MsdDesc)], "vvhip_msd_stop": [vp], "vvhip_msd_info": [vp, P(MsdLayout)],
         "vvhip_msd_read": [vp, vp, C.c_int64, P(MsdCounts), i32],
+        "vvhip_rdf_start": [vp, P(RdfDesc)], "vvhip_rdf_sample": [vp], "vvhip_rdf_stop": [vp], "vvhip_rdf_info": [vp, P(RdfLayout)],
+        "vvhip_rdf_read": [vp, vp, C.c_int64, P(RdfCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
