@@ -704,6 +704,104 @@ int vvhip_rdf_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words,
 int vvhip_rdf_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_rdf_info(const vvhip_plan* plan, vvhip_rdf_layout* out);
+/* ---------------------------------------------------------------- collective current correlations accumulated on the device
+ * What the ionic conductivity needs: the Einstein-Helfand slope of the collective translational dipole M(t) = sum q_i r_i, or the Green-Kubo
+ * integral of the charge current J(t) = sum q_i v_i, both split into cation-cation, anion-anion and cation-anion parts.  The MSD table cannot
+ * give it: a product of sums is not a sum of per-particle terms, the cross terms between different ions are missing there.  A stand-alone
+ * host gets it from float64 frames, 48 B per particle and sample, O(samples^2 N) work, the frame ring's capacity bounding the statistics; the
+ * collective quantity is a handful of 3-vectors per sample, and a collective property has ONE value per time origin, so it needs far more
+ * origins than the MSD.  After every full step whose count is a multiple of `interval` -- counted exactly as for the other riders, by the
+ * same entry points; a sample "after step k" is enqueued behind that step's RDF sample -- the step entry point enqueues three kernels
+ * (csrc/vv_dev_current.inc): the reduce, the correlate and the advance.  No memset, no host work; inside a captured graph they are part of
+ * the graph and the steps that take a sample are part of the graph-cache key.  The recorder reads posq, posqCorrection and velm and writes
+ * its own words, nothing else; a plan that never starts one launches what it launched before and allocates nothing.
+ * Inputs.  weight[num_atoms] (float64, required, read at the start: later changes of posq.w are not followed; the charges q_i, or
+ * Q_m m_i / M_m for the molecules' centres of mass: then sum w_i X_i = sum_m Q_m COM_m, the translational dipole without the intramolecular
+ * and Drude part).  group[num_atoms]: -1 is not recorded, NULL: everything in group 0; G = num_groups, 1 .. 8.
+ * Per-sample sums, as integers.  X_i = (double) posq + (double) posqCorrection in mixed precision, (double) posq otherwise, positions
+ * unwrapped, exactly as a float64 frame defines it; v_i = (double) velm.xyz.  For component a
+ *     p_ia = llrint((w_i * X_ia) * 2^Fp),   u_ia = llrint((w_i * v_ia) * 2^Fv)      (float64 without contraction, round-half-even)
+ *     P_g,a = sum_{i in g} p_ia,            U_g,a = sum_{i in g} u_ia                (int64)
+ * W (weight_bound) is the smallest power of two above max |w_i| over the recorded particles of the WHOLE System (1 if all are 0), N their
+ * number, and Fp = min(40, 62 - ceil_log2(N + 1) - log2 W - log2 limit_position), Fv likewise with limit_velocity: no sum can overflow.
+ * The limits (nm, nm/ps; 0: the default of 64) are rounded up to a power of two.  A recorded particle with any X_ia or v_ia that is NaN
+ * or at or beyond its limit is out of range: it adds 1 to out_of_range and makes the sample INVALID.  An invalid sample adds nothing to any
+ * row, is not usable as an origin, and adds 1 to invalid_samples; the ordinal still advances.
+ * Schedule.  Sample ordinal j = 0, 1, ... counts the due steps since the start or the last reset, valid or not.  Every sample whose ordinal
+ * is a multiple of origin_every (E) is also stored as an origin, in slot (j / E) mod num_origins of a device ring of the sums, int64
+ * ring[num_origins][G][6] (P_x P_y P_z U_x U_y U_z), with a word per slot that says which sample the slot holds, or -1;
+ * num_origins = ceil(num_lags / E) is derived.
+ * Table: int64 words[num_lags + 1][row_words], row_words = 1 + 3 (ND + NC): word 0 of a row is an integer count, then disp[ND][3], then
+ * cur[NC][3], the bits of doubles.  ND = G (G + 1) / 2 displacement classes c(g, h), g <= h, in the order (0,0) (0,1) .. (0,G-1) (1,1) ..;
+ * NC = G^2 current classes (g, h) at index g G + h.  ROW l IS THE LAG OF l * interval STEPS AND ROW 0 IS THE ZERO LAG (unlike the MSD:
+ * row 0 holds the t = 0 term of Green-Kubo; its disp words stay 0).  At a valid sample j, all in float64 without contraction:
+ *     row 0:   cur[0][g][h][a] += J_g,a(j) * J_h,a(j)   with J = (double) U * 2^-Fv;   count[0] += 1
+ *     rows l = 1 .. num_lags, where the origin o = j - l is usable -- o is a multiple of E, origin_floor <= o, and the slot still holds
+ *     sample o and it was valid:
+ *              disp[l][c(g,h)][a] += dP_g,a * dP_h,a     with dP_g,a = (double) (P_g,a(j) - P_g,a(o)) * 2^-Fp, the subtraction in int64
+ *              cur[l][g][h][a]    += J_g,a(o) * J_h,a(j)  (the origin is the first index);   count[l] += 1
+ * A cell receives at most one term per sample, so its value is the sequential float64 sum in ascending sample order, and that order is
+ * part of the definition: one thread owns a cell for a sample, there are no float atomics, and the bits are the same for any grid, block
+ * size or particle order.  Accumulation comes first, the origin store second: when num_origins * E == num_lags the slot that is
+ * overwritten at sample j was read in the same sample.  Past max_samples a sample adds nothing, stores no origin and counts as dropped.
+ * inv_volume_sum is the sequential float64 sum of 1 / ((Lx * Ly) * Lz), formed on the host, over the valid samples.
+ * What rewrites positions outside the steps.  vvhip_barostat_scale and vvhip_barostat_restore, with a recorder running, set origin_floor
+ * to the current ordinal: older origins are dead, the table is kept.  vvhip_checkpoint_load is refused while a recorder runs.  Host uploads
+ * into the bound arrays are NOT detected, as for the MSD.
+ * Recovery.  Neither the table nor the ring is idempotent under the repeat of failed steps, so the rider's recovery words are the WHOLE
+ * allocation: head, sums, table, ring and the slots' words. */
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096: row l is the lag of l * interval steps, row 0 the zero lag */
+    int32_t origin_every;           /* E, 1 .. num_lags: every E-th sample is stored as an origin */
+    int32_t num_groups;             /* G, 1 .. 8 */
+    const double* weight;           /* [num_atoms] required, finite */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: not recorded; NULL: everything in group 0 */
+    int64_t max_samples;            /* >= 1 */
+    double limit_position;          /* nm: a position component at or beyond it is out of range; rounded up to a power of two; 0: 64 */
+    double limit_velocity;          /* nm/ps, likewise */
+} vvhip_current_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset, valid or not (at most max_samples): the next ordinal */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added or stored for them */
+    int64_t out_of_range;           /* recorded particles found out of range, over all samples taken */
+    int64_t invalid_samples;        /* samples taken with at least one of them: count[0] = samples - invalid_samples */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+    double inv_volume_sum;          /* the valid samples' 1 / V, summed in sample order */
+} vvhip_current_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, num_groups;
+    int32_t num_particles;          /* recorded particles (group >= 0) */
+    int32_t num_origins;            /* ceil(num_lags / origin_every) */
+    int32_t num_disp_classes;       /* ND = G (G + 1) / 2 */
+    int32_t num_cur_classes;        /* NC = G^2 */
+    int32_t row_words;              /* 1 + 3 (ND + NC) */
+    int32_t frac_bits_position;     /* Fp */
+    int32_t frac_bits_velocity;     /* Fv */
+    int64_t max_samples;
+    int64_t words;                  /* (num_lags + 1) * row_words */
+    int64_t ring_bytes;             /* num_origins * (G * 6 + 1) * 8: the origins' sums and the slots' words */
+    int64_t start_step;             /* the plan's step count at vvhip_current_start */
+    double limit_position, limit_velocity;      /* as applied */
+    double weight_bound;            /* W */
+} vvhip_current_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, num_groups outside 1 .. 8, max_samples
+ * < 1, a limit_position, then a limit_velocity that is negative or not finite, weight NULL, a group entry outside -1 .. num_groups - 1, a
+ * weight that is not finite (VVHIP_ERR_INVALID naming the argument); Fp, then Fv below 8 (VVHIP_ERR_INVALID); a sharded plan
+ * (VVHIP_ERR_UNSUPPORTED: the shards' sums would have to be combined before the products are formed); an unbound plan; inside a graph
+ * capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes the checks in
+ * front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_current_info answers for it, for sizing. */
+int vvhip_current_start(vvhip_plan* plan, const vvhip_current_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the ordinal at 0 with no
+ * live origin: the step schedule continues without gap or repeat. */
+int vvhip_current_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_current_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and ring are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_current_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_current_info(const vvhip_plan* plan, vvhip_current_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

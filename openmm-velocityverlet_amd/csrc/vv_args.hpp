@@ -422,4 +422,34 @@ struct RdfArgs {
     double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
 };
 
+// Current sample (vv_dev_current.inc, include/vvhip.h: vvhip_current_* states the sums, the table and the order of its float64 adds).  The
+// sample ordinal, the origin floor and the ring are device-side words, so a replayed graph (same arguments every time) finds the origins
+// where the last sample left them and stops adding at max_samples.  One allocation: head, sums, table, ring, holds.
+enum { CUR_SAMPLES = 0, CUR_DROPPED = 1, CUR_OUT_OF_RANGE = 2, CUR_INVALID = 3, CUR_FLOOR = 4, CUR_INV_VOLUME = 5,      // ([5]: the bits of a double)
+       CUR_BAD = 6,                 // the out-of-range particles of the sample in flight (the advance kernel zeroes it)
+       CUR_HEAD = 8 };              // the words in front of the sample's sums
+constexpr int CUR_MAX_GROUPS = 8;
+struct CurrentArgs {
+    const void* posq;               // real4 [particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const void* velm;               // mixed4
+    const int32_t* index;           // [n] the recorded particles, ordered by group, inside a group ascending
+    const double* weight;           // [n] beside index
+    const unsigned char* group;     // [n] beside index
+    long long* words;               // [CUR_HEAD] head, [G][6] the sample's sums P_x P_y P_z U_x U_y U_z, then the table, the ring, the holds
+    long long* table;               // [num_lags + 1][row_words]
+    long long* ring;                // [num_origins][G][6] the origins' sums
+    long long* hold;                // [num_origins] the ordinal of the sample a slot holds, -1: none that is usable
+    long long* slabs;               // two-level form: [num_slabs][G * 6 + 1] every reduce block's sums and bad count, rewritten by every sample; null: one level
+    int64_t max_samples;
+    int32_t n, num_groups;
+    int32_t num_lags, origin_every;
+    int32_t num_origins, row_words; // ceil(num_lags / origin_every); 1 + 3 (ND + NC)
+    int32_t num_slabs, pad_;        // the reduce's blocks (set by the launcher)
+    double scale_p, scale_v;        // 2^Fp, 2^Fv
+    double inv_scale_p, inv_scale_v;
+    double limit_p, limit_v;        // |X_a| / |v_a| at or beyond it is out of range
+    double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
+};
+
 }  // namespace vv

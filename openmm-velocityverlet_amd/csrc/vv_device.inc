@@ -21,3 +21,4 @@
 #include "vv_dev_profile.inc"
 #include "vv_dev_msd.inc"
 #include "vv_dev_rdf.inc"
+#include "vv_dev_current.inc"

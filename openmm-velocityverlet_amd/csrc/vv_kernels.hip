@@ -513,6 +513,30 @@ hipError_t launch_rdf(int precision, const RdfArgs& a, int grid_cap, hipStream_t
     hipLaunchKernelGGL(vv_kernel_rdf_advance, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
+hipError_t launch_current(int precision, const CurrentArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: the block's LDS copy holds the groups, the row's words are the classes'
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    if (a.num_groups < 1 || a.num_groups > CUR_MAX_GROUPS || a.n < 0 || a.num_origins < 1 ||
+        a.row_words != 1 + 3 * (a.num_groups * (a.num_groups + 1) / 2 + a.num_groups * a.num_groups))
+        return hipErrorInvalidValue;
+    const dim3 g((unsigned) std::max(1, std::min((a.n + block_threads - 1) / block_threads, std::max(1, grid_cap))));
+    CurrentArgs b = a;
+    b.num_slabs = (int32_t) g.x;
+    if (b.slabs) hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_current_reduce, true), g, dim3((unsigned) block_threads), 0, s, b);
+    else hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_current_reduce, false), g, dim3((unsigned) block_threads), 0, s, b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const long long cells = (long long) (a.num_origins + 1) * (a.row_words - 1);
+    const dim3 gc((unsigned) std::max<long long>(1, std::min<long long>((cells + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(vv_kernel_current_correlate, gc, dim3(256), 0, s, b);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_current_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_current_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_current_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

@@ -84,5 +84,12 @@ hipError_t launch_msd_floor(long long* words, hipStream_t s);
 // a.max_jsites * RDF_TILE >= 2^32: a block's private 32-bit words could wrap.
 size_t rdf_lds_bytes(int nbins, int copies);
 hipError_t launch_rdf(int precision, const RdfArgs& a, int grid_cap, hipStream_t s);
+// One current sample (vv_dev_current.inc): the reduce over a.n recorded particles in blocks of block_threads threads (64 .. 512, a multiple
+// of 64), at most grid_cap of them (the kernel strides beyond; one idle block where a.n = 0), the correlate kernel with one thread per
+// (ring slot or zero lag, class, component) in blocks of 256, then the one-wave kernel that stores the origin and counts the sample.
+// a.slabs selects the two-level form: it must hold (a.n + 63) / 64 + 1 slabs of a.num_groups * 6 + 1 words (no launch has more blocks).
+hipError_t launch_current(int precision, const CurrentArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as CurrentArgs::words.
+hipError_t launch_current_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

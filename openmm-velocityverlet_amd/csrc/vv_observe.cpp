@@ -1,5 +1,5 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
+// the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current correlations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
 // ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
 #include "vv_plan.hpp"
 
@@ -137,6 +137,39 @@ static int rdf_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_rdf(p->hp.precision, a, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ collective current correlations (vvhip_current_*)
+// One sample behind the step just enqueued (or captured), and behind its RDF sample: the reduce, the correlate and the one-wave kernel that
+// stores the origin and counts the sample.  Three launches, no memset and no host synchronisation.  1 / V is an argument: what changes the
+// box drops the captured graphs.
+static int current_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Current& K = p->current;
+    const vvhip_current_layout& L = K.lay;
+    vv::CurrentArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.index = K.d_index.get(); a.weight = K.d_weight.get(); a.group = K.d_group.get();
+    a.words = K.d_words.get(); a.table = a.words + vv::CUR_HEAD + K.sums_words(); a.ring = a.table + L.words;
+    a.hold = a.ring + (size_t) L.num_origins * K.sums_words();
+    a.slabs = K.d_slabs.get();      // (null: one level)
+    a.max_samples = L.max_samples;
+    a.n = L.num_particles; a.num_groups = L.num_groups; a.num_lags = L.num_lags; a.origin_every = L.origin_every;
+    a.num_origins = L.num_origins; a.row_words = L.row_words;
+    a.scale_p = std::ldexp(1.0, L.frac_bits_position); a.scale_v = std::ldexp(1.0, L.frac_bits_velocity);
+    a.inv_scale_p = std::ldexp(1.0, -L.frac_bits_position); a.inv_scale_v = std::ldexp(1.0, -L.frac_bits_velocity);
+    a.limit_p = L.limit_position; a.limit_v = L.limit_velocity;
+    a.inv_volume = 1.0 / ((p->box[0] * p->box[1]) * p->box[2]);
+    // blocks as for an MSD sample: 512 threads where they still make 128 blocks, else the largest of 256, 128, 64 that does
+    int threads = p->current_block_threads;
+    if (threads == 0)
+        for (threads = 512; threads > 64 && (a.n + threads - 1) / threads < 128; threads /= 2) {}
+    HIP_TRY(p, vv::launch_current(p->hp.precision, a, threads, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    return VVHIP_OK;
+}
+// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
+int current_positions_rewritten(vvhip_plan* p) {
+    if (!p->current.on) return VVHIP_OK;
+    HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -176,14 +209,16 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 // profile sample, then the MSD sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
 // (one-off calls allocate it too), and of a profile the WHOLE allocation, counts and table: a row or a frame written twice is the same row
 // or frame, a sample added twice is not the same table.  Of an MSD recorder likewise the whole allocation, the ring of origins included.
-// The RDF sample goes last, behind the MSD sample; its late words are counts and table (its gather scratch is rewritten by every sample).
+// The RDF sample goes behind the MSD sample; its late words are counts and table (its gather scratch is rewritten by every sample).  The
+// current sample goes last; its late words are the whole allocation, as the MSD's.
 Riders riders(vvhip_plan* p) {
     return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue},
              {p->msd.on, p->msd.when, false, p->msd.on ? p->msd.d_words.get() : nullptr, p->msd.bytes(), msd_enqueue},
-             {p->rdf.on, p->rdf.when, false, p->rdf.on ? p->rdf.d_words.get() : nullptr, p->rdf.bytes(), rdf_enqueue}}};
+             {p->rdf.on, p->rdf.when, false, p->rdf.on ? p->rdf.d_words.get() : nullptr, p->rdf.bytes(), rdf_enqueue},
+             {p->current.on, p->current.when, false, p->current.on ? p->current.d_words.get() : nullptr, p->current.bytes(), current_enqueue}}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -202,6 +237,7 @@ static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
 static void profile_release(vvhip_plan* p) { p->profile = vvhip_plan::Profile{}; }
 static void msd_release(vvhip_plan* p) { p->msd = vvhip_plan::Msd{}; }
 static void rdf_release(vvhip_plan* p) { p->rdf = vvhip_plan::Rdf{}; }
+static void current_release(vvhip_plan* p) { p->current = vvhip_plan::Current{}; }
 // frexp's view of a positive finite x: the smallest power of two >= x / > x, and the exponent of a power of two
 static double pow2_at_least(double x) { int e; const double f = std::frexp(x, &e); return f == 0.5 ? x : std::ldexp(1.0, e); }
 static double pow2_above(double x) { int e; (void) std::frexp(x, &e); return std::ldexp(1.0, e); }
@@ -940,6 +976,126 @@ int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) {
     if (!p || !out) return VVHIP_ERR_INVALID;
     vvhip_rdf_layout r{};
     if (p->rdf.described) { r = p->rdf.lay; r.active = p->rdf.on; }
+    *out = r;
+    return VVHIP_OK;
+}
+
+int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "current: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "current: interval must be >= 1 step");
+    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "current: num_lags must be in [1, 4096]");
+    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "current: origin_every must be in [1, num_lags]");
+    if (d->num_groups < 1 || d->num_groups > vv::CUR_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "current: num_groups must be in [1, 8]");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "current: max_samples must be >= 1");
+    if (!(d->limit_position >= 0) || !std::isfinite(d->limit_position)) return fail(p, VVHIP_ERR_INVALID, "current: limit_position must be finite and >= 0 (0: the default of 64 nm)");
+    if (!(d->limit_velocity >= 0) || !std::isfinite(d->limit_velocity)) return fail(p, VVHIP_ERR_INVALID, "current: limit_velocity must be finite and >= 0 (0: the default of 64 nm/ps)");
+    if (!d->weight) return fail(p, VVHIP_ERR_INVALID, "current: weight must not be NULL");
+    const vv::HostPlan& hp = p->hp;
+    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
+        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
+            return fail(p, VVHIP_ERR_INVALID, "current: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    for (int32_t i = 0; i < hp.num_atoms; i++)
+        if (!std::isfinite(d->weight[i])) return fail(p, VVHIP_ERR_INVALID, "current: weight[" + std::to_string(i) + "] is not finite");
+    // ---- the recorded particles, the layout and the fixed point, host only
+    vvhip_plan::Current N;
+    vvhip_current_layout& L = N.lay;
+    struct Unit { int group; int32_t id; };
+    std::vector<Unit> units;
+    double wmax = 0;
+    for (int32_t i = 0; i < hp.num_atoms; i++) {
+        const int g = d->group ? (int) d->group[i] : 0;
+        if (g < 0) continue;
+        units.push_back({g, i});
+        wmax = std::max(wmax, std::fabs(d->weight[i]));
+    }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
+    const int G = d->num_groups;
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.num_groups = G;
+    L.max_samples = d->max_samples;
+    L.num_particles = (int32_t) units.size();
+    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.num_disp_classes = G * (G + 1) / 2; L.num_cur_classes = G * G;
+    L.row_words = 1 + 3 * (L.num_disp_classes + L.num_cur_classes);
+    L.words = (int64_t) (L.num_lags + 1) * L.row_words;
+    L.ring_bytes = (int64_t) L.num_origins * (G * 6 + 1) * (int64_t) sizeof(long long);
+    L.limit_position = d->limit_position > 0 ? pow2_at_least(d->limit_position) : 64.0;
+    L.limit_velocity = d->limit_velocity > 0 ? pow2_at_least(d->limit_velocity) : 64.0;
+    L.weight_bound = wmax > 0 ? pow2_above(wmax) : 1.0;
+    const int head_room = 62 - ceil_log2((long long) units.size() + 1) - std::ilogb(L.weight_bound);
+    L.frac_bits_position = std::min(40, head_room - std::ilogb(L.limit_position));
+    L.frac_bits_velocity = std::min(40, head_room - std::ilogb(L.limit_velocity));
+    for (int q = 0; q < 2; q++) {
+        const int f = q ? L.frac_bits_velocity : L.frac_bits_position;
+        if (f < 8)
+            return fail(p, VVHIP_ERR_INVALID, std::string("current: the ") + (q ? "velocity" : "position") + " sums would keep " + std::to_string(f) + " fraction bits (< 8) with " +
+                                              std::to_string(units.size()) + " particles, weights below " + std::to_string(L.weight_bound) + " and limit " +
+                                              std::to_string(q ? L.limit_velocity : L.limit_position) + ": lower the limit or scale the weights");
+    }
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "current: a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
+                                              "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
+    for (const Unit& u : units) { N.index.push_back(u.id); N.weight.push_back(d->weight[u.id]); N.group.push_back((unsigned char) u.group); }
+    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
+    if (p->capturing || p->current.on) TRY(quiesce(p, "current", true, true));
+    current_release(p);
+    vvhip_plan::Current& K = p->current;
+    K = std::move(N);
+    K.when = {d->interval, SCHEDULE_LINEAR};
+    K.lay.start_step = p->cur.step_count;
+    K.described = true;
+    NEED_BOUND(p);
+    TRY(quiesce(p, "current", true, true));
+    auto alloc_fail = [&](hipError_t e, size_t bytes) {
+        K.d_words.reset(); K.d_index.reset(); K.d_weight.reset(); K.d_group.reset(); K.d_slabs.reset();
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string("current: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
+    };
+    hipError_t e = vv::zeros(K.d_words, K.bytes(), p->stream);
+    if (e != hipSuccess) return alloc_fail(e, K.bytes());
+    if ((e = vv::upload(K.d_index, K.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.index.size() * sizeof(int32_t)));
+    if ((e = vv::upload(K.d_weight, K.weight, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.weight.size() * sizeof(double)));
+    if ((e = vv::upload(K.d_group, K.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.group.size()));
+    if (p->current_two_level && (e = vv::zeros(K.d_slabs, K.slab_words() * sizeof(long long), p->stream)) != hipSuccess) return alloc_fail(e, K.slab_words() * sizeof(long long));
+    // (no slot holds a sample: the slots' words, the allocation's last num_origins, are -1)
+    HIP_TRY(p, hipMemsetAsync(K.d_words.get() + K.bytes() / sizeof(long long) - K.lay.num_origins, 0xFF, (size_t) K.lay.num_origins * sizeof(long long), p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    K.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
+    K.on = true;
+    return VVHIP_OK;
+}
+int vvhip_current_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_current_counts* out, int32_t reset) {
+    NEED_BOUND(p);
+    vvhip_plan::Current& K = p->current;
+    if (!K.on) return fail(p, VVHIP_ERR_INVALID, "current: none started (vvhip_current_start)");
+    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < K.lay.words))
+        return fail(p, VVHIP_ERR_INVALID, "current: the table has " + std::to_string((long long) K.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
+    TRY(quiesce(p, "current", true, false));
+    long long head[vv::CUR_HEAD];
+    HIP_TRY(p, hipMemcpy(head, K.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
+    if (words_out) HIP_TRY(p, hipMemcpy(words_out, K.d_words.get() + vv::CUR_HEAD + K.sums_words(), (size_t) K.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    if (out) {
+        double s;
+        std::memcpy(&s, &head[vv::CUR_INV_VOLUME], sizeof s);
+        *out = {head[vv::CUR_SAMPLES], head[vv::CUR_DROPPED], head[vv::CUR_OUT_OF_RANGE], head[vv::CUR_INVALID], head[vv::CUR_FLOOR], s};
+    }
+    if (reset) {      // (head, sums and table to zero, the slots' words to -1: no slot holds a sample, so the ring may keep its bits)
+        HIP_TRY(p, hipMemsetAsync(K.d_words.get(), 0, K.front_words() * sizeof(long long), p->stream));
+        HIP_TRY(p, hipMemsetAsync(K.d_words.get() + K.bytes() / sizeof(long long) - K.lay.num_origins, 0xFF, (size_t) K.lay.num_origins * sizeof(long long), p->stream));
+        HIP_TRY(p, hipStreamSynchronize(p->stream));
+    }
+    return VVHIP_OK;
+}
+int vvhip_current_stop(vvhip_plan* p) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing || p->current.on) TRY(quiesce(p, "current", true, true));
+    current_release(p);                                 // (also the description an unbound plan kept)
+    return VVHIP_OK;
+}
+int vvhip_current_info(const vvhip_plan* p, vvhip_current_layout* out) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    vvhip_current_layout r{};
+    if (p->current.described) { r = p->current.lay; r.active = p->current.on; }
     *out = r;
     return VVHIP_OK;
 }

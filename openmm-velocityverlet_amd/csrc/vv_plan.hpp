@@ -80,7 +80,7 @@ inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (u
 inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
-constexpr int kRiders = 6;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample, RDF sample
+constexpr int kRiders = 7;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample, RDF sample, current sample
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -150,6 +150,8 @@ struct vvhip_plan {
     int profile_grid_cap = 256;    // most blocks of a profile sample's accumulating kernel, besides grid_cap_a: every block flushes a table of its own (test hook "profile_grid_cap"; TUNING_LOG.md)
     int msd_block_threads = 0;     // threads per block of an MSD sample's accumulating kernel, 0: by the number of units (msd_enqueue; test hook "msd_block_threads")
     int msd_wave_reduce = 1;       // an MSD sample's waves whose units share a group add their four sums once (test hook "msd_wave_reduce": 0 = every lane adds; same bits)
+    int current_two_level = 0;     // a current sample's reduce stores per-block slabs that the correlate kernel sums, instead of agent-scope adds (test hook "current_two_level", read at the start; same bits; TUNING_LOG.md)
+    int current_block_threads = 0; // threads per block of a current sample's reduce, 0: by the number of particles (current_enqueue; test hook "current_block_threads"; same bits)
     int rdf_hist_copies = 1;       // private histograms per block of an RDF sample's pair kernel: 1, or 4 = one per wave where they fit the LDS budget (test hook "rdf_hist_copies"; same bits; TUNING_LOG.md)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
@@ -390,6 +392,25 @@ struct vvhip_plan {
         int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
         size_t bytes() const { return (size_t) (vv::RDF_HEAD + lay.words) * sizeof(long long); }
     } rdf;
+    // Collective current correlations (vvhip_current_*; vv_dev_current.inc), scheduled by cur.step_count.  `described` / `on` as for the
+    // profiles.  The compact list of the recorded particles, ordered by group, then by index, is built when the recorder starts
+    struct Current {
+        bool on = false, described = false;
+        Schedule when;                            // (linear)
+        vvhip_current_layout lay{};
+        std::vector<int32_t> index;               // [num_particles] the recorded particles
+        std::vector<double> weight;               // beside index
+        std::vector<unsigned char> group;         // beside index
+        vv::DevBuf<int32_t> d_index;
+        vv::DevBuf<double> d_weight;
+        vv::DevBuf<unsigned char> d_group;
+        vv::DevBuf<long long> d_words;            // head, sums, table, ring, the slots' words -- ALL of it the rider's late words
+        vv::DevBuf<long long> d_slabs;            // two-level form only: the reduce blocks' slabs, rewritten by every sample, not saved
+        size_t slab_words() const { return ((size_t) (lay.num_particles + 63) / 64 + 1) * (sums_words() + 1); }
+        size_t sums_words() const { return (size_t) lay.num_groups * 6; }
+        size_t front_words() const { return (size_t) vv::CUR_HEAD + sums_words() + (size_t) lay.words; }      // what a reset zeroes
+        size_t bytes() const { return front_words() * sizeof(long long) + (size_t) lay.ring_bytes; }
+    } current;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -521,6 +542,7 @@ int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
 int msd_positions_rewritten(vvhip_plan* p);      // vvhip_barostat_scale / _restore: an MSD recorder's origins so far are dead
+int current_positions_rewritten(vvhip_plan* p);  // ... and a current recorder's
 // One of the device work items that hang on the plan's step counter.  A new one is a descriptor in riders() with its enqueue function and its
 // entry points: the step hooks, the graph keys (vv_run.cpp) and the recovery (recovery_items) walk the list.
 struct Rider {
@@ -541,7 +563,8 @@ Riders riders(vvhip_plan* p);
 // frame recorder these are the cursors: the repeat writes the same rows and frames at the same places.  For a profile recorder they are the
 // whole allocation, counts and table: an accumulating table is not idempotent under the repeat, so it goes back as the snapshot took it.
 // For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.  For an RDF
-// recorder counts and table; its gather scratch is rewritten by every sample and is not saved.
+// recorder counts and table; its gather scratch is rewritten by every sample and is not saved.  For a current recorder the whole
+// allocation again: head, sums, table and the ring of origins.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

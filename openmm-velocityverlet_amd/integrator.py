@@ -20,7 +20,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import vvhip as H
-from .systems import SystemSpec
+from .systems import BOLTZ, SystemSpec
 
 
 def padded(n: int) -> int:
@@ -476,6 +476,137 @@ def rdf_from_words(words, layout, counts) -> Rdf:
                counts=table)
 
 
+# Conductivity in S/m from e^2 / (nm ps kJ/mol): CODATA 2018 elementary charge (C) and Avogadro constant (1/mol), both exact.
+ELEMENTARY_CHARGE = 1.602176634e-19
+AVOGADRO = 6.02214076e23
+SIEMENS_PER_METRE = ELEMENTARY_CHARGE * ELEMENTARY_CHARGE * AVOGADRO / (1e-9 * 1e-12 * 1e3)
+
+
+def current_weights(system, molecules: bool = False) -> np.ndarray:
+    """float64 [num_atoms]: the weights of a current recorder (include/vvhip.h: vvhip_current_*).  The charges q_i, or with molecules=True
+    Q_m m_i / M_m with Q_m and M_m summed in ascending particle index (massless particles: 0), so that sum w_i X_i = sum_m Q_m COM_m."""
+    q = np.ascontiguousarray(system.charges, dtype=np.float64)
+    if not molecules:
+        return q.copy()
+    m = np.ascontiguousarray(system.masses, dtype=np.float64)
+    mol = np.ascontiguousarray(system.mol_id, dtype=np.int64)
+    nmol = int(mol.max()) + 1 if mol.size else 0
+    Q = np.bincount(mol, weights=q, minlength=nmol)                  # (sequential float64 sums in ascending particle index)
+    M = np.bincount(mol, weights=m, minlength=nmol)
+    heavy = (m > 0) & (M[mol] > 0)
+    return np.where(heavy, Q[mol] * m / np.where(M[mol] > 0, M[mol], 1.0), 0.0)
+
+
+@dataclasses.dataclass
+class Currents:
+    """Collective current correlations per lag (Context.current_read; include/vvhip.h: vvhip_current_* states the sums, the schedule and
+    the table).  `words` is the device's table as it stands, int64 [num_lags + 1, 1 + 3 (ND + NC)]: the count, then the bits of the float64
+    sums disp[ND][3] and cur[NC][3]; row l is the lag of l * interval steps, row 0 the zero lag."""
+    samples: int                           # samples taken, valid or not
+    dropped: int                           # samples that were due past max_samples
+    out_of_range: int                      # recorded particles found out of range
+    invalid_samples: int                   # samples with at least one of them: they add nothing and are no origin
+    origin_floor: int                      # origins with an ordinal below it are dead (a barostat move rewrote the positions)
+    inv_volume_sum: float                  # the valid samples' 1 / V (nm^-3), summed in sample order
+    interval: int
+    origin_every: int
+    num_groups: int
+    frac_bits_position: int
+    frac_bits_velocity: int
+    words: np.ndarray                      # int64 [num_lags + 1, row_words]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [num_lags + 1]: row l is the lag of l * interval steps."""
+        return np.arange(self.words.shape[0], dtype=np.int64) * self.interval
+
+    @property
+    def count(self) -> np.ndarray:
+        """int64 [num_lags + 1]: the time origins behind every row."""
+        return self.words[:, 0]
+
+    @property
+    def mean_inv_volume(self) -> float:
+        """<1 / V> in nm^-3 over the valid samples, NaN without one."""
+        valid = self.samples - self.invalid_samples
+        return self.inv_volume_sum / valid if valid > 0 else float("nan")
+
+    def _mean(self, first_word: int) -> np.ndarray:
+        n = self.count[:, None]
+        sums = np.ascontiguousarray(self.words[:, first_word:first_word + 3]).view(np.float64)
+        return np.where(n > 0, sums / np.where(n > 0, n, 1), np.nan)
+
+    def displacement(self, g: int, h: int) -> np.ndarray:
+        """float64 [num_lags + 1, 3]: <dP_g,a(t) dP_h,a(t)> in (weight nm)^2 for a = x, y, z; symmetric in g, h.  Row 0 is 0."""
+        G = self.num_groups
+        g, h = (int(g), int(h)) if g <= h else (int(h), int(g))
+        if not 0 <= g <= h < G:
+            raise ValueError("groups must be in [0, %d)" % G)
+        c = g * G - g * (g - 1) // 2 + (h - g)
+        return self._mean(1 + 3 * c)
+
+    def correlation(self, g: int, h: int) -> np.ndarray:
+        """float64 [num_lags + 1, 3]: <J_g,a(0) J_h,a(t)> in (weight nm/ps)^2 for a = x, y, z; the origin is the first index."""
+        G = self.num_groups
+        if not (0 <= int(g) < G and 0 <= int(h) < G):
+            raise ValueError("groups must be in [0, %d)" % G)
+        return self._mean(1 + 3 * (G * (G + 1) // 2 + int(g) * G + int(h)))
+
+    def _per_kt(self, T: float) -> float:
+        return SIEMENS_PER_METRE * self.mean_inv_volume / (BOLTZ * float(T))
+
+    def conductivity_einstein_partial(self, T: float, dt: float, fit) -> np.ndarray:
+        """float64 [G, G] in S/m: entry (g, h) is the least-squares slope of sum_a <dP_g,a dP_h,a> against the lag time (lag_steps * dt, dt in
+        ps) over rows fit = (lo, hi), inclusive, divided by 6 V kB T.  Symmetric; the sum over ALL entries is conductivity_einstein."""
+        lo, hi = int(fit[0]), int(fit[1])
+        rows = slice(lo, hi + 1)
+        t = self.lag_steps[rows].astype(np.float64) * float(dt)
+        if t.size < 2:
+            raise ValueError("a slope needs at least two lags")
+        tc = t - t.mean()
+        G = self.num_groups
+        out = np.empty((G, G))
+        for g in range(G):
+            for h in range(g, G):
+                y = self.displacement(g, h)[rows].sum(axis=1)
+                out[g, h] = out[h, g] = ((y - y.mean()) * tc).sum() / (tc * tc).sum() * self._per_kt(T) / 6.0
+        return out
+
+    def conductivity_einstein(self, T: float, dt: float, fit) -> float:
+        """The Einstein-Helfand conductivity in S/m: slope / (6 V kB T), the slope of <|dM(t)|^2> summed over all classes, with the weights
+        in e, T in K, dt in ps and 1 / V the recorded mean."""
+        return float(self.conductivity_einstein_partial(T, dt, fit).sum())
+
+    def conductivity_green_kubo_partial(self, T: float, dt: float, upto: int) -> np.ndarray:
+        """float64 [G, G] in S/m: entry (g, h) is the trapezoid of sum_a <J_g,a(0) J_h,a(t)> over rows 0 .. upto against the lag time,
+        divided by 3 V kB T.  The sum over all entries is conductivity_green_kubo."""
+        upto = int(upto)
+        if not 1 <= upto < self.words.shape[0]:
+            raise ValueError("upto must be in [1, num_lags]")
+        h_t = float(self.interval) * float(dt)
+        G = self.num_groups
+        out = np.empty((G, G))
+        for g in range(G):
+            for h in range(G):
+                y = self.correlation(g, h)[: upto + 1].sum(axis=1)
+                out[g, h] = (0.5 * (y[0] + y[-1]) + y[1:-1].sum()) * h_t * self._per_kt(T) / 3.0
+        return out
+
+    def conductivity_green_kubo(self, T: float, dt: float, upto: int) -> float:
+        """The Green-Kubo conductivity in S/m: the trapezoid of <J(0) . J(t)> over rows 0 .. upto, summed over all classes, / (3 V kB T)."""
+        return float(self.conductivity_green_kubo_partial(T, dt, upto).sum())
+
+
+def currents_from_words(words, layout, counts) -> Currents:
+    """A Currents from a table's int64 words, its layout (H.CurrentLayout) and counts (H.CurrentCounts)."""
+    words = np.ascontiguousarray(words, dtype=np.int64).reshape(int(layout.num_lags) + 1, int(layout.row_words))
+    return Currents(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range),
+                    invalid_samples=int(counts.invalid_samples), origin_floor=int(counts.origin_floor),
+                    inv_volume_sum=float(counts.inv_volume_sum), interval=int(layout.interval), origin_every=int(layout.origin_every),
+                    num_groups=int(layout.num_groups), frac_bits_position=int(layout.frac_bits_position),
+                    frac_bits_velocity=int(layout.frac_bits_velocity), words=words)
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -858,6 +989,52 @@ class Context:
         H.check(H.lib.vvhip_rdf_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
         return rdf_from_words(words[: info.words], info, counts)
 
+    # ---- collective current correlations accumulated on the device inside the steps (include/vvhip.h: vvhip_current_*)
+    def current_start(self, interval: int, num_lags: int, origin_every: int = 1, weights=None, molecules: bool = False, groups=None,
+                      max_samples: int = 1 << 20, limit_position: float = 0.0, limit_velocity: float = 0.0):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), sum w_i X_i and w_i v_i per group
+        as fixed-point integers and correlate the sums against the stored origins: per lag of 0 .. `num_lags` samples the products of the
+        groups' collective displacements and currents, in float64 in sample order, so that the table is the same bits for any launch
+        shape.  `weights`: one float per particle of the System; None: the charges, or with molecules=True Q_m m_i / M_m (the molecules'
+        centres of mass carry their net charge).  Every `origin_every`-th sample is stored as an origin.  `groups`: one int per particle
+        (-1: not recorded, at most 8 groups); None: everything in group 0.  A position or velocity component at or beyond its limit (nm,
+        nm/ps; 0: 64) makes the whole sample invalid.  A sharded context raises ERR_UNSUPPORTED.  No host synchronisation until
+        current_read."""
+        n = self.system.num_atoms
+        if weights is None:
+            w = current_weights(self.system, molecules)
+        else:
+            if molecules:
+                raise ValueError("give either weights or molecules=True")
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n:
+            raise ValueError("weights must have one entry per particle of the System")
+        grp = None
+        if groups is not None:
+            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+            if grp.size != n:
+                raise ValueError("groups must have one entry per particle of the System")
+        desc = H.CurrentDesc(int(interval), int(num_lags), int(origin_every), 1 if grp is None else max(int(grp.max()) + 1, 1), w.ctypes.data,
+                             None if grp is None else grp.ctypes.data, int(max_samples), float(limit_position), float(limit_velocity))
+        H.check(H.lib.vvhip_current_start(self.plan, C.byref(desc)), self.plan)
+
+    def current_stop(self):
+        H.check(H.lib.vvhip_current_stop(self.plan), self.plan)
+
+    def current_info(self) -> H.CurrentLayout:
+        out = H.CurrentLayout()
+        H.check(H.lib.vvhip_current_info(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def current_read(self, reset: bool = False) -> Currents:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        info = self.current_info()
+        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
+        counts = H.CurrentCounts()
+        H.check(H.lib.vvhip_current_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
+        return currents_from_words(words[: info.words], info, counts)
+
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
         """Subtract the centre-of-mass velocity of all massive particles in front of every step whose 0-based number (steps counted as for
@@ -930,7 +1107,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD or RDF recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF or current recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

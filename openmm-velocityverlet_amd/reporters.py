@@ -22,6 +22,8 @@ latest three kept.
 
 ``write_rdf`` writes device-side radial distribution functions (``Context.rdf_read``) as text columns, one line per bin.
 
+``write_current`` writes a device-side collective current correlation table (``Context.current_read``) as text columns, one line per lag.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -268,6 +270,37 @@ def write_rdf(file, rdf, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for b in range(rdf.counts.shape[1]):
             print(*[repr(float(v[b])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def current_columns(cur, dt):
+    """[(name, values per lag)] of a current table's text file: the lag in ps, the count, then per displacement class g <= h
+    sum_a <dP_g,a dP_h,a> and per current class (g, h) sum_a <J_g,a(0) J_h,a(t)>."""
+    cols = [("lag (ps)", cur.lag_steps.astype(np.float64) * float(dt)), ("count", cur.count.astype(np.float64))]
+    G = cur.num_groups
+    cols += [("disp[%d-%d] (e^2 nm^2)" % (g, h), cur.displacement(g, h).sum(axis=1)) for g in range(G) for h in range(g, G)]
+    cols += [("cur[%d-%d] (e^2 nm^2/ps^2)" % (g, h), cur.correlation(g, h).sum(axis=1)) for g in range(G) for h in range(G)]
+    return cols
+
+
+def write_current(file, cur, dt, append=False, header=True):
+    """A collective current correlation table (Context.current_read) as text: two comment lines (samples, dropped, out of range, invalid
+    samples, origin floor, the sum of 1 / V; the column names) unless header=False, then one tab-separated line per lag from the zero lag
+    on -- the lag in ps (lag steps x `dt`), the count of time origins, per pair of groups g <= h the mean product of the collective
+    displacements summed over x, y, z, and per ordered pair (g, h) the mean product of the currents (nan where a lag has no origin).
+    Floats are written with repr, so np.loadtxt reads back the bits.  `file`: a path or an open text stream."""
+    cols = current_columns(cur, dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"InvalidSamples"\t%d\t"OriginFloor"\t%d\t"InvVolumeSum"\t%r' %
+                  (cur.samples, cur.dropped, cur.out_of_range, cur.invalid_samples, cur.origin_floor, float(cur.inv_volume_sum)), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for l in range(cur.words.shape[0]):
+            print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:
         if own:

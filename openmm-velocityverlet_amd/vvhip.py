@@ -182,6 +182,26 @@ class RdfLayout(C.Structure):
                 ("scratch_bytes", C.c_int64), ("start_step", C.c_int64), ("r_max", C.c_double), ("dr", C.c_double)]
 
 
+class CurrentDesc(C.Structure):
+    """What a current recorder is to accumulate (include/vvhip.h: vvhip_current_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("weight", C.c_void_p), ("group", C.c_void_p), ("max_samples", C.c_int64), ("limit_position", C.c_double),
+                ("limit_velocity", C.c_double)]
+
+
+class CurrentCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64), ("invalid_samples", C.c_int64),
+                ("origin_floor", C.c_int64), ("inv_volume_sum", C.c_double)]
+
+
+class CurrentLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("num_particles", C.c_int32), ("num_origins", C.c_int32), ("num_disp_classes", C.c_int32), ("num_cur_classes", C.c_int32),
+                ("row_words", C.c_int32), ("frac_bits_position", C.c_int32), ("frac_bits_velocity", C.c_int32), ("max_samples", C.c_int64),
+                ("words", C.c_int64), ("ring_bytes", C.c_int64), ("start_step", C.c_int64), ("limit_position", C.c_double),
+                ("limit_velocity", C.c_double), ("weight_bound", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -270,6 +290,8 @@ def _load():
         "vvhip_profile_read": [vp, vp, C.c_int64, P(ProfileCounts), i32], "vvhip_debug_recover": [vp],
         "vvhip_msd_start": [vp, P(MsdDesc)], "vvhip_msd_stop": [vp], "vvhip_msd_info": [vp, P(MsdLayout)],
         "vvhip_msd_read": [vp, vp, C.c_int64, P(MsdCounts), i32],
+        "vvhip_current_start": [vp, P(CurrentDesc)], "vvhip_current_stop": [vp], "vvhip_current_info": [vp, P(CurrentLayout)],
+        "vvhip_current_read": [vp, vp, C.c_int64, P(CurrentCounts), i32],
         "vvhip_rdf_start": [vp, P(RdfDesc)], "vvhip_rdf_sample": [vp], "vvhip_rdf_stop": [vp], "vvhip_rdf_info": [vp, P(RdfLayout)],
         "vvhip_rdf_read": [vp, vp, C.c_int64, P(RdfCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
