@@ -1,6 +1,8 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
-// the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current correlations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled
-// ones are listed once (riders: when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.
+// the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
+// correlations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The four accumulating recorders
+// share one life cycle (recorder_*).
 #include "vv_plan.hpp"
 
 #include <algorithm>
@@ -73,13 +75,22 @@ static int profile_enqueue(vvhip_plan* p) {
     const vvhip_profile_layout& L = P.lay;
     vv::ProfileArgs a{};
     a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
-    a.index = P.index.empty() ? nullptr : P.d_index.get(); a.group = P.grouped ? P.d_group.get() : nullptr; a.mass = P.d_mass.get();
+    a.index = P.index.empty() ? nullptr : P.dev.index.get(); a.group = P.grouped ? P.dev.group.get() : nullptr; a.mass = P.dev.mass.get();
     a.words = P.d_words.get(); a.max_samples = L.max_samples;
     a.n = L.num_particles; a.nbins = L.nbins; a.axis = L.axis; a.mask = L.mask; a.rows = L.rows; a.table_words = (int32_t) L.words;
     a.inv_L = 1.0 / p->box[L.axis];
     for (int q = 0; q < 4; q++) { a.scale[q] = std::ldexp(1.0, L.frac_bits[q + 1]); a.limit[q] = L.limit[q + 1]; }
     HIP_TRY(p, vv::launch_profile(p->hp.precision, a, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
+}
+// The threads per block of an MSD or current sample's accumulating kernel (`pinned` != 0: a test hook's): 512 where they still make 128
+// blocks, else the largest of 256, 128, 64 that does (64 at the least): few units in few blocks leave their gathers to a handful of CUs
+// (TUNING_LOG.md)
+static int block_threads_for(int pinned, int n) {
+    int threads = pinned;
+    if (threads == 0)
+        for (threads = 512; threads > 64 && (n + threads - 1) / threads < 128; threads /= 2) {}
+    return threads;
 }
 // ------------------------------------------------------------------------------------------ mean-squared displacements (vvhip_msd_*)
 // One sample behind the step just enqueued (or captured), and behind its profile sample: the accumulating kernel and the one-thread kernel
@@ -90,20 +101,15 @@ static int msd_enqueue(vvhip_plan* p) {
     vv::MsdArgs a{};
     a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
     const bool molecules = L.mode == VVHIP_MSD_MOLECULES;
-    a.index = M.index.empty() ? nullptr : M.d_index.get();
-    a.first = molecules ? M.d_first.get() : nullptr; a.weight = molecules ? M.d_weight.get() : nullptr; a.total = molecules ? M.d_total.get() : nullptr;
-    a.group = M.grouped ? M.d_group.get() : nullptr;
-    a.words = M.d_words.get(); a.ring = (double*) (M.d_words.get() + vv::MSD_HEAD + L.words);
+    a.index = M.index.empty() ? nullptr : M.dev.index.get();
+    a.first = molecules ? M.dev.first.get() : nullptr; a.weight = molecules ? M.dev.weight.get() : nullptr; a.total = molecules ? M.dev.total.get() : nullptr;
+    a.group = M.grouped ? M.dev.group.get() : nullptr;
+    a.words = M.d_words.get(); a.ring = (double*) (M.d_words.get() + M.table_offset() + L.words);
     a.max_samples = L.max_samples;
     a.n = L.num_units; a.stride = M.stride(); a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
     a.table_words = (int32_t) L.words; a.wave_reduce = p->msd_wave_reduce;
     a.scale = std::ldexp(1.0, L.frac_bits); a.limit = L.limit;
-    // blocks of 512 threads where they still make 128 blocks, else the largest of 256, 128, 64 that does (64 at the least): few units in
-    // few blocks leave their gathers to a handful of CUs (TUNING_LOG.md)
-    int threads = p->msd_block_threads;
-    if (threads == 0)
-        for (threads = 512; threads > 64 && (a.n + threads - 1) / threads < 128; threads /= 2) {}
-    HIP_TRY(p, vv::launch_msd(p->hp.precision, a, threads, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    HIP_TRY(p, vv::launch_msd(p->hp.precision, a, block_threads_for(p->msd_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
 // vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
@@ -123,8 +129,8 @@ static int rdf_enqueue(vvhip_plan* p) {
     const vvhip_rdf_layout& L = R.lay;
     vv::RdfArgs a{};
     a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
-    a.index = R.d_index.get(); a.mol = L.exclude_same_molecule ? R.d_mol.get() : nullptr; a.items = R.d_items.get();
-    a.scratch = R.d_scratch.get(); a.words = R.d_words.get();
+    a.index = R.dev.index.get(); a.mol = L.exclude_same_molecule ? R.dev.mol.get() : nullptr; a.items = R.dev.items.get();
+    a.scratch = R.dev.scratch.get(); a.words = R.d_words.get();
     a.max_samples = L.max_samples;
     a.n = (int32_t) R.index.size(); a.stride = R.stride(); a.nbins = L.nbins; a.num_items = (int32_t) R.items.size();
     // (one histogram per wave only where all of them fit beside the staged tile)
@@ -146,10 +152,10 @@ static int current_enqueue(vvhip_plan* p) {
     const vvhip_current_layout& L = K.lay;
     vv::CurrentArgs a{};
     a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
-    a.index = K.d_index.get(); a.weight = K.d_weight.get(); a.group = K.d_group.get();
-    a.words = K.d_words.get(); a.table = a.words + vv::CUR_HEAD + K.sums_words(); a.ring = a.table + L.words;
+    a.index = K.dev.index.get(); a.weight = K.dev.weight.get(); a.group = K.dev.group.get();
+    a.words = K.d_words.get(); a.table = a.words + K.table_offset(); a.ring = a.table + L.words;
     a.hold = a.ring + (size_t) L.num_origins * K.sums_words();
-    a.slabs = K.d_slabs.get();      // (null: one level)
+    a.slabs = K.dev.slabs.get();    // (null: one level)
     a.max_samples = L.max_samples;
     a.n = L.num_particles; a.num_groups = L.num_groups; a.num_lags = L.num_lags; a.origin_every = L.origin_every;
     a.num_origins = L.num_origins; a.row_words = L.row_words;
@@ -157,11 +163,7 @@ static int current_enqueue(vvhip_plan* p) {
     a.inv_scale_p = std::ldexp(1.0, -L.frac_bits_position); a.inv_scale_v = std::ldexp(1.0, -L.frac_bits_velocity);
     a.limit_p = L.limit_position; a.limit_v = L.limit_velocity;
     a.inv_volume = 1.0 / ((p->box[0] * p->box[1]) * p->box[2]);
-    // blocks as for an MSD sample: 512 threads where they still make 128 blocks, else the largest of 256, 128, 64 that does
-    int threads = p->current_block_threads;
-    if (threads == 0)
-        for (threads = 512; threads > 64 && (a.n + threads - 1) / threads < 128; threads /= 2) {}
-    HIP_TRY(p, vv::launch_current(p->hp.precision, a, threads, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    HIP_TRY(p, vv::launch_current(p->hp.precision, a, block_threads_for(p->current_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
 // vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
@@ -205,20 +207,22 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
     return VVHIP_OK;
 }
 // ------------------------------------------------------------------------------------------ the step's scheduled riders
-// In this order everywhere (item k of GraphKey::due, of Recovery::late): behind a step the series' row goes first, then the frame, then the
-// profile sample, then the MSD sample.  `late`: the series' and the recorder's cursors while they run, the record of the scheduled removals whenever it exists
-// (one-off calls allocate it too), and of a profile the WHOLE allocation, counts and table: a row or a frame written twice is the same row
-// or frame, a sample added twice is not the same table.  Of an MSD recorder likewise the whole allocation, the ring of origins included.
-// The RDF sample goes behind the MSD sample; its late words are counts and table (its gather scratch is rewritten by every sample).  The
-// current sample goes last; its late words are the whole allocation, as the MSD's.
+// In this order everywhere (item k of GraphKey::due, of Recovery::late), which is the order they ride in, each with its late words:
+//   0 series row        behind its step; the ring's cursor while the series runs: a row written twice is the same row
+//   1 removal of the centre-of-mass motion   in FRONT of its step; the schedule's record whenever it exists (one-off calls allocate it too)
+//   2 trajectory frame  behind the row; the ring's cursor while the recorder runs: a frame written twice is the same frame
+//   3 profile sample    behind the frame; ALL of d_words, counts and table: a sample added twice is not the same table
+//   4 MSD sample        behind the profile sample; all of d_words, the ring of origins included: the repeat needs the origins it overwrote
+//   5 RDF sample        behind the MSD sample; all of d_words, counts and table (its gather scratch is rewritten by every sample)
+//   6 current sample    last; all of d_words: head, sums, table, the ring of origins and the slots' words
+template <class R>
+static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
     return {{{p->series.on, p->series.when, false, p->series.on ? p->series.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), series_row},
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
-             {p->profile.on, p->profile.when, false, p->profile.on ? p->profile.d_words.get() : nullptr, p->profile.bytes(), profile_enqueue},
-             {p->msd.on, p->msd.when, false, p->msd.on ? p->msd.d_words.get() : nullptr, p->msd.bytes(), msd_enqueue},
-             {p->rdf.on, p->rdf.when, false, p->rdf.on ? p->rdf.d_words.get() : nullptr, p->rdf.bytes(), rdf_enqueue},
-             {p->current.on, p->current.when, false, p->current.on ? p->current.d_words.get() : nullptr, p->current.bytes(), current_enqueue}}};
+             recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
+             recorder_rider(p->current, current_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -232,16 +236,85 @@ int step_done(vvhip_plan* p) {
     p->cur.step_count++;
     return enqueue_due(p, false);
 }
-static void series_release(vvhip_plan* p) { p->series = vvhip_plan::Series{}; }
-static void frames_release(vvhip_plan* p) { p->frames = vvhip_plan::Frames{}; }
-static void profile_release(vvhip_plan* p) { p->profile = vvhip_plan::Profile{}; }
-static void msd_release(vvhip_plan* p) { p->msd = vvhip_plan::Msd{}; }
-static void rdf_release(vvhip_plan* p) { p->rdf = vvhip_plan::Rdf{}; }
-static void current_release(vvhip_plan* p) { p->current = vvhip_plan::Current{}; }
 // frexp's view of a positive finite x: the smallest power of two >= x / > x, and the exponent of a power of two
 static double pow2_at_least(double x) { int e; const double f = std::frexp(x, &e); return f == 0.5 ? x : std::ldexp(1.0, e); }
 static double pow2_above(double x) { int e; (void) std::frexp(x, &e); return std::ldexp(1.0, e); }
 static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) k++; return k; }      // smallest k with 2^k >= n (1 <= n <= 2^62)
+// max_samples + more as the fixed point counts it: 2^62 at the most
+static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
+
+// ------------------------------------------------------------------------------------------ the recorders' one life cycle
+// What the series, the frame recorder and the four accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// plan's member, `name` the prefix of its messages and the middle of its entry points' names.
+// One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
+// with it.  All of *_stop, and the front of a start over a running recorder.
+template <class R>
+static int recorder_stop(vvhip_plan* p, R vvhip_plan::* which, const char* name) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (p->capturing || (p->*which).on) TRY(quiesce(p, name, true, true));
+    p->*which = R{};
+    return VVHIP_OK;
+}
+// The tail of *_start, behind the host-only part that built `N` and every refusal of the description: the running recorder goes, the
+// description moves in (an unbound plan keeps it, and is refused only then), the device tables follow.
+template <class R>
+static int recorder_install(vvhip_plan* p, R vvhip_plan::* which, const char* name, R& N, int32_t interval) {
+    TRY(recorder_stop(p, which, name));
+    R& rec = p->*which;
+    rec = std::move(N);
+    rec.when = {interval, SCHEDULE_LINEAR};
+    rec.lay.start_step = p->cur.step_count;
+    rec.described = true;
+    NEED_BOUND(p);
+    TRY(quiesce(p, name, true, true));
+    size_t asked = 0;
+    const hipError_t e = rec.alloc(p->stream, &asked);
+    if (e != hipSuccess) {
+        rec.d_words.reset(); rec.dev = {};
+        (void) hipGetLastError();
+        return fail(p, VVHIP_ERR_HIP, std::string(name) + ": allocating " + std::to_string((unsigned long long) asked) + " bytes failed: " + hipGetErrorString(e));
+    }
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    rec.lay.start_step = p->cur.step_count;                 // (a settled recovery may have moved the counter)
+    rec.on = true;
+    return VVHIP_OK;
+}
+// The front of *_read: the refusals, then the stream drained and R::kHead count words in `head`, the table in `words_out`
+template <class R>
+static int recorder_fetch(vvhip_plan* p, R vvhip_plan::* which, const char* name, int64_t* words_out, int64_t capacity_words, long long* head) {
+    NEED_BOUND(p);
+    const R& rec = p->*which;
+    if (!rec.on) return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": none started (vvhip_" + name + "_start)");
+    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < rec.lay.words))
+        return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": the table has " + std::to_string((long long) rec.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
+    TRY(quiesce(p, name, true, false));
+    HIP_TRY(p, hipMemcpy(head, rec.d_words.get(), R::kHead * sizeof(long long), hipMemcpyDeviceToHost));
+    if (words_out && rec.lay.words > 0) HIP_TRY(p, hipMemcpy(words_out, rec.d_words.get() + rec.table_offset(), (size_t) rec.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    return VVHIP_OK;
+}
+// ... and its end, behind the entry point's conversion of the count words: the reset, complete on return
+template <class R>
+static int recorder_reset(vvhip_plan* p, R& rec) {
+    HIP_TRY(p, rec.reset(p->stream));
+    HIP_TRY(p, hipStreamSynchronize(p->stream));
+    return VVHIP_OK;
+}
+// *_info: `blank` (zeroes, but for a profile's row_of) until a description passed, then its layout
+template <class R, class L>
+static int recorder_info(const vvhip_plan* p, R vvhip_plan::* which, L* out, L blank = L{}) {
+    if (!p || !out) return VVHIP_ERR_INVALID;
+    const R& rec = p->*which;
+    if (rec.described) { blank = rec.lay; blank.active = rec.on; }
+    *out = blank;
+    return VVHIP_OK;
+}
+// group[i] of every particle of the System against [-1, num_groups) (group = null: everything in group 0)
+static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups) {
+    for (int32_t i = 0; group && i < p->hp.num_atoms; i++)
+        if (group[i] < -1 || group[i] >= num_groups)
+            return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": group[" + std::to_string(i) + "] = " + std::to_string((int) group[i]) + " is outside [-1, num_groups = " + std::to_string(num_groups) + ")");
+    return VVHIP_OK;
+}
 
 extern "C" {
 
@@ -390,7 +463,7 @@ int vvhip_series_start(vvhip_plan* p, int32_t interval, int32_t capacity, int32_
         return fail(p, VVHIP_ERR_UNSUPPORTED, "Drude temperature report: " + p->hp.report_unsupported);
     NEED_BOUND(p);
     TRY(quiesce(p, "series", true, true));
-    series_release(p);
+    p->series = vvhip_plan::Series{};
     vvhip_plan::Series& S = p->series;
     size_t asked = 0;
     HIP_TRY(p, S.ring.alloc(sizeof(vvhip_series_row), capacity, p->stream, &asked));
@@ -419,12 +492,7 @@ int vvhip_series_read(vvhip_plan* p, vvhip_series_row* rows_out, int32_t max_row
     }
     return VVHIP_OK;
 }
-int vvhip_series_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->series.on) TRY(quiesce(p, "series", true, true));
-    series_release(p);
-    return VVHIP_OK;
-}
+int vvhip_series_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::series, "series"); }
 int vvhip_series_info(const vvhip_plan* p, vvhip_series_layout* out) {
     if (!p || !out) return VVHIP_ERR_INVALID;
     vvhip_series_layout r{};
@@ -470,8 +538,7 @@ int vvhip_frames_start(vvhip_plan* p, const vvhip_frames_desc* d) {
             return fail(p, VVHIP_ERR_INVALID, "frames: subset must be strictly ascending (subset[" + std::to_string(j) + "] = " + std::to_string(d->subset[j]) + " follows " + std::to_string(d->subset[j - 1]) + ")");
     }
     // ---- a recorder that runs is settled and goes first (its frames may still be in flight); then the description, host only
-    if (p->capturing || p->frames.on) TRY(quiesce(p, "frames", true, true));
-    frames_release(p);
+    TRY(recorder_stop(p, &vvhip_plan::frames, "frames"));
     vvhip_plan::Frames& F = p->frames;
     F.when = {d->interval, d->schedule}; F.capacity = d->capacity; F.mask = d->mask; F.has_subset = has_subset;
     if (has_subset) {
@@ -540,12 +607,7 @@ int vvhip_frames_read(vvhip_plan* p, void* frames_out, int64_t* steps_out, int32
     }
     return VVHIP_OK;
 }
-int vvhip_frames_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->frames.on) TRY(quiesce(p, "frames", true, true));
-    frames_release(p);                                  // (also the description an unbound plan kept)
-    return VVHIP_OK;
-}
+int vvhip_frames_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::frames, "frames"); }
 int vvhip_frames_info(const vvhip_plan* p, vvhip_frames_layout* out) {
     if (!p || !out) return VVHIP_ERR_INVALID;
     const vvhip_plan::Frames& F = p->frames;
@@ -584,9 +646,7 @@ int vvhip_profile_start(vvhip_plan* p, const vvhip_profile_desc* d) {
         if (!(d->limit[q] >= 0) || !std::isfinite(d->limit[q]))
             return fail(p, VVHIP_ERR_INVALID, std::string("profile: limit[") + std::to_string(q) + "] (" + kQuantity[q + 1] + ") must be finite and >= 0 (0: the default)");
     const vv::HostPlan& hp = p->hp;
-    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
-        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
-            return fail(p, VVHIP_ERR_INVALID, "profile: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_groups(p, "profile", d->group, d->num_groups));
     // ---- the particles this plan records, the layout and the fixed point, host only
     vvhip_plan::Profile N;
     vvhip_profile_layout& L = N.lay;
@@ -619,7 +679,7 @@ int vvhip_profile_start(vvhip_plan* p, const vvhip_profile_desc* d) {
     L.limit[VVHIP_PROFILE_Q_MASS] = mass_limit;
     L.limit[VVHIP_PROFILE_Q_MOMENTUM] = d->limit[2] > 0 ? pow2_at_least(d->limit[2]) : mass_limit * 64.0;
     L.limit[VVHIP_PROFILE_Q_KINETIC] = d->limit[3] > 0 ? pow2_at_least(d->limit[3]) : mass_limit * 4096.0;
-    const int head = 62 - ceil_log2(described + 1) -ceil_log2(L.max_samples < (1ll << 62) ? L.max_samples + 1 : (1ll << 62));
+    const int head = 62 - ceil_log2(described + 1) - ceil_log2(samples_plus(L.max_samples, 1));
     for (int q = 1; q < VVHIP_PROFILE_QUANTITIES; q++) {
         L.frac_bits[q] = std::min(40, head - std::ilogb(L.limit[q]));
         if ((L.mask & (1 << q)) && L.frac_bits[q] < 8)
@@ -627,61 +687,19 @@ int vvhip_profile_start(vvhip_plan* p, const vvhip_profile_desc* d) {
                                               std::to_string(L.num_particles) + " particles, max_samples = " + std::to_string((long long) L.max_samples) + " and limit " +
                                               std::to_string(L.limit[q]) + ": lower max_samples or the limit");
     }
-    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
-    if (p->capturing || p->profile.on) TRY(quiesce(p, "profile", true, true));
-    profile_release(p);
-    vvhip_plan::Profile& P = p->profile;
-    P = std::move(N);
-    P.when = {d->interval, SCHEDULE_LINEAR};
-    P.lay.start_step = p->cur.step_count;
-    P.described = true;
-    NEED_BOUND(p);
-    TRY(quiesce(p, "profile", true, true));
-    auto alloc_fail = [&](hipError_t e, size_t bytes) {
-        P.d_words.reset(); P.d_index.reset(); P.d_group.reset(); P.d_mass.reset();
-        (void) hipGetLastError();
-        return fail(p, VVHIP_ERR_HIP, std::string("profile: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
-    };
-    hipError_t e = vv::zeros(P.d_words, P.bytes(), p->stream);
-    if (e != hipSuccess) return alloc_fail(e, P.bytes());
-    if ((e = vv::upload(P.d_mass, P.mass, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.mass.size() * sizeof(double)));
-    if (!P.index.empty() && (e = vv::upload(P.d_index, P.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.index.size() * sizeof(int32_t)));
-    if (P.grouped && (e = vv::upload(P.d_group, P.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, P.group.size()));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    P.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
-    P.on = true;
-    return VVHIP_OK;
+    return recorder_install(p, &vvhip_plan::profile, "profile", N, d->interval);
 }
 int vvhip_profile_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_profile_counts* out, int32_t reset) {
-    NEED_BOUND(p);
-    vvhip_plan::Profile& P = p->profile;
-    if (!P.on) return fail(p, VVHIP_ERR_INVALID, "profile: none started (vvhip_profile_start)");
-    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < P.lay.words))
-        return fail(p, VVHIP_ERR_INVALID, "profile: the table has " + std::to_string((long long) P.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
-    TRY(quiesce(p, "profile", true, false));
     long long head[vv::PROFILE_HEAD];
-    HIP_TRY(p, hipMemcpy(head, P.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
-    if (words_out && P.lay.words > 0) HIP_TRY(p, hipMemcpy(words_out, P.d_words.get() + vv::PROFILE_HEAD, (size_t) P.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    TRY(recorder_fetch(p, &vvhip_plan::profile, "profile", words_out, capacity_words, head));
     if (out) *out = {head[vv::PROFILE_SAMPLES], head[vv::PROFILE_DROPPED], head[vv::PROFILE_OUT_OF_RANGE]};
-    if (reset) {
-        HIP_TRY(p, hipMemsetAsync(P.d_words.get(), 0, P.bytes(), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-    }
-    return VVHIP_OK;
+    return reset ? recorder_reset(p, p->profile) : VVHIP_OK;
 }
-int vvhip_profile_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->profile.on) TRY(quiesce(p, "profile", true, true));
-    profile_release(p);                                 // (also the description an unbound plan kept)
-    return VVHIP_OK;
-}
+int vvhip_profile_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::profile, "profile"); }
 int vvhip_profile_info(const vvhip_plan* p, vvhip_profile_layout* out) {
-    if (!p || !out) return VVHIP_ERR_INVALID;
-    vvhip_profile_layout r{};
-    for (int q = 0; q < VVHIP_PROFILE_QUANTITIES; q++) r.row_of[q] = -1;
-    if (p->profile.described) { r = p->profile.lay; r.active = p->profile.on; }
-    *out = r;
-    return VVHIP_OK;
+    vvhip_profile_layout blank{};
+    for (int q = 0; q < VVHIP_PROFILE_QUANTITIES; q++) blank.row_of[q] = -1;
+    return recorder_info(p, &vvhip_plan::profile, out, blank);
 }
 
 int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
@@ -695,9 +713,7 @@ int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
     if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "msd: max_samples must be >= 1");
     if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "msd: limit must be finite and >= 0 (0: the default of 64 nm)");
     const vv::HostPlan& hp = p->hp;
-    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
-        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
-            return fail(p, VVHIP_ERR_INVALID, "msd: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_groups(p, "msd", d->group, d->num_groups));
     // ---- the units this plan records, the layout and the fixed point, host only
     vvhip_plan::Msd N;
     vvhip_msd_layout& L = N.lay;
@@ -746,7 +762,7 @@ int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
     L.words = (int64_t) L.num_groups * L.num_lags * 4;
     L.limit = d->limit > 0 ? pow2_at_least(d->limit) : 64.0;
     L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
-    const long long max_origins = (L.max_samples < (1ll << 62) ? L.max_samples + L.origin_every - 1 : (1ll << 62)) / L.origin_every;
+    const long long max_origins = samples_plus(L.max_samples, L.origin_every - 1) / L.origin_every;
     L.frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(L.limit));
     if (L.frac_bits < 8)
         return fail(p, VVHIP_ERR_INVALID, "msd: the sums would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
@@ -769,65 +785,16 @@ int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
     }
     if (molecules) N.first.push_back((int32_t) N.index.size());
     if (!molecules && !N.grouped && L.num_units == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
-    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
-    if (p->capturing || p->msd.on) TRY(quiesce(p, "msd", true, true));
-    msd_release(p);
-    vvhip_plan::Msd& M = p->msd;
-    M = std::move(N);
-    M.when = {d->interval, SCHEDULE_LINEAR};
-    M.lay.start_step = p->cur.step_count;
-    M.described = true;
-    NEED_BOUND(p);
-    TRY(quiesce(p, "msd", true, true));
-    auto alloc_fail = [&](hipError_t e, size_t bytes) {
-        M.d_words.reset(); M.d_index.reset(); M.d_first.reset(); M.d_weight.reset(); M.d_total.reset(); M.d_group.reset();
-        (void) hipGetLastError();
-        return fail(p, VVHIP_ERR_HIP, std::string("msd: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
-    };
-    hipError_t e = vv::zeros(M.d_words, M.bytes(), p->stream);
-    if (e != hipSuccess) return alloc_fail(e, M.bytes());
-    if (!M.index.empty() && (e = vv::upload(M.d_index, M.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.index.size() * sizeof(int32_t)));
-    if (molecules) {
-        if ((e = vv::upload(M.d_first, M.first, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.first.size() * sizeof(int32_t)));
-        if ((e = vv::upload(M.d_weight, M.weight, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.weight.size() * sizeof(double)));
-        if ((e = vv::upload(M.d_total, M.total, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.total.size() * sizeof(double)));
-    }
-    if (M.grouped && (e = vv::upload(M.d_group, M.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, M.group.size()));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    M.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
-    M.on = true;
-    return VVHIP_OK;
+    return recorder_install(p, &vvhip_plan::msd, "msd", N, d->interval);
 }
 int vvhip_msd_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_msd_counts* out, int32_t reset) {
-    NEED_BOUND(p);
-    vvhip_plan::Msd& M = p->msd;
-    if (!M.on) return fail(p, VVHIP_ERR_INVALID, "msd: none started (vvhip_msd_start)");
-    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < M.lay.words))
-        return fail(p, VVHIP_ERR_INVALID, "msd: the table has " + std::to_string((long long) M.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
-    TRY(quiesce(p, "msd", true, false));
     long long head[vv::MSD_HEAD];
-    HIP_TRY(p, hipMemcpy(head, M.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
-    if (words_out) HIP_TRY(p, hipMemcpy(words_out, M.d_words.get() + vv::MSD_HEAD, (size_t) M.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    TRY(recorder_fetch(p, &vvhip_plan::msd, "msd", words_out, capacity_words, head));
     if (out) *out = {head[vv::MSD_SAMPLES], head[vv::MSD_DROPPED], head[vv::MSD_OUT_OF_RANGE], head[vv::MSD_FLOOR]};
-    if (reset) {      // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
-        HIP_TRY(p, hipMemsetAsync(M.d_words.get(), 0, (size_t) (vv::MSD_HEAD + M.lay.words) * sizeof(long long), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-    }
-    return VVHIP_OK;
+    return reset ? recorder_reset(p, p->msd) : VVHIP_OK;
 }
-int vvhip_msd_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->msd.on) TRY(quiesce(p, "msd", true, true));
-    msd_release(p);                                     // (also the description an unbound plan kept)
-    return VVHIP_OK;
-}
-int vvhip_msd_info(const vvhip_plan* p, vvhip_msd_layout* out) {
-    if (!p || !out) return VVHIP_ERR_INVALID;
-    vvhip_msd_layout r{};
-    if (p->msd.described) { r = p->msd.lay; r.active = p->msd.on; }
-    *out = r;
-    return VVHIP_OK;
-}
+int vvhip_msd_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::msd, "msd"); }
+int vvhip_msd_info(const vvhip_plan* p, vvhip_msd_layout* out) { return recorder_info(p, &vvhip_plan::msd, out); }
 
 int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
@@ -840,9 +807,7 @@ int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "rdf: classes must not be NULL");
     if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "rdf: max_samples must be >= 1");
     const vv::HostPlan& hp = p->hp;
-    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
-        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
-            return fail(p, VVHIP_ERR_INVALID, "rdf: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_groups(p, "rdf", d->group, d->num_groups));
     for (int32_t c = 0; c < d->num_classes; c++)
         for (int q = 0; q < 2; q++)
             if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= d->num_groups)
@@ -912,32 +877,7 @@ int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     }
     L.num_items = (int32_t) N.items.size();
     L.scratch_bytes = (int64_t) 3 * N.stride() * (int64_t) sizeof(double);
-    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
-    if (p->capturing || p->rdf.on) TRY(quiesce(p, "rdf", true, true));
-    rdf_release(p);
-    vvhip_plan::Rdf& R = p->rdf;
-    R = std::move(N);
-    R.when = {d->interval, SCHEDULE_LINEAR};
-    R.lay.start_step = p->cur.step_count;
-    R.described = true;
-    NEED_BOUND(p);
-    TRY(quiesce(p, "rdf", true, true));
-    auto alloc_fail = [&](hipError_t e, size_t bytes) {
-        R.d_words.reset(); R.d_index.reset(); R.d_mol.reset(); R.d_items.reset(); R.d_scratch.reset();
-        (void) hipGetLastError();
-        return fail(p, VVHIP_ERR_HIP, std::string("rdf: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
-    };
-    hipError_t e = vv::zeros(R.d_words, R.bytes(), p->stream);
-    if (e != hipSuccess) return alloc_fail(e, R.bytes());
-    const size_t scratch = std::max<size_t>(16, (size_t) R.lay.scratch_bytes);
-    if ((e = vv::zeros(R.d_scratch, scratch, p->stream)) != hipSuccess) return alloc_fail(e, scratch);
-    if ((e = vv::upload(R.d_index, R.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, R.index.size() * sizeof(int32_t)));
-    if (R.lay.exclude_same_molecule && (e = vv::upload(R.d_mol, R.mol, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, R.mol.size() * sizeof(int32_t)));
-    if ((e = vv::upload(R.d_items, R.items, 32)) != hipSuccess) return alloc_fail(e, std::max<size_t>(32, R.items.size() * sizeof(vv::RdfItem)));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    R.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
-    R.on = true;
-    return VVHIP_OK;
+    return recorder_install(p, &vvhip_plan::rdf, "rdf", N, d->interval);
 }
 int vvhip_rdf_sample(vvhip_plan* p) {
     NEED_BOUND(p);
@@ -946,39 +886,17 @@ int vvhip_rdf_sample(vvhip_plan* p) {
     return rdf_enqueue(p);
 }
 int vvhip_rdf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_rdf_counts* out, int32_t reset) {
-    NEED_BOUND(p);
-    vvhip_plan::Rdf& R = p->rdf;
-    if (!R.on) return fail(p, VVHIP_ERR_INVALID, "rdf: none started (vvhip_rdf_start)");
-    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < R.lay.words))
-        return fail(p, VVHIP_ERR_INVALID, "rdf: the table has " + std::to_string((long long) R.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
-    TRY(quiesce(p, "rdf", true, false));
     long long head[vv::RDF_HEAD];
-    HIP_TRY(p, hipMemcpy(head, R.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
-    if (words_out) HIP_TRY(p, hipMemcpy(words_out, R.d_words.get() + vv::RDF_HEAD, (size_t) R.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    TRY(recorder_fetch(p, &vvhip_plan::rdf, "rdf", words_out, capacity_words, head));
     if (out) {
         double s;
         std::memcpy(&s, &head[vv::RDF_INV_VOLUME], sizeof s);
         *out = {head[vv::RDF_SAMPLES], head[vv::RDF_DROPPED], head[vv::RDF_INVALID], s};
     }
-    if (reset) {
-        HIP_TRY(p, hipMemsetAsync(R.d_words.get(), 0, R.bytes(), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-    }
-    return VVHIP_OK;
+    return reset ? recorder_reset(p, p->rdf) : VVHIP_OK;
 }
-int vvhip_rdf_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->rdf.on) TRY(quiesce(p, "rdf", true, true));
-    rdf_release(p);                                     // (also the description an unbound plan kept)
-    return VVHIP_OK;
-}
-int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) {
-    if (!p || !out) return VVHIP_ERR_INVALID;
-    vvhip_rdf_layout r{};
-    if (p->rdf.described) { r = p->rdf.lay; r.active = p->rdf.on; }
-    *out = r;
-    return VVHIP_OK;
-}
+int vvhip_rdf_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::rdf, "rdf"); }
+int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) { return recorder_info(p, &vvhip_plan::rdf, out); }
 
 int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
@@ -992,9 +910,7 @@ int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
     if (!(d->limit_velocity >= 0) || !std::isfinite(d->limit_velocity)) return fail(p, VVHIP_ERR_INVALID, "current: limit_velocity must be finite and >= 0 (0: the default of 64 nm/ps)");
     if (!d->weight) return fail(p, VVHIP_ERR_INVALID, "current: weight must not be NULL");
     const vv::HostPlan& hp = p->hp;
-    for (int32_t i = 0; d->group && i < hp.num_atoms; i++)
-        if (d->group[i] < -1 || d->group[i] >= d->num_groups)
-            return fail(p, VVHIP_ERR_INVALID, "current: group[" + std::to_string(i) + "] = " + std::to_string((int) d->group[i]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_groups(p, "current", d->group, d->num_groups));
     for (int32_t i = 0; i < hp.num_atoms; i++)
         if (!std::isfinite(d->weight[i])) return fail(p, VVHIP_ERR_INVALID, "current: weight[" + std::to_string(i) + "] is not finite");
     // ---- the recorded particles, the layout and the fixed point, host only
@@ -1036,68 +952,20 @@ int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
         return fail(p, VVHIP_ERR_UNSUPPORTED, "current: a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
                                               "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
     for (const Unit& u : units) { N.index.push_back(u.id); N.weight.push_back(d->weight[u.id]); N.group.push_back((unsigned char) u.group); }
-    // ---- a recorder that runs is settled and goes first (its samples may still be in flight); then the description
-    if (p->capturing || p->current.on) TRY(quiesce(p, "current", true, true));
-    current_release(p);
-    vvhip_plan::Current& K = p->current;
-    K = std::move(N);
-    K.when = {d->interval, SCHEDULE_LINEAR};
-    K.lay.start_step = p->cur.step_count;
-    K.described = true;
-    NEED_BOUND(p);
-    TRY(quiesce(p, "current", true, true));
-    auto alloc_fail = [&](hipError_t e, size_t bytes) {
-        K.d_words.reset(); K.d_index.reset(); K.d_weight.reset(); K.d_group.reset(); K.d_slabs.reset();
-        (void) hipGetLastError();
-        return fail(p, VVHIP_ERR_HIP, std::string("current: allocating ") + std::to_string((unsigned long long) bytes) + " bytes failed: " + hipGetErrorString(e));
-    };
-    hipError_t e = vv::zeros(K.d_words, K.bytes(), p->stream);
-    if (e != hipSuccess) return alloc_fail(e, K.bytes());
-    if ((e = vv::upload(K.d_index, K.index, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.index.size() * sizeof(int32_t)));
-    if ((e = vv::upload(K.d_weight, K.weight, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.weight.size() * sizeof(double)));
-    if ((e = vv::upload(K.d_group, K.group, 16)) != hipSuccess) return alloc_fail(e, std::max<size_t>(16, K.group.size()));
-    if (p->current_two_level && (e = vv::zeros(K.d_slabs, K.slab_words() * sizeof(long long), p->stream)) != hipSuccess) return alloc_fail(e, K.slab_words() * sizeof(long long));
-    // (no slot holds a sample: the slots' words, the allocation's last num_origins, are -1)
-    HIP_TRY(p, hipMemsetAsync(K.d_words.get() + K.bytes() / sizeof(long long) - K.lay.num_origins, 0xFF, (size_t) K.lay.num_origins * sizeof(long long), p->stream));
-    HIP_TRY(p, hipStreamSynchronize(p->stream));
-    K.lay.start_step = p->cur.step_count;                   // (a settled recovery may have moved the counter)
-    K.on = true;
-    return VVHIP_OK;
+    N.two_level = p->current_two_level != 0;
+    return recorder_install(p, &vvhip_plan::current, "current", N, d->interval);
 }
 int vvhip_current_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_current_counts* out, int32_t reset) {
-    NEED_BOUND(p);
-    vvhip_plan::Current& K = p->current;
-    if (!K.on) return fail(p, VVHIP_ERR_INVALID, "current: none started (vvhip_current_start)");
-    if (capacity_words < 0 || (capacity_words > 0 && !words_out) || (words_out && capacity_words < K.lay.words))
-        return fail(p, VVHIP_ERR_INVALID, "current: the table has " + std::to_string((long long) K.lay.words) + " words; words_out must hold them all (or be NULL with capacity_words = 0)");
-    TRY(quiesce(p, "current", true, false));
     long long head[vv::CUR_HEAD];
-    HIP_TRY(p, hipMemcpy(head, K.d_words.get(), sizeof(head), hipMemcpyDeviceToHost));
-    if (words_out) HIP_TRY(p, hipMemcpy(words_out, K.d_words.get() + vv::CUR_HEAD + K.sums_words(), (size_t) K.lay.words * sizeof(long long), hipMemcpyDeviceToHost));
+    TRY(recorder_fetch(p, &vvhip_plan::current, "current", words_out, capacity_words, head));
     if (out) {
         double s;
         std::memcpy(&s, &head[vv::CUR_INV_VOLUME], sizeof s);
         *out = {head[vv::CUR_SAMPLES], head[vv::CUR_DROPPED], head[vv::CUR_OUT_OF_RANGE], head[vv::CUR_INVALID], head[vv::CUR_FLOOR], s};
     }
-    if (reset) {      // (head, sums and table to zero, the slots' words to -1: no slot holds a sample, so the ring may keep its bits)
-        HIP_TRY(p, hipMemsetAsync(K.d_words.get(), 0, K.front_words() * sizeof(long long), p->stream));
-        HIP_TRY(p, hipMemsetAsync(K.d_words.get() + K.bytes() / sizeof(long long) - K.lay.num_origins, 0xFF, (size_t) K.lay.num_origins * sizeof(long long), p->stream));
-        HIP_TRY(p, hipStreamSynchronize(p->stream));
-    }
-    return VVHIP_OK;
+    return reset ? recorder_reset(p, p->current) : VVHIP_OK;
 }
-int vvhip_current_stop(vvhip_plan* p) {
-    if (!p) return VVHIP_ERR_INVALID;
-    if (p->capturing || p->current.on) TRY(quiesce(p, "current", true, true));
-    current_release(p);                                 // (also the description an unbound plan kept)
-    return VVHIP_OK;
-}
-int vvhip_current_info(const vvhip_plan* p, vvhip_current_layout* out) {
-    if (!p || !out) return VVHIP_ERR_INVALID;
-    vvhip_current_layout r{};
-    if (p->current.described) { r = p->current.lay; r.active = p->current.on; }
-    *out = r;
-    return VVHIP_OK;
-}
+int vvhip_current_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::current, "current"); }
+int vvhip_current_info(const vvhip_plan* p, vvhip_current_layout* out) { return recorder_info(p, &vvhip_plan::current, out); }
 
 }  // extern "C"

@@ -8,9 +8,10 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: Drude report, series, trajectory frames, profiles, removal of the centre-of-mass motion, start
-//                    velocities; the list of the step's scheduled riders (riders), step_begin / step_done, quiesce; their one schedule is
-//                    vv_schedule.hpp (integers only, no HIP in it)
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the seven scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current sample, with their
+//                    late words: the rings' cursors, the removals' record, the four recorders' d_words; the recorders' one life cycle
+//                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
 //                    vvhip_run_graph / vvhip_run_eager(_unfused), vvhip_synth_tether_force
@@ -80,7 +81,10 @@ inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (u
 inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
-constexpr int kRiders = 7;          // the step's scheduled riders (riders()): series row, removal of the centre-of-mass motion, trajectory frame, profile sample, MSD sample, RDF sample, current sample
+// The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
+//   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample (3 .. 6: all of d_words)
+constexpr int kRiders = 7;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -171,7 +175,8 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // the series' rows (vvhip_series_*) and of the removals of the centre-of-mass motion
+        // all seven riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF and current sample.  A
+        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the four recorders' d_words
         long long step_count = 0;
     } cur;
     bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
@@ -343,73 +348,136 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // Profiles (vvhip_profile_*; vv_dev_profile.inc), scheduled by cur.step_count.  `described` / `on` as for the frames: `lay` is the
-    // layout of the last description that passed vvhip_profile_start's checks, the device buffers exist while the recorder runs
-    struct Profile {
-        bool on = false, described = false, grouped = false;
+    // What the four accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
+    // `on`: the recorder runs and the device buffers exist.  Each recorder adds
+    //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
+    //   kHead, table_offset()  the count words in front of d_words; where the table starts in it, in words
+    //   bytes()                of d_words
+    //   alloc(s, &asked)       d_words, zeroed on stream s, and dev from the host tables; a request that fails leaves its bytes in `asked`
+    //   reset(s)               what *_read's reset enqueues
+    struct Recorder {
+        bool on = false, described = false;
         Schedule when;                            // (linear)
+        vv::DevBuf<long long> d_words;            // counts, then what the recorder accumulates -- ALL of it the rider's late words
+        // one table as the host built it, of 16 bytes at the least
+        template <class T, class U>
+        static hipError_t put(vv::DevBuf<T>& buf, const std::vector<U>& v, size_t* asked, size_t floor = 16) {
+            *asked = std::max(floor, v.size() * sizeof(U));
+            return vv::upload(buf, v, floor);
+        }
+    };
+    // Profiles (vvhip_profile_*; vv_dev_profile.inc), scheduled by cur.step_count
+    struct Profile : Recorder {
+        bool grouped = false;
         vvhip_profile_layout lay{};
         std::vector<int32_t> index;               // shard-relative indices of the recorded particles, ascending; empty: every particle of the shard
         std::vector<unsigned char> group;         // [num_particles] their groups (grouped)
         std::vector<double> mass;                 // [num_particles] their masses
-        vv::DevBuf<int32_t> d_index;
-        vv::DevBuf<unsigned char> d_group;
-        vv::DevBuf<double> d_mass;
-        vv::DevBuf<long long> d_words;            // [PROFILE_HEAD + lay.words]: counts, then the table -- ALL of it the rider's late words
-        size_t bytes() const { return (size_t) (vv::PROFILE_HEAD + lay.words) * sizeof(long long); }
+        struct Dev { vv::DevBuf<int32_t> index; vv::DevBuf<unsigned char> group; vv::DevBuf<double> mass; } dev;
+        static constexpr int kHead = vv::PROFILE_HEAD;      // d_words: [kHead + lay.words] counts, then the table
+        size_t table_offset() const { return kHead; }
+        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long); }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = put(dev.mass, mass, asked);
+            if (e == hipSuccess && !index.empty()) e = put(dev.index, index, asked);
+            if (e == hipSuccess && grouped) e = put(dev.group, group, asked);
+            return e;
+        }
+        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, bytes(), s); }
     } profile;
-    // Mean-squared displacements (vvhip_msd_*; vv_dev_msd.inc), scheduled by cur.step_count.  `described` / `on` as for the profiles.  The
-    // unit tables are built from the plan's molecules when the recorder starts: units ordered by group, then by particle / molecule index
-    struct Msd {
-        bool on = false, described = false, grouped = false;
-        Schedule when;                            // (linear)
+    // Mean-squared displacements (vvhip_msd_*; vv_dev_msd.inc), scheduled by cur.step_count.  The unit tables are built from the plan's
+    // molecules when the recorder starts: units ordered by group, then by particle / molecule index
+    struct Msd : Recorder {
+        bool grouped = false;
         vvhip_msd_layout lay{};
         std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending
         std::vector<int32_t> first;               // molecules: [num_units + 1] offsets into index / weight
         std::vector<double> weight, total;        // molecules: the members' masses; [num_units] their sums M in the members' order
         std::vector<unsigned char> group;         // [num_units] (grouped)
-        vv::DevBuf<int32_t> d_index, d_first;
-        vv::DevBuf<double> d_weight, d_total;
-        vv::DevBuf<unsigned char> d_group;
-        vv::DevBuf<long long> d_words;            // [MSD_HEAD + lay.words] counts, floor and table, then the ring -- ALL of it the rider's late words
+        struct Dev { vv::DevBuf<int32_t> index, first; vv::DevBuf<double> weight, total; vv::DevBuf<unsigned char> group; } dev;
+        static constexpr int kHead = vv::MSD_HEAD;          // d_words: [kHead + lay.words] counts, floor and table, then the ring of origins
+        size_t table_offset() const { return kHead; }
         int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
-        size_t bytes() const { return (size_t) (vv::MSD_HEAD + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
+        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess && !index.empty()) e = put(dev.index, index, asked);
+            if (lay.mode == VVHIP_MSD_MOLECULES) {
+                if (e == hipSuccess) e = put(dev.first, first, asked);
+                if (e == hipSuccess) e = put(dev.weight, weight, asked);
+                if (e == hipSuccess) e = put(dev.total, total, asked);
+            }
+            if (e == hipSuccess && grouped) e = put(dev.group, group, asked);
+            return e;
+        }
+        // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
+        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, (size_t) (kHead + lay.words) * sizeof(long long), s); }
     } msd;
-    // Radial distribution functions (vvhip_rdf_*; vv_dev_rdf.inc), scheduled by cur.step_count.  `described` / `on` as for the profiles.  The
-    // site list (ordered by group, inside a group ascending by particle), the sites' molecules and the pair kernel's work items are built
-    // when the recorder starts
-    struct Rdf {
-        bool on = false, described = false;
-        Schedule when;                            // (linear)
+    // Radial distribution functions (vvhip_rdf_*; vv_dev_rdf.inc), scheduled by cur.step_count.  The site list (ordered by group, inside a
+    // group ascending by particle), the sites' molecules and the pair kernel's work items are built when the recorder starts
+    struct Rdf : Recorder {
         vvhip_rdf_layout lay{};
         std::vector<int32_t> index, mol;          // [sites] particle and molecule of every site (mol: with the exclusion on)
         std::vector<vv::RdfItem> items;
         int max_jsites = 64;                      // no item has more j-sites
-        vv::DevBuf<int32_t> d_index, d_mol;
-        vv::DevBuf<vv::RdfItem> d_items;
-        vv::DevBuf<double> d_scratch;             // [3][stride()] rewritten by every sample, not saved
-        vv::DevBuf<long long> d_words;            // [RDF_HEAD + lay.words]: counts, then the table -- ALL of it the rider's late words
+        struct Dev {
+            vv::DevBuf<int32_t> index, mol;
+            vv::DevBuf<vv::RdfItem> items;
+            vv::DevBuf<double> scratch;           // [3][stride()] rewritten by every sample, not saved
+        } dev;
+        static constexpr int kHead = vv::RDF_HEAD;          // d_words: [kHead + lay.words] counts, then the table
+        size_t table_offset() const { return kHead; }
         int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
-        size_t bytes() const { return (size_t) (vv::RDF_HEAD + lay.words) * sizeof(long long); }
+        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long); }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = vv::zeros(dev.scratch, *asked = std::max<size_t>(16, (size_t) lay.scratch_bytes), s);
+            if (e == hipSuccess) e = put(dev.index, index, asked);
+            if (e == hipSuccess && lay.exclude_same_molecule) e = put(dev.mol, mol, asked);
+            if (e == hipSuccess) e = put(dev.items, items, asked, 32);
+            return e;
+        }
+        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, bytes(), s); }
     } rdf;
-    // Collective current correlations (vvhip_current_*; vv_dev_current.inc), scheduled by cur.step_count.  `described` / `on` as for the
-    // profiles.  The compact list of the recorded particles, ordered by group, then by index, is built when the recorder starts
-    struct Current {
-        bool on = false, described = false;
-        Schedule when;                            // (linear)
+    // Collective current correlations (vvhip_current_*; vv_dev_current.inc), scheduled by cur.step_count.  The compact list of the recorded
+    // particles, ordered by group, then by index, is built when the recorder starts
+    struct Current : Recorder {
+        bool two_level = false;                   // vvhip_plan::current_two_level as the start found it
         vvhip_current_layout lay{};
         std::vector<int32_t> index;               // [num_particles] the recorded particles
         std::vector<double> weight;               // beside index
         std::vector<unsigned char> group;         // beside index
-        vv::DevBuf<int32_t> d_index;
-        vv::DevBuf<double> d_weight;
-        vv::DevBuf<unsigned char> d_group;
-        vv::DevBuf<long long> d_words;            // head, sums, table, ring, the slots' words -- ALL of it the rider's late words
-        vv::DevBuf<long long> d_slabs;            // two-level form only: the reduce blocks' slabs, rewritten by every sample, not saved
+        struct Dev {
+            vv::DevBuf<int32_t> index;
+            vv::DevBuf<double> weight;
+            vv::DevBuf<unsigned char> group;
+            vv::DevBuf<long long> slabs;          // two-level form only: the reduce blocks' slabs, rewritten by every sample, not saved
+        } dev;
+        static constexpr int kHead = vv::CUR_HEAD;          // d_words: head, sums, table, ring, the slots' words
+        size_t table_offset() const { return kHead + sums_words(); }
         size_t slab_words() const { return ((size_t) (lay.num_particles + 63) / 64 + 1) * (sums_words() + 1); }
         size_t sums_words() const { return (size_t) lay.num_groups * 6; }
-        size_t front_words() const { return (size_t) vv::CUR_HEAD + sums_words() + (size_t) lay.words; }      // what a reset zeroes
+        size_t front_words() const { return (size_t) kHead + sums_words() + (size_t) lay.words; }      // what a reset zeroes
         size_t bytes() const { return front_words() * sizeof(long long) + (size_t) lay.ring_bytes; }
+        // no slot holds a sample: the slots' words, the allocation's last num_origins, are -1
+        hipError_t empty_slots(hipStream_t s) {
+            return hipMemsetAsync(d_words.get() + bytes() / sizeof(long long) - lay.num_origins, 0xFF, (size_t) lay.num_origins * sizeof(long long), s);
+        }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = put(dev.index, index, asked);
+            if (e == hipSuccess) e = put(dev.weight, weight, asked);
+            if (e == hipSuccess) e = put(dev.group, group, asked);
+            if (e == hipSuccess && two_level) e = vv::zeros(dev.slabs, *asked = slab_words() * sizeof(long long), s);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
+        // (head, sums and table to zero, the slots' words to -1, so the ring may keep its bits)
+        hipError_t reset(hipStream_t s) {
+            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
     } current;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them

@@ -870,6 +870,30 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
+    # ---- what the four accumulating recorders below share: profile, msd, rdf, current (include/vvhip.h: vvhip_<name>_*)
+    def _groups(self, groups):
+        """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
+        if groups is None:
+            return None
+        grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+        if grp.size != self.system.num_atoms:
+            raise ValueError("groups must have one entry per particle of the System")
+        return grp
+
+    def _recorder_stop(self, name):
+        H.check(getattr(H.lib, f"vvhip_{name}_stop")(self.plan), self.plan)
+
+    def _recorder_info(self, name, layout):
+        out = layout()
+        H.check(getattr(H.lib, f"vvhip_{name}_info")(self.plan, C.byref(out)), self.plan)
+        return out
+
+    def _recorder_read(self, name, layout, counts, from_words, reset, *more):
+        info, counts = self._recorder_info(name, layout), counts()
+        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
+        H.check(getattr(H.lib, f"vvhip_{name}_read")(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
+        return from_words(words[: info.words], info, counts, *more)
+
     # ---- profiles: density and velocity profiles accumulated on the device inside the steps (include/vvhip.h: vvhip_profile_*)
     def profile_start(self, interval: int, nbins: int, axis: int = 2, groups=None, charge: bool = True, mass: bool = False,
                       momentum: bool = False, kinetic: bool = False, max_samples: int = 1 << 20, limits=None):
@@ -879,11 +903,7 @@ class Context:
         (-1: not recorded), each group a table of its own; None: everything in group 0.  `limits`: {"charge" | "mass" | "momentum" |
         "kinetic": largest |term|}; a particle beyond one is left out of every row and counted in out_of_range.  At most `max_samples`
         samples are added (the fixed point is sized for them).  No host synchronisation until profile_read."""
-        grp = None
-        if groups is not None:
-            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
-            if grp.size != self.system.num_atoms:
-                raise ValueError("groups must have one entry per particle of the System")
+        grp = self._groups(groups)
         unknown = set(limits or {}) - set(H.PROFILE_QUANTITIES[1:])
         if unknown:
             raise ValueError(f"limits: unknown quantity {sorted(unknown)}")
@@ -895,20 +915,14 @@ class Context:
         H.check(H.lib.vvhip_profile_start(self.plan, C.byref(desc)), self.plan)
 
     def profile_stop(self):
-        H.check(H.lib.vvhip_profile_stop(self.plan), self.plan)
+        self._recorder_stop("profile")
 
     def profile_info(self) -> H.ProfileLayout:
-        out = H.ProfileLayout()
-        H.check(H.lib.vvhip_profile_info(self.plan, C.byref(out)), self.plan)
-        return out
+        return self._recorder_info("profile", H.ProfileLayout)
 
     def profile_read(self, reset: bool = False) -> Profile:
         """The table accumulated so far (synchronises).  reset=True zeroes it; the schedule continues without gap or repeat."""
-        info = self.profile_info()
-        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
-        counts = H.ProfileCounts()
-        H.check(H.lib.vvhip_profile_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
-        return profile_from_words(words[: info.words], info, counts, self._box)
+        return self._recorder_read("profile", H.ProfileLayout, H.ProfileCounts, profile_from_words, reset, self._box)
 
     # ---- mean-squared displacements accumulated on the device inside the steps (include/vvhip.h: vvhip_msd_*)
     def msd_start(self, interval: int, num_lags: int, origin_every: int = 1, molecules: bool = False, groups=None,
@@ -920,32 +934,22 @@ class Context:
         not recorded), each group a table of its own; None: everything in group 0.  `limit` (nm, 0: 64): a displacement component at or
         beyond it leaves the pair out and counts in out_of_range.  At most `max_samples` samples are taken (the fixed point is sized for
         them).  No host synchronisation until msd_read."""
-        grp = None
-        if groups is not None:
-            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
-            if grp.size != self.system.num_atoms:
-                raise ValueError("groups must have one entry per particle of the System")
+        grp = self._groups(groups)
         desc = H.MsdDesc(int(interval), int(num_lags), int(origin_every), H.MSD_MOLECULES if molecules else H.MSD_PARTICLES,
                          1 if grp is None else max(int(grp.max()) + 1, 1), 0, None if grp is None else grp.ctypes.data, int(max_samples),
                          float(limit))
         H.check(H.lib.vvhip_msd_start(self.plan, C.byref(desc)), self.plan)
 
     def msd_stop(self):
-        H.check(H.lib.vvhip_msd_stop(self.plan), self.plan)
+        self._recorder_stop("msd")
 
     def msd_info(self) -> H.MsdLayout:
-        out = H.MsdLayout()
-        H.check(H.lib.vvhip_msd_info(self.plan, C.byref(out)), self.plan)
-        return out
+        return self._recorder_info("msd", H.MsdLayout)
 
     def msd_read(self, reset: bool = False) -> Msd:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
-        info = self.msd_info()
-        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
-        counts = H.MsdCounts()
-        H.check(H.lib.vvhip_msd_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
-        return msd_from_words(words[: info.words], info, counts)
+        return self._recorder_read("msd", H.MsdLayout, H.MsdCounts, msd_from_words, reset)
 
     # ---- radial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_rdf_*)
     def rdf_start(self, interval: int, r_max: float, nbins: int, classes, groups=None, exclude_same_molecule: bool = False,
@@ -956,11 +960,7 @@ class Context:
         `classes`: pairs of groups (ga, gb); ga == gb counts every unordered pair of the group once.  exclude_same_molecule leaves out the
         pairs inside one molecule.  r_max must not exceed half the shortest box edge.  At most `max_samples` samples are taken.  A sharded
         context raises ERR_UNSUPPORTED.  No host synchronisation until rdf_read."""
-        grp = None
-        if groups is not None:
-            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
-            if grp.size != self.system.num_atoms:
-                raise ValueError("groups must have one entry per particle of the System")
+        grp = self._groups(groups)
         cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1, 2)
         num_groups = max(1, 0 if grp is None else int(grp.max()) + 1, int(cls.max()) + 1 if cls.size else 1)      # (a class may name a group without sites)
         desc = H.RdfDesc(int(interval), int(nbins), num_groups, int(cls.shape[0]),
@@ -973,21 +973,15 @@ class Context:
         H.check(H.lib.vvhip_rdf_sample(self.plan), self.plan)
 
     def rdf_stop(self):
-        H.check(H.lib.vvhip_rdf_stop(self.plan), self.plan)
+        self._recorder_stop("rdf")
 
     def rdf_info(self) -> H.RdfLayout:
-        out = H.RdfLayout()
-        H.check(H.lib.vvhip_rdf_info(self.plan, C.byref(out)), self.plan)
-        return out
+        return self._recorder_info("rdf", H.RdfLayout)
 
     def rdf_read(self, reset: bool = False) -> Rdf:
         """The histograms accumulated so far (synchronises).  reset=True zeroes counts and table; the step schedule continues without gap
         or repeat."""
-        info = self.rdf_info()
-        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
-        counts = H.RdfCounts()
-        H.check(H.lib.vvhip_rdf_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
-        return rdf_from_words(words[: info.words], info, counts)
+        return self._recorder_read("rdf", H.RdfLayout, H.RdfCounts, rdf_from_words, reset)
 
     # ---- collective current correlations accumulated on the device inside the steps (include/vvhip.h: vvhip_current_*)
     def current_start(self, interval: int, num_lags: int, origin_every: int = 1, weights=None, molecules: bool = False, groups=None,
@@ -1009,31 +1003,21 @@ class Context:
             w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w.size != n:
             raise ValueError("weights must have one entry per particle of the System")
-        grp = None
-        if groups is not None:
-            grp = np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
-            if grp.size != n:
-                raise ValueError("groups must have one entry per particle of the System")
+        grp = self._groups(groups)
         desc = H.CurrentDesc(int(interval), int(num_lags), int(origin_every), 1 if grp is None else max(int(grp.max()) + 1, 1), w.ctypes.data,
                              None if grp is None else grp.ctypes.data, int(max_samples), float(limit_position), float(limit_velocity))
         H.check(H.lib.vvhip_current_start(self.plan, C.byref(desc)), self.plan)
 
     def current_stop(self):
-        H.check(H.lib.vvhip_current_stop(self.plan), self.plan)
+        self._recorder_stop("current")
 
     def current_info(self) -> H.CurrentLayout:
-        out = H.CurrentLayout()
-        H.check(H.lib.vvhip_current_info(self.plan, C.byref(out)), self.plan)
-        return out
+        return self._recorder_info("current", H.CurrentLayout)
 
     def current_read(self, reset: bool = False) -> Currents:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
-        info = self.current_info()
-        words = np.zeros(max(int(info.words), 1), dtype=np.int64)
-        counts = H.CurrentCounts()
-        H.check(H.lib.vvhip_current_read(self.plan, words.ctypes.data, words.size, C.byref(counts), int(bool(reset))), self.plan)
-        return currents_from_words(words[: info.words], info, counts)
+        return self._recorder_read("current", H.CurrentLayout, H.CurrentCounts, currents_from_words, reset)
 
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):
