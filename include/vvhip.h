@@ -802,6 +802,116 @@ int vvhip_current_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_wo
 int vvhip_current_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_current_info(const vvhip_plan* plan, vvhip_current_layout* out);
+/* ---------------------------------------------------------------- density modes accumulated on the device: S(k) and F(k, t)
+ * The scattering side of the observables: the partial and charge structure factors S_gh(k) = <rho_g*(k) rho_h(k)> / sqrt(N_g N_h), whose
+ * prepeak is the fingerprint of an ionic liquid, and the coherent intermediate scattering function F_gh(k, t) = <rho_g*(k, 0) rho_h(k, t)> /
+ * sqrt(N_g N_h), with rho_g(k) = sum_{i in g} w_i exp(i k . X_i).  Neither follows from the other recorders: the Fourier transform of a g(r)
+ * cut at L / 2 is useless below k ~ 4 pi / L, where the prepeak sits, and F(k, t) is a product of collective sums at two times, which is not
+ * a sum of per-particle terms.  A stand-alone host gets it from float64 frames, 24 B per particle and sample, then N K sines and cosines.
+ * After every full step whose count is a multiple of `interval` -- counted as for the other riders; a sample "after step k" is enqueued
+ * behind that step's current sample -- the step entry point enqueues four kernels (csrc/vv_dev_modes.inc): the gather, the mode kernel,
+ * the correlate and the advance.  No memset, no host work; inside a captured graph they are part of the graph and the steps that take a
+ * sample are part of the graph-cache key.  The recorder reads posq and posqCorrection and writes its own words and scratch, nothing else;
+ * a plan that never starts one launches what it launched before and allocates nothing.
+ * Inputs.  weight[num_atoms] (float64, required, finite, read at the start: 1 gives number densities, the charges the charge structure
+ * factor).  group[num_atoms]: -1 is not recorded, NULL: everything in group 0; G = num_groups, 1 .. 8.  modes[K][3] (int32, K = num_modes,
+ * 1 .. 4096, every component in -4095 .. 4095): mode k is the wave vector 2 pi (n_x / L_x, n_y / L_y, n_z / L_z) of the box AS IT STANDS AT
+ * THE SAMPLE, commensurate with any orthorhombic box, also after a barostat move.  (0,0,0), duplicates and +-pairs are the caller's business.
+ * Position to integer turns.  X_i = (double) posq + (double) posqCorrection in mixed precision, (double) posq otherwise, positions
+ * unwrapped, as for the other recorders.  Per axis a, with inv_L_a = 1.0 / box[a] formed on the host at enqueue:
+ *     t = X_a * inv_L_a,   u = t - floor(t),   T_a = (uint64) floor(u * 2^32) & 0xFFFFFFFF
+ * u = 1.0 (from t = -1e-20) becomes 2^32 and wraps to 0, which is the right phase: no clamp.
+ * Phase.  phi = (n_x T_x + n_y T_y + n_z T_z) mod 2^32 in two's-complement 32-bit arithmetic: the multiple of a turn drops out exactly and
+ * there is no floating-point argument reduction.
+ * Phasor (csrc/vv_layout.h: phasor_turns).  t = (phi + 2^29) mod 2^32, quadrant q = t >> 30, r = (int) (t & (2^30 - 1)) - 2^29,
+ * x = (double) r * C with C the double nearest to pi 2^-31 (|x| <= pi / 4), z = x * x,
+ *     sn = x + (x * z) * PS(z),   cs = (1.0 - 0.5 * z) + (z * z) * PC(z)
+ * with PS = S1 + z (S2 + z (.. S6)) and PC = C1 + z (C2 + z (.. C6)) the six-term fdlibm k_sin / k_cos polynomials, by Horner from the
+ * highest coefficient, every * and + rounded on its own, NO fma; (cos, sin) = (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs) for q = 0 .. 3.
+ * Only correctly rounded + - * occur, so NumPy states it bit for bit (tests/modes_reference.py); the absolute error is below 2^-51.
+ * Terms and sums.  W (weight_bound) is the smallest power of two above max |w_i| over the recorded particles (1 if all are 0) and
+ * F = 30 - log2 W, so that every term fits an int32:
+ *     a_ik = (int32) rint((w_i * c_ik) * 2^F),   b_ik = (int32) rint((w_i * s_ik) * 2^F)          (float64, round-half-even)
+ *     A_g(k) = sum_{i in g} a_ik,                B_g(k) = sum_{i in g} b_ik                        (int64)
+ * Integer adds commute: the sums are the same bits for any grid, block size or particle order.
+ * Invalid samples, as for the currents: a recorded particle with a position component that is NaN or at or beyond limit_position (nm;
+ * 0: the default of 64; rounded up to a power of two) is out of range: it adds 1 to out_of_range and makes the sample INVALID.  An invalid
+ * sample adds nothing to any row, is not usable as an origin, and adds 1 to invalid_samples; the ordinal still advances.
+ * Schedule, ring and table, as for vvhip_current_*.  Sample ordinal j = 0, 1, ... counts the due steps since the start or the last reset,
+ * valid or not.  num_lags = 0 .. 4096; 0 means the static S(k) only: then there is no ring and num_origins = 0.  Otherwise every sample
+ * whose ordinal is a multiple of origin_every (E) is also stored as an origin, in slot (j / E) mod num_origins of a device ring
+ * int64 ring[num_origins][G][K][2] (A, B), with a word per slot that says which sample it holds, or -1; num_origins = ceil(num_lags / E).
+ * Table: int64 words[num_lags + 1][row_words], row_words = 1 + G^2 K: word 0 of a row is an integer count, then cell[g][h][k], the bits of
+ * doubles.  With a = (double) A * 2^-F, b likewise, at a valid sample j, all in float64 without contraction:
+ *     row 0:   cell[g][h][k] += a_g(j) * a_h(j) + b_g(j) * b_h(j);   count[0] += 1
+ *     rows l = 1 .. num_lags, where the origin o = j - l is usable -- o is a multiple of E, origin_floor <= o, and the slot still holds
+ *     sample o and it was valid:
+ *              cell[g][h][k] += a_g(o) * a_h(j) + b_g(o) * b_h(j)    (the origin is the first index);   count[l] += 1
+ * This is Re rho_g*(o) rho_h(j).  The imaginary part averages to zero in equilibrium and is NOT kept.  A cell receives at most one term
+ * per sample, so its value is the sequential float64 sum in ascending sample order, and that order is part of the definition: one thread
+ * owns a cell for a sample, there are no float atomics.  Accumulation comes first, the origin store second.  Past max_samples a sample adds
+ * nothing, stores no origin and counts as dropped.  box_sum[a] is the sequential float64 sum of L_a over the valid samples: the host needs
+ * it for |k| under a barostat.
+ * What rewrites positions outside the steps.  vvhip_barostat_scale and vvhip_barostat_restore, with a recorder running, set origin_floor
+ * to the current ordinal: older origins are dead, the table is kept; later samples use the new box's wave vectors.  vvhip_checkpoint_load is
+ * refused while a recorder runs.  Host uploads into the bound arrays are NOT detected.
+ * Recovery.  The rider's recovery words are the WHOLE allocation: head, sums, table, ring and the slots' words.  The turns are scratch,
+ * rewritten by every sample, and not saved. */
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 0 .. 4096: row l is the lag of l * interval steps, row 0 the zero lag; 0: S(k) only, no ring */
+    int32_t origin_every;           /* E, 1 .. max(1, num_lags): every E-th sample is stored as an origin */
+    int32_t num_groups;             /* G, 1 .. 8 */
+    int32_t num_modes;              /* K, 1 .. 4096 */
+    const double* weight;           /* [num_atoms] required, finite */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: not recorded; NULL: everything in group 0 */
+    const int32_t* modes;           /* [num_modes][3] required, every component in -4095 .. 4095 */
+    int64_t max_samples;            /* >= 1 */
+    double limit_position;          /* nm: a position component at or beyond it is out of range; rounded up to a power of two; 0: 64 */
+} vvhip_modes_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset, valid or not (at most max_samples): the next ordinal */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added or stored for them */
+    int64_t out_of_range;           /* recorded particles found out of range, over all samples taken */
+    int64_t invalid_samples;        /* samples taken with at least one of them: count[0] = samples - invalid_samples */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+    double box_sum[3];              /* the valid samples' L_x, L_y, L_z, summed in sample order */
+} vvhip_modes_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, num_groups, num_modes;
+    int32_t num_particles;          /* recorded particles (group >= 0) */
+    int32_t num_origins;            /* ceil(num_lags / origin_every); 0 with num_lags = 0 */
+    int32_t row_words;              /* 1 + G^2 K */
+    int32_t frac_bits;              /* F */
+    int32_t group_sites[8];         /* N_g: the recorded particles of every group */
+    int32_t num_items;              /* the mode kernel's work items (blocks) ... */
+    int32_t sites_per_thread, k_tile, block_threads;      /* ... and the shape they were built for */
+    int64_t max_samples;
+    int64_t words;                  /* (num_lags + 1) * row_words */
+    int64_t ring_bytes;             /* num_origins * (G * K * 2 + 1) * 8: the origins' sums and the slots' words */
+    int64_t scratch_bytes;          /* the turns: 3 planes of uint32, num_particles rounded up to 16 each */
+    int64_t start_step;             /* the plan's step count at vvhip_modes_start */
+    double limit_position;          /* as applied */
+    double weight_bound;            /* W */
+} vvhip_modes_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 0 .. 4096, origin_every outside 1 .. max(1, num_lags), num_groups outside 1 .. 8,
+ * num_modes outside 1 .. 4096, max_samples < 1, a limit_position that is negative or not finite, weight NULL, modes NULL, a mode component
+ * outside -4095 .. 4095, a group entry outside -1 .. num_groups - 1, a weight that is not finite (VVHIP_ERR_INVALID naming the argument);
+ * F below 8, 31 + ceil_log2(N + 1) above 62 for N recorded particles, a table above 2^26 words (VVHIP_ERR_INVALID); a sharded plan
+ * (VVHIP_ERR_UNSUPPORTED: the shards' sums would have to be combined before the products are formed); an unbound plan; inside a graph
+ * capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes the checks in
+ * front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_modes_info answers for it, for sizing. */
+int vvhip_modes_start(vvhip_plan* plan, const vvhip_modes_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the ordinal at 0 with no
+ * live origin: the step schedule continues without gap or repeat. */
+int vvhip_modes_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_modes_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table, ring and scratch are released, the description is forgotten; synchronises and
+ * drops the captured graphs. */
+int vvhip_modes_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_modes_info(const vvhip_plan* plan, vvhip_modes_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

@@ -452,4 +452,38 @@ struct CurrentArgs {
     double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
 };
 
+// Density-mode sample (vv_dev_modes.inc, include/vvhip.h: vvhip_modes_* states the turns, the phase, the phasor, the sums, the table and the
+// order of its float64 adds).  As for a current sample the ordinal, the origin floor and the ring are device-side words.  One allocation:
+// head, sums, table, ring, holds; the turns are scratch of their own, rewritten by every sample.
+enum { MODES_SAMPLES = 0, MODES_DROPPED = 1, MODES_OUT_OF_RANGE = 2, MODES_INVALID = 3, MODES_FLOOR = 4,
+       MODES_BOX_SUM = 5,           // [5 .. 7]: the bits of three doubles
+       MODES_BAD = 8,               // the out-of-range sites of the sample in flight (the advance kernel zeroes it)
+       MODES_HEAD = 12 };           // the words in front of the sample's sums
+constexpr int MODES_MAX_GROUPS = 8, MODES_MAX_K_TILE = 1024;
+// A block's work: the sites s0 .. s1 - 1 of the compact list, all of group `group`, against the modes k0 .. k1 - 1 (k1 - k0 <= MODES_MAX_K_TILE,
+// s1 - s0 <= threads per block * sites per thread)
+struct ModesItem { int32_t group, s0, s1, k0, k1, pad_[3]; };
+struct ModesArgs {
+    const void* posq;               // real4 [particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // [n] the recorded sites, ordered by group, inside a group ascending by particle
+    const double* weight;           // [n] beside index
+    const int32_t* modes;           // [num_modes][3]
+    const ModesItem* items;         // [num_items]
+    unsigned int* turns;            // [3][stride] the sites' T_x, T_y, T_z planes, rewritten by every sample's gather
+    long long* words;               // [MODES_HEAD] head, then sums[G][K][2] (A, B), the table, the ring, the holds
+    long long* table;               // [num_lags + 1][row_words]
+    long long* ring;                // [num_origins][G][K][2] the origins' sums
+    long long* hold;                // [num_origins] the ordinal of the sample a slot holds, -1: none that is usable
+    int64_t max_samples;
+    int32_t n, stride;              // sites; n rounded up to 16
+    int32_t num_groups, num_modes;
+    int32_t num_lags, origin_every;
+    int32_t num_origins, row_words; // ceil(num_lags / origin_every); 1 + G^2 K
+    int32_t num_items, pad_;
+    double inv_L[3], box[3];        // 1.0 / L[a], formed on the host, and the plan's box at enqueue
+    double limit;                   // |X_a| at or beyond it is out of range
+    double scale, inv_scale;        // 2^F, 2^-F
+};
+
 }  // namespace vv

@@ -61,6 +61,7 @@ int vvhip_barostat_scale(vvhip_plan* p, const double scale[3]) {
         return fail(p, VVHIP_ERR_OVERFLOW, "barostat: a position is not finite or beyond 2^22 nm; nothing was moved and the box stays");
     TRY(msd_positions_rewritten(p));
     TRY(current_positions_rewritten(p));
+    TRY(modes_positions_rewritten(p));
     for (int k = 0; k < 3; k++) { B.box_before[k] = p->box[k]; p->box[k] *= scale[k]; B.box_after[k] = p->box[k]; }
     drop_graphs(p);                 // the box is baked into the captured kernel arguments
     p->rec.valid = false;           // (a snapshot from before the scale would put the old positions back under the new box)
@@ -88,6 +89,7 @@ int vvhip_barostat_restore(vvhip_plan* p) {
     if (hp.precision == VVHIP_MIXED) HIP_TRY(p, hipMemcpyAsync(p->buf.posq_correction, B.corr.get(), pos_bytes, hipMemcpyDeviceToDevice, p->stream));
     TRY(msd_positions_rewritten(p));
     TRY(current_positions_rewritten(p));
+    TRY(modes_positions_rewritten(p));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     for (int k = 0; k < 3; k++) p->box[k] = B.box_before[k];
     drop_graphs(p);

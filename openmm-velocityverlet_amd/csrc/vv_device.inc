@@ -22,3 +22,4 @@
 #include "vv_dev_msd.inc"
 #include "vv_dev_rdf.inc"
 #include "vv_dev_current.inc"
+#include "vv_dev_modes.inc"

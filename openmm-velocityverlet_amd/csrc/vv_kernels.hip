@@ -537,6 +537,36 @@ hipError_t launch_current_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_current_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+hipError_t launch_modes(int precision, const ModesArgs& a, int sites_per_thread, int block_threads, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: the planes hold the sites, an item's sites fit its block's registers (the host built the items for this shape)
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    if (a.num_groups < 1 || a.num_groups > MODES_MAX_GROUPS || a.num_modes < 1 || a.n < 0 || a.stride < a.n || a.num_items < 0 || a.num_origins < 0 ||
+        (long long) a.row_words != 1 + (long long) a.num_groups * a.num_groups * a.num_modes)
+        return hipErrorInvalidValue;
+    const dim3 gg((unsigned) std::max(1, std::min((a.n + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_modes_gather), gg, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 gm((unsigned) std::max(1, a.num_items)), bm((unsigned) block_threads);
+    switch (sites_per_thread) {
+        case 1: hipLaunchKernelGGL(vv_kernel_modes<1>, gm, bm, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(vv_kernel_modes<2>, gm, bm, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(vv_kernel_modes<4>, gm, bm, 0, s, a); break;
+        case 8: hipLaunchKernelGGL(vv_kernel_modes<8>, gm, bm, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const long long cells = (long long) (a.num_origins + 1) * (a.row_words - 1);
+    const dim3 gc((unsigned) std::max<long long>(1, std::min<long long>((cells + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(vv_kernel_modes_correlate, gc, dim3(256), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_modes_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_modes_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_modes_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

@@ -91,5 +91,13 @@ hipError_t launch_rdf(int precision, const RdfArgs& a, int grid_cap, hipStream_t
 hipError_t launch_current(int precision, const CurrentArgs& a, int block_threads, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as CurrentArgs::words.
 hipError_t launch_current_floor(long long* words, hipStream_t s);
+// One density-mode sample (vv_dev_modes.inc): the gather over a.n sites in blocks of 256, at most grid_cap of them; the mode kernel with one
+// block of block_threads threads (64 .. 512, a multiple of 64) and sites_per_thread (1, 2, 4, 8) sites per thread for each of a.num_items
+// work items (one idle block where there is none) -- the items must have been built for this shape: no item has more than block_threads *
+// sites_per_thread sites or MODES_MAX_K_TILE modes --; the correlate kernel with one thread per (ring slot or zero lag, g, h, k) in blocks
+// of 256, at most grid_cap; then the one-wave kernel that stores the origin and counts the sample.
+hipError_t launch_modes(int precision, const ModesArgs& a, int sites_per_thread, int block_threads, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as ModesArgs::words.
+hipError_t launch_modes_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

@@ -97,4 +97,33 @@ VV_HOST_DEVICE inline double cos_short_range(double x, bool& ok) {
     return (n == 1 || n == 2) ? -res : res;
 }
 
+// ---- (cos, sin) of a phase given in 2^-32 turns, for the density modes (include/vvhip.h: vvhip_modes_* states it; vv_dev_modes.inc)
+// The phase is an integer, so the multiple of a turn has dropped out exactly before this function sees it and there is no floating-point
+// argument reduction at all: the quadrant is the top two bits of phi + 1/8 turn, the rest is an exact signed offset r from the quadrant's
+// centre, |r| <= 2^29, and x = r * C (C the double next to pi 2^-31) has |x| <= pi/4 with ONE rounding.  Then the six-term fdlibm
+// polynomials (k_sin.c / k_cos.c: the coefficients of cos_short_range above) by Horner from the highest coefficient, every * and + rounded
+// on its own -- NO fma, unlike cos_short_range: NumPy states this function bit for bit (tests/modes_reference.py), and the host build is
+// held to that by a digest (tests/cpp/phasor_check.cpp).  Worst absolute error against long double over 2^22 random phases and every
+// quadrant and octant edge +- 1: below 2^-51 (tests/test_modes.py).
+VV_HOST_DEVICE inline void phasor_turns(unsigned int phi, double& c, double& s) {
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    const double TURN = 0x1.921fb54442d18p-30;                            // the double next to pi 2^-31 (1.4629180792671596e-09)
+    const unsigned int t = phi + 0x20000000u;                             // (mod 2^32)
+    const unsigned int q = t >> 30;
+    const int r = (int) (t & 0x3FFFFFFFu) - 0x20000000;
+    const double x = (double) r * TURN;
+    const double z = x * x;
+    const double ps = S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))));
+    const double pc = C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))));
+    const double sn = x + (x * z) * ps;
+    const double cs = (1.0 - 0.5 * z) + (z * z) * pc;
+    c = (q & 1) ? sn : cs;                                                // (cs, sn), (-sn, cs), (-cs, -sn), (sn, -cs)
+    s = (q & 1) ? cs : sn;
+    if (q == 1 || q == 2) c = -c;
+    if (q >= 2) s = -s;
+}
+
 }  // namespace vv

@@ -1,7 +1,7 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The four accumulating recorders
+// correlations, density modes, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The five accumulating recorders
 // share one life cycle (recorder_*).
 #include "vv_plan.hpp"
 
@@ -172,6 +172,35 @@ int current_positions_rewritten(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ density modes (vvhip_modes_*)
+// One sample behind the step just enqueued (or captured), and behind its current sample: the gather, the mode kernel, the correlate and the
+// one-wave kernel that stores the origin and counts the sample.  Four launches, no memset and no host synchronisation.  1 / L and the box
+// are arguments: what changes the box drops the captured graphs, and the wave vectors follow the new box.
+static int modes_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Modes& M = p->modes;
+    const vvhip_modes_layout& L = M.lay;
+    vv::ModesArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.index = M.dev.index.get(); a.weight = M.dev.weight.get(); a.modes = M.dev.modes.get(); a.items = M.dev.items.get();
+    a.turns = M.dev.turns.get();
+    a.words = M.d_words.get(); a.table = a.words + M.table_offset(); a.ring = a.table + L.words;
+    a.hold = a.ring + (size_t) L.num_origins * M.sums_words();
+    a.max_samples = L.max_samples;
+    a.n = L.num_particles; a.stride = M.stride(); a.num_groups = L.num_groups; a.num_modes = L.num_modes;
+    a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins; a.row_words = L.row_words;
+    a.num_items = L.num_items;
+    for (int k = 0; k < 3; k++) { a.inv_L[k] = 1.0 / p->box[k]; a.box[k] = p->box[k]; }
+    a.limit = L.limit_position;
+    a.scale = std::ldexp(1.0, L.frac_bits); a.inv_scale = std::ldexp(1.0, -L.frac_bits);
+    HIP_TRY(p, vv::launch_modes(p->hp.precision, a, L.sites_per_thread, L.block_threads, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
+// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
+int modes_positions_rewritten(vvhip_plan* p) {
+    if (!p->modes.on) return VVHIP_OK;
+    HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -214,7 +243,8 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   3 profile sample    behind the frame; ALL of d_words, counts and table: a sample added twice is not the same table
 //   4 MSD sample        behind the profile sample; all of d_words, the ring of origins included: the repeat needs the origins it overwrote
 //   5 RDF sample        behind the MSD sample; all of d_words, counts and table (its gather scratch is rewritten by every sample)
-//   6 current sample    last; all of d_words: head, sums, table, the ring of origins and the slots' words
+//   6 current sample    behind the RDF sample; all of d_words: head, sums, table, the ring of origins and the slots' words
+//   7 density-mode sample   last; all of d_words likewise (its turns are scratch, rewritten by every sample)
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -222,7 +252,7 @@ Riders riders(vvhip_plan* p) {
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
-             recorder_rider(p->current, current_enqueue)}};
+             recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -244,7 +274,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the four accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the five accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -967,5 +997,105 @@ int vvhip_current_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words
 }
 int vvhip_current_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::current, "current"); }
 int vvhip_current_info(const vvhip_plan* p, vvhip_current_layout* out) { return recorder_info(p, &vvhip_plan::current, out); }
+
+int vvhip_modes_start(vvhip_plan* p, const vvhip_modes_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "modes: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "modes: interval must be >= 1 step");
+    if (d->num_lags < 0 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "modes: num_lags must be in [0, 4096]");
+    if (d->origin_every < 1 || d->origin_every > std::max(1, d->num_lags)) return fail(p, VVHIP_ERR_INVALID, "modes: origin_every must be in [1, max(1, num_lags)]");
+    if (d->num_groups < 1 || d->num_groups > vv::MODES_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "modes: num_groups must be in [1, 8]");
+    if (d->num_modes < 1 || d->num_modes > 4096) return fail(p, VVHIP_ERR_INVALID, "modes: num_modes must be in [1, 4096]");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "modes: max_samples must be >= 1");
+    if (!(d->limit_position >= 0) || !std::isfinite(d->limit_position)) return fail(p, VVHIP_ERR_INVALID, "modes: limit_position must be finite and >= 0 (0: the default of 64 nm)");
+    if (!d->weight) return fail(p, VVHIP_ERR_INVALID, "modes: weight must not be NULL");
+    if (!d->modes) return fail(p, VVHIP_ERR_INVALID, "modes: modes must not be NULL");
+    for (int32_t k = 0; k < d->num_modes; k++)
+        for (int c = 0; c < 3; c++)
+            if (d->modes[3 * k + c] < -4095 || d->modes[3 * k + c] > 4095)
+                return fail(p, VVHIP_ERR_INVALID, "modes: modes[" + std::to_string(k) + "][" + std::to_string(c) + "] = " + std::to_string(d->modes[3 * k + c]) + " is outside [-4095, 4095]");
+    const vv::HostPlan& hp = p->hp;
+    TRY(check_groups(p, "modes", d->group, d->num_groups));
+    for (int32_t i = 0; i < hp.num_atoms; i++)
+        if (!std::isfinite(d->weight[i])) return fail(p, VVHIP_ERR_INVALID, "modes: weight[" + std::to_string(i) + "] is not finite");
+    // ---- the recorded sites, the layout, the fixed point and the mode kernel's work list, host only
+    vvhip_plan::Modes N;
+    vvhip_modes_layout& L = N.lay;
+    const int G = d->num_groups, K = d->num_modes;
+    double wmax = 0;
+    for (int32_t i = 0; i < hp.num_atoms; i++) {
+        const int g = d->group ? (int) d->group[i] : 0;
+        if (g < 0) continue;
+        L.group_sites[g]++;
+        wmax = std::max(wmax, std::fabs(d->weight[i]));
+    }
+    int32_t first[vv::MODES_MAX_GROUPS + 1] = {0};
+    for (int g = 0; g < G; g++) first[g + 1] = first[g] + L.group_sites[g];
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.num_groups = G; L.num_modes = K;
+    L.max_samples = d->max_samples;
+    L.num_particles = first[G];
+    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.row_words = 1 + G * G * K;
+    L.words = (int64_t) (L.num_lags + 1) * L.row_words;
+    L.ring_bytes = (int64_t) L.num_origins * ((int64_t) G * K * 2 + 1) * (int64_t) sizeof(long long);
+    L.limit_position = d->limit_position > 0 ? pow2_at_least(d->limit_position) : 64.0;
+    L.weight_bound = wmax > 0 ? pow2_above(wmax) : 1.0;
+    L.frac_bits = 30 - std::ilogb(L.weight_bound);
+    if (L.frac_bits < 8)
+        return fail(p, VVHIP_ERR_INVALID, "modes: the terms would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with weights below " +
+                                          std::to_string(L.weight_bound) + ": scale the weights");
+    if (31 + ceil_log2((long long) L.num_particles + 1) > 62)
+        return fail(p, VVHIP_ERR_INVALID, "modes: " + std::to_string(L.num_particles) + " terms of 31 bits could overflow a 64-bit sum");
+    if (L.words > (1ll << 26))
+        return fail(p, VVHIP_ERR_INVALID, "modes: the table would have " + std::to_string((long long) L.words) + " words (num_lags + 1 rows of 1 + G^2 K), above 2^26: "
+                                          "record fewer lags, modes or groups");
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "modes: a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
+                                              "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
+    N.index.resize((size_t) first[G]); N.weight.resize((size_t) first[G]);
+    {
+        int32_t next[vv::MODES_MAX_GROUPS];
+        std::copy(first, first + vv::MODES_MAX_GROUPS, next);
+        for (int32_t i = 0; i < hp.num_atoms; i++) {        // ascending by particle inside every group
+            const int g = d->group ? (int) d->group[i] : 0;
+            if (g < 0) continue;
+            N.index[(size_t) next[g]] = i; N.weight[(size_t) next[g]] = d->weight[i];
+            next[g]++;
+        }
+    }
+    N.modes.assign(d->modes, d->modes + 3 * (size_t) K);
+    // the work list: per group its sites in runs of block_threads * sites_per_thread, the modes in runs of k_tile.  First choices (nothing
+    // here has been scanned on a device yet: TUNING_LOG.md): blocks of 256 threads; 4 sites per thread and 32 modes per item where that
+    // still makes 1024 items, else fewer of either (sites first: a short mode run pays the wave sum and the flush more often)
+    L.block_threads = p->modes_block_threads ? p->modes_block_threads : 256;
+    auto count_items = [&](int P, int kt) {
+        long long n = 0;
+        for (int g = 0; g < G; g++) n += (long long) ((L.group_sites[g] + L.block_threads * P - 1) / (L.block_threads * P)) * ((K + kt - 1) / kt);
+        return n;
+    };
+    int P = p->modes_sites_per_thread ? p->modes_sites_per_thread : 4, kt = p->modes_k_tile ? p->modes_k_tile : 32;
+    while (!p->modes_sites_per_thread && P > 1 && count_items(P, kt) < 1024) P /= 2;
+    while (!p->modes_k_tile && kt > 8 && count_items(P, kt) < 1024) kt /= 2;
+    L.sites_per_thread = P; L.k_tile = kt;
+    const int run = L.block_threads * P;
+    for (int g = 0; g < G; g++)
+        for (int32_t s0 = first[g]; s0 < first[g + 1]; s0 += run)
+            for (int32_t k0 = 0; k0 < K; k0 += kt)
+                N.items.push_back({g, s0, std::min(first[g + 1], s0 + run), k0, std::min(K, k0 + kt), {0, 0, 0}});
+    L.num_items = (int32_t) N.items.size();
+    L.scratch_bytes = (int64_t) 3 * N.stride() * (int64_t) sizeof(unsigned int);
+    return recorder_install(p, &vvhip_plan::modes, "modes", N, d->interval);
+}
+int vvhip_modes_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_modes_counts* out, int32_t reset) {
+    long long head[vv::MODES_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::modes, "modes", words_out, capacity_words, head));
+    if (out) {
+        *out = {head[vv::MODES_SAMPLES], head[vv::MODES_DROPPED], head[vv::MODES_OUT_OF_RANGE], head[vv::MODES_INVALID], head[vv::MODES_FLOOR], {0, 0, 0}};
+        std::memcpy(out->box_sum, &head[vv::MODES_BOX_SUM], sizeof out->box_sum);
+    }
+    return reset ? recorder_reset(p, p->modes) : VVHIP_OK;
+}
+int vvhip_modes_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::modes, "modes"); }
+int vvhip_modes_info(const vvhip_plan* p, vvhip_modes_layout* out) { return recorder_info(p, &vvhip_plan::modes, out); }
 
 }  // extern "C"

@@ -8,9 +8,9 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the seven scheduled riders in ride order (riders) --
-//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current sample, with their
-//                    late words: the rings' cursors, the removals' record, the four recorders' d_words; the recorders' one life cycle
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the eight scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode sample, with their
+//                    late words: the rings' cursors, the removals' record, the five recorders' d_words; the recorders' one life cycle
 //                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -83,8 +83,8 @@ constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 // The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
 //   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
-//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample (3 .. 6: all of d_words)
-constexpr int kRiders = 7;
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample (3 .. 7: all of d_words)
+constexpr int kRiders = 8;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -156,6 +156,9 @@ struct vvhip_plan {
     int msd_wave_reduce = 1;       // an MSD sample's waves whose units share a group add their four sums once (test hook "msd_wave_reduce": 0 = every lane adds; same bits)
     int current_two_level = 0;     // a current sample's reduce stores per-block slabs that the correlate kernel sums, instead of agent-scope adds (test hook "current_two_level", read at the start; same bits; TUNING_LOG.md)
     int current_block_threads = 0; // threads per block of a current sample's reduce, 0: by the number of particles (current_enqueue; test hook "current_block_threads"; same bits)
+    int modes_sites_per_thread = 0; // sites a thread of a density-mode sample's mode kernel keeps in registers: 1, 2, 4, 8; 0: by the number of work items (vvhip_modes_start; test hook "modes_sites_per_thread", read at the start; same bits)
+    int modes_k_tile = 0;          // modes per work item of that kernel, 1 .. 1024; 0: by the number of work items (test hook "modes_k_tile", read at the start; same bits)
+    int modes_block_threads = 0;   // threads per block of that kernel, 0: 256 (test hook "modes_block_threads", read at the start; same bits)
     int rdf_hist_copies = 1;       // private histograms per block of an RDF sample's pair kernel: 1, or 4 = one per wave where they fit the LDS budget (test hook "rdf_hist_copies"; same bits; TUNING_LOG.md)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
@@ -175,7 +178,7 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // all seven riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF and current sample.  A
+        // all eight riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current and density-mode sample.  A
         // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the four recorders' d_words
         long long step_count = 0;
     } cur;
@@ -348,7 +351,7 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // What the four accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // What the five accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
     // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
     // `on`: the recorder runs and the device buffers exist.  Each recorder adds
     //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
@@ -479,6 +482,47 @@ struct vvhip_plan {
             return e == hipSuccess ? empty_slots(s) : e;
         }
     } current;
+    // Density modes for the structure factors (vvhip_modes_*; vv_dev_modes.inc), scheduled by cur.step_count.  The compact list of the
+    // recorded sites (ordered by group, then by index), the modes and the mode kernel's work items are built when the recorder starts;
+    // lay holds the shape the items were built for (sites_per_thread, k_tile, block_threads)
+    struct Modes : Recorder {
+        vvhip_modes_layout lay{};
+        std::vector<int32_t> index;               // [num_particles] the recorded sites
+        std::vector<double> weight;               // beside index
+        std::vector<int32_t> modes;               // [num_modes][3]
+        std::vector<vv::ModesItem> items;
+        struct Dev {
+            vv::DevBuf<int32_t> index, modes;
+            vv::DevBuf<double> weight;
+            vv::DevBuf<vv::ModesItem> items;
+            vv::DevBuf<unsigned int> turns;       // [3][stride()] rewritten by every sample, not saved
+        } dev;
+        static constexpr int kHead = vv::MODES_HEAD;        // d_words: head, sums, table, ring, the slots' words
+        size_t table_offset() const { return kHead + sums_words(); }
+        int32_t stride() const { return (lay.num_particles + 15) / 16 * 16; }
+        size_t sums_words() const { return (size_t) lay.num_groups * (size_t) lay.num_modes * 2; }
+        size_t front_words() const { return (size_t) kHead + sums_words() + (size_t) lay.words; }      // what a reset zeroes
+        size_t bytes() const { return front_words() * sizeof(long long) + (size_t) lay.ring_bytes; }
+        // no slot holds a sample: the slots' words, the allocation's last num_origins, are -1
+        hipError_t empty_slots(hipStream_t s) {
+            if (lay.num_origins == 0) return hipSuccess;
+            return hipMemsetAsync(d_words.get() + bytes() / sizeof(long long) - lay.num_origins, 0xFF, (size_t) lay.num_origins * sizeof(long long), s);
+        }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = vv::zeros(dev.turns, *asked = std::max<size_t>(16, (size_t) lay.scratch_bytes), s);
+            if (e == hipSuccess) e = put(dev.index, index, asked);
+            if (e == hipSuccess) e = put(dev.weight, weight, asked);
+            if (e == hipSuccess) e = put(dev.modes, modes, asked);
+            if (e == hipSuccess) e = put(dev.items, items, asked, 32);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
+        // (head, sums and table to zero, the slots' words to -1, so the ring may keep its bits)
+        hipError_t reset(hipStream_t s) {
+            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
+    } modes;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -610,6 +654,7 @@ int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
 int msd_positions_rewritten(vvhip_plan* p);      // vvhip_barostat_scale / _restore: an MSD recorder's origins so far are dead
+int modes_positions_rewritten(vvhip_plan* p);    // ... and a density-mode recorder's
 int current_positions_rewritten(vvhip_plan* p);  // ... and a current recorder's
 // One of the device work items that hang on the plan's step counter.  A new one is a descriptor in riders() with its enqueue function and its
 // entry points: the step hooks, the graph keys (vv_run.cpp) and the recovery (recovery_items) walk the list.

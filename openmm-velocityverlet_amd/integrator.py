@@ -607,6 +607,140 @@ def currents_from_words(words, layout, counts) -> Currents:
                     frac_bits_velocity=int(layout.frac_bits_velocity), words=words)
 
 
+def modes_in_shells(box, k_max: float, max_per_shell: Optional[int] = None, seed: int = 0) -> np.ndarray:
+    """int32 [K, 3]: the integer triples n != 0 of the orthorhombic `box` (nm) with |k| = 2 pi |n / L| <= k_max (1/nm), ONE of every +-pair
+    (the first non-zero component is positive), sorted by |n|^2, then by the triple.  max_per_shell thins every |n|^2 shell to at most
+    that many triples, drawn without replacement by a generator seeded with (seed, |n|^2), so a shell's choice does not depend on k_max."""
+    L = np.asarray(box, dtype=np.float64).reshape(3)
+    top = [int(np.floor(float(k_max) * L[a] / (2.0 * np.pi))) for a in range(3)]
+    if max(top) > 4095:
+        raise ValueError("a mode component beyond 4095: lower k_max")
+    axes = [np.arange(-t, t + 1, dtype=np.int64) for t in top]
+    n = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
+    half = (n[:, 0] > 0) | ((n[:, 0] == 0) & (n[:, 1] > 0)) | ((n[:, 0] == 0) & (n[:, 1] == 0) & (n[:, 2] > 0))
+    k = 2.0 * np.pi * np.sqrt((((n / L) ** 2)).sum(axis=1))
+    n = n[half & (k <= float(k_max))]
+    n2 = (n * n).sum(axis=1)
+    n = n[np.lexsort((n[:, 2], n[:, 1], n[:, 0], n2))]
+    n2 = (n * n).sum(axis=1)
+    if max_per_shell is not None:
+        keep = []
+        for shell in np.unique(n2):
+            at = np.nonzero(n2 == shell)[0]
+            if at.size > int(max_per_shell):
+                at = np.sort(np.random.default_rng([int(seed), int(shell)]).choice(at, int(max_per_shell), replace=False))
+            keep.append(at)
+        n = n[np.concatenate(keep)] if keep else n
+    return np.ascontiguousarray(n, dtype=np.int32)
+
+
+@dataclasses.dataclass
+class DensityModes:
+    """Density-mode correlations per lag (Context.modes_read; include/vvhip.h: vvhip_modes_* states the sums, the schedule and the table).
+    `words` is the device's table as it stands, int64 [num_lags + 1, 1 + G^2 K]: the count, then the bits of the float64 sums
+    cell[g][h][k] of Re rho_g*(0) rho_h(t); row l is the lag of l * interval steps, row 0 the zero lag."""
+    samples: int                           # samples taken, valid or not
+    dropped: int                           # samples that were due past max_samples
+    out_of_range: int                      # recorded particles found out of range
+    invalid_samples: int                   # samples with at least one of them: they add nothing and are no origin
+    origin_floor: int                      # origins with an ordinal below it are dead (a barostat move rewrote the positions)
+    box_sum: np.ndarray                    # float64 [3]: the valid samples' box edges (nm), summed in sample order
+    interval: int
+    origin_every: int
+    num_groups: int
+    frac_bits: int
+    group_sites: np.ndarray                # int64 [G]: N_g
+    modes: Optional[np.ndarray]            # int32 [K, 3] as given to modes_start (None: unknown to this object)
+    words: np.ndarray                      # int64 [num_lags + 1, row_words]
+
+    @property
+    def num_modes(self) -> int:
+        return (self.words.shape[1] - 1) // (self.num_groups * self.num_groups)
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [num_lags + 1]: row l is the lag of l * interval steps."""
+        return np.arange(self.words.shape[0], dtype=np.int64) * self.interval
+
+    @property
+    def count(self) -> np.ndarray:
+        """int64 [num_lags + 1]: the time origins behind every row."""
+        return self.words[:, 0]
+
+    @property
+    def mean_box(self) -> np.ndarray:
+        """float64 [3]: the mean box edges over the valid samples, NaN without one."""
+        valid = self.samples - self.invalid_samples
+        return self.box_sum / valid if valid > 0 else np.full(3, np.nan)
+
+    def _cells(self, g: int, h: int) -> np.ndarray:
+        G, K = self.num_groups, self.num_modes
+        if not (0 <= int(g) < G and 0 <= int(h) < G):
+            raise ValueError("groups must be in [0, %d)" % G)
+        first = 1 + (int(g) * G + int(h)) * K
+        return np.ascontiguousarray(self.words[:, first:first + K]).view(np.float64)
+
+    def F(self, g: int = 0, h: int = 0) -> np.ndarray:
+        """float64 [num_lags + 1, K]: <Re rho_g*(0) rho_h(t)> / sqrt(N_g N_h), the origin the first index; NaN where a lag has no origin
+        or a group no site."""
+        cells = self._cells(g, h)
+        n = self.count[:, None].astype(np.float64)
+        norm = np.sqrt(float(self.group_sites[int(g)]) * float(self.group_sites[int(h)]))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where((n > 0) & (norm > 0), cells / n / norm, np.nan)
+
+    def S(self, g: int = 0, h: int = 0) -> np.ndarray:
+        """float64 [K]: the static structure factor, row 0 / count / sqrt(N_g N_h)."""
+        return self.F(g, h)[0]
+
+    def k_magnitudes(self) -> np.ndarray:
+        """float64 [K]: |k| = 2 pi |n / <L>| in 1/nm from the mean box."""
+        if self.modes is None:
+            raise ValueError("the modes are unknown to this object")
+        return 2.0 * np.pi * np.sqrt(((self.modes.astype(np.float64) / self.mean_box) ** 2).sum(axis=1))
+
+    def shells(self) -> np.ndarray:
+        """int64 [K]: the shell of every mode, the rank of its |n|^2 among the distinct values."""
+        if self.modes is None:
+            raise ValueError("the modes are unknown to this object")
+        m = self.modes.astype(np.int64)
+        return np.unique((m * m).sum(axis=1), return_inverse=True)[1].reshape(-1)
+
+    def shell_average(self, values) -> Tuple[np.ndarray, np.ndarray]:
+        """(k [shells], mean [..., shells]): `values` [..., K] (S or F) averaged over the modes of every |n|^2 shell, against the shell's
+        mean |k|."""
+        sh = self.shells()
+        ns = int(sh.max()) + 1 if sh.size else 0
+        member = (sh[None, :] == np.arange(ns)[:, None]).astype(np.float64)      # [shells, K]
+        per = member.sum(axis=1)
+        v = np.asarray(values, dtype=np.float64)
+        return member @ self.k_magnitudes() / per, (v[..., None, :] * member).sum(axis=-1) / per
+
+    def relaxation_time(self, g: int, k_shell: int, dt: float = 1.0) -> float:
+        """The first lag time (lag steps x dt) at which the shell-averaged F_gg(k, t) / S_gg(k) of shell `k_shell` falls below 1 / e,
+        linearly interpolated between the two rows around it; NaN if it never does within the table."""
+        y = self.shell_average(self.F(g, g))[1][:, int(k_shell)]
+        y = y / y[0]
+        t = self.lag_steps.astype(np.float64) * float(dt)
+        below = np.nonzero(y < np.exp(-1.0))[0]
+        if below.size == 0 or below[0] == 0:
+            return float("nan")
+        i = int(below[0])
+        return float(t[i - 1] + (t[i] - t[i - 1]) * (y[i - 1] - np.exp(-1.0)) / (y[i - 1] - y[i]))
+
+
+def modes_from_words(words, layout, counts, modes=None) -> DensityModes:
+    """A DensityModes from a table's int64 words, its layout (H.ModesLayout), counts (H.ModesCounts) and the modes given at the start."""
+    words = np.ascontiguousarray(words, dtype=np.int64).reshape(int(layout.num_lags) + 1, int(layout.row_words))
+    G = int(layout.num_groups)
+    return DensityModes(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range),
+                        invalid_samples=int(counts.invalid_samples), origin_floor=int(counts.origin_floor),
+                        box_sum=np.array([float(counts.box_sum[a]) for a in range(3)]), interval=int(layout.interval),
+                        origin_every=int(layout.origin_every), num_groups=G, frac_bits=int(layout.frac_bits),
+                        group_sites=np.array([int(layout.group_sites[g]) for g in range(G)], dtype=np.int64),
+                        modes=None if modes is None else np.ascontiguousarray(modes, dtype=np.int32).reshape(-1, 3), words=words)
+
+
 def _viscosity_of_rows(v_bias, box, cos_acc, inv_mass_total, single):
     """vvhip_calc_viscosity's arithmetic, in its order, on every row (float64, no contraction: the same bits as the C function)."""
     v = v_bias.astype(np.float32).astype(np.float64) if single else v_bias.copy()      # vMaxBuffer is `mixed`
@@ -870,7 +1004,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the four accumulating recorders below share: profile, msd, rdf, current (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the five accumulating recorders below share: profile, msd, rdf, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1018,6 +1152,41 @@ class Context:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
         return self._recorder_read("current", H.CurrentLayout, H.CurrentCounts, currents_from_words, reset)
+
+    # ---- density modes, S(k) and F(k, t), accumulated on the device inside the steps (include/vvhip.h: vvhip_modes_*)
+    def modes_start(self, interval: int, modes, num_lags: int = 0, origin_every: int = 1, weights=None, groups=None,
+                    max_samples: int = 1 << 20, limit_position: float = 0.0):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), sum w_i exp(i k . X_i) per group
+        and mode as fixed-point integers and correlate the sums against the stored origins: per lag of 0 .. `num_lags` samples
+        Re rho_g*(0) rho_h(t), in float64 in sample order, so that the table is the same bits for any launch shape.  `modes`: integer
+        triples [K, 3] (modes_in_shells), mode k being 2 pi n / L of the box as it stands at the sample.  `weights`: one float per particle
+        of the System; None: 1 (number densities); the charges give the charge structure factor.  num_lags = 0: S(k) only, no ring.
+        `groups`: one int per particle (-1: not recorded, at most 8 groups); None: everything in group 0.  A position component at or
+        beyond the limit (nm; 0: 64) makes the whole sample invalid.  A sharded context raises ERR_UNSUPPORTED.  No host synchronisation
+        until modes_read."""
+        n = self.system.num_atoms
+        w = np.ones(n, dtype=np.float64) if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n:
+            raise ValueError("weights must have one entry per particle of the System")
+        m = np.ascontiguousarray(modes, dtype=np.int32).reshape(-1, 3)
+        if not np.array_equal(m, np.asarray(modes).reshape(-1, 3)):
+            raise ValueError("modes must be integer triples")
+        grp = self._groups(groups)
+        desc = H.ModesDesc(int(interval), int(num_lags), int(origin_every), 1 if grp is None else max(int(grp.max()) + 1, 1), int(m.shape[0]),
+                           w.ctypes.data, None if grp is None else grp.ctypes.data, m.ctypes.data, int(max_samples), float(limit_position))
+        H.check(H.lib.vvhip_modes_start(self.plan, C.byref(desc)), self.plan)
+        self._modes = m.copy()
+
+    def modes_stop(self):
+        self._recorder_stop("modes")
+
+    def modes_info(self) -> H.ModesLayout:
+        return self._recorder_info("modes", H.ModesLayout)
+
+    def modes_read(self, reset: bool = False) -> DensityModes:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        return self._recorder_read("modes", H.ModesLayout, H.ModesCounts, modes_from_words, reset, getattr(self, "_modes", None))
 
     # ---- removal of the centre-of-mass motion on the device (include/vvhip.h: vvhip_cm_motion_*); nothing is on by default
     def remove_cm_motion_every(self, frequency: int):

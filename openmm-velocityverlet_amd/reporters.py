@@ -24,6 +24,8 @@ latest three kept.
 
 ``write_current`` writes a device-side collective current correlation table (``Context.current_read``) as text columns, one line per lag.
 
+``write_modes`` writes device-side density-mode correlations (``Context.modes_read``), S(k) and F(k, t), as text columns, one line per mode.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -301,6 +303,30 @@ def write_current(file, cur, dt, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for l in range(cur.words.shape[0]):
             print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_modes(file, dm, dt, g=0, h=0, append=False, header=True):
+    """Density-mode correlations (Context.modes_read) as text: two comment lines (samples, dropped, out of range, invalid samples, origin
+    floor, the box sums; the column names) unless header=False, then one tab-separated line per mode -- n_x, n_y, n_z, |k| in 1/nm from
+    the mean box, S_gh(k), then F_gh(k, t) for every lag from the first on (the lag times in ps, lag steps x `dt`, are in the column
+    names; nan where a lag has no origin).  Floats are written with repr, so np.loadtxt reads back the bits.  `file`: a path or an open
+    text stream."""
+    F = dm.F(g, h)
+    k = dm.k_magnitudes()
+    lags = dm.lag_steps.astype(np.float64) * float(dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"InvalidSamples"\t%d\t"OriginFloor"\t%d\t"BoxSum"\t%r\t%r\t%r' %
+                  (dm.samples, dm.dropped, dm.out_of_range, dm.invalid_samples, dm.origin_floor, *[float(x) for x in dm.box_sum]), file=out)
+            names = ["nx", "ny", "nz", "k (1/nm)", "S[%d-%d]" % (g, h)] + ["F[%d-%d](%r ps)" % (g, h, float(t)) for t in lags[1:]]
+            print("#" + "\t".join('"%s"' % name for name in names), file=out)
+        for m in range(F.shape[1]):
+            print(*[str(int(c)) for c in dm.modes[m]], repr(float(k[m])), *[repr(float(v)) for v in F[:, m]], sep="\t", file=out)
         out.flush()
     finally:
         if own:

@@ -202,6 +202,27 @@ class CurrentLayout(C.Structure):
                 ("limit_velocity", C.c_double), ("weight_bound", C.c_double)]
 
 
+class ModesDesc(C.Structure):
+    """What a density-mode recorder is to accumulate (include/vvhip.h: vvhip_modes_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("num_modes", C.c_int32), ("weight", C.c_void_p), ("group", C.c_void_p), ("modes", C.c_void_p),
+                ("max_samples", C.c_int64), ("limit_position", C.c_double)]
+
+
+class ModesCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64), ("invalid_samples", C.c_int64),
+                ("origin_floor", C.c_int64), ("box_sum", C.c_double * 3)]
+
+
+class ModesLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("num_modes", C.c_int32), ("num_particles", C.c_int32), ("num_origins", C.c_int32), ("row_words", C.c_int32),
+                ("frac_bits", C.c_int32), ("group_sites", C.c_int32 * 8), ("num_items", C.c_int32), ("sites_per_thread", C.c_int32),
+                ("k_tile", C.c_int32), ("block_threads", C.c_int32), ("max_samples", C.c_int64), ("words", C.c_int64),
+                ("ring_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("start_step", C.c_int64), ("limit_position", C.c_double),
+                ("weight_bound", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -292,6 +313,8 @@ def _load():
         "vvhip_msd_read": [vp, vp, C.c_int64, P(MsdCounts), i32],
         "vvhip_current_start": [vp, P(CurrentDesc)], "vvhip_current_stop": [vp], "vvhip_current_info": [vp, P(CurrentLayout)],
         "vvhip_current_read": [vp, vp, C.c_int64, P(CurrentCounts), i32],
+        "vvhip_modes_start": [vp, P(ModesDesc)], "vvhip_modes_stop": [vp], "vvhip_modes_info": [vp, P(ModesLayout)],
+        "vvhip_modes_read": [vp, vp, C.c_int64, P(ModesCounts), i32],
         "vvhip_rdf_start": [vp, P(RdfDesc)], "vvhip_rdf_sample": [vp], "vvhip_rdf_stop": [vp], "vvhip_rdf_info": [vp, P(RdfLayout)],
         "vvhip_rdf_read": [vp, vp, C.c_int64, P(RdfCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
