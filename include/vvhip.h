@@ -912,6 +912,112 @@ int vvhip_modes_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_word
 int vvhip_modes_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_modes_info(const vvhip_plan* plan, vvhip_modes_layout* out);
+/* ---------------------------------------------------------------- contact lifetime correlations accumulated on the device
+ * How long ion pairs and ion cages live: which anion sits in which cation's first shell, and for how long -- the intermittent and the
+ * continuous contact correlation functions that explain the transport coefficients.  The RDF says how many neighbours there are, not which;
+ * from frames every sample is an all-pairs pass and a time-correlation function wants hundreds of origins.  On the device a sample is a
+ * bit matrix and a lag is a popcount of an AND.  After every full step whose count is a multiple of `interval` -- counted exactly as for
+ * the other riders, by the same entry points; a sample "after step k" is enqueued behind that step's density-mode sample -- the step entry
+ * point enqueues four kernels (csrc/vv_dev_contacts.inc): a gather of the sites' float64 positions, the mask kernel that builds the sample's
+ * bit matrices, the correlate kernel, and a one-wave kernel that counts the sample: no memset, no host work.  Inside a captured graph all
+ * four are graph nodes and the steps that take a sample are part of the graph-cache key.  The recorder reads posq and posqCorrection and
+ * writes its own words and scratch, nothing else; a plan that never starts one launches what it launched before and allocates nothing.
+ * Sites.  As for the RDF: the particles with group[i] >= 0, each in the one group it names; `group` covers the whole System, NULL puts
+ * every particle into group 0; num_groups is 1 .. 16.
+ * Classes.  num_classes (1 .. 8) ORDERED pairs of groups, classes[c] = {ga, gb}, each with its own cutoff r_cut[c].  The rows of class c are
+ * the sites of ga (N_a of them), the columns the sites of gb (N_b), both in ascending particle index.  ga == gb is allowed: the diagonal (a
+ * site with itself) is 0, and every unordered pair {i, j} appears twice, as (i, j) and as (j, i) -- every word of the table counts it
+ * twice.  With exclude_same_molecule != 0 pairs whose particles have equal vvhip_system_desc.mol_id are 0 in every class.
+ * Contact.  r2 is exactly the RDF's: positions in float64, (double) posq + (double) posqCorrection in mixed precision; per axis, with L the
+ * plan's box when the sample is enqueued and inv_L_a = 1.0 / L_a,  d = X_i,a - X_j,a;  n = rint(d * inv_L_a);  d = d - L_a * n;  then
+ * r2 = (dx * dx + dy * dy) + dz * dz, no contraction.  h_ij = 1 iff r2 < r_cut[c] * r_cut[c] (float64, the compare is strict: a pair AT the
+ * cutoff is no contact).  A pair whose r2 is NaN has h = 0 and adds 1 to `invalid` (a cleared pair -- diagonal, same molecule -- adds nothing).
+ * Per sample.  j = the 0-based ordinal of the counted samples, E = origin_every, R = num_origins = ceil(num_lags / E) slots, each with
+ * origin[s], cont[s] (bit matrices of every class) and ord[s] (-1: empty).  In this order:
+ *   1. h(j) is built for every class.
+ *   2. If j mod E = 0, slot s = (j / E) mod R takes origin[s] = h(j), cont[s] = h(j), ord[s] = j.
+ *   3. Every slot with ord[s] >= 0 and l = j - ord[s] < num_lags (the slot just stored included, at l = 0): cont[s] &= h(j), and for every
+ *      class c the four integers  1,  popcount(origin[s]_c),  popcount(origin[s]_c & h(j)_c),  popcount(cont[s]_c)  are added to
+ *      table[c][l][0 .. 3].  A slot with l >= num_lags adds nothing (R E > num_lags).
+ *   4. samples += 1.
+ * Table: int64 table[num_classes][num_lags][4].  Word 2 / word 1 is the intermittent correlation C(t) (the pair is in contact at 0 and at
+ * t), word 3 / word 1 the continuous one S(t) (in contact at every sample from 0 to t), word 1 / (word 0 N_a) the mean number of contacts
+ * per row site.  continuous = 0 keeps no cont ring: word 3 stays 0.  Integer adds commute: the table is the same bits for any work list.
+ * Limits.  num_lags 1 .. 4096, origin_every 1 .. num_lags, R <= 1024.  r_cut[c] finite, > 0 and <= min(Lx, Ly, Lz) / 2 of the plan's box
+ * at the start.  Refused where the largest N_a N_b times max_samples reaches 2^62, and where the recorder's whole allocation -- counts,
+ * table, slot ordinals, both rings, the sample's matrix and the gather's planes: total_bytes of the layout -- is above
+ * VVHIP_CONTACTS_MAX_BYTES = 2^32: the recovery snapshot copies it.  A matrix of class c has ceil(N_b / 64) words for each of N_a rounded
+ * up to 64 rows; a ring holds R matrices.
+ * Counts.  samples; dropped (due past max_samples, or enqueued while min(L) / 2 is below the largest cutoff: the host decides at enqueue,
+ * as for the RDF; nothing is added and j does not move); invalid.
+ * Barostat moves (vvhip_barostat_scale / _restore) raise NO origin floor: a contact set is a property of a configuration, not a
+ * displacement from one, so the origins stored before a move stay valid.
+ * Sharded plans are refused (VVHIP_ERR_UNSUPPORTED): the pairs across shards exist on no device.
+ * Recovery.  The rider's recovery words are the whole allocation -- counts, table, ord and both rings (words_bytes of the layout):
+ * neither the table nor the surviving contacts are idempotent under the repeat of failed steps, and the repeat needs the origins the
+ * failed window overwrote, as for the MSD.  The sample's matrix and the planes are rewritten by every sample and are not saved.
+ * vvhip_checkpoint_load is refused while a recorder runs; a re-bind drops the captured graphs. */
+#define VVHIP_CONTACTS_MAX_BYTES (1ll << 32)
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096 */
+    int32_t origin_every;           /* 1 .. num_lags */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t num_classes;            /* 1 .. 8 */
+    int32_t exclude_same_molecule;  /* != 0: pairs inside one molecule (mol_id) are no contacts */
+    int32_t continuous;             /* != 0: keep the surviving contacts (word 3) */
+    int32_t reserved;               /* 0 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: no site; NULL: everything in group 0 */
+    const int32_t* classes;         /* [num_classes][2] the groups ga (rows), gb (columns) of every class */
+    const double* r_cut;            /* [num_classes] nm */
+    int64_t max_samples;            /* >= 1 */
+} vvhip_contacts_desc;
+typedef struct {
+    int64_t samples;                /* samples counted since the start or the last reset (at most max_samples) */
+    int64_t dropped;                /* samples that were due past max_samples or in a box with min(L) / 2 below the largest cutoff */
+    int64_t invalid;                /* pairs whose r2 was NaN */
+} vvhip_contacts_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, num_groups, num_classes, exclude_same_molecule, continuous;
+    int32_t num_origins;            /* R */
+    int32_t rows_per_tile;          /* rows a block of the mask kernel stages (test hook "contacts_rows_per_tile") */
+    int32_t words_per_item;         /* column words per work item of the mask kernel (test hook "contacts_words_per_item") */
+    int32_t skip_zero_words;        /* the correlate kernel skips zero origin words (test hook "contacts_skip_zero") */
+    int32_t num_mask_items, num_corr_items;      /* blocks of the mask kernel per sample; of the correlate kernel per sample and slot */
+    int32_t num_sites[16];          /* per group */
+    int32_t classes[8][2];
+    int32_t rows[8], cols[8];       /* per class: N_a, N_b */
+    int64_t class_words[8];         /* per class: ceil(N_b / 64) * (N_a rounded up to 64) */
+    int64_t sample_words;           /* their sum: one matrix */
+    int64_t max_samples;
+    int64_t words;                  /* num_classes * num_lags * 4 */
+    int64_t words_bytes;            /* counts, table, ord, rings */
+    int64_t scratch_bytes;          /* the sample's matrix and the gather's planes */
+    int64_t total_bytes;            /* both: what VVHIP_CONTACTS_MAX_BYTES bounds */
+    int64_t start_step;             /* the plan's step count at vvhip_contacts_start */
+    double r_cut[8];
+} vvhip_contacts_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, num_groups outside 1 .. 16, num_classes
+ * outside 1 .. 8, classes NULL, r_cut NULL, max_samples < 1, a group entry outside -1 .. num_groups - 1, a class entry outside 0 ..
+ * num_groups - 1, a cutoff that is not finite or <= 0 (VVHIP_ERR_INVALID naming the argument); num_origins above 1024; the largest class's
+ * N_a N_b times max_samples at or above 2^62; total_bytes above VVHIP_CONTACTS_MAX_BYTES ("contacts: ... VVHIP_CONTACTS_MAX_BYTES"); a
+ * cutoff above half the shortest edge of the plan's box (VVHIP_ERR_INVALID); a sharded plan (VVHIP_ERR_UNSUPPORTED); an unbound plan;
+ * inside a graph capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes
+ * the checks in front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_contacts_info answers for it. */
+int vvhip_contacts_start(vvhip_plan* plan, const vvhip_contacts_desc* desc);
+/* Enqueues one sample now, behind what is queued, whatever the schedule says; it counts as a sample like a scheduled one (a host that
+ * analyses a configuration it has uploaded).  VVHIP_ERR_INVALID without a running recorder or inside a graph capture. */
+int vvhip_contacts_sample(vvhip_plan* plan);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts and table, marks every slot empty and restarts j at 0:
+ * the step schedule continues without gap or repeat. */
+int vvhip_contacts_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_contacts_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table, rings and scratch are released, the description is forgotten; synchronises and
+ * drops the captured graphs. */
+int vvhip_contacts_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_contacts_info(const vvhip_plan* plan, vvhip_contacts_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

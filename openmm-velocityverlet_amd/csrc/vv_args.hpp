@@ -486,4 +486,41 @@ struct ModesArgs {
     double scale, inv_scale;        // 2^F, 2^-F
 };
 
+// Contact sample (vv_dev_contacts.inc, include/vvhip.h: vvhip_contacts_* states the sites, the classes, the contact, the slots and the table).
+// The ordinal and the slots' ordinals are device-side words, so a replayed graph (same arguments every time) finds the origins where the last
+// sample left them and stops adding at max_samples; whether the box still holds the largest cutoff is the host's decision at enqueue
+// (`live`), as for an RDF sample.  One allocation: head, table, ord, the ring of origins, the ring of surviving contacts (vv_layout.h:
+// ContactsLayout); the sample's matrix and the gather's planes are scratch of their own, rewritten by every sample.
+enum { CONTACTS_SAMPLES = 0, CONTACTS_DROPPED = 1, CONTACTS_INVALID = 2, CONTACTS_HEAD = 4 };      // the words in front of the table
+constexpr int CONTACTS_MAX_ROWS_PER_TILE = 1024;      // the mask kernel's staged rows: 28 B each in LDS
+struct ContactsArgs {
+    const void* posq;               // real4 [particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // [n] particle of site s; the sites are ordered by group, inside a group ascending by particle
+    const int32_t* mol;             // [n] molecule of site s (exclusion on, else null)
+    const ContactsMaskItem* mask_items;     // [num_mask_items]
+    const ContactsCorrItem* corr_items;     // [num_corr_items]
+    double* scratch;                // [3][stride] the sites' x, y, z planes, rewritten by every sample's gather
+    unsigned long long* mask;       // [sample_words] h(j), rewritten by every sample's mask kernel
+    long long* words;               // [CONTACTS_HEAD] samples, dropped, invalid, then the table, ord and the rings
+    long long* table;               // [num_classes][num_lags][4]
+    long long* ord;                 // [num_origins] the ordinal of the sample a slot holds, -1: none
+    unsigned long long* origin;     // [num_origins][sample_words]
+    unsigned long long* cont;       // [num_origins][sample_words], null without the continuous correlation
+    int64_t max_samples;
+    int64_t sample_words;
+    int32_t n, stride;              // sites; n rounded up to 16
+    int32_t num_mask_items, num_corr_items;
+    int32_t num_classes, num_lags;
+    int32_t origin_every, num_origins;
+    int32_t live, skip_zero;        // 0: the box no longer holds the largest cutoff, the sample is dropped; 1: a zero origin word costs no further load
+    int32_t rows_per_tile, pad_;
+    double L[3], inv_L[3];          // the plan's box at enqueue and 1.0 / L[a], formed on the host
+    double cut2[CONTACTS_MAX_CLASSES];               // r_cut[c] * r_cut[c]
+    int64_t class_offset[CONTACTS_MAX_CLASSES];      // ContactsLayout
+    int32_t rows_padded[CONTACTS_MAX_CLASSES];
+    int32_t rows[CONTACTS_MAX_CLASSES], cols[CONTACTS_MAX_CLASSES];          // N_a, N_b
+    int32_t first_row[CONTACTS_MAX_CLASSES], first_col[CONTACTS_MAX_CLASSES];  // where the class's groups start in the site list
+};
+
 }  // namespace vv

@@ -23,3 +23,4 @@
 #include "vv_dev_rdf.inc"
 #include "vv_dev_current.inc"
 #include "vv_dev_modes.inc"
+#include "vv_dev_contacts.inc"

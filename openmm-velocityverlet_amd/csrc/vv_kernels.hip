@@ -567,6 +567,28 @@ hipError_t launch_modes_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_modes_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+hipError_t launch_contacts(int precision, const ContactsArgs& a, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: the staged rows fit the block's LDS, the planes hold the sites, the slots are a grid dimension
+    if (a.rows_per_tile < 64 || a.rows_per_tile > CONTACTS_MAX_ROWS_PER_TILE || a.rows_per_tile % 64) return hipErrorInvalidValue;
+    if (a.n < 0 || a.stride < a.n || a.num_mask_items < 0 || a.num_corr_items < 1 || a.num_origins < 1 || a.num_origins > 1024 ||
+        a.num_classes < 1 || a.num_classes > CONTACTS_MAX_CLASSES || a.sample_words % 2)
+        return hipErrorInvalidValue;
+    const dim3 gg((unsigned) std::max(1, std::min((a.n + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_contacts_gather), gg, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 gm((unsigned) std::max(1, a.num_mask_items));
+    const unsigned lds = (unsigned) a.rows_per_tile * (3 * sizeof(double) + sizeof(int)) + sizeof(long long);
+    if (a.mol) hipLaunchKernelGGL(vv_kernel_contacts_mask<true>, gm, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(vv_kernel_contacts_mask<false>, gm, dim3(256), lds, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const dim3 gc((unsigned) a.num_corr_items, (unsigned) a.num_origins);
+    if (a.cont) hipLaunchKernelGGL(vv_kernel_contacts_correlate<true>, gc, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(vv_kernel_contacts_correlate<false>, gc, dim3(256), 0, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_contacts_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

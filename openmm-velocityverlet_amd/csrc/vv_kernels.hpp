@@ -99,5 +99,11 @@ hipError_t launch_current_floor(long long* words, hipStream_t s);
 hipError_t launch_modes(int precision, const ModesArgs& a, int sites_per_thread, int block_threads, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as ModesArgs::words.
 hipError_t launch_modes_floor(long long* words, hipStream_t s);
+// One contact sample (vv_dev_contacts.inc): the gather over a.n sites in blocks of 256, at most grid_cap of them; the mask kernel with one
+// block of 256 threads per work item (one idle block where there is none) and dynamic LDS for a.rows_per_tile staged rows (a multiple of 64,
+// at most CONTACTS_MAX_ROWS_PER_TILE) -- the items must have been built for that tile --; the correlate kernel with one block of 256 per
+// (work item, slot of the ring); then the one-wave kernel that writes the slot's ordinal and counts the sample.  a.mol selects the mask
+// kernel that clears pairs of one molecule, a.cont the correlate kernel that keeps the surviving contacts.
+hipError_t launch_contacts(int precision, const ContactsArgs& a, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -126,4 +126,76 @@ VV_HOST_DEVICE inline void phasor_turns(unsigned int phi, double& c, double& s) 
     if (q >= 2) s = -s;
 }
 
+// ---- contact matrices (include/vvhip.h: vvhip_contacts_* states the sites, the classes, the contact and the table; vv_dev_contacts.inc)
+// One matrix holds every class's bits, word-major: class c starts at class_offset[c] and its word (jw, i) -- the columns 64 jw .. 64 jw + 63
+// of row i -- is at class_offset[c] + jw * rows_padded[c] + i.  rows_padded = N_a rounded up to 64 (the mask kernel stores 64 rows at a time;
+// the rows and columns past the last site are 0 bits), so a class's words are a multiple of 64 and every class starts on 16 bytes.
+// The recorder's words: [head_words] counts, table[C][num_lags][4], ord[R] (rounded up to an even count), then the ring of origins
+// [R][sample_words] and, with the continuous correlation, the ring of the surviving contacts, the same size.  The sample's own matrix and
+// the gather's planes are scratch.  Integers only: the host (vv_observe.cpp) and tests/cpp/contacts_layout_check.cpp share it.
+constexpr int CONTACTS_MAX_CLASSES = 8, CONTACTS_MAX_GROUPS = 16;
+constexpr int CONTACTS_CORR_PAIRS = 1024;      // pairs of words per work item of the correlate kernel (256 threads, four 128-bit loads each)
+struct ContactsLayout {
+    long long rows_padded[CONTACTS_MAX_CLASSES], col_words[CONTACTS_MAX_CLASSES];
+    long long class_words[CONTACTS_MAX_CLASSES], class_offset[CONTACTS_MAX_CLASSES];
+    long long sample_words;         // words of one matrix
+    int num_origins, ord_words;     // R = ceil(num_lags / origin_every); R rounded up to 2
+    long long table_words;          // num_classes * num_lags * 4
+    long long ring_words;           // R * sample_words, times 2 with the continuous correlation
+    long long words_bytes;          // counts, table, ord and rings: what a recovery snapshot copies
+    long long scratch_bytes;        // the sample's matrix and the gather's three planes (the sites rounded up to 16)
+    long long total_bytes;
+};
+inline ContactsLayout contacts_layout(int num_classes, const int* rows, const int* cols, int num_lags, int origin_every, bool continuous,
+                                      long long sites, int head_words) {
+    ContactsLayout L{};
+    for (int c = 0; c < num_classes; c++) {
+        L.rows_padded[c] = ((long long) rows[c] + 63) / 64 * 64;
+        L.col_words[c] = ((long long) cols[c] + 63) / 64;
+        L.class_words[c] = L.rows_padded[c] * L.col_words[c];
+        L.class_offset[c] = L.sample_words;
+        L.sample_words += L.class_words[c];
+    }
+    L.num_origins = (num_lags + origin_every - 1) / origin_every;
+    L.ord_words = (L.num_origins + 1) / 2 * 2;
+    L.table_words = (long long) num_classes * num_lags * 4;
+    L.ring_words = (long long) L.num_origins * L.sample_words * (continuous ? 2 : 1);
+    L.words_bytes = ((long long) head_words + L.table_words + L.ord_words + L.ring_words) * 8;
+    L.scratch_bytes = L.sample_words * 8 + 3 * ((sites + 15) / 16 * 16) * 8;
+    L.total_bytes = L.words_bytes + L.scratch_bytes;
+    return L;
+}
+// A block's work in the mask kernel: the rows i0 .. i1 - 1 of class cls (multiples of 64, i1 - i0 <= rows per tile, i1 <= rows_padded)
+// against the column words jw0 .. jw1 - 1
+struct ContactsMaskItem { int cls, i0, i1, jw0, jw1, pad_[3]; };
+// ... and in the correlate kernel: the pairs of words p0 .. p0 + np - 1 of a matrix (word 2 p), all of class cls; first != 0: the class's
+// designated block, which counts the visit.  A class without words still has that one item, with np = 0
+struct ContactsCorrItem { int cls, first; long long p0; int np, pad_; };
+// The two work lists; out = null: only the count.  rows_per_tile is a multiple of 64, words_per_item >= 1
+inline long long contacts_mask_items(const ContactsLayout& L, int num_classes, int rows_per_tile, int words_per_item, ContactsMaskItem* out) {
+    long long n = 0;
+    for (int c = 0; c < num_classes; c++)
+        for (long long i0 = 0; i0 < L.rows_padded[c]; i0 += rows_per_tile)
+            for (long long jw0 = 0; jw0 < L.col_words[c]; jw0 += words_per_item, n++) {
+                if (!out) continue;
+                const long long i1 = i0 + rows_per_tile < L.rows_padded[c] ? i0 + rows_per_tile : L.rows_padded[c];
+                const long long jw1 = jw0 + words_per_item < L.col_words[c] ? jw0 + words_per_item : L.col_words[c];
+                out[n] = {c, (int) i0, (int) i1, (int) jw0, (int) jw1, {0, 0, 0}};
+            }
+    return n;
+}
+inline long long contacts_corr_items(const ContactsLayout& L, int num_classes, ContactsCorrItem* out) {
+    long long n = 0;
+    for (int c = 0; c < num_classes; c++) {
+        const long long pairs = L.class_words[c] / 2;
+        long long p = 0;
+        do {
+            const long long np = pairs - p < CONTACTS_CORR_PAIRS ? pairs - p : CONTACTS_CORR_PAIRS;
+            if (out) out[n] = {c, p == 0 ? 1 : 0, L.class_offset[c] / 2 + p, (int) np, 0};
+            n++; p += np;
+        } while (p < pairs);
+    }
+    return n;
+}
+
 }  // namespace vv

@@ -1,7 +1,7 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, density modes, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The five accumulating recorders
+// correlations, density modes, contact lifetimes, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The six accumulating recorders
 // share one life cycle (recorder_*).
 #include "vv_plan.hpp"
 
@@ -201,6 +201,41 @@ int modes_positions_rewritten(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ contact lifetime correlations (vvhip_contacts_*)
+// One sample behind the step just enqueued (or captured), and behind its density-mode sample -- or behind what is queued
+// (vvhip_contacts_sample): the gather, the mask kernel, the correlate kernel and the one-wave kernel that counts the sample.  Four launches,
+// no memset and no host synchronisation.  The box and whether it still holds the largest cutoff are arguments: what changes the box drops
+// the captured graphs.  A barostat move leaves the origins alone: a contact set belongs to a configuration, not to a displacement.
+static int contacts_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Contacts& K = p->contacts;
+    const vvhip_contacts_layout& L = K.lay;
+    const vv::ContactsLayout& G = K.geo;
+    vv::ContactsArgs a{};
+    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.index = K.dev.index.get(); a.mol = L.exclude_same_molecule ? K.dev.mol.get() : nullptr;
+    a.mask_items = K.dev.mask_items.get(); a.corr_items = K.dev.corr_items.get();
+    a.scratch = K.dev.scratch.get(); a.mask = K.dev.mask.get();
+    a.words = K.d_words.get(); a.table = a.words + K.table_offset(); a.ord = a.table + L.words;
+    a.origin = (unsigned long long*) (a.ord + G.ord_words);
+    a.cont = L.continuous ? a.origin + (size_t) G.num_origins * (size_t) G.sample_words : nullptr;
+    a.max_samples = L.max_samples; a.sample_words = G.sample_words;
+    a.n = (int32_t) K.index.size(); a.stride = K.stride();
+    a.num_mask_items = L.num_mask_items; a.num_corr_items = L.num_corr_items;
+    a.num_classes = L.num_classes; a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
+    a.skip_zero = p->contacts_skip_zero; a.rows_per_tile = L.rows_per_tile;
+    double largest = 0;
+    for (int c = 0; c < L.num_classes; c++) {
+        largest = std::max(largest, L.r_cut[c]);
+        a.cut2[c] = L.r_cut[c] * L.r_cut[c];
+        a.class_offset[c] = G.class_offset[c]; a.rows_padded[c] = (int32_t) G.rows_padded[c];
+        a.rows[c] = L.rows[c]; a.cols[c] = L.cols[c];
+        a.first_row[c] = K.first[L.classes[c][0]]; a.first_col[c] = K.first[L.classes[c][1]];
+    }
+    a.live = rdf_box_holds(p->box, largest) ? 1 : 0;
+    for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
+    HIP_TRY(p, vv::launch_contacts(p->hp.precision, a, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -244,7 +279,8 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   4 MSD sample        behind the profile sample; all of d_words, the ring of origins included: the repeat needs the origins it overwrote
 //   5 RDF sample        behind the MSD sample; all of d_words, counts and table (its gather scratch is rewritten by every sample)
 //   6 current sample    behind the RDF sample; all of d_words: head, sums, table, the ring of origins and the slots' words
-//   7 density-mode sample   last; all of d_words likewise (its turns are scratch, rewritten by every sample)
+//   7 density-mode sample   behind the current sample; all of d_words likewise (its turns are scratch, rewritten by every sample)
+//   8 contact sample    last; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -252,7 +288,7 @@ Riders riders(vvhip_plan* p) {
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
-             recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue)}};
+             recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -274,7 +310,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the five accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the six accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -1097,5 +1133,103 @@ int vvhip_modes_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, 
 }
 int vvhip_modes_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::modes, "modes"); }
 int vvhip_modes_info(const vvhip_plan* p, vvhip_modes_layout* out) { return recorder_info(p, &vvhip_plan::modes, out); }
+
+int vvhip_contacts_start(vvhip_plan* p, const vvhip_contacts_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "contacts: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "contacts: interval must be >= 1 step");
+    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "contacts: num_lags must be in [1, 4096]");
+    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "contacts: origin_every must be in [1, num_lags]");
+    if (d->num_groups < 1 || d->num_groups > vv::CONTACTS_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "contacts: num_groups must be in [1, 16]");
+    if (d->num_classes < 1 || d->num_classes > vv::CONTACTS_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "contacts: num_classes must be in [1, 8]");
+    if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "contacts: classes must not be NULL");
+    if (!d->r_cut) return fail(p, VVHIP_ERR_INVALID, "contacts: r_cut must not be NULL");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "contacts: max_samples must be >= 1");
+    const vv::HostPlan& hp = p->hp;
+    TRY(check_groups(p, "contacts", d->group, d->num_groups));
+    for (int32_t c = 0; c < d->num_classes; c++)
+        for (int q = 0; q < 2; q++)
+            if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= d->num_groups)
+                return fail(p, VVHIP_ERR_INVALID, "contacts: classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(d->classes[2 * c + q]) + " is outside [0, num_groups = " + std::to_string(d->num_groups) + ")");
+    for (int32_t c = 0; c < d->num_classes; c++)
+        if (!(d->r_cut[c] > 0) || !std::isfinite(d->r_cut[c]))
+            return fail(p, VVHIP_ERR_INVALID, "contacts: r_cut[" + std::to_string(c) + "] must be finite and > 0");
+    // ---- the sites, the layout and the two kernels' work lists, host only
+    vvhip_plan::Contacts N;
+    vvhip_contacts_layout& L = N.lay;
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.num_groups = d->num_groups;
+    L.num_classes = d->num_classes; L.exclude_same_molecule = d->exclude_same_molecule != 0; L.continuous = d->continuous != 0;
+    L.max_samples = d->max_samples; L.words = (int64_t) d->num_classes * d->num_lags * 4;
+    L.rows_per_tile = p->contacts_rows_per_tile; L.words_per_item = p->contacts_words_per_item; L.skip_zero_words = p->contacts_skip_zero;
+    for (int32_t i = 0; i < hp.num_atoms; i++) {
+        const int g = d->group ? (int) d->group[i] : 0;
+        if (g >= 0) L.num_sites[g]++;
+    }
+    for (int g = 0; g < d->num_groups; g++) N.first[g + 1] = N.first[g] + L.num_sites[g];
+    int64_t largest = 0;
+    double longest = 0;
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int ga = d->classes[2 * c], gb = d->classes[2 * c + 1];
+        L.classes[c][0] = ga; L.classes[c][1] = gb;
+        L.rows[c] = L.num_sites[ga]; L.cols[c] = L.num_sites[gb];
+        L.r_cut[c] = d->r_cut[c];
+        largest = std::max(largest, (int64_t) L.rows[c] * L.cols[c]);
+        longest = std::max(longest, d->r_cut[c]);
+    }
+    N.geo = vv::contacts_layout(L.num_classes, L.rows, L.cols, L.num_lags, L.origin_every, L.continuous != 0, N.first[d->num_groups], vv::CONTACTS_HEAD);
+    const vv::ContactsLayout& G = N.geo;
+    L.num_origins = G.num_origins; L.sample_words = G.sample_words;
+    for (int32_t c = 0; c < d->num_classes; c++) L.class_words[c] = G.class_words[c];
+    L.words_bytes = G.words_bytes; L.scratch_bytes = G.scratch_bytes; L.total_bytes = G.total_bytes;
+    if (L.num_origins > 1024)
+        return fail(p, VVHIP_ERR_INVALID, "contacts: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
+    if ((unsigned __int128) largest * (unsigned __int128) d->max_samples >= ((unsigned __int128) 1 << 62))
+        return fail(p, VVHIP_ERR_INVALID, "contacts: " + std::to_string((long long) largest) + " pairs per sample times max_samples = " + std::to_string((long long) d->max_samples) +
+                                          " reaches 2^62: a word could overflow; lower max_samples");
+    if (L.total_bytes > VVHIP_CONTACTS_MAX_BYTES)
+        return fail(p, VVHIP_ERR_INVALID, "contacts: the recorder would hold " + std::to_string((long long) L.total_bytes) + " bytes (" + std::to_string(L.num_origins) + " slots of " +
+                                          std::to_string((long long) L.sample_words * 8) + " bytes" + (L.continuous ? ", twice" : "") + "), above VVHIP_CONTACTS_MAX_BYTES = 2^32: raise origin_every, record fewer lags or fewer sites");
+    if (!rdf_box_holds(p->box, longest))
+        return fail(p, VVHIP_ERR_INVALID, "contacts: the cutoff " + std::to_string(longest) + " nm is above half the shortest edge of the box (" +
+                                          std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm): a pair would have more than one image in range");
+    if (cmm_sharded(p))
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "contacts: a sharded plan holds its own particles' positions only, so the pairs across shards exist on no device; "
+                                              "a partial matrix is not recorded (run the analysis on an unsharded plan)");
+    N.index.resize((size_t) N.first[d->num_groups]);
+    if (L.exclude_same_molecule) N.mol.resize(N.index.size());
+    {
+        int32_t next[vv::CONTACTS_MAX_GROUPS];
+        std::copy(N.first, N.first + vv::CONTACTS_MAX_GROUPS, next);
+        for (int32_t i = 0; i < hp.num_atoms; i++) {      // ascending by particle inside every group
+            const int g = d->group ? (int) d->group[i] : 0;
+            if (g < 0) continue;
+            N.index[(size_t) next[g]] = i;
+            if (L.exclude_same_molecule) N.mol[(size_t) next[g]] = hp.mol_id[(size_t) i];
+            next[g]++;
+        }
+    }
+    // the work lists (vv_layout.h): per class, tile of rows and run of column words a block of the mask kernel; per class and run of
+    // CONTACTS_CORR_PAIRS pairs of words a block of the correlate kernel for every slot
+    N.mask_items.resize((size_t) vv::contacts_mask_items(G, L.num_classes, L.rows_per_tile, L.words_per_item, nullptr));
+    vv::contacts_mask_items(G, L.num_classes, L.rows_per_tile, L.words_per_item, N.mask_items.data());
+    N.corr_items.resize((size_t) vv::contacts_corr_items(G, L.num_classes, nullptr));
+    vv::contacts_corr_items(G, L.num_classes, N.corr_items.data());
+    L.num_mask_items = (int32_t) N.mask_items.size(); L.num_corr_items = (int32_t) N.corr_items.size();
+    return recorder_install(p, &vvhip_plan::contacts, "contacts", N, d->interval);
+}
+int vvhip_contacts_sample(vvhip_plan* p) {
+    NEED_BOUND(p);
+    if (!p->contacts.on) return fail(p, VVHIP_ERR_INVALID, "contacts: none started (vvhip_contacts_start)");
+    TRY(quiesce(p, "contacts", false, false));
+    return contacts_enqueue(p);
+}
+int vvhip_contacts_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_contacts_counts* out, int32_t reset) {
+    long long head[vv::CONTACTS_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::contacts, "contacts", words_out, capacity_words, head));
+    if (out) *out = {head[vv::CONTACTS_SAMPLES], head[vv::CONTACTS_DROPPED], head[vv::CONTACTS_INVALID]};
+    return reset ? recorder_reset(p, p->contacts) : VVHIP_OK;
+}
+int vvhip_contacts_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::contacts, "contacts"); }
+int vvhip_contacts_info(const vvhip_plan* p, vvhip_contacts_layout* out) { return recorder_info(p, &vvhip_plan::contacts, out); }
 
 }  // extern "C"

@@ -8,9 +8,9 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the eight scheduled riders in ride order (riders) --
-//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode sample, with their
-//                    late words: the rings' cursors, the removals' record, the five recorders' d_words; the recorders' one life cycle
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the nine scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact sample, with their
+//                    late words: the rings' cursors, the removals' record, the six recorders' d_words; the recorders' one life cycle
 //                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -83,8 +83,8 @@ constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 // The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
 //   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
-//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample (3 .. 7: all of d_words)
-constexpr int kRiders = 8;
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample (3 .. 8: all of d_words)
+constexpr int kRiders = 9;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -160,6 +160,9 @@ struct vvhip_plan {
     int modes_k_tile = 0;          // modes per work item of that kernel, 1 .. 1024; 0: by the number of work items (test hook "modes_k_tile", read at the start; same bits)
     int modes_block_threads = 0;   // threads per block of that kernel, 0: 256 (test hook "modes_block_threads", read at the start; same bits)
     int rdf_hist_copies = 1;       // private histograms per block of an RDF sample's pair kernel: 1, or 4 = one per wave where they fit the LDS budget (test hook "rdf_hist_copies"; same bits; TUNING_LOG.md)
+    int contacts_rows_per_tile = 128;   // rows a block of a contact sample's mask kernel stages in LDS: a multiple of 64 up to 1024 (test hook "contacts_rows_per_tile", read at the start; same bits; TUNING_LOG.md)
+    int contacts_words_per_item = 4;    // column words per work item of that kernel, one per wave and trip: 1 .. 64 (test hook "contacts_words_per_item", read at the start; same bits)
+    int contacts_skip_zero = 1;         // the correlate kernel loads neither the sample's nor the surviving words behind a zero origin word (test hook "contacts_skip_zero"; same bits)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
@@ -178,7 +181,7 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // all eight riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current and density-mode sample.  A
+        // all nine riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode and contact sample.  A
         // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the four recorders' d_words
         long long step_count = 0;
     } cur;
@@ -351,7 +354,7 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // What the five accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // What the six accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
     // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
     // `on`: the recorder runs and the device buffers exist.  Each recorder adds
     //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
@@ -523,6 +526,46 @@ struct vvhip_plan {
             return e == hipSuccess ? empty_slots(s) : e;
         }
     } modes;
+    // Contact lifetime correlations (vvhip_contacts_*; vv_dev_contacts.inc), scheduled by cur.step_count.  The site list (ordered by group,
+    // inside a group ascending by particle), the sites' molecules and the two kernels' work items are built when the recorder starts;
+    // lay holds the shape the mask items were built for (rows_per_tile, words_per_item)
+    struct Contacts : Recorder {
+        vvhip_contacts_layout lay{};
+        vv::ContactsLayout geo{};                 // where every word lies (vv_layout.h)
+        int32_t first[vv::CONTACTS_MAX_GROUPS + 1] = {0};      // where a group's sites start in the list
+        std::vector<int32_t> index, mol;          // [sites] particle and molecule of every site (mol: with the exclusion on)
+        std::vector<vv::ContactsMaskItem> mask_items;
+        std::vector<vv::ContactsCorrItem> corr_items;
+        struct Dev {
+            vv::DevBuf<int32_t> index, mol;
+            vv::DevBuf<vv::ContactsMaskItem> mask_items;
+            vv::DevBuf<vv::ContactsCorrItem> corr_items;
+            vv::DevBuf<double> scratch;           // [3][stride()] rewritten by every sample, not saved
+            vv::DevBuf<unsigned long long> mask;  // [sample_words] likewise
+        } dev;
+        static constexpr int kHead = vv::CONTACTS_HEAD;     // d_words: head, table, ord, the ring of origins, the ring of surviving contacts
+        size_t table_offset() const { return kHead; }
+        int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
+        size_t front_words() const { return (size_t) kHead + (size_t) lay.words; }      // what a reset zeroes
+        size_t bytes() const { return (size_t) geo.words_bytes; }
+        // no slot holds a sample: the ord words are -1
+        hipError_t empty_slots(hipStream_t s) { return hipMemsetAsync(d_words.get() + front_words(), 0xFF, (size_t) geo.ord_words * sizeof(long long), s); }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = vv::zeros(dev.scratch, *asked = std::max<size_t>(16, 3 * (size_t) stride() * sizeof(double)), s);
+            if (e == hipSuccess) e = vv::zeros(dev.mask, *asked = std::max<size_t>(16, (size_t) geo.sample_words * sizeof(long long)), s);
+            if (e == hipSuccess) e = put(dev.index, index, asked);
+            if (e == hipSuccess && lay.exclude_same_molecule) e = put(dev.mol, mol, asked);
+            if (e == hipSuccess) e = put(dev.mask_items, mask_items, asked, 32);
+            if (e == hipSuccess) e = put(dev.corr_items, corr_items, asked, 32);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
+        // (head and table to zero, the ord words to -1, so the rings may keep their bits)
+        hipError_t reset(hipStream_t s) {
+            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
+            return e == hipSuccess ? empty_slots(s) : e;
+        }
+    } contacts;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -677,7 +720,8 @@ Riders riders(vvhip_plan* p);
 // whole allocation, counts and table: an accumulating table is not idempotent under the repeat, so it goes back as the snapshot took it.
 // For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.  For an RDF
 // recorder counts and table; its gather scratch is rewritten by every sample and is not saved.  For a current recorder the whole
-// allocation again: head, sums, table and the ring of origins.
+// allocation again: head, sums, table and the ring of origins.  For a density-mode recorder likewise.  For a contact recorder head, table,
+// the slots' ordinals and both rings of bit matrices: the surviving contacts are not idempotent under the repeat either.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

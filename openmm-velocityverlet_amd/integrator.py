@@ -476,6 +476,87 @@ def rdf_from_words(words, layout, counts) -> Rdf:
                counts=table)
 
 
+@dataclasses.dataclass
+class Contacts:
+    """Contact lifetime correlations per class and lag (Context.contacts_read; include/vvhip.h: vvhip_contacts_* states the sites, the
+    classes, the contact, the slots and the table).  `words` is the device's table as it stands, int64 [classes, lags, 4]: per lag the
+    visits, and the contacts at the origin, at the origin and now, and at every sample from the origin to now, summed over the visits."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples or in a box too small for the largest cutoff
+    invalid: int                           # pairs whose squared distance was NaN
+    interval: int
+    origin_every: int
+    continuous_kept: bool                  # the recorder kept the surviving contacts (word 3)
+    classes: np.ndarray                    # int32 [classes, 2] the groups of every class: rows, columns
+    rows: np.ndarray                       # int64 [classes] N_a
+    cols: np.ndarray                       # int64 [classes] N_b
+    r_cut: np.ndarray                      # float64 [classes] nm
+    words: np.ndarray                      # int64 [classes, lags, 4]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [lags]: the lag of every row in steps, 0 first."""
+        return np.arange(self.words.shape[1], dtype=np.int64) * self.interval
+
+    @property
+    def origins(self) -> np.ndarray:
+        """int64 [lags]: the (origin, sample) pairs every lag has seen (word 0; the same for every class)."""
+        return self.words[0, :, 0].copy()
+
+    def _ratio(self, c: int, word: int) -> np.ndarray:
+        den = self.words[int(c), :, 1].astype(np.float64)
+        return np.where(den > 0, self.words[int(c), :, word] / np.where(den > 0, den, 1.0), np.nan)
+
+    def intermittent(self, c: int) -> np.ndarray:
+        """float64 [lags]: C(t) of class c, the fraction of the origins' contacts that are contacts again at t; NaN where no origin had one."""
+        return self._ratio(c, 2)
+
+    def continuous(self, c: int) -> np.ndarray:
+        """float64 [lags]: S(t) of class c, the fraction of the origins' contacts that held at every sample up to t."""
+        if not self.continuous_kept:
+            raise ValueError("the recorder was started with continuous=False")
+        return self._ratio(c, 3)
+
+    def mean_contacts(self, c: int) -> float:
+        """Contacts per row site of class c, averaged over the origins (lag 0); NaN without a sample or a row."""
+        den = float(self.words[int(c), 0, 0]) * float(self.rows[int(c)])
+        return float(self.words[int(c), 0, 1]) / den if den > 0 else float("nan")
+
+    def _curve(self, c: int, kind: str) -> np.ndarray:
+        if kind not in ("intermittent", "continuous"):
+            raise ValueError("kind must be 'intermittent' or 'continuous'")
+        return self.intermittent(c) if kind == "intermittent" else self.continuous(c)
+
+    def time_to(self, c: int, kind: str = "intermittent", level: float = float(np.exp(-1.0)), dt: float = 1.0) -> float:
+        """The first lag time (lag steps x dt) at which the correlation of class c falls below `level`, linearly interpolated between the
+        two rows around it; NaN if it never does within the table."""
+        y = self._curve(c, kind)
+        t = self.lag_steps.astype(np.float64) * float(dt)
+        below = np.nonzero(y < level)[0]
+        if below.size == 0 or below[0] == 0:
+            return float("nan")
+        i = int(below[0])
+        return float(t[i - 1] + (t[i] - t[i - 1]) * (y[i - 1] - level) / (y[i - 1] - y[i]))
+
+    def lifetime(self, c: int, kind: str = "continuous", dt: float = 1.0) -> float:
+        """The trapezoid integral of the correlation of class c over the recorded lags (lag steps x dt): a lower bound of the lifetime
+        where the correlation has not decayed within the table."""
+        y = self._curve(c, kind)
+        t = self.lag_steps.astype(np.float64) * float(dt)
+        return float(np.sum(0.5 * (y[1:] + y[:-1]) * (t[1:] - t[:-1])))
+
+
+def contacts_from_words(words, layout, counts) -> Contacts:
+    """A Contacts from a table's int64 words [classes * lags * 4], its layout (H.ContactsLayout) and counts (H.ContactsCounts)."""
+    nc = int(layout.num_classes)
+    table = np.ascontiguousarray(words, dtype=np.int64).reshape(nc, int(layout.num_lags), 4)
+    return Contacts(samples=int(counts.samples), dropped=int(counts.dropped), invalid=int(counts.invalid), interval=int(layout.interval),
+                    origin_every=int(layout.origin_every), continuous_kept=bool(layout.continuous),
+                    classes=np.array([[layout.classes[c][0], layout.classes[c][1]] for c in range(nc)], dtype=np.int32).reshape(nc, 2),
+                    rows=np.array(layout.rows[:nc], dtype=np.int64), cols=np.array(layout.cols[:nc], dtype=np.int64),
+                    r_cut=np.array(layout.r_cut[:nc], dtype=np.float64), words=table)
+
+
 # Conductivity in S/m from e^2 / (nm ps kJ/mol): CODATA 2018 elementary charge (C) and Avogadro constant (1/mol), both exact.
 ELEMENTARY_CHARGE = 1.602176634e-19
 AVOGADRO = 6.02214076e23
@@ -1004,7 +1085,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the five accumulating recorders below share: profile, msd, rdf, current, modes (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the six accumulating recorders below share: profile, msd, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1116,6 +1197,43 @@ class Context:
         """The histograms accumulated so far (synchronises).  reset=True zeroes counts and table; the step schedule continues without gap
         or repeat."""
         return self._recorder_read("rdf", H.RdfLayout, H.RdfCounts, rdf_from_words, reset)
+
+    # ---- contact lifetime correlations accumulated on the device inside the steps (include/vvhip.h: vvhip_contacts_*)
+    def contacts_start(self, interval: int, num_lags: int, classes, r_cut, origin_every: int = 1, groups=None,
+                       exclude_same_molecule: bool = False, continuous: bool = True, max_samples: int = 1 << 20):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), build the contact matrix of every
+        class -- `classes`: ordered pairs of groups (rows, columns), `r_cut`: one cutoff in nm per class; a pair is a contact where its
+        minimum-image distance is strictly below the cutoff -- and correlate it against the stored origins: per lag of 0 .. `num_lags` - 1
+        samples the contacts at the origin, those that are contacts again, and (continuous=True) those that never broke, as integers, so
+        that the table is the same bits for any launch shape.  Every `origin_every`-th sample is stored as an origin.  `groups`: one int
+        per particle of the System (-1: no site); None: everything in group 0.  A class of one group with itself holds every pair twice.
+        The cutoffs must not exceed half the shortest box edge.  A sharded context raises ERR_UNSUPPORTED.  No host synchronisation until
+        contacts_read."""
+        grp = self._groups(groups)
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1, 2)
+        cut = np.ascontiguousarray(r_cut, dtype=np.float64).reshape(-1)
+        if cut.size != cls.shape[0]:
+            raise ValueError("r_cut must have one entry per class")
+        num_groups = max(1, 0 if grp is None else int(grp.max()) + 1, int(cls.max()) + 1 if cls.size else 1)      # (a class may name a group without sites)
+        desc = H.ContactsDesc(int(interval), int(num_lags), int(origin_every), num_groups, int(cls.shape[0]), int(bool(exclude_same_molecule)),
+                              int(bool(continuous)), 0, None if grp is None else grp.ctypes.data, cls.ctypes.data, cut.ctypes.data,
+                              int(max_samples))
+        H.check(H.lib.vvhip_contacts_start(self.plan, C.byref(desc)), self.plan)
+
+    def contacts_sample(self):
+        """One sample now, behind what is queued, whatever the schedule says (a configuration the host has just uploaded)."""
+        H.check(H.lib.vvhip_contacts_sample(self.plan), self.plan)
+
+    def contacts_stop(self):
+        self._recorder_stop("contacts")
+
+    def contacts_info(self) -> H.ContactsLayout:
+        return self._recorder_info("contacts", H.ContactsLayout)
+
+    def contacts_read(self, reset: bool = False) -> Contacts:
+        """The table accumulated so far (synchronises).  reset=True zeroes counts and table, empties every slot and restarts the sample
+        ordinal; the step schedule continues without gap or repeat."""
+        return self._recorder_read("contacts", H.ContactsLayout, H.ContactsCounts, contacts_from_words, reset)
 
     # ---- collective current correlations accumulated on the device inside the steps (include/vvhip.h: vvhip_current_*)
     def current_start(self, interval: int, num_lags: int, origin_every: int = 1, weights=None, molecules: bool = False, groups=None,
@@ -1260,7 +1378,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF or current recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode or contact recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

@@ -26,6 +26,8 @@ latest three kept.
 
 ``write_modes`` writes device-side density-mode correlations (``Context.modes_read``), S(k) and F(k, t), as text columns, one line per mode.
 
+``write_contacts`` writes device-side contact lifetime correlations (``Context.contacts_read``) as text columns, one line per lag.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -327,6 +329,39 @@ def write_modes(file, dm, dt, g=0, h=0, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name in names), file=out)
         for m in range(F.shape[1]):
             print(*[str(int(c)) for c in dm.modes[m]], repr(float(k[m])), *[repr(float(v)) for v in F[:, m]], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def contacts_columns(con, dt):
+    """[(name, values per lag)] of a contact table's text file: the lag in ps, the visits, then per class the contacts at the origin, those
+    that are contacts again, those that never broke, and the two correlations C(t) and S(t)."""
+    cols = [("lag (ps)", con.lag_steps.astype(np.float64) * float(dt)), ("origins", con.origins.astype(np.float64))]
+    for c in range(con.words.shape[0]):
+        tag = "%d-%d" % (int(con.classes[c, 0]), int(con.classes[c, 1]))
+        cols += [("at_origin[%s]" % tag, con.words[c, :, 1].astype(np.float64)), ("again[%s]" % tag, con.words[c, :, 2].astype(np.float64)),
+                 ("unbroken[%s]" % tag, con.words[c, :, 3].astype(np.float64)), ("C[%s]" % tag, con.intermittent(c))]
+        if con.continuous_kept:
+            cols.append(("S[%s]" % tag, con.continuous(c)))
+    return cols
+
+
+def write_contacts(file, con, dt, append=False, header=True):
+    """Contact lifetime correlations (Context.contacts_read) as text: two comment lines (samples, dropped, invalid; the column names)
+    unless header=False, then one tab-separated line per lag from the zero lag on -- the lag in ps (lag steps x `dt`), the count of
+    (origin, sample) pairs, then per class the three contact counts (exact below 2^53), the intermittent correlation C(t) and, where the
+    recorder kept it, the continuous one S(t) (nan where no origin had a contact).  Floats are written with repr, so np.loadtxt reads
+    back the bits.  `file`: a path or an open text stream."""
+    cols = contacts_columns(con, dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"Invalid"\t%d' % (con.samples, con.dropped, con.invalid), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for l in range(con.words.shape[1]):
+            print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:
         if own:

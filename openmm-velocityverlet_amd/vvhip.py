@@ -223,6 +223,30 @@ class ModesLayout(C.Structure):
                 ("weight_bound", C.c_double)]
 
 
+class ContactsDesc(C.Structure):
+    """What a contact recorder is to accumulate (include/vvhip.h: vvhip_contacts_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("continuous", C.c_int32), ("reserved", C.c_int32),
+                ("group", C.c_void_p), ("classes", C.c_void_p), ("r_cut", C.c_void_p), ("max_samples", C.c_int64)]
+
+
+class ContactsCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("invalid", C.c_int64)]
+
+
+class ContactsLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("num_groups", C.c_int32),
+                ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("continuous", C.c_int32), ("num_origins", C.c_int32),
+                ("rows_per_tile", C.c_int32), ("words_per_item", C.c_int32), ("skip_zero_words", C.c_int32), ("num_mask_items", C.c_int32),
+                ("num_corr_items", C.c_int32), ("num_sites", C.c_int32 * 16), ("classes", (C.c_int32 * 2) * 8), ("rows", C.c_int32 * 8),
+                ("cols", C.c_int32 * 8), ("class_words", C.c_int64 * 8), ("sample_words", C.c_int64), ("max_samples", C.c_int64),
+                ("words", C.c_int64), ("words_bytes", C.c_int64), ("scratch_bytes", C.c_int64), ("total_bytes", C.c_int64),
+                ("start_step", C.c_int64), ("r_cut", C.c_double * 8)]
+
+
+CONTACTS_MAX_BYTES = 1 << 32
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -317,6 +341,8 @@ def _load():
         "vvhip_modes_read": [vp, vp, C.c_int64, P(ModesCounts), i32],
         "vvhip_rdf_start": [vp, P(RdfDesc)], "vvhip_rdf_sample": [vp], "vvhip_rdf_stop": [vp], "vvhip_rdf_info": [vp, P(RdfLayout)],
         "vvhip_rdf_read": [vp, vp, C.c_int64, P(RdfCounts), i32],
+        "vvhip_contacts_start": [vp, P(ContactsDesc)], "vvhip_contacts_sample": [vp], "vvhip_contacts_stop": [vp],
+        "vvhip_contacts_info": [vp, P(ContactsLayout)], "vvhip_contacts_read": [vp, vp, C.c_int64, P(ContactsCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
