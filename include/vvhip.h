@@ -1018,6 +1018,119 @@ int vvhip_contacts_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_w
 int vvhip_contacts_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_contacts_info(const vvhip_plan* plan, vvhip_contacts_layout* out);
+/* ---------------------------------------------------------------- velocity and orientation autocorrelations accumulated on the device
+ * The autocorrelation of a per-unit vector a(t).  Of a velocity it is the Green-Kubo route to the self-diffusion coefficient -- the
+ * cross-check of the MSD's slope -- and its cosine transform is the vibrational density of states, which shows where the Drude oscillators
+ * sit relative to the thermostat's frequencies; velocity Verlet has the synchronous on-step velocities it wants.  Of a body-fixed unit vector
+ * u it is C1(t) = <u(0).u(t)> and C2(t) = <P2(u(0).u(t))>, the rotational relaxation times.  Both want a short sampling interval over many
+ * origins: from frames that is 24 - 32 B per particle every few steps and O(samples lags N) work on the host.  After every full step whose
+ * count is a multiple of `interval` -- counted exactly as for the other riders, by the same entry points; a sample "after step k" is
+ * enqueued behind that step's contact sample, last of the riders -- the step entry point enqueues one accumulating kernel
+ * (csrc/vv_dev_acf.inc) and a one-thread kernel that advances the sample ordinal: two launches, no memset, no host work.  Inside a captured
+ * graph both are part of the graph and the steps that take a sample are part of the graph-cache key.  The recorder reads velm (the velocity
+ * modes) or posq and posqCorrection (orientation mode) and writes its own words, nothing else; a plan that never starts one launches what
+ * it launched before and allocates nothing.
+ * Units and their vector.
+ *   VVHIP_ACF_VELOCITY_PARTICLES  every recorded particle is a unit; a = (double) velm.xyz, the bits a float64 velocity frame records at
+ *                        the same step.
+ *   VVHIP_ACF_VELOCITY_MOLECULES  a unit is a molecule of vvhip_system_desc.mol_id, restricted to its particles with mass > 0; a is the
+ *                        velocity of its centre of mass in float64 without contraction:  s = 0; for i in ascending particle index:
+ *                        s = s + m_i * v_i;  a = s / M,  M summed on the host in the same order: the MSD's definition with v for X, and
+ *                        the MSD's rules: the group of a molecule is the group of its massive particles, mixed groups inside one molecule
+ *                        are refused, a molecule with group -1 or without mass is not recorded, a shard that holds some but not all massive
+ *                        particles of a molecule gives VVHIP_ERR_UNSUPPORTED.
+ *   VVHIP_ACF_ORIENTATION  a unit is an ordered pair (head, tail) of particle indices of the System, pairs[2 u], pairs[2 u + 1], with
+ *                        group[u] its group (one byte per PAIR, -1: not recorded).  Head and tail differ and lie in the same molecule.
+ *                        Positions are stored unwrapped and molecules whole, so no minimum image is taken.  d = X_head - X_tail with X as
+ *                        the MSD defines it,  n2 = (d_x d_x + d_y d_y) + d_z d_z,  a = u = d * y  with  y ~ n2^(-1/2)  from ONE sequence of
+ *                        correctly rounded +, -, * and exact scalings by powers of two -- no sqrt, no rsqrt, no division, no fma -- so that
+ *                        device and host give the same bits (csrc/vv_layout.h: acf_inverse_norm; tests/acf_reference.py in NumPy):
+ *                        with ex the exponent of n2 and e = ex - (ex & 1), m = n2 2^-e in [1, 4);  y = 1.2929 - 0.2929 m  where m < 2,
+ *                        else  y = 0.9142 - 0.10355 m;  four times  y = y * (1.5 - (0.5 * m) * (y * y));  then y = y * 2^(-e / 2).
+ *                        | |u|^2 - 1 | <= 2^-49.  On a sharded plan both particles must be in the shard (so for shards on molecule
+ *                        boundaries), else VVHIP_ERR_UNSUPPORTED.
+ * Bad vectors.  In the velocity modes a vector with a component that is NaN or has |a_c| >= limit (nm/ps, rounded up to a power of two; 0
+ * takes the default of 64); in orientation mode one whose n2 is NaN or outside [2^-40, 2^40) nm^2 (limit must be 0 there).  A bad vector is
+ * stored in the ring as NaN; a pair with a bad vector at either end is left out of every word and adds 1 to out_of_range.
+ * Schedule.  Sample ordinal j = 0, 1, ... counts the due steps since the start or the last reset.  Every sample whose ordinal is a multiple
+ * of origin_every (E) is an origin, stored in slot (j / E) mod num_origins of a device ring; num_origins = ceil(num_lags / E) is derived,
+ * at most 1024.  ROW l (0 <= l < num_lags) IS THE LAG OF l * interval STEPS: ROW 0 IS THE ZERO LAG (the MSD's row 0 is one interval).  At
+ * sample j every origin o = k E with  origin_floor <= o <= j  and  j - o < num_lags  contributes to row j - o; the self term o = j comes
+ * from the sample's own vector.  The slot a new origin overwrites held origin j - num_origins E <= j - num_lags, which no row can use.
+ * Past max_samples a sample adds nothing, stores nothing and counts as dropped.
+ * Terms.  p_c = a_c(o) * a_c(j) in float64, c = x, y, z, signed.  The words of a row: the pair count as the integer 1;
+ * llrint(p_x * 2^frac_bits), llrint(p_y * 2^frac_bits), llrint(p_z * 2^frac_bits), round-half-even; in orientation mode a fifth,
+ * llrint(cs * cs * 2^frac_bits) with cs = (p_x + p_y) + p_z, for P2.
+ * Table: int64 table[num_groups][num_lags][row_words], row_words = 4 in the velocity modes, 5 in orientation mode.
+ * frac_bits = min(40, 62 - ceil_log2(U + 1) - ceil_log2(ceil(max_samples / E) + 1) - 2 log2(limit)), log2(limit) = 0 in orientation mode,
+ * so that no word can overflow within max_samples samples; U is the number of units the description records over the WHOLE System: a
+ * sharded plan records the units of its own shard, every shard scales alike, and the shards' tables add as integers to the unsharded
+ * table.  Integer adds commute: the table is the same bits for any grid, block size, unit order or shard split.
+ * What rewrites the inputs outside the steps.  vvhip_set_velocities_to_temperature, with a velocity-mode recorder running, sets origin_floor
+ * to the current sample ordinal (one one-thread kernel in the stream): older origins are dead, the table is kept; an orientation recorder
+ * is left alone.  vvhip_barostat_scale / _restore set NO floor: they leave the velocities alone, and a rigid shift of a molecule keeps its
+ * internal vectors up to rounding.  Scheduled removals of the centre-of-mass motion are part of the dynamics.  vvhip_checkpoint_load is
+ * refused while a recorder runs.  Host uploads into the bound arrays (vvhip_memcpy_h2d into velm or posq, a re-bind to other arrays) are NOT
+ * detected: the next samples correlate against origins of the values that were there before; stop the recorder and start it again.
+ * Recovery.  Neither the table nor the ring is idempotent under the repeat of failed steps -- an origin overwritten inside the failed
+ * window is needed again by the repeat -- so the rider's recovery words are the WHOLE allocation: counts, floor, table and origin ring,
+ * (4 + words) * 8 B + ring_bytes with ring_bytes = num_origins x 3 x stride x 8 B, stride = num_units rounded up to 16.  Nothing caps
+ * it: 1024 origins of 111 000 units are 2.7 GB, which every run call that may recover copies once; vvhip_acf_info on an unbound plan
+ * gives ring_bytes for a description before anything is allocated -- raise origin_every where the ring is too large. */
+#define VVHIP_ACF_VELOCITY_PARTICLES 0
+#define VVHIP_ACF_VELOCITY_MOLECULES 1
+#define VVHIP_ACF_ORIENTATION 2
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096: row l is the lag of l * interval steps */
+    int32_t origin_every;           /* E, 1 .. num_lags: every E-th sample is an origin */
+    int32_t mode;                   /* VVHIP_ACF_VELOCITY_PARTICLES, VVHIP_ACF_VELOCITY_MOLECULES, VVHIP_ACF_ORIENTATION */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t num_pairs;              /* orientation mode: the pairs given, >= 0; else 0 */
+    const signed char* group;       /* velocity modes: [num_atoms] the group of every particle of the System; orientation mode: [num_pairs]
+                                       the group of every pair; -1: not recorded; NULL: everything in group 0 */
+    const int32_t* pairs;           /* orientation mode: [num_pairs][2] head, tail as particle indices of the System; else NULL */
+    int64_t max_samples;            /* >= 1 */
+    double limit;                   /* velocity modes: nm/ps, a component at or beyond it is bad; rounded up to a power of two; 0: 64.
+                                       Orientation mode: 0 */
+} vvhip_acf_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset (at most max_samples): the next sample's ordinal */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added or stored for them */
+    int64_t out_of_range;           /* unit-pairs left out of every word */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+} vvhip_acf_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, mode, num_groups;
+    int32_t num_units;              /* units this plan records (those of its shard) */
+    int32_t num_origins;            /* ceil(num_lags / origin_every) */
+    int32_t frac_bits, row_words;   /* value = word * 2^-frac_bits (pairs: the word itself); 4, or 5 in orientation mode */
+    int64_t max_samples;
+    int64_t words;                  /* num_groups * num_lags * row_words */
+    int64_t ring_bytes;             /* num_origins * 3 * stride * 8 */
+    int64_t start_step;             /* the plan's step count at vvhip_acf_start */
+    double limit;                   /* as applied (orientation mode: 1) */
+} vvhip_acf_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, an unknown mode, num_groups outside 1 ..
+ * 16, max_samples < 1, a limit that is negative or not finite, or not 0 in orientation mode; in orientation mode num_pairs < 0 or pairs
+ * NULL with num_pairs > 0, in the velocity modes pairs or num_pairs given; a group entry outside -1 .. num_groups - 1 (VVHIP_ERR_INVALID
+ * naming the argument); in molecule mode a molecule whose massive particles lie in different groups, in orientation mode a pair with an
+ * index outside the System, with head = tail or with head and tail in different molecules (VVHIP_ERR_INVALID naming it); frac_bits below
+ * 8; num_origins above 1024 (VVHIP_ERR_INVALID); a shard that cuts a molecule (molecule mode) or a recorded pair (orientation mode)
+ * (VVHIP_ERR_UNSUPPORTED); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the
+ * byte count).  A description that passes the checks in front of "an unbound plan" is kept even where the start is then refused (active =
+ * 0): vvhip_acf_info answers for it, for sizing. */
+int vvhip_acf_start(vvhip_plan* plan, const vvhip_acf_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the ordinal at 0 with no
+ * live origin: the step schedule continues without gap or repeat. */
+int vvhip_acf_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_acf_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and ring are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_acf_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_acf_info(const vvhip_plan* plan, vvhip_acf_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the

@@ -523,4 +523,30 @@ struct ContactsArgs {
     int32_t first_row[CONTACTS_MAX_CLASSES], first_col[CONTACTS_MAX_CLASSES];  // where the class's groups start in the site list
 };
 
+// Autocorrelation sample (vv_dev_acf.inc, include/vvhip.h: vvhip_acf_* states the units and their vector, the schedule and the terms).  The
+// sample ordinal and the origin floor are read from the device-side words, so a replayed graph (same arguments every time) finds the
+// origins where the last sample left them and stops adding at max_samples.  One allocation: head, table, ring.
+enum { ACF_SAMPLES = 0, ACF_DROPPED = 1, ACF_OUT_OF_RANGE = 2, ACF_FLOOR = 3, ACF_HEAD = 4 };      // the words in front of the table
+enum { ACF_VELOCITY_PARTICLES = 0, ACF_VELOCITY_MOLECULES = 1, ACF_ORIENTATION = 2 };               // = VVHIP_ACF_*
+constexpr int ACF_MAX_SLOTS_IN_FLIGHT = 8;
+struct AcfArgs {
+    const void* velm;               // mixed4 [shard particles] (the velocity modes)
+    const void* posq;               // real4 [shard particles] (orientation mode)
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // particles: [n] shard-relative index of unit u, null: unit u is particle u.  Molecules: the member
+                                    // lists.  Orientation: [2 n] head and tail of unit u at 2 u, 2 u + 1
+    const int32_t* first;           // molecules: [n + 1] unit u's members are index[first[u]] .. index[first[u + 1] - 1], ascending
+    const double* weight;           // molecules: the mass of every member, beside index
+    const double* total;            // molecules: [n] M, the members' masses summed in their order
+    const unsigned char* group;     // [n] group of unit u (GROUPED kernels only)
+    long long* words;               // [ACF_HEAD + table_words]: samples, dropped, out_of_range, origin floor, then table[group][lag][row_words]
+    double* ring;                   // [num_origins][3][stride] the origins' vectors, behind the table in the same allocation
+    int64_t max_samples;
+    int32_t n, stride;              // recorded units; n rounded up to 16
+    int32_t num_lags, origin_every;
+    int32_t num_origins, table_words;      // ceil(num_lags / origin_every); num_groups * num_lags * row_words
+    int32_t wave_reduce, slots_in_flight;  // 1: a wave whose lanes share a group adds its sums once; ring loads issued together, 1 .. ACF_MAX_SLOTS_IN_FLIGHT
+    double scale, limit;            // 2^frac_bits; the velocity modes: |component| at or beyond it is bad
+};
+
 }  // namespace vv

@@ -24,3 +24,4 @@
 #include "vv_dev_current.inc"
 #include "vv_dev_modes.inc"
 #include "vv_dev_contacts.inc"
+#include "vv_dev_acf.inc"

@@ -589,6 +589,35 @@ hipError_t launch_contacts(int precision, const ContactsArgs& a, int grid_cap, h
     hipLaunchKernelGGL(vv_kernel_contacts_advance, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
+template <int MODE, bool GROUPED>
+static auto pick_acf(int precision, bool lds) {
+    return lds ? VV_PICK(precision, vv_kernel_acf, MODE, GROUPED, true) : VV_PICK(precision, vv_kernel_acf, MODE, GROUPED, false);
+}
+template <int MODE>
+static auto pick_acf(int precision, bool grouped, bool lds) { return grouped ? pick_acf<MODE, true>(precision, lds) : pick_acf<MODE, false>(precision, lds); }
+hipError_t launch_acf(int precision, const AcfArgs& a, int mode, int block_threads, int grid_cap, hipStream_t s) {
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    // what the kernel relies on: the ring's columns hold the units, the slots in flight fit its registers, the mode has its tables
+    if (a.n < 0 || a.stride < a.n || a.num_origins < 1 || a.slots_in_flight < 1 || a.slots_in_flight > ACF_MAX_SLOTS_IN_FLIGHT) return hipErrorInvalidValue;
+    if (mode != ACF_VELOCITY_PARTICLES && mode != ACF_VELOCITY_MOLECULES && mode != ACF_ORIENTATION) return hipErrorInvalidValue;
+    if (a.n > 0 && (mode == ACF_VELOCITY_MOLECULES ? !(a.first && a.weight && a.total && a.index) : mode == ACF_ORIENTATION && !a.index)) return hipErrorInvalidValue;
+    const dim3 g((unsigned) std::max(1, std::min((a.n + block_threads - 1) / block_threads, std::max(1, grid_cap))));
+    const size_t table_bytes = (size_t) a.table_words * sizeof(long long);
+    const bool lds = table_bytes <= PROFILE_LDS_BYTES;
+    const bool grouped = a.group != nullptr;
+    const auto k = mode == ACF_VELOCITY_MOLECULES ? pick_acf<ACF_VELOCITY_MOLECULES>(precision, grouped, lds)
+                   : mode == ACF_ORIENTATION      ? pick_acf<ACF_ORIENTATION>(precision, grouped, lds)
+                                                  : pick_acf<ACF_VELOCITY_PARTICLES>(precision, grouped, lds);
+    hipLaunchKernelGGL(k, g, dim3((unsigned) block_threads), lds ? (unsigned) table_bytes : 0u, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_acf_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_acf_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_acf_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

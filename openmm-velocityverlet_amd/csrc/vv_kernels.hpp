@@ -105,5 +105,11 @@ hipError_t launch_modes_floor(long long* words, hipStream_t s);
 // (work item, slot of the ring); then the one-wave kernel that writes the slot's ordinal and counts the sample.  a.mol selects the mask
 // kernel that clears pairs of one molecule, a.cont the correlate kernel that keeps the surviving contacts.
 hipError_t launch_contacts(int precision, const ContactsArgs& a, int grid_cap, hipStream_t s);
+// One autocorrelation sample (vv_dev_acf.inc): the accumulating kernel over a.n units in blocks of block_threads (64 .. 512, a multiple of
+// 64), at most grid_cap of them, then the one-thread kernel that advances the sample ordinal.  mode (ACF_*) and a.group select the kernel;
+// a table of at most PROFILE_LDS_BYTES is accumulated per block in LDS.
+hipError_t launch_acf(int precision, const AcfArgs& a, int mode, int block_threads, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as AcfArgs::words.
+hipError_t launch_acf_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

@@ -126,6 +126,29 @@ VV_HOST_DEVICE inline void phasor_turns(unsigned int phi, double& c, double& s) 
     if (q >= 2) s = -s;
 }
 
+// ---- y ~ n2^(-1/2) for the orientation autocorrelation's unit vectors (include/vvhip.h: vvhip_acf_* states it; vv_dev_acf.inc)
+// One sequence of correctly rounded +, -, * and exact scalings by powers of two: no sqrt, no rsqrt, no division, no fma, so the device,
+// the host and NumPy (tests/acf_reference.py) give the same bits; the host build is held to that by a digest
+// (tests/cpp/acf_unit_check.cpp).  n2 is normal and positive (the caller has refused what lies outside [2^-40, 2^40)).  With e the
+// exponent of n2 made even (e = exponent - (exponent & 1)), m = n2 2^-e lies in [1, 4) and is formed by rewriting the exponent field;
+// the seed is the chord of m^(-1/2) over [1, 2) or over [2, 4) (at most 4.6 % high), four Newton steps y = y (1.5 - (0.5 m) (y y))
+// square that error down to the rounding of the last step, and the result is y 2^(-e/2), exact.  With u = d y, | |u|^2 - 1 | stays
+// below 7.1e-16 < 2^-50 over 2e5 random vectors of 2^-19 .. 2^19 nm; the recorder's condition is 2^-49 (tests/test_acf.py).
+VV_HOST_DEVICE inline double acf_inverse_norm(double n2) {
+    const unsigned long long bits = __builtin_bit_cast(unsigned long long, n2);
+    const long long e = (long long) ((bits >> 52) & 0x7FFull) - 1023;
+    const long long odd = e & 1;
+    const double m = __builtin_bit_cast(double, (bits & 0x000FFFFFFFFFFFFFull) | ((unsigned long long) (1023 + odd) << 52));
+    const long long h = (e - odd) / 2;                                     // (e - odd is even: exact for either sign)
+    double y = m < 2.0 ? 1.2929 - 0.2929 * m : 0.9142 - 0.10355 * m;
+    const double hm = 0.5 * m;
+    y = y * (1.5 - hm * (y * y));
+    y = y * (1.5 - hm * (y * y));
+    y = y * (1.5 - hm * (y * y));
+    y = y * (1.5 - hm * (y * y));
+    return y * __builtin_bit_cast(double, (unsigned long long) (1023 - h) << 52);
+}
+
 // ---- contact matrices (include/vvhip.h: vvhip_contacts_* states the sites, the classes, the contact and the table; vv_dev_contacts.inc)
 // One matrix holds every class's bits, word-major: class c starts at class_offset[c] and its word (jw, i) -- the columns 64 jw .. 64 jw + 63
 // of row i -- is at class_offset[c] + jw * rows_padded[c] + i.  rows_padded = N_a rounded up to 64 (the mask kernel stores 64 rows at a time;

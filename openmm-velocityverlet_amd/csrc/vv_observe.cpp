@@ -1,7 +1,7 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, density modes, contact lifetimes, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The six accumulating recorders
+// correlations, density modes, contact lifetimes, autocorrelations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The seven accumulating recorders
 // share one life cycle (recorder_*).
 #include "vv_plan.hpp"
 
@@ -83,7 +83,7 @@ static int profile_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_profile(p->hp.precision, a, std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
-// The threads per block of an MSD or current sample's accumulating kernel (`pinned` != 0: a test hook's): 512 where they still make 128
+// The threads per block of an MSD, current or autocorrelation sample's accumulating kernel (`pinned` != 0: a test hook's): 512 where they still make 128
 // blocks, else the largest of 256, 128, 64 that does (64 at the least): few units in few blocks leave their gathers to a handful of CUs
 // (TUNING_LOG.md)
 static int block_threads_for(int pinned, int n) {
@@ -236,6 +236,32 @@ static int contacts_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_contacts(p->hp.precision, a, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ autocorrelations (vvhip_acf_*)
+// One sample behind the step just enqueued (or captured), and behind its contact sample: the accumulating kernel and the one-thread kernel
+// that advances the ordinal.  Two launches, no memset and no host synchronisation.
+static int acf_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Acf& A = p->acf;
+    const vvhip_acf_layout& L = A.lay;
+    vv::AcfArgs a{};
+    a.velm = p->buf.velm; a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    const bool molecules = L.mode == VVHIP_ACF_VELOCITY_MOLECULES;
+    a.index = A.index.empty() ? nullptr : A.dev.index.get();
+    a.first = molecules ? A.dev.first.get() : nullptr; a.weight = molecules ? A.dev.weight.get() : nullptr; a.total = molecules ? A.dev.total.get() : nullptr;
+    a.group = A.grouped ? A.dev.group.get() : nullptr;
+    a.words = A.d_words.get(); a.ring = (double*) (A.d_words.get() + A.table_offset() + L.words);
+    a.max_samples = L.max_samples;
+    a.n = L.num_units; a.stride = A.stride(); a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
+    a.table_words = (int32_t) L.words; a.wave_reduce = p->acf_wave_reduce; a.slots_in_flight = p->acf_slots_in_flight;
+    a.scale = std::ldexp(1.0, L.frac_bits); a.limit = L.limit;
+    HIP_TRY(p, vv::launch_acf(p->hp.precision, a, L.mode, block_threads_for(p->acf_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    return VVHIP_OK;
+}
+// vvhip_set_velocities_to_temperature rewrote the velocities outside the steps: a velocity-mode recorder's origins so far are dead
+int acf_velocities_rewritten(vvhip_plan* p) {
+    if (!p->acf.on || p->acf.lay.mode == VVHIP_ACF_ORIENTATION) return VVHIP_OK;
+    HIP_TRY(p, vv::launch_acf_floor(p->acf.d_words.get(), p->stream));
+    return VVHIP_OK;
+}
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
 static bool cmm_sharded(const vvhip_plan* p) { return p->hp.shard_begin != 0 || p->hp.shard_end != p->hp.num_atoms; }
 static const char kCmmSharded[] = "centre-of-mass motion: a sharded plan holds a part of the momentum only (summing over the ranks is not implemented)";
@@ -280,7 +306,8 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   5 RDF sample        behind the MSD sample; all of d_words, counts and table (its gather scratch is rewritten by every sample)
 //   6 current sample    behind the RDF sample; all of d_words: head, sums, table, the ring of origins and the slots' words
 //   7 density-mode sample   behind the current sample; all of d_words likewise (its turns are scratch, rewritten by every sample)
-//   8 contact sample    last; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
+//   8 contact sample    behind the density-mode sample; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
+//   9 autocorrelation sample   last; all of d_words, the ring of origins included, as for the MSD
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -288,7 +315,8 @@ Riders riders(vvhip_plan* p) {
              {p->cmm.on, p->cmm.when, true, p->cmm.d_rec.get(), sizeof(vv::CmmDevRecord), [](vvhip_plan* q) { return cmm_enqueue(q, 0); }},
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
-             recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue)}};
+             recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue),
+             recorder_rider(p->acf, acf_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -310,7 +338,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the six accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the seven accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -512,6 +540,7 @@ int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, doubl
         TRY(run_a(p, cons_a(p), 0));
         r.constrained = 1;
     }
+    TRY(acf_velocities_rewritten(p));
     if (remove_cm) {      // (either way the call's one synchronisation)
         TRY(cmm_one_off(p, r.v_removed));
         r.cm_removed = 1;
@@ -1231,5 +1260,124 @@ int vvhip_contacts_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_word
 }
 int vvhip_contacts_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::contacts, "contacts"); }
 int vvhip_contacts_info(const vvhip_plan* p, vvhip_contacts_layout* out) { return recorder_info(p, &vvhip_plan::contacts, out); }
+
+int vvhip_acf_start(vvhip_plan* p, const vvhip_acf_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "acf: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "acf: interval must be >= 1 step");
+    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "acf: num_lags must be in [1, 4096]");
+    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "acf: origin_every must be in [1, num_lags]");
+    if (d->mode != VVHIP_ACF_VELOCITY_PARTICLES && d->mode != VVHIP_ACF_VELOCITY_MOLECULES && d->mode != VVHIP_ACF_ORIENTATION)
+        return fail(p, VVHIP_ERR_INVALID, "acf: mode must be VVHIP_ACF_VELOCITY_PARTICLES, VVHIP_ACF_VELOCITY_MOLECULES or VVHIP_ACF_ORIENTATION");
+    if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "acf: num_groups must be in [1, 16]");
+    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "acf: max_samples must be >= 1");
+    if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "acf: limit must be finite and >= 0 (0: the default of 64 nm/ps)");
+    const bool orientation = d->mode == VVHIP_ACF_ORIENTATION, molecules = d->mode == VVHIP_ACF_VELOCITY_MOLECULES;
+    if (orientation && d->limit != 0) return fail(p, VVHIP_ERR_INVALID, "acf: limit must be 0 in orientation mode (a unit vector has no range to choose)");
+    if (orientation && (d->num_pairs < 0 || (d->num_pairs > 0 && !d->pairs))) return fail(p, VVHIP_ERR_INVALID, "acf: orientation mode needs pairs[2 * num_pairs] and num_pairs >= 0");
+    if (!orientation && (d->pairs || d->num_pairs != 0)) return fail(p, VVHIP_ERR_INVALID, "acf: pairs and num_pairs belong to orientation mode only");
+    const vv::HostPlan& hp = p->hp;
+    if (!orientation) TRY(check_groups(p, "acf", d->group, d->num_groups));
+    for (int32_t u = 0; orientation && d->group && u < d->num_pairs; u++)
+        if (d->group[u] < -1 || d->group[u] >= d->num_groups)
+            return fail(p, VVHIP_ERR_INVALID, "acf: group[" + std::to_string(u) + "] = " + std::to_string((int) d->group[u]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    // ---- the units this plan records, the layout and the fixed point, host only
+    vvhip_plan::Acf N;
+    vvhip_acf_layout& L = N.lay;
+    N.grouped = d->group != nullptr;
+    auto group_of = [&](int32_t i) { return d->group ? (int) d->group[i] : 0; };      // (of a particle, or of a pair)
+    auto in_shard = [&](int32_t i) { return i >= hp.shard_begin && i < hp.shard_end; };
+    struct Unit { int group; int32_t id; };      // id: the particle, the molecule, or the pair
+    std::vector<Unit> units;                      // of this plan
+    long long described = 0;                      // U: the units the DESCRIPTION records, of the whole System
+    std::vector<std::vector<int32_t>> members;    // molecules: per molecule id its massive particles, ascending
+    bool cut = false;
+    if (orientation) {
+        for (int32_t u = 0; u < d->num_pairs; u++) {
+            const int32_t h = d->pairs[2 * u], t = d->pairs[2 * u + 1];
+            const std::string name = "acf: pair " + std::to_string(u) + " (head " + std::to_string(h) + ", tail " + std::to_string(t) + ")";
+            if (h < 0 || h >= hp.num_atoms || t < 0 || t >= hp.num_atoms) return fail(p, VVHIP_ERR_INVALID, name + " names a particle outside the System's " + std::to_string(hp.num_atoms));
+            if (h == t) return fail(p, VVHIP_ERR_INVALID, name + " has head = tail: no direction");
+            if (hp.mol_id[(size_t) h] != hp.mol_id[(size_t) t])
+                return fail(p, VVHIP_ERR_INVALID, name + " joins molecules " + std::to_string(hp.mol_id[(size_t) h]) + " and " + std::to_string(hp.mol_id[(size_t) t]) + ": no minimum image is taken, head and tail must lie in one molecule");
+            if (group_of(u) < 0) continue;
+            described++;
+            const int here = in_shard(h) + in_shard(t);
+            cut = cut || here == 1;
+            if (here == 2) units.push_back({group_of(u), u});
+        }
+    } else if (!molecules) {
+        for (int32_t i = 0; i < hp.num_atoms; i++) {
+            if (group_of(i) < 0) continue;
+            described++;
+            if (in_shard(i)) units.push_back({group_of(i), i});
+        }
+    } else {
+        int32_t nmol = 0;
+        for (int32_t i = 0; i < hp.num_atoms; i++) nmol = std::max(nmol, hp.mol_id[(size_t) i] + 1);
+        members.resize((size_t) nmol);
+        for (int32_t i = 0; i < hp.num_atoms; i++)
+            if (hp.masses[(size_t) i] > 0) members[(size_t) hp.mol_id[(size_t) i]].push_back(i);
+        for (int32_t m = 0; m < nmol; m++) {
+            const std::vector<int32_t>& mem = members[(size_t) m];
+            if (mem.empty()) continue;
+            int here = 0;
+            for (int32_t i : mem) {
+                here += in_shard(i);
+                if (group_of(i) != group_of(mem[0]))
+                    return fail(p, VVHIP_ERR_INVALID, "acf: molecule " + std::to_string(m) + " has massive particles in different groups (particle " + std::to_string(mem[0]) + ": " +
+                                                      std::to_string(group_of(mem[0])) + ", particle " + std::to_string(i) + ": " + std::to_string(group_of(i)) + ")");
+            }
+            cut = cut || (here != 0 && here != (int) mem.size());
+            if (group_of(mem[0]) < 0) continue;
+            described++;
+            if (here == (int) mem.size()) units.push_back({group_of(mem[0]), m});
+        }
+    }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.mode = d->mode; L.num_groups = d->num_groups;
+    L.max_samples = d->max_samples;
+    L.num_units = (int32_t) units.size();
+    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.row_words = orientation ? 5 : 4;
+    L.words = (int64_t) L.num_groups * L.num_lags * L.row_words;
+    L.limit = orientation ? 1.0 : d->limit > 0 ? pow2_at_least(d->limit) : 64.0;
+    L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
+    const long long max_origins = samples_plus(L.max_samples, L.origin_every - 1) / L.origin_every;
+    L.frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(L.limit));
+    if (L.frac_bits < 8)
+        return fail(p, VVHIP_ERR_INVALID, "acf: the sums would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
+                                          std::to_string((long long) L.max_samples) + ", origin_every = " + std::to_string(L.origin_every) + " and limit " + std::to_string(L.limit) +
+                                          ": lower max_samples or the limit");
+    if (L.num_origins > 1024)
+        return fail(p, VVHIP_ERR_INVALID, "acf: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
+    if (molecules && cut)
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "acf: the particle shard cuts a molecule: its centre-of-mass velocity needs particles of another shard");
+    if (orientation && cut)
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "acf: the particle shard cuts a recorded pair: its vector needs a particle of another shard (shard on molecule boundaries)");
+    for (const Unit& u : units) {
+        if (N.grouped) N.group.push_back((unsigned char) u.group);
+        if (orientation) { N.index.push_back(d->pairs[2 * u.id] - hp.shard_begin); N.index.push_back(d->pairs[2 * u.id + 1] - hp.shard_begin); continue; }
+        if (!molecules) { N.index.push_back(u.id - hp.shard_begin); continue; }
+        N.first.push_back((int32_t) N.index.size());
+        double M = 0;
+        for (int32_t i : members[(size_t) u.id]) {
+            N.index.push_back(i - hp.shard_begin); N.weight.push_back(hp.masses[(size_t) i]);
+            M = M + hp.masses[(size_t) i];
+        }
+        N.total.push_back(M);
+    }
+    if (molecules) N.first.push_back((int32_t) N.index.size());
+    if (!molecules && !orientation && !N.grouped && L.num_units == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
+    return recorder_install(p, &vvhip_plan::acf, "acf", N, d->interval);
+}
+int vvhip_acf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_acf_counts* out, int32_t reset) {
+    long long head[vv::ACF_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::acf, "acf", words_out, capacity_words, head));
+    if (out) *out = {head[vv::ACF_SAMPLES], head[vv::ACF_DROPPED], head[vv::ACF_OUT_OF_RANGE], head[vv::ACF_FLOOR]};
+    return reset ? recorder_reset(p, p->acf) : VVHIP_OK;
+}
+int vvhip_acf_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::acf, "acf"); }
+int vvhip_acf_info(const vvhip_plan* p, vvhip_acf_layout* out) { return recorder_info(p, &vvhip_plan::acf, out); }
 
 }  // extern "C"

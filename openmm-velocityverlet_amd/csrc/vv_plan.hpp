@@ -8,9 +8,9 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the nine scheduled riders in ride order (riders) --
-//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact sample, with their
-//                    late words: the rings' cursors, the removals' record, the six recorders' d_words; the recorders' one life cycle
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the ten scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact / autocorrelation sample, with their
+//                    late words: the rings' cursors, the removals' record, the seven recorders' d_words; the recorders' one life cycle
 //                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -80,11 +80,12 @@ inline unsigned long long* rv_words(unsigned long long* rv, int parity) { return
 inline unsigned int* rv_late_row(unsigned long long* rv, int parity) { return (unsigned int*) (rv + kRvLateWord) + vv::ACC_SLOTS * parity; }
 inline unsigned long long* rv_dead_tail(unsigned long long* rv) { return rv + kRvDeadWord; }
 constexpr int kGuardByte = 0xA5;    // fills the guard item behind a ring's last item (Ring)
+static_assert(vv::ACF_VELOCITY_PARTICLES == VVHIP_ACF_VELOCITY_PARTICLES && vv::ACF_VELOCITY_MOLECULES == VVHIP_ACF_VELOCITY_MOLECULES && vv::ACF_ORIENTATION == VVHIP_ACF_ORIENTATION, "vv_args.hpp states the ABI's three modes");
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 // The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
 //   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
-//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample (3 .. 8: all of d_words)
-constexpr int kRiders = 9;
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample   9 autocorrelation sample (3 .. 9: all of d_words)
+constexpr int kRiders = 10;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -163,6 +164,9 @@ struct vvhip_plan {
     int contacts_rows_per_tile = 128;   // rows a block of a contact sample's mask kernel stages in LDS: a multiple of 64 up to 1024 (test hook "contacts_rows_per_tile", read at the start; same bits; TUNING_LOG.md)
     int contacts_words_per_item = 4;    // column words per work item of that kernel, one per wave and trip: 1 .. 64 (test hook "contacts_words_per_item", read at the start; same bits)
     int contacts_skip_zero = 1;         // the correlate kernel loads neither the sample's nor the surviving words behind a zero origin word (test hook "contacts_skip_zero"; same bits)
+    int acf_block_threads = 0;          // threads per block of an autocorrelation sample's accumulating kernel, 0: by the number of units (acf_enqueue; test hook "acf_block_threads")
+    int acf_wave_reduce = 1;            // an autocorrelation sample's waves whose units share a group add their sums once (test hook "acf_wave_reduce": 0 = every lane adds; same bits)
+    int acf_slots_in_flight = 4;        // ring slots whose loads that kernel issues before it uses the first, 1 .. 8 (test hook "acf_slots_in_flight"; same bits; TUNING_LOG.md)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
@@ -181,8 +185,8 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // all nine riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode and contact sample.  A
-        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the four recorders' d_words
+        // all ten riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode, contact and autocorrelation sample.  A
+        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the seven recorders' d_words
         long long step_count = 0;
     } cur;
     bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
@@ -354,7 +358,7 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // What the six accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // What the seven accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
     // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
     // `on`: the recorder runs and the device buffers exist.  Each recorder adds
     //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
@@ -566,6 +570,34 @@ struct vvhip_plan {
             return e == hipSuccess ? empty_slots(s) : e;
         }
     } contacts;
+    // Autocorrelations of a per-unit vector (vvhip_acf_*; vv_dev_acf.inc), scheduled by cur.step_count: the MSD recorder's sibling.  The
+    // unit tables are built when the recorder starts: units ordered by group, then by particle / molecule / pair index
+    struct Acf : Recorder {
+        bool grouped = false;
+        vvhip_acf_layout lay{};
+        std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending; orientation: head, tail per unit
+        std::vector<int32_t> first;               // molecules: [num_units + 1] offsets into index / weight
+        std::vector<double> weight, total;        // molecules: the members' masses; [num_units] their sums M in the members' order
+        std::vector<unsigned char> group;         // [num_units] (grouped)
+        struct Dev { vv::DevBuf<int32_t> index, first; vv::DevBuf<double> weight, total; vv::DevBuf<unsigned char> group; } dev;
+        static constexpr int kHead = vv::ACF_HEAD;          // d_words: [kHead + lay.words] counts, floor and table, then the ring of origins
+        size_t table_offset() const { return kHead; }
+        int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
+        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess && !index.empty()) e = put(dev.index, index, asked);
+            if (lay.mode == VVHIP_ACF_VELOCITY_MOLECULES) {
+                if (e == hipSuccess) e = put(dev.first, first, asked);
+                if (e == hipSuccess) e = put(dev.weight, weight, asked);
+                if (e == hipSuccess) e = put(dev.total, total, asked);
+            }
+            if (e == hipSuccess && grouped) e = put(dev.group, group, asked);
+            return e;
+        }
+        // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
+        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, (size_t) (kHead + lay.words) * sizeof(long long), s); }
+    } acf;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -696,6 +728,7 @@ int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_ind
 int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
+int acf_velocities_rewritten(vvhip_plan* p);      // vvhip_set_velocities_to_temperature: a velocity autocorrelation recorder's origins so far are dead
 int msd_positions_rewritten(vvhip_plan* p);      // vvhip_barostat_scale / _restore: an MSD recorder's origins so far are dead
 int modes_positions_rewritten(vvhip_plan* p);    // ... and a density-mode recorder's
 int current_positions_rewritten(vvhip_plan* p);  // ... and a current recorder's
@@ -721,7 +754,8 @@ Riders riders(vvhip_plan* p);
 // For an MSD recorder likewise, the ring of origins included: the repeat needs the origins that the failed window overwrote.  For an RDF
 // recorder counts and table; its gather scratch is rewritten by every sample and is not saved.  For a current recorder the whole
 // allocation again: head, sums, table and the ring of origins.  For a density-mode recorder likewise.  For a contact recorder head, table,
-// the slots' ordinals and both rings of bit matrices: the surviving contacts are not idempotent under the repeat either.
+// the slots' ordinals and both rings of bit matrices: the surviving contacts are not idempotent under the repeat either.  For an
+// autocorrelation recorder the whole allocation as for the MSD: head, table and the ring of origins.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

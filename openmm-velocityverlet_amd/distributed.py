@@ -186,6 +186,19 @@ def msd_sum(msds):
     return dataclasses.replace(first, words=np.sum([m.words for m in msds], axis=0, dtype=np.int64), out_of_range=sum(m.out_of_range for m in msds))
 
 
+def acf_sum(acfs):
+    """The autocorrelation table of a sharded run from its shards' tables (Context.acf_read of every shard, the same description and the
+    same steps behind each): the words added as int64 -- the result is the unsharded table bit for bit -- and out_of_range added; samples,
+    dropped and the origin floor are the same on every shard."""
+    import dataclasses
+    first = acfs[0]
+    key = lambda m: (m.words.shape, m.frac_bits, m.interval, m.origin_every, m.mode, m.samples, m.dropped, m.origin_floor)
+    for m in acfs[1:]:
+        if key(m) != key(first):
+            raise ValueError("the autocorrelation tables differ in layout, fixed point, schedule or number of samples: not shards of one run")
+    return dataclasses.replace(first, words=np.sum([m.words for m in acfs], axis=0, dtype=np.int64), out_of_range=sum(m.out_of_range for m in acfs))
+
+
 def drude_temperature_series(ctx, group=None, reset=False):
     """A sharded run's series (Context.series_read): every rank's raw rows -- six fixed-point sums and the overflow flag per row, of its
     own particles -- summed over the process group in one all-reduce, then turned into KE / T with the whole system's DOFs.  Every rank

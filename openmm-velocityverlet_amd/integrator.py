@@ -405,6 +405,128 @@ def msd_from_words(words, layout, counts) -> Msd:
                frac_bits=int(layout.frac_bits), molecules=layout.mode == H.MSD_MOLECULES, words=words)
 
 
+ACF_MODES = ("velocity", "molecules", "orientation")      # = H.ACF_VELOCITY_PARTICLES, H.ACF_VELOCITY_MOLECULES, H.ACF_ORIENTATION
+
+
+@dataclasses.dataclass
+class Autocorrelations:
+    """Autocorrelations of a per-unit vector per group and lag (Context.acf_read; include/vvhip.h: vvhip_acf_* states the units and their
+    vector, the schedule and the terms).  `words` is the device's table as it stands, int64 [groups, lags, 4 or 5]: pairs, then the sums of
+    a_x(0) a_x(t), a_y(0) a_y(t), a_z(0) a_z(t) and, in orientation mode, of (u(0).u(t))^2, scaled by 2^frac_bits.  Row 0 is the zero lag."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples: nothing was added or stored for them
+    out_of_range: int                      # unit-pairs left out (a bad vector at either end)
+    origin_floor: int                      # origins with an ordinal below it are dead (the velocities were drawn anew)
+    interval: int
+    origin_every: int
+    frac_bits: int
+    mode: str                              # "velocity", "molecules" or "orientation"
+    words: np.ndarray                      # int64 [groups, lags, 4 | 5]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [lags]: row l is the lag of l * interval steps."""
+        return np.arange(self.words.shape[1], dtype=np.int64) * self.interval
+
+    @property
+    def pairs(self) -> np.ndarray:
+        """int64 [groups, lags]: unit-pairs behind every row."""
+        return self.words[:, :, 0]
+
+    @property
+    def sums(self) -> np.ndarray:
+        """float64 [groups, lags, 3]: the sums of a_x(0) a_x(t), a_y(0) a_y(t), a_z(0) a_z(t) = word * 2^-frac_bits."""
+        return self.words[:, :, 1:4].astype(np.float64) * 2.0 ** -self.frac_bits
+
+    @property
+    def squares(self) -> np.ndarray:
+        """float64 [groups, lags]: the sums of (u(0).u(t))^2 (orientation mode)."""
+        if self.mode != "orientation":
+            raise ValueError("squares are recorded in orientation mode only")
+        return self.words[:, :, 4].astype(np.float64) * 2.0 ** -self.frac_bits
+
+    def _per_pair(self, g: int, values: np.ndarray) -> np.ndarray:
+        n = self.pairs[int(g)].reshape((-1,) + (1,) * (values.ndim - 1))
+        return np.where(n > 0, values / np.where(n > 0, n, 1), np.nan)
+
+    def components(self, g: int) -> np.ndarray:
+        """float64 [lags, 3]: <a_x(0) a_x(t)>, <a_y(0) a_y(t)>, <a_z(0) a_z(t)> of group g, NaN where a row has no pairs."""
+        return self._per_pair(g, self.sums[int(g)])
+
+    def C(self, g: int) -> np.ndarray:
+        """float64 [lags]: <a(0).a(t)> of group g = sum over the components of sums / pairs (velocity modes: nm^2/ps^2)."""
+        return self.components(g).sum(axis=1)
+
+    def normalized(self, g: int) -> np.ndarray:
+        """float64 [lags]: C(t) / C(0) of group g."""
+        c = self.C(g)
+        return c / c[0]
+
+    def _velocity_only(self, what):
+        if self.mode == "orientation":
+            raise ValueError(what + " belongs to the velocity modes")
+
+    def diffusion_green_kubo(self, g: int, dt_ps: float, upto=None) -> float:
+        """The Green-Kubo self-diffusion coefficient of group g in nm^2/ps, the unit Msd.diffusion returns: the trapezoid integral of
+        C(t) / 3 over the lags 0 .. `upto` (inclusive; None: the whole table), lag time = lag steps x `dt_ps`."""
+        self._velocity_only("diffusion_green_kubo")
+        last = self.words.shape[1] - 1 if upto is None else int(upto)
+        y = self.C(g)[: last + 1] / 3.0
+        t = self.lag_steps[: last + 1].astype(np.float64) * float(dt_ps)
+        return float(np.sum(0.5 * (y[1:] + y[:-1]) * (t[1:] - t[:-1])))
+
+    def spectrum(self, g: int, dt_ps: float, window: str = "hann"):
+        """(frequencies in THz, the cosine transform of C(t) of group g): I(f_m) = 2 h sum'_l w_l C(l h) cos(2 pi f_m l h), h = interval x
+        `dt_ps`, the zero lag taken half (the trapezoid of an even function), f_m = m / (2 L h) for m = 0 .. L - 1 with L lags.  `window`:
+        "hann" (w_l = cos^2(pi l / (2 L)), one-sided) or None / "none".  The vibrational density of states up to a constant."""
+        self._velocity_only("spectrum")
+        if window not in ("hann", "none", None):
+            raise ValueError("window must be 'hann' or 'none'")
+        c = self.C(g)
+        L = c.size
+        h = float(self.interval) * float(dt_ps)
+        l = np.arange(L, dtype=np.float64)
+        w = np.cos(np.pi * l / (2.0 * L)) ** 2 if window == "hann" else np.ones(L)
+        w[0] *= 0.5
+        f = np.arange(L, dtype=np.float64) / (2.0 * L * h)
+        return f, 2.0 * h * (np.cos(2.0 * np.pi * np.outer(f, l * h)) * (w * c)).sum(axis=1)
+
+    def P1(self, g: int) -> np.ndarray:
+        """float64 [lags]: <u(0).u(t)> of group g (orientation mode)."""
+        if self.mode != "orientation":
+            raise ValueError("P1 belongs to orientation mode")
+        return self.C(g)
+
+    def P2(self, g: int) -> np.ndarray:
+        """float64 [lags]: <P2(u(0).u(t))> = (3 squares / pairs - 1) / 2 of group g (orientation mode)."""
+        if self.mode != "orientation":
+            raise ValueError("P2 belongs to orientation mode")
+        return (3.0 * self._per_pair(g, self.squares[int(g)]) - 1.0) / 2.0
+
+    def relaxation_time(self, g: int, l: int, dt: float = 1.0) -> float:
+        """The first lag time at which P_l of group g, divided by its zero-lag value, falls below 1 / e, linearly interpolated between
+        the two rows around it; NaN if it never does within the table (DensityModes.relaxation_time's time).  `dt`: the step in the unit
+        the time is wanted in, as there; the default of 1 gives the time in steps."""
+        if int(l) not in (1, 2):
+            raise ValueError("l must be 1 or 2")
+        y = self.P1(g) if int(l) == 1 else self.P2(g)
+        y = y / y[0]
+        t = self.lag_steps.astype(np.float64) * float(dt)
+        below = np.nonzero(y < np.exp(-1.0))[0]
+        if below.size == 0 or below[0] == 0:
+            return float("nan")
+        i = int(below[0])
+        return float(t[i - 1] + (t[i] - t[i - 1]) * (y[i - 1] - np.exp(-1.0)) / (y[i - 1] - y[i]))
+
+
+def acf_from_words(words, layout, counts) -> Autocorrelations:
+    """An Autocorrelations from a table's int64 words [groups * lags * row_words], its layout (H.AcfLayout) and counts (H.AcfCounts)."""
+    words = np.ascontiguousarray(words, dtype=np.int64).reshape(int(layout.num_groups), int(layout.num_lags), int(layout.row_words))
+    return Autocorrelations(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range),
+                            origin_floor=int(counts.origin_floor), interval=int(layout.interval), origin_every=int(layout.origin_every),
+                            frac_bits=int(layout.frac_bits), mode=ACF_MODES[int(layout.mode)], words=words)
+
+
 def rdf_edges(r_max: float, nbins: int) -> np.ndarray:
     """float64 [nbins + 1]: the SQUARED bin edges e(k) = ((double) k * dr)^2 with dr = r_max / nbins, as include/vvhip.h defines them."""
     t = np.arange(int(nbins) + 1, dtype=np.float64) * (np.float64(r_max) / np.float64(nbins))
@@ -1085,7 +1207,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the six accumulating recorders below share: profile, msd, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the seven accumulating recorders below share: profile, msd, acf, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1165,6 +1287,49 @@ class Context:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
         return self._recorder_read("msd", H.MsdLayout, H.MsdCounts, msd_from_words, reset)
+
+    # ---- velocity and orientation autocorrelations accumulated on the device inside the steps (include/vvhip.h: vvhip_acf_*)
+    def acf_start(self, interval: int, num_lags: int, origin_every: int = 1, mode: str = "velocity", groups=None, pairs=None,
+                  max_samples: int = 1 << 20, limit: float = 0.0):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), correlate every recorded unit's
+        vector -- mode "velocity": a particle's velocity; "molecules": a molecule's centre-of-mass velocity; "orientation": the unit vector
+        from tail to head of every pair of `pairs` ([n, 2] particle indices, head first, both in one molecule) -- with the stored origins
+        and add, per group and lag of 0 .. `num_lags` - 1 samples, the pair count and the three products (in orientation mode also the
+        squared cosine) as fixed-point integers, so that the table is the same bits for any launch shape or shard split.  Every
+        `origin_every`-th sample is an origin.  `groups`: one int per particle of the System -- in orientation mode one per pair -- (-1:
+        not recorded), each group a table of its own; None: everything in group 0.  `limit` (velocity modes; nm/ps, 0: 64): a velocity
+        component at or beyond it makes the vector bad; a pair with a bad vector at either end is left out and counts in out_of_range.  At
+        most `max_samples` samples are taken.  setVelocitiesToTemperature kills the origins stored so far in the velocity modes; host
+        uploads of velocities or positions are not detected.  No host synchronisation until acf_read."""
+        if mode not in ACF_MODES:
+            raise ValueError("mode must be 'velocity', 'molecules' or 'orientation'")
+        pr = None
+        if mode == "orientation":
+            if pairs is None:
+                raise ValueError("orientation mode needs pairs")
+            pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            grp = None if groups is None else np.ascontiguousarray(groups, dtype=np.int8).reshape(-1)
+            if grp is not None and grp.size != pr.shape[0]:
+                raise ValueError("groups must have one entry per pair in orientation mode")
+        else:
+            if pairs is not None:
+                raise ValueError("pairs belong to orientation mode")
+            grp = self._groups(groups)
+        num_groups = 1 if grp is None or grp.size == 0 else max(int(grp.max()) + 1, 1)
+        desc = H.AcfDesc(int(interval), int(num_lags), int(origin_every), ACF_MODES.index(mode), num_groups, 0 if pr is None else int(pr.shape[0]),
+                         None if grp is None else grp.ctypes.data, None if pr is None or pr.size == 0 else pr.ctypes.data, int(max_samples), float(limit))
+        H.check(H.lib.vvhip_acf_start(self.plan, C.byref(desc)), self.plan)
+
+    def acf_stop(self):
+        self._recorder_stop("acf")
+
+    def acf_info(self) -> H.AcfLayout:
+        return self._recorder_info("acf", H.AcfLayout)
+
+    def acf_read(self, reset: bool = False) -> Autocorrelations:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        return self._recorder_read("acf", H.AcfLayout, H.AcfCounts, acf_from_words, reset)
 
     # ---- radial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_rdf_*)
     def rdf_start(self, interval: int, r_max: float, nbins: int, classes, groups=None, exclude_same_molecule: bool = False,
@@ -1378,7 +1543,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode or contact recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode, contact or autocorrelation recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

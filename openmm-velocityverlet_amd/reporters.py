@@ -28,6 +28,8 @@ latest three kept.
 
 ``write_contacts`` writes device-side contact lifetime correlations (``Context.contacts_read``) as text columns, one line per lag.
 
+``write_acf`` writes device-side velocity or orientation autocorrelations (``Context.acf_read``) as text columns, one line per lag.
+
 ``write_cm_motion_record`` appends what the device-side removal of the centre-of-mass motion has done so far (``Context.cm_motion_record``).
 """
 from __future__ import annotations
@@ -361,6 +363,40 @@ def write_contacts(file, con, dt, append=False, header=True):
             print('#"Samples"\t%d\t"Dropped"\t%d\t"Invalid"\t%d' % (con.samples, con.dropped, con.invalid), file=out)
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for l in range(con.words.shape[1]):
+            print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def acf_columns(acf, dt):
+    """[(name, values per lag)] of an autocorrelation table's text file: the lag in ps, then per group the pairs and, in the velocity modes,
+    C = <v(0).v(t)> with its three components, in orientation mode P1 and P2."""
+    cols = [("lag (ps)", acf.lag_steps.astype(np.float64) * float(dt))]
+    for g in range(acf.words.shape[0]):
+        cols.append(("pairs[%d]" % g, acf.pairs[g].astype(np.float64)))
+        if acf.mode == "orientation":
+            cols += [("P1[%d]" % g, acf.P1(g)), ("P2[%d]" % g, acf.P2(g))]
+        else:
+            comp = acf.components(g)
+            cols.append(("C[%d] (nm^2/ps^2)" % g, acf.C(g)))
+            cols += [("C_%s[%d] (nm^2/ps^2)" % ("xyz"[k], g), comp[:, k]) for k in range(3)]
+    return cols
+
+
+def write_acf(file, acf, dt, append=False, header=True):
+    """An autocorrelation table (Context.acf_read, distributed.acf_sum) as text: two comment lines (samples, dropped, out of range, origin
+    floor; the column names) unless header=False, then one tab-separated line per lag from the zero lag on -- the lag in ps (lag steps x
+    `dt`), then per group the pair count and the correlations (nan where a row has no pairs).  Floats are written with repr, so np.loadtxt
+    reads back the bits.  `file`: a path or an open text stream."""
+    cols = acf_columns(acf, dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"OriginFloor"\t%d' % (acf.samples, acf.dropped, acf.out_of_range, acf.origin_floor), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for l in range(acf.words.shape[1]):
             print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:

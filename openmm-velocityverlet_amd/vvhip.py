@@ -247,6 +247,26 @@ class ContactsLayout(C.Structure):
 CONTACTS_MAX_BYTES = 1 << 32
 
 
+ACF_VELOCITY_PARTICLES, ACF_VELOCITY_MOLECULES, ACF_ORIENTATION = 0, 1, 2
+
+
+class AcfDesc(C.Structure):
+    """What an autocorrelation recorder is to accumulate (include/vvhip.h: vvhip_acf_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32), ("num_groups", C.c_int32),
+                ("num_pairs", C.c_int32), ("group", C.c_void_p), ("pairs", C.c_void_p), ("max_samples", C.c_int64), ("limit", C.c_double)]
+
+
+class AcfCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64), ("origin_floor", C.c_int64)]
+
+
+class AcfLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32),
+                ("num_groups", C.c_int32), ("num_units", C.c_int32), ("num_origins", C.c_int32), ("frac_bits", C.c_int32),
+                ("row_words", C.c_int32), ("max_samples", C.c_int64), ("words", C.c_int64), ("ring_bytes", C.c_int64),
+                ("start_step", C.c_int64), ("limit", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -343,6 +363,8 @@ def _load():
         "vvhip_rdf_read": [vp, vp, C.c_int64, P(RdfCounts), i32],
         "vvhip_contacts_start": [vp, P(ContactsDesc)], "vvhip_contacts_sample": [vp], "vvhip_contacts_stop": [vp],
         "vvhip_contacts_info": [vp, P(ContactsLayout)], "vvhip_contacts_read": [vp, vp, C.c_int64, P(ContactsCounts), i32],
+        "vvhip_acf_start": [vp, P(AcfDesc)], "vvhip_acf_stop": [vp], "vvhip_acf_info": [vp, P(AcfLayout)],
+        "vvhip_acf_read": [vp, vp, C.c_int64, P(AcfCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
