@@ -1508,6 +1508,14 @@ int vvhip_debug_old_delta(vvhip_plan* plan, void** device_ptr);                 
  * buffers.  Process-wide counters of the owners themselves (csrc/vv_devmem.hpp), so a test can see that a destroyed plan has returned
  * everything without watching the device's free memory, which moves under other processes' work.  Host only. */
 int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes);
+/* FNV-1a 64 over the host tables that the last accepted vvhip_<name>_start built, name = "profile", "msd", "rdf", "current", "modes",
+ * "contacts" or "acf"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
+ * Per vector its size as uint64, then its bytes; flags as one byte; in this order:
+ *   profile   grouped, index, group, mass                 msd, acf   grouped, index, first, weight, total, group
+ *   rdf       index, mol, items, max_jsites (int32)       current    two_level, index, weight, group
+ *   modes     index, weight, modes, items                 contacts   first[0 .. 16], index, mol, mask_items, corr_items, then the fields
+ *                                                                    of the word layout (csrc/vv_layout.h: ContactsLayout) one by one */
+int vvhip_debug_recorder_digest(const vvhip_plan* plan, const char* name, uint64_t* out);
 
 #ifdef __cplusplus
 }

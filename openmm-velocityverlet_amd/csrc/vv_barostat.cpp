@@ -46,7 +46,7 @@ int vvhip_barostat_scale(vvhip_plan* p, const double scale[3]) {
         HIP_TRY(p, hipMemcpyAsync(B.corr.get(), p->buf.posq_correction, pos_bytes, hipMemcpyDeviceToDevice, p->stream));
     }
     vv::BarostatArgs a{};
-    a.posq = p->buf.posq; a.corr = mixed ? p->buf.posq_correction : nullptr;
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
     a.slots = p->d_slots.get(); a.lane_mol = B.d_lane_mol.get(); a.laneless = B.d_laneless.get(); a.mol_count = B.d_mol_count.get();
     a.words = B.d_words.get();
     a.nwaves = hp.info.num_waves; a.nlaneless = (int32_t) (hp.baro_laneless.size() / 2); a.nmol = (int32_t) hp.baro_mol_count.size();
@@ -59,9 +59,7 @@ int vvhip_barostat_scale(vvhip_plan* p, const double scale[3]) {
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     if (B.h_bad[0] != 0)
         return fail(p, VVHIP_ERR_OVERFLOW, "barostat: a position is not finite or beyond 2^22 nm; nothing was moved and the box stays");
-    TRY(msd_positions_rewritten(p));
-    TRY(current_positions_rewritten(p));
-    TRY(modes_positions_rewritten(p));
+    TRY(origins_dead(p, Rewrote::POSITIONS));
     for (int k = 0; k < 3; k++) { B.box_before[k] = p->box[k]; p->box[k] *= scale[k]; B.box_after[k] = p->box[k]; }
     drop_graphs(p);                 // the box is baked into the captured kernel arguments
     p->rec.valid = false;           // (a snapshot from before the scale would put the old positions back under the new box)
@@ -87,9 +85,7 @@ int vvhip_barostat_restore(vvhip_plan* p) {
     TRY(settle_recovery(p));
     HIP_TRY(p, hipMemcpyAsync(p->buf.posq, B.posq.get(), pos_bytes, hipMemcpyDeviceToDevice, p->stream));
     if (hp.precision == VVHIP_MIXED) HIP_TRY(p, hipMemcpyAsync(p->buf.posq_correction, B.corr.get(), pos_bytes, hipMemcpyDeviceToDevice, p->stream));
-    TRY(msd_positions_rewritten(p));
-    TRY(current_positions_rewritten(p));
-    TRY(modes_positions_rewritten(p));
+    TRY(origins_dead(p, Rewrote::POSITIONS));
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     for (int k = 0; k < 3; k++) p->box[k] = B.box_before[k];
     drop_graphs(p);

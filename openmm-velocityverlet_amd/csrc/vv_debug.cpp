@@ -29,6 +29,25 @@ static void span_pairs(const std::vector<long long>& h, size_t r0, size_t r1, st
 }
 #endif
 
+// FNV-1a 64 over the host tables a recorder's start built (tests/test_recorder_tables.py pins them): per vector its size as uint64, then
+// its bytes; scalars and arrays of scalars as their bytes.  The order is the one stated in include/vvhip.h, not the structs' declarations.
+// Host only: an unbound plan keeps the description of a start that passed its checks.  0: nothing described.
+namespace {
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void* q, size_t n) {
+        const unsigned char* b = (const unsigned char*) q;
+        for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; }
+    }
+    template <class T> void scalar(const T& v) { static_assert(std::is_arithmetic<T>::value, "scalars only: a struct has padding"); bytes(&v, sizeof(T)); }
+    template <class T, size_t N> void array(const T (&a)[N]) { static_assert(std::is_arithmetic<T>::value, "arrays of scalars only"); bytes(a, sizeof(a)); }
+    void flag(bool b) { scalar((unsigned char) (b ? 1 : 0)); }
+    // (the item structs of vv_args.hpp / vv_layout.h state their padding as zeroed members: bytes)
+    template <class T> void vec(const std::vector<T>& v) { scalar((uint64_t) v.size()); if (!v.empty()) bytes(v.data(), v.size() * sizeof(T)); }
+};
+template <class U> void digest_units(Fnv& f, const U& u) { f.flag(u.grouped); f.vec(u.index); f.vec(u.first); f.vec(u.weight); f.vec(u.total); f.vec(u.group); }
+}  // namespace
+
 extern "C" {
 
 // The stage bits vvhip_step_middle launches kernel A (kernel = 0) / kernel B with for this plan (timing and probe entry points)
@@ -261,6 +280,46 @@ int vvhip_debug_recover(vvhip_plan* p) {
     if (!p->rec.valid || p->rec.replaying) return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_recover: no unverified snapshot (a run call of at least recover_min_steps steps since the last synchronisation)");
     HIP_TRY(p, hipStreamSynchronize(p->stream));
     return recover_rendezvous(p, true);
+}
+// The digest of one recorder's host tables (Fnv, digest_units: the top of the file; include/vvhip.h states the order)
+int vvhip_debug_recorder_digest(const vvhip_plan* p, const char* name, uint64_t* out) {
+    if (!p || !name || !out) return VVHIP_ERR_INVALID;
+    const std::string which(name);
+    Fnv f;
+    bool described = false;
+    if (which == "profile") {
+        const vvhip_plan::Profile& R = p->profile;
+        described = R.described;
+        f.flag(R.grouped); f.vec(R.index); f.vec(R.group); f.vec(R.mass);
+    } else if (which == "msd") {
+        described = p->msd.described;
+        digest_units(f, p->msd);
+    } else if (which == "acf") {
+        described = p->acf.described;
+        digest_units(f, p->acf);
+    } else if (which == "rdf") {
+        const vvhip_plan::Rdf& R = p->rdf;
+        described = R.described;
+        f.vec(R.index); f.vec(R.mol); f.vec(R.items); f.scalar((int32_t) R.max_jsites);
+    } else if (which == "current") {
+        const vvhip_plan::Current& R = p->current;
+        described = R.described;
+        f.flag(R.two_level); f.vec(R.index); f.vec(R.weight); f.vec(R.group);
+    } else if (which == "modes") {
+        const vvhip_plan::Modes& R = p->modes;
+        described = R.described;
+        f.vec(R.index); f.vec(R.weight); f.vec(R.modes); f.vec(R.items);
+    } else if (which == "contacts") {
+        const vvhip_plan::Contacts& R = p->contacts;
+        const vv::ContactsLayout& G = R.geo;
+        described = R.described;
+        f.array(R.first); f.vec(R.index); f.vec(R.mol); f.vec(R.mask_items); f.vec(R.corr_items);
+        f.array(G.rows_padded); f.array(G.col_words); f.array(G.class_words); f.array(G.class_offset);
+        f.scalar(G.sample_words); f.scalar(G.num_origins); f.scalar(G.ord_words); f.scalar(G.table_words); f.scalar(G.ring_words);
+        f.scalar(G.words_bytes); f.scalar(G.scratch_bytes); f.scalar(G.total_bytes);
+    } else return VVHIP_ERR_INVALID;
+    *out = described ? f.h : 0;
+    return VVHIP_OK;
 }
 
 }  // extern "C"

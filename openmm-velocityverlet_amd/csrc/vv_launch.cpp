@@ -137,7 +137,7 @@ vv::KArgs make_args(vvhip_plan* p, uint32_t flags, uint32_t random_index) {
     vv::KArgs a{};
     a.velm = p->buf.velm;
     a.posq = p->buf.posq;
-    a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.corr = posq_corr(p);
     a.force = (const long long*) p->buf.force;
     a.fextra = p->d_fextra.get();
     a.pos_delta = p->buf.pos_delta ? p->buf.pos_delta : p->d_pos_delta.get();

@@ -2,7 +2,8 @@
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
 // correlations, density modes, contact lifetimes, autocorrelations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
 // when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The seven accumulating recorders
-// share one life cycle (recorder_*).
+// share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for five,
+// units for two, sites ordered by group for four, classes for two); origins_dead tells the four with origins that the state was rewritten.
 #include "vv_plan.hpp"
 
 #include <algorithm>
@@ -58,7 +59,7 @@ static int series_row(vvhip_plan* p) {
 static int frame_enqueue(vvhip_plan* p) {
     const vvhip_plan::Frames& F = p->frames;
     vv::FrameArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.posq = p->buf.posq; a.corr = posq_corr(p); a.velm = p->buf.velm;
     a.subset = F.has_subset ? F.d_subset.get() : nullptr;
     a.frames = F.ring.d_items.get(); a.cursor = F.ring.d_cursor.get();
     a.frame_bytes = F.frame_bytes; a.off_positions = F.off_positions; a.off_velocities = F.off_velocities;
@@ -74,7 +75,7 @@ static int profile_enqueue(vvhip_plan* p) {
     const vvhip_plan::Profile& P = p->profile;
     const vvhip_profile_layout& L = P.lay;
     vv::ProfileArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.posq = p->buf.posq; a.corr = posq_corr(p); a.velm = p->buf.velm;
     a.index = P.index.empty() ? nullptr : P.dev.index.get(); a.group = P.grouped ? P.dev.group.get() : nullptr; a.mass = P.dev.mass.get();
     a.words = P.d_words.get(); a.max_samples = L.max_samples;
     a.n = L.num_particles; a.nbins = L.nbins; a.axis = L.axis; a.mask = L.mask; a.rows = L.rows; a.table_words = (int32_t) L.words;
@@ -99,8 +100,8 @@ static int msd_enqueue(vvhip_plan* p) {
     const vvhip_plan::Msd& M = p->msd;
     const vvhip_msd_layout& L = M.lay;
     vv::MsdArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
-    const bool molecules = L.mode == VVHIP_MSD_MOLECULES;
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
+    const bool molecules = M.molecules;
     a.index = M.index.empty() ? nullptr : M.dev.index.get();
     a.first = molecules ? M.dev.first.get() : nullptr; a.weight = molecules ? M.dev.weight.get() : nullptr; a.total = molecules ? M.dev.total.get() : nullptr;
     a.group = M.grouped ? M.dev.group.get() : nullptr;
@@ -112,15 +113,14 @@ static int msd_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_msd(p->hp.precision, a, block_threads_for(p->msd_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
-// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
-int msd_positions_rewritten(vvhip_plan* p) {
-    if (!p->msd.on) return VVHIP_OK;
-    HIP_TRY(p, vv::launch_msd_floor(p->msd.d_words.get(), p->stream));
-    return VVHIP_OK;
-}
 // ------------------------------------------------------------------------------------------ radial distribution functions (vvhip_rdf_*)
-// r_max against the box: one image per pair
-static bool rdf_box_holds(const double box[3], double r_max) { return r_max <= std::min(box[0], std::min(box[1], box[2])) / 2; }
+// r against the box: one image per pair.  `what` names r in the refusal ("r_max = ", "the cutoff ")
+static bool box_holds(const double box[3], double r) { return r <= std::min(box[0], std::min(box[1], box[2])) / 2; }
+static int check_half_box(vvhip_plan* p, const char* name, const char* what, double r) {
+    if (box_holds(p->box, r)) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": " + what + std::to_string(r) + " nm is above half the shortest edge of the box (" +
+                                      std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm): a pair would have more than one image in range");
+}
 // One sample behind the step just enqueued (or captured), and behind its MSD sample -- or behind what is queued (vvhip_rdf_sample): the
 // gather, the pair kernel and the one-thread kernel that counts the sample.  Three launches, no memset and no host synchronisation.  The
 // box and whether it still holds r_max are arguments: what changes the box drops the captured graphs.
@@ -128,14 +128,14 @@ static int rdf_enqueue(vvhip_plan* p) {
     const vvhip_plan::Rdf& R = p->rdf;
     const vvhip_rdf_layout& L = R.lay;
     vv::RdfArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
     a.index = R.dev.index.get(); a.mol = L.exclude_same_molecule ? R.dev.mol.get() : nullptr; a.items = R.dev.items.get();
     a.scratch = R.dev.scratch.get(); a.words = R.d_words.get();
     a.max_samples = L.max_samples;
     a.n = (int32_t) R.index.size(); a.stride = R.stride(); a.nbins = L.nbins; a.num_items = (int32_t) R.items.size();
     // (one histogram per wave only where all of them fit beside the staged tile)
     a.copies = p->rdf_hist_copies > 1 && vv::rdf_lds_bytes(L.nbins, vv::RDF_TILE / 64) <= vv::PROFILE_LDS_BYTES ? vv::RDF_TILE / 64 : 1;
-    a.live = rdf_box_holds(p->box, L.r_max) ? 1 : 0;
+    a.live = box_holds(p->box, L.r_max) ? 1 : 0;
     a.max_jsites = R.max_jsites;
     for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
     a.dr = L.dr; a.cut2 = ((double) L.nbins * L.dr) * ((double) L.nbins * L.dr); a.inv_dr = (float) (1.0 / L.dr);
@@ -151,7 +151,7 @@ static int current_enqueue(vvhip_plan* p) {
     const vvhip_plan::Current& K = p->current;
     const vvhip_current_layout& L = K.lay;
     vv::CurrentArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; a.velm = p->buf.velm;
+    a.posq = p->buf.posq; a.corr = posq_corr(p); a.velm = p->buf.velm;
     a.index = K.dev.index.get(); a.weight = K.dev.weight.get(); a.group = K.dev.group.get();
     a.words = K.d_words.get(); a.table = a.words + K.table_offset(); a.ring = a.table + L.words;
     a.hold = a.ring + (size_t) L.num_origins * K.sums_words();
@@ -166,12 +166,6 @@ static int current_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_current(p->hp.precision, a, block_threads_for(p->current_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
-// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
-int current_positions_rewritten(vvhip_plan* p) {
-    if (!p->current.on) return VVHIP_OK;
-    HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
-    return VVHIP_OK;
-}
 // ------------------------------------------------------------------------------------------ density modes (vvhip_modes_*)
 // One sample behind the step just enqueued (or captured), and behind its current sample: the gather, the mode kernel, the correlate and the
 // one-wave kernel that stores the origin and counts the sample.  Four launches, no memset and no host synchronisation.  1 / L and the box
@@ -180,7 +174,7 @@ static int modes_enqueue(vvhip_plan* p) {
     const vvhip_plan::Modes& M = p->modes;
     const vvhip_modes_layout& L = M.lay;
     vv::ModesArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
     a.index = M.dev.index.get(); a.weight = M.dev.weight.get(); a.modes = M.dev.modes.get(); a.items = M.dev.items.get();
     a.turns = M.dev.turns.get();
     a.words = M.d_words.get(); a.table = a.words + M.table_offset(); a.ring = a.table + L.words;
@@ -195,12 +189,6 @@ static int modes_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_modes(p->hp.precision, a, L.sites_per_thread, L.block_threads, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
-// vvhip_barostat_scale / _restore rewrote the positions outside the steps: the origins stored so far are dead (vv_barostat.cpp)
-int modes_positions_rewritten(vvhip_plan* p) {
-    if (!p->modes.on) return VVHIP_OK;
-    HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
-    return VVHIP_OK;
-}
 // ------------------------------------------------------------------------------------------ contact lifetime correlations (vvhip_contacts_*)
 // One sample behind the step just enqueued (or captured), and behind its density-mode sample -- or behind what is queued
 // (vvhip_contacts_sample): the gather, the mask kernel, the correlate kernel and the one-wave kernel that counts the sample.  Four launches,
@@ -211,7 +199,7 @@ static int contacts_enqueue(vvhip_plan* p) {
     const vvhip_contacts_layout& L = K.lay;
     const vv::ContactsLayout& G = K.geo;
     vv::ContactsArgs a{};
-    a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
     a.index = K.dev.index.get(); a.mol = L.exclude_same_molecule ? K.dev.mol.get() : nullptr;
     a.mask_items = K.dev.mask_items.get(); a.corr_items = K.dev.corr_items.get();
     a.scratch = K.dev.scratch.get(); a.mask = K.dev.mask.get();
@@ -231,7 +219,7 @@ static int contacts_enqueue(vvhip_plan* p) {
         a.rows[c] = L.rows[c]; a.cols[c] = L.cols[c];
         a.first_row[c] = K.first[L.classes[c][0]]; a.first_col[c] = K.first[L.classes[c][1]];
     }
-    a.live = rdf_box_holds(p->box, largest) ? 1 : 0;
+    a.live = box_holds(p->box, largest) ? 1 : 0;
     for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
     HIP_TRY(p, vv::launch_contacts(p->hp.precision, a, p->grid_cap_a, p->stream));
     return VVHIP_OK;
@@ -243,8 +231,8 @@ static int acf_enqueue(vvhip_plan* p) {
     const vvhip_plan::Acf& A = p->acf;
     const vvhip_acf_layout& L = A.lay;
     vv::AcfArgs a{};
-    a.velm = p->buf.velm; a.posq = p->buf.posq; a.corr = p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr;
-    const bool molecules = L.mode == VVHIP_ACF_VELOCITY_MOLECULES;
+    a.velm = p->buf.velm; a.posq = p->buf.posq; a.corr = posq_corr(p);
+    const bool molecules = A.molecules;
     a.index = A.index.empty() ? nullptr : A.dev.index.get();
     a.first = molecules ? A.dev.first.get() : nullptr; a.weight = molecules ? A.dev.weight.get() : nullptr; a.total = molecules ? A.dev.total.get() : nullptr;
     a.group = A.grouped ? A.dev.group.get() : nullptr;
@@ -256,10 +244,15 @@ static int acf_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_acf(p->hp.precision, a, L.mode, block_threads_for(p->acf_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
-// vvhip_set_velocities_to_temperature rewrote the velocities outside the steps: a velocity-mode recorder's origins so far are dead
-int acf_velocities_rewritten(vvhip_plan* p) {
-    if (!p->acf.on || p->acf.lay.mode == VVHIP_ACF_ORIENTATION) return VVHIP_OK;
-    HIP_TRY(p, vv::launch_acf_floor(p->acf.d_words.get(), p->stream));
+// The positions or the velocities were rewritten outside the steps (vv_barostat.cpp; vvhip_set_velocities_to_temperature): the origins that
+// the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, their floors raised in this order; velocities:
+// acf, unless it records orientations.  A contact set belongs to a configuration, not to a displacement: contacts reacts to neither.
+int origins_dead(vvhip_plan* p, Rewrote what) {
+    if (what == Rewrote::POSITIONS) {
+        if (p->msd.on) HIP_TRY(p, vv::launch_msd_floor(p->msd.d_words.get(), p->stream));
+        if (p->current.on) HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
+        if (p->modes.on) HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
+    } else if (p->acf.on && p->acf.lay.mode != VVHIP_ACF_ORIENTATION) HIP_TRY(p, vv::launch_acf_floor(p->acf.d_words.get(), p->stream));
     return VVHIP_OK;
 }
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
@@ -308,6 +301,9 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   7 density-mode sample   behind the current sample; all of d_words likewise (its turns are scratch, rewritten by every sample)
 //   8 contact sample    behind the density-mode sample; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
 //   9 autocorrelation sample   last; all of d_words, the ring of origins included, as for the MSD
+// Riders 3 .. 9 are the seven accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
+// host tables come from "the shared pieces of a start" below (units: 4 and 9; sites ordered by group: 5 .. 8; the lag schedule: 4, 6 .. 9),
+// and origins_dead above reaches 4, 6, 7 (positions) and 9 (velocities).
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -402,12 +398,180 @@ static int recorder_info(const vvhip_plan* p, R vvhip_plan::* which, L* out, L b
     *out = blank;
     return VVHIP_OK;
 }
-// group[i] of every particle of the System against [-1, num_groups) (group = null: everything in group 0)
-static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups) {
-    for (int32_t i = 0; group && i < p->hp.num_atoms; i++)
+
+// ------------------------------------------------------------------------------------------ the shared pieces of a start
+// The host-only part of the accumulating recorders' *_start, stated once; `name` is the prefix of the messages.  What a recorder still
+// writes itself: its own argument checks, its layout, its fixed point (but for units_frac_bits), its work list, its enqueue.
+//   check_groups, check_max_samples   all seven               check_lags            msd, acf, current, modes, contacts
+//   num_origins_of                    msd, acf, current, modes; check_origins       msd, acf, contacts
+//   plan_units, units_frac_bits, fill_units   msd, acf        sites_by_group        rdf, current, modes, contacts
+//   check_classes, check_pair_count, check_half_box (beside box_holds), no_pairs_across_shards   rdf, contacts;   no_sums_across_shards   current, modes
+// group[i] of every particle of the System (or, count >= 0, of `count` entries) against [-1, num_groups) (group = null: everything in group 0)
+static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups, int32_t count = -1) {
+    for (int32_t i = 0; group && i < (count < 0 ? p->hp.num_atoms : count); i++)
         if (group[i] < -1 || group[i] >= num_groups)
             return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": group[" + std::to_string(i) + "] = " + std::to_string((int) group[i]) + " is outside [-1, num_groups = " + std::to_string(num_groups) + ")");
     return VVHIP_OK;
+}
+static int check_max_samples(vvhip_plan* p, const char* name, int64_t max_samples) {
+    return max_samples < 1 ? fail(p, VVHIP_ERR_INVALID, std::string(name) + ": max_samples must be >= 1") : VVHIP_OK;
+}
+// weight[i] of every particle of the System (current, modes)
+static int check_weights(vvhip_plan* p, const char* name, const double* weight) {
+    for (int32_t i = 0; i < p->hp.num_atoms; i++)
+        if (!std::isfinite(weight[i])) return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": weight[" + std::to_string(i) + "] is not finite");
+    return VVHIP_OK;
+}
+// The lag schedule: a sample every `interval` steps, lags 0 .. num_lags - 1 of them, every origin_every-th sample an origin.  min_lags = 0
+// (density modes): no lags, no origins, the equal-time table alone.  (max_samples is checked behind the recorder's group and class counts.)
+static int check_lags(vvhip_plan* p, const char* name, int32_t interval, int32_t num_lags, int32_t origin_every, int min_lags = 1) {
+    const std::string n(name);
+    if (interval < 1) return fail(p, VVHIP_ERR_INVALID, n + ": interval must be >= 1 step");
+    if (num_lags < min_lags || num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, n + ": num_lags must be in [" + std::to_string(min_lags) + ", 4096]");
+    if (origin_every < 1 || origin_every > std::max(1, num_lags))
+        return fail(p, VVHIP_ERR_INVALID, n + ": origin_every must be in " + (min_lags ? "[1, num_lags]" : "[1, max(1, num_lags)]"));
+    return VVHIP_OK;
+}
+// ... its ring of ceil(num_lags / origin_every) slots, one per origin that is alive; the refusal of more than 1024 stands apart, because
+// msd and acf refuse their fixed point in front of it
+static int32_t num_origins_of(int32_t num_lags, int32_t origin_every) { return (num_lags + origin_every - 1) / origin_every; }
+static int check_origins(vvhip_plan* p, const char* name, int32_t num_origins) {
+    if (num_origins <= 1024) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": num_origins = ceil(num_lags / origin_every) = " + std::to_string(num_origins) + " is above 1024: raise origin_every");
+}
+// ---- units (msd, acf): the particles, or the molecules' massive members, of the description and of this shard.  A unit belongs to the
+// plan when all of it lies in the shard, and its tables hold SHARD-RELATIVE particle indices (sites_by_group below: global ones).
+struct Unit { int group; int32_t id; };          // id: the particle, the molecule, or (acf) the pair
+struct PlanUnits {
+    std::vector<Unit> units;                      // of this plan
+    long long described = 0;                      // U: the units the DESCRIPTION records, of the whole System -- the fixed point follows these, not the shard
+    std::vector<std::vector<int32_t>> members;    // molecules: per molecule id its massive particles, ascending
+    bool cut = false;                             // the shard holds a part of some molecule (one that no group records too)
+};
+static int plan_units(vvhip_plan* p, const char* name, const signed char* group, bool molecules, PlanUnits& U) {
+    const vv::HostPlan& hp = p->hp;
+    auto group_of = [&](int32_t i) { return group ? (int) group[i] : 0; };
+    auto in_shard = [&](int32_t i) { return i >= hp.shard_begin && i < hp.shard_end; };
+    if (!molecules) {
+        for (int32_t i = 0; i < hp.num_atoms; i++) {
+            if (group_of(i) < 0) continue;
+            U.described++;
+            if (in_shard(i)) U.units.push_back({group_of(i), i});
+        }
+        return VVHIP_OK;
+    }
+    int32_t nmol = 0;
+    for (int32_t i = 0; i < hp.num_atoms; i++) nmol = std::max(nmol, hp.mol_id[(size_t) i] + 1);
+    U.members.resize((size_t) nmol);
+    for (int32_t i = 0; i < hp.num_atoms; i++)
+        if (hp.masses[(size_t) i] > 0) U.members[(size_t) hp.mol_id[(size_t) i]].push_back(i);
+    for (int32_t m = 0; m < nmol; m++) {
+        const std::vector<int32_t>& mem = U.members[(size_t) m];
+        if (mem.empty()) continue;
+        int here = 0;
+        for (int32_t i : mem) {
+            here += in_shard(i);
+            if (group_of(i) != group_of(mem[0]))
+                return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": molecule " + std::to_string(m) + " has massive particles in different groups (particle " + std::to_string(mem[0]) + ": " +
+                                                  std::to_string(group_of(mem[0])) + ", particle " + std::to_string(i) + ": " + std::to_string(group_of(i)) + ")");
+        }
+        U.cut = U.cut || (here != 0 && here != (int) mem.size());
+        if (group_of(mem[0]) < 0) continue;
+        U.described++;
+        if (here == (int) mem.size()) U.units.push_back({group_of(mem[0]), m});
+    }
+    return VVHIP_OK;
+}
+// The fixed point of sums over the described units and the origins that max_samples samples store, of products below limit^2: at most 40
+// fraction bits, refused below 8
+static int units_frac_bits(vvhip_plan* p, const char* name, long long described, int64_t max_samples, int32_t origin_every, double limit, int32_t* frac_bits) {
+    const long long max_origins = samples_plus(max_samples, origin_every - 1) / origin_every;
+    *frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(limit));
+    if (*frac_bits >= 8) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": the sums would keep " + std::to_string(*frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
+                                      std::to_string((long long) max_samples) + ", origin_every = " + std::to_string(origin_every) + " and limit " + std::to_string(limit) +
+                                      ": lower max_samples or the limit");
+}
+// The units' tables, by group, then by id: index, and for molecules (N.molecules) first / weight / total; `pairs` (acf's orientation
+// mode): head and tail of unit u instead
+template <class R>
+static void fill_units(const vv::HostPlan& hp, R& N, PlanUnits& U, const int32_t* pairs = nullptr) {
+    std::stable_sort(U.units.begin(), U.units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });
+    for (const Unit& u : U.units) {
+        if (N.grouped) N.group.push_back((unsigned char) u.group);
+        if (pairs) { N.index.push_back(pairs[2 * u.id] - hp.shard_begin); N.index.push_back(pairs[2 * u.id + 1] - hp.shard_begin); continue; }
+        if (!N.molecules) { N.index.push_back(u.id - hp.shard_begin); continue; }
+        N.first.push_back((int32_t) N.index.size());
+        double M = 0;
+        for (int32_t i : U.members[(size_t) u.id]) {
+            N.index.push_back(i - hp.shard_begin); N.weight.push_back(hp.masses[(size_t) i]);
+            M = M + hp.masses[(size_t) i];
+        }
+        N.total.push_back(M);
+    }
+    if (N.molecules) N.first.push_back((int32_t) N.index.size());
+    if (!N.molecules && !pairs && !N.grouped && (int32_t) U.units.size() == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
+}
+// ---- sites ordered by group (rdf, contacts, modes, current): every particle of the System with a group >= 0, by its GLOBAL index --
+// these four record on unsharded plans only (no_pairs_ / no_sums_across_shards), where units hold shard-relative ones.  count[g] sites
+// of group g from first[g] on; beside index, where asked for, the site's molecule, weight (and the largest |weight|) and group.
+constexpr int kMaxSiteGroups = 16;
+static_assert(vv::RDF_MAX_GROUPS <= kMaxSiteGroups && vv::CONTACTS_MAX_GROUPS <= kMaxSiteGroups && vv::CUR_MAX_GROUPS <= kMaxSiteGroups && vv::MODES_MAX_GROUPS <= kMaxSiteGroups, "");
+struct Sites {
+    int32_t count[kMaxSiteGroups] = {0}, first[kMaxSiteGroups + 1] = {0};
+    std::vector<int32_t> index, mol;
+    std::vector<double> weight;
+    std::vector<unsigned char> group;
+    double wmax = 0;
+};
+static Sites sites_by_group(const vv::HostPlan& hp, const signed char* group, int num_groups, bool with_mol, const double* weight, bool with_group) {
+    Sites S;
+    auto group_of = [&](int32_t i) { return group ? (int) group[i] : 0; };
+    for (int32_t i = 0; i < hp.num_atoms; i++)
+        if (group_of(i) >= 0) S.count[group_of(i)]++;
+    for (int g = 0; g < num_groups; g++) S.first[g + 1] = S.first[g] + S.count[g];
+    const size_t n = (size_t) S.first[num_groups];
+    S.index.resize(n);
+    if (with_mol) S.mol.resize(n);
+    if (weight) S.weight.resize(n);
+    if (with_group) S.group.resize(n);
+    int32_t next[kMaxSiteGroups];
+    std::copy(S.first, S.first + kMaxSiteGroups, next);
+    for (int32_t i = 0; i < hp.num_atoms; i++) {      // ascending by particle inside every group
+        const int g = group_of(i);
+        if (g < 0) continue;
+        const size_t s = (size_t) next[g]++;
+        S.index[s] = i;
+        if (with_mol) S.mol[s] = hp.mol_id[(size_t) i];
+        if (weight) { S.weight[s] = weight[i]; S.wmax = std::max(S.wmax, std::fabs(weight[i])); }
+        if (with_group) S.group[s] = (unsigned char) g;
+    }
+    return S;
+}
+// ---- classes of pairs of groups (rdf, contacts)
+static int check_classes(vvhip_plan* p, const char* name, const int32_t* classes, int32_t num_classes, int32_t num_groups) {
+    for (int32_t c = 0; c < num_classes; c++)
+        for (int q = 0; q < 2; q++)
+            if (classes[2 * c + q] < 0 || classes[2 * c + q] >= num_groups)
+                return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(classes[2 * c + q]) + " is outside [0, num_groups = " + std::to_string(num_groups) + ")");
+    return VVHIP_OK;
+}
+// `pairs`: the most pairs a sample adds to one `word` ("bin", "word") of the table
+static int check_pair_count(vvhip_plan* p, const char* name, int64_t pairs, int64_t max_samples, const char* word) {
+    if ((unsigned __int128) pairs * (unsigned __int128) max_samples < ((unsigned __int128) 1 << 62)) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_INVALID, std::string(name) + ": " + std::to_string((long long) pairs) + " pairs per sample times max_samples = " + std::to_string((long long) max_samples) +
+                                      " reaches 2^62: a " + word + " could overflow; lower max_samples");
+}
+// ---- a sharded plan: the two families' refusals (`table`: "histogram", "matrix")
+static int no_pairs_across_shards(vvhip_plan* p, const char* name, const char* table) {
+    if (!cmm_sharded(p)) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_UNSUPPORTED, std::string(name) + ": a sharded plan holds its own particles' positions only, so the pairs across shards exist on no device; "
+                                          "a partial " + table + " is not recorded (run the analysis on an unsharded plan)");
+}
+static int no_sums_across_shards(vvhip_plan* p, const char* name) {
+    if (!cmm_sharded(p)) return VVHIP_OK;
+    return fail(p, VVHIP_ERR_UNSUPPORTED, std::string(name) + ": a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
+                                          "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
 }
 
 extern "C" {
@@ -540,7 +704,7 @@ int vvhip_set_velocities_to_temperature(vvhip_plan* p, double temperature, doubl
         TRY(run_a(p, cons_a(p), 0));
         r.constrained = 1;
     }
-    TRY(acf_velocities_rewritten(p));
+    TRY(origins_dead(p, Rewrote::VELOCITIES));
     if (remove_cm) {      // (either way the call's one synchronisation)
         TRY(cmm_one_off(p, r.v_removed));
         r.cm_removed = 1;
@@ -735,7 +899,7 @@ int vvhip_profile_start(vvhip_plan* p, const vvhip_profile_desc* d) {
     constexpr int kAll = VVHIP_PROFILE_COUNT | VVHIP_PROFILE_CHARGE | VVHIP_PROFILE_MASS | VVHIP_PROFILE_MOMENTUM | VVHIP_PROFILE_KINETIC;
     if (d->mask & ~kAll) return fail(p, VVHIP_ERR_INVALID, "profile: mask holds bits besides VVHIP_PROFILE_COUNT / CHARGE / MASS / MOMENTUM / KINETIC");
     if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "profile: num_groups must be in [1, 16]");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "profile: max_samples must be >= 1");
+    TRY(check_max_samples(p, "profile", d->max_samples));
     static const char* const kQuantity[VVHIP_PROFILE_QUANTITIES] = {"count", "charge", "mass", "momentum", "kinetic"};
     for (int q = 0; q < 4; q++)
         if (!(d->limit[q] >= 0) || !std::isfinite(d->limit[q]))
@@ -800,86 +964,30 @@ int vvhip_profile_info(const vvhip_plan* p, vvhip_profile_layout* out) {
 int vvhip_msd_start(vvhip_plan* p, const vvhip_msd_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
     if (!d) return fail(p, VVHIP_ERR_INVALID, "msd: null description");
-    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "msd: interval must be >= 1 step");
-    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "msd: num_lags must be in [1, 4096]");
-    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "msd: origin_every must be in [1, num_lags]");
+    TRY(check_lags(p, "msd", d->interval, d->num_lags, d->origin_every));
     if (d->mode != VVHIP_MSD_PARTICLES && d->mode != VVHIP_MSD_MOLECULES) return fail(p, VVHIP_ERR_INVALID, "msd: mode must be VVHIP_MSD_PARTICLES or VVHIP_MSD_MOLECULES");
     if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "msd: num_groups must be in [1, 16]");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "msd: max_samples must be >= 1");
+    TRY(check_max_samples(p, "msd", d->max_samples));
     if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "msd: limit must be finite and >= 0 (0: the default of 64 nm)");
-    const vv::HostPlan& hp = p->hp;
     TRY(check_groups(p, "msd", d->group, d->num_groups));
     // ---- the units this plan records, the layout and the fixed point, host only
     vvhip_plan::Msd N;
     vvhip_msd_layout& L = N.lay;
-    N.grouped = d->group != nullptr;
-    const bool molecules = d->mode == VVHIP_MSD_MOLECULES;
-    auto group_of = [&](int32_t i) { return d->group ? (int) d->group[i] : 0; };
-    auto in_shard = [&](int32_t i) { return i >= hp.shard_begin && i < hp.shard_end; };
-    struct Unit { int group; int32_t id; };      // id: the particle, or the molecule
-    std::vector<Unit> units;                      // of this plan
-    long long described = 0;                      // U: the units the DESCRIPTION records, of the whole System
-    std::vector<std::vector<int32_t>> members;    // molecules: per molecule id its massive particles, ascending
-    bool cut = false;
-    if (!molecules) {
-        for (int32_t i = 0; i < hp.num_atoms; i++) {
-            if (group_of(i) < 0) continue;
-            described++;
-            if (in_shard(i)) units.push_back({group_of(i), i});
-        }
-    } else {
-        int32_t nmol = 0;
-        for (int32_t i = 0; i < hp.num_atoms; i++) nmol = std::max(nmol, hp.mol_id[(size_t) i] + 1);
-        members.resize((size_t) nmol);
-        for (int32_t i = 0; i < hp.num_atoms; i++)
-            if (hp.masses[(size_t) i] > 0) members[(size_t) hp.mol_id[(size_t) i]].push_back(i);
-        for (int32_t m = 0; m < nmol; m++) {
-            const std::vector<int32_t>& mem = members[(size_t) m];
-            if (mem.empty()) continue;
-            int here = 0;
-            for (int32_t i : mem) {
-                here += in_shard(i);
-                if (group_of(i) != group_of(mem[0]))
-                    return fail(p, VVHIP_ERR_INVALID, "msd: molecule " + std::to_string(m) + " has massive particles in different groups (particle " + std::to_string(mem[0]) + ": " +
-                                                      std::to_string(group_of(mem[0])) + ", particle " + std::to_string(i) + ": " + std::to_string(group_of(i)) + ")");
-            }
-            cut = cut || (here != 0 && here != (int) mem.size());
-            if (group_of(mem[0]) < 0) continue;
-            described++;
-            if (here == (int) mem.size()) units.push_back({group_of(mem[0]), m});
-        }
-    }
-    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
+    N.grouped = d->group != nullptr; N.molecules = d->mode == VVHIP_MSD_MOLECULES;
+    PlanUnits U;
+    TRY(plan_units(p, "msd", d->group, N.molecules, U));
     L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.mode = d->mode; L.num_groups = d->num_groups;
     L.max_samples = d->max_samples;
-    L.num_units = (int32_t) units.size();
-    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.num_units = (int32_t) U.units.size();
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every);
     L.words = (int64_t) L.num_groups * L.num_lags * 4;
     L.limit = d->limit > 0 ? pow2_at_least(d->limit) : 64.0;
     L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
-    const long long max_origins = samples_plus(L.max_samples, L.origin_every - 1) / L.origin_every;
-    L.frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(L.limit));
-    if (L.frac_bits < 8)
-        return fail(p, VVHIP_ERR_INVALID, "msd: the sums would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
-                                          std::to_string((long long) L.max_samples) + ", origin_every = " + std::to_string(L.origin_every) + " and limit " + std::to_string(L.limit) +
-                                          ": lower max_samples or the limit");
-    if (L.num_origins > 1024)
-        return fail(p, VVHIP_ERR_INVALID, "msd: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
-    if (molecules && cut)
+    TRY(units_frac_bits(p, "msd", U.described, L.max_samples, L.origin_every, L.limit, &L.frac_bits));
+    TRY(check_origins(p, "msd", L.num_origins));
+    if (N.molecules && U.cut)
         return fail(p, VVHIP_ERR_UNSUPPORTED, "msd: the particle shard cuts a molecule: its centre of mass needs particles of another shard");
-    for (const Unit& u : units) {
-        if (N.grouped) N.group.push_back((unsigned char) u.group);
-        if (!molecules) { N.index.push_back(u.id - hp.shard_begin); continue; }
-        N.first.push_back((int32_t) N.index.size());
-        double M = 0;
-        for (int32_t i : members[(size_t) u.id]) {
-            N.index.push_back(i - hp.shard_begin); N.weight.push_back(hp.masses[(size_t) i]);
-            M = M + hp.masses[(size_t) i];
-        }
-        N.total.push_back(M);
-    }
-    if (molecules) N.first.push_back((int32_t) N.index.size());
-    if (!molecules && !N.grouped && L.num_units == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
+    fill_units(p->hp, N, U);
     return recorder_install(p, &vvhip_plan::msd, "msd", N, d->interval);
 }
 int vvhip_msd_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_msd_counts* out, int32_t reset) {
@@ -900,13 +1008,9 @@ int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     if (d->num_groups < 1 || d->num_groups > vv::RDF_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "rdf: num_groups must be in [1, 16]");
     if (d->num_classes < 1 || d->num_classes > vv::RDF_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "rdf: num_classes must be in [1, 32]");
     if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "rdf: classes must not be NULL");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "rdf: max_samples must be >= 1");
-    const vv::HostPlan& hp = p->hp;
+    TRY(check_max_samples(p, "rdf", d->max_samples));
     TRY(check_groups(p, "rdf", d->group, d->num_groups));
-    for (int32_t c = 0; c < d->num_classes; c++)
-        for (int q = 0; q < 2; q++)
-            if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= d->num_groups)
-                return fail(p, VVHIP_ERR_INVALID, "rdf: classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(d->classes[2 * c + q]) + " is outside [0, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_classes(p, "rdf", d->classes, d->num_classes, d->num_groups));
     // ---- the sites, the layout and the pair kernel's work list, host only
     vvhip_plan::Rdf N;
     vvhip_rdf_layout& L = N.lay;
@@ -914,12 +1018,9 @@ int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     L.exclude_same_molecule = d->exclude_same_molecule != 0; L.tile = vv::RDF_TILE;
     L.max_samples = d->max_samples; L.words = (int64_t) d->num_classes * d->nbins;
     L.r_max = d->r_max; L.dr = d->r_max / (double) d->nbins;
-    for (int32_t i = 0; i < hp.num_atoms; i++) {
-        const int g = d->group ? (int) d->group[i] : 0;
-        if (g >= 0) L.num_sites[g]++;
-    }
-    int32_t first[vv::RDF_MAX_GROUPS + 1] = {0};
-    for (int g = 0; g < d->num_groups; g++) first[g + 1] = first[g] + L.num_sites[g];
+    Sites S = sites_by_group(p->hp, d->group, d->num_groups, L.exclude_same_molecule != 0, nullptr, false);
+    std::copy(S.count, S.count + d->num_groups, L.num_sites);
+    const int32_t* first = S.first;
     int64_t largest = 0;
     for (int32_t c = 0; c < d->num_classes; c++) {
         const int ga = d->classes[2 * c], gb = d->classes[2 * c + 1];
@@ -928,28 +1029,10 @@ int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
         L.pairs_per_sample[c] = ga == gb ? na * (na - 1) / 2 : na * nb;
         largest = std::max(largest, L.pairs_per_sample[c]);
     }
-    if ((unsigned __int128) largest * (unsigned __int128) d->max_samples >= ((unsigned __int128) 1 << 62))
-        return fail(p, VVHIP_ERR_INVALID, "rdf: " + std::to_string((long long) largest) + " pairs per sample times max_samples = " + std::to_string((long long) d->max_samples) +
-                                          " reaches 2^62: a bin could overflow; lower max_samples");
-    if (!rdf_box_holds(p->box, d->r_max))
-        return fail(p, VVHIP_ERR_INVALID, "rdf: r_max = " + std::to_string(d->r_max) + " nm is above half the shortest edge of the box (" +
-                                          std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm): a pair would have more than one image in range");
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "rdf: a sharded plan holds its own particles' positions only, so the pairs across shards exist on no device; "
-                                              "a partial histogram is not recorded (run the analysis on an unsharded plan)");
-    N.index.resize((size_t) first[d->num_groups]);
-    if (L.exclude_same_molecule) N.mol.resize(N.index.size());
-    {
-        int32_t next[vv::RDF_MAX_GROUPS];
-        std::copy(first, first + vv::RDF_MAX_GROUPS, next);
-        for (int32_t i = 0; i < hp.num_atoms; i++) {      // ascending by particle inside every group
-            const int g = d->group ? (int) d->group[i] : 0;
-            if (g < 0) continue;
-            N.index[(size_t) next[g]] = i;
-            if (L.exclude_same_molecule) N.mol[(size_t) next[g]] = hp.mol_id[(size_t) i];
-            next[g]++;
-        }
-    }
+    TRY(check_pair_count(p, "rdf", largest, d->max_samples, "bin"));
+    TRY(check_half_box(p, "rdf", "r_max = ", d->r_max));
+    TRY(no_pairs_across_shards(p, "rdf", "histogram"));
+    N.index = std::move(S.index); N.mol = std::move(S.mol);
     // the work list: per class and i-tile the j-sites in runs of `max_jsites`, a multiple of 64; a class of one group with itself from
     // the i-tile's first site on.  A small workload gets runs of 64, so that its blocks fill the device; beyond rdf_items_target blocks
     // a run grows, so that the flush of a block's histogram and its launch are shared (at most 2^18 sites: 2^26 pairs, far inside what
@@ -996,57 +1079,42 @@ int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) { return recorder
 int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
     if (!d) return fail(p, VVHIP_ERR_INVALID, "current: null description");
-    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "current: interval must be >= 1 step");
-    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "current: num_lags must be in [1, 4096]");
-    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "current: origin_every must be in [1, num_lags]");
+    TRY(check_lags(p, "current", d->interval, d->num_lags, d->origin_every));
     if (d->num_groups < 1 || d->num_groups > vv::CUR_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "current: num_groups must be in [1, 8]");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "current: max_samples must be >= 1");
+    TRY(check_max_samples(p, "current", d->max_samples));
     if (!(d->limit_position >= 0) || !std::isfinite(d->limit_position)) return fail(p, VVHIP_ERR_INVALID, "current: limit_position must be finite and >= 0 (0: the default of 64 nm)");
     if (!(d->limit_velocity >= 0) || !std::isfinite(d->limit_velocity)) return fail(p, VVHIP_ERR_INVALID, "current: limit_velocity must be finite and >= 0 (0: the default of 64 nm/ps)");
     if (!d->weight) return fail(p, VVHIP_ERR_INVALID, "current: weight must not be NULL");
-    const vv::HostPlan& hp = p->hp;
     TRY(check_groups(p, "current", d->group, d->num_groups));
-    for (int32_t i = 0; i < hp.num_atoms; i++)
-        if (!std::isfinite(d->weight[i])) return fail(p, VVHIP_ERR_INVALID, "current: weight[" + std::to_string(i) + "] is not finite");
+    TRY(check_weights(p, "current", d->weight));
     // ---- the recorded particles, the layout and the fixed point, host only
     vvhip_plan::Current N;
     vvhip_current_layout& L = N.lay;
-    struct Unit { int group; int32_t id; };
-    std::vector<Unit> units;
-    double wmax = 0;
-    for (int32_t i = 0; i < hp.num_atoms; i++) {
-        const int g = d->group ? (int) d->group[i] : 0;
-        if (g < 0) continue;
-        units.push_back({g, i});
-        wmax = std::max(wmax, std::fabs(d->weight[i]));
-    }
-    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
+    Sites S = sites_by_group(p->hp, d->group, d->num_groups, false, d->weight, true);
     const int G = d->num_groups;
     L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.num_groups = G;
     L.max_samples = d->max_samples;
-    L.num_particles = (int32_t) units.size();
-    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.num_particles = (int32_t) S.index.size();
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every);
     L.num_disp_classes = G * (G + 1) / 2; L.num_cur_classes = G * G;
     L.row_words = 1 + 3 * (L.num_disp_classes + L.num_cur_classes);
     L.words = (int64_t) (L.num_lags + 1) * L.row_words;
     L.ring_bytes = (int64_t) L.num_origins * (G * 6 + 1) * (int64_t) sizeof(long long);
     L.limit_position = d->limit_position > 0 ? pow2_at_least(d->limit_position) : 64.0;
     L.limit_velocity = d->limit_velocity > 0 ? pow2_at_least(d->limit_velocity) : 64.0;
-    L.weight_bound = wmax > 0 ? pow2_above(wmax) : 1.0;
-    const int head_room = 62 - ceil_log2((long long) units.size() + 1) - std::ilogb(L.weight_bound);
+    L.weight_bound = S.wmax > 0 ? pow2_above(S.wmax) : 1.0;
+    const int head_room = 62 - ceil_log2((long long) S.index.size() + 1) - std::ilogb(L.weight_bound);
     L.frac_bits_position = std::min(40, head_room - std::ilogb(L.limit_position));
     L.frac_bits_velocity = std::min(40, head_room - std::ilogb(L.limit_velocity));
     for (int q = 0; q < 2; q++) {
         const int f = q ? L.frac_bits_velocity : L.frac_bits_position;
         if (f < 8)
             return fail(p, VVHIP_ERR_INVALID, std::string("current: the ") + (q ? "velocity" : "position") + " sums would keep " + std::to_string(f) + " fraction bits (< 8) with " +
-                                              std::to_string(units.size()) + " particles, weights below " + std::to_string(L.weight_bound) + " and limit " +
+                                              std::to_string(S.index.size()) + " particles, weights below " + std::to_string(L.weight_bound) + " and limit " +
                                               std::to_string(q ? L.limit_velocity : L.limit_position) + ": lower the limit or scale the weights");
     }
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "current: a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
-                                              "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
-    for (const Unit& u : units) { N.index.push_back(u.id); N.weight.push_back(d->weight[u.id]); N.group.push_back((unsigned char) u.group); }
+    TRY(no_sums_across_shards(p, "current"));
+    N.index = std::move(S.index); N.weight = std::move(S.weight); N.group = std::move(S.group);
     N.two_level = p->current_two_level != 0;
     return recorder_install(p, &vvhip_plan::current, "current", N, d->interval);
 }
@@ -1066,12 +1134,10 @@ int vvhip_current_info(const vvhip_plan* p, vvhip_current_layout* out) { return 
 int vvhip_modes_start(vvhip_plan* p, const vvhip_modes_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
     if (!d) return fail(p, VVHIP_ERR_INVALID, "modes: null description");
-    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "modes: interval must be >= 1 step");
-    if (d->num_lags < 0 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "modes: num_lags must be in [0, 4096]");
-    if (d->origin_every < 1 || d->origin_every > std::max(1, d->num_lags)) return fail(p, VVHIP_ERR_INVALID, "modes: origin_every must be in [1, max(1, num_lags)]");
+    TRY(check_lags(p, "modes", d->interval, d->num_lags, d->origin_every, 0));
     if (d->num_groups < 1 || d->num_groups > vv::MODES_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "modes: num_groups must be in [1, 8]");
     if (d->num_modes < 1 || d->num_modes > 4096) return fail(p, VVHIP_ERR_INVALID, "modes: num_modes must be in [1, 4096]");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "modes: max_samples must be >= 1");
+    TRY(check_max_samples(p, "modes", d->max_samples));
     if (!(d->limit_position >= 0) || !std::isfinite(d->limit_position)) return fail(p, VVHIP_ERR_INVALID, "modes: limit_position must be finite and >= 0 (0: the default of 64 nm)");
     if (!d->weight) return fail(p, VVHIP_ERR_INVALID, "modes: weight must not be NULL");
     if (!d->modes) return fail(p, VVHIP_ERR_INVALID, "modes: modes must not be NULL");
@@ -1079,32 +1145,24 @@ int vvhip_modes_start(vvhip_plan* p, const vvhip_modes_desc* d) {
         for (int c = 0; c < 3; c++)
             if (d->modes[3 * k + c] < -4095 || d->modes[3 * k + c] > 4095)
                 return fail(p, VVHIP_ERR_INVALID, "modes: modes[" + std::to_string(k) + "][" + std::to_string(c) + "] = " + std::to_string(d->modes[3 * k + c]) + " is outside [-4095, 4095]");
-    const vv::HostPlan& hp = p->hp;
     TRY(check_groups(p, "modes", d->group, d->num_groups));
-    for (int32_t i = 0; i < hp.num_atoms; i++)
-        if (!std::isfinite(d->weight[i])) return fail(p, VVHIP_ERR_INVALID, "modes: weight[" + std::to_string(i) + "] is not finite");
+    TRY(check_weights(p, "modes", d->weight));
     // ---- the recorded sites, the layout, the fixed point and the mode kernel's work list, host only
     vvhip_plan::Modes N;
     vvhip_modes_layout& L = N.lay;
     const int G = d->num_groups, K = d->num_modes;
-    double wmax = 0;
-    for (int32_t i = 0; i < hp.num_atoms; i++) {
-        const int g = d->group ? (int) d->group[i] : 0;
-        if (g < 0) continue;
-        L.group_sites[g]++;
-        wmax = std::max(wmax, std::fabs(d->weight[i]));
-    }
-    int32_t first[vv::MODES_MAX_GROUPS + 1] = {0};
-    for (int g = 0; g < G; g++) first[g + 1] = first[g] + L.group_sites[g];
+    Sites S = sites_by_group(p->hp, d->group, G, false, d->weight, false);
+    std::copy(S.count, S.count + G, L.group_sites);
+    const int32_t* first = S.first;
     L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.num_groups = G; L.num_modes = K;
     L.max_samples = d->max_samples;
     L.num_particles = first[G];
-    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every);
     L.row_words = 1 + G * G * K;
     L.words = (int64_t) (L.num_lags + 1) * L.row_words;
     L.ring_bytes = (int64_t) L.num_origins * ((int64_t) G * K * 2 + 1) * (int64_t) sizeof(long long);
     L.limit_position = d->limit_position > 0 ? pow2_at_least(d->limit_position) : 64.0;
-    L.weight_bound = wmax > 0 ? pow2_above(wmax) : 1.0;
+    L.weight_bound = S.wmax > 0 ? pow2_above(S.wmax) : 1.0;
     L.frac_bits = 30 - std::ilogb(L.weight_bound);
     if (L.frac_bits < 8)
         return fail(p, VVHIP_ERR_INVALID, "modes: the terms would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with weights below " +
@@ -1114,20 +1172,8 @@ int vvhip_modes_start(vvhip_plan* p, const vvhip_modes_desc* d) {
     if (L.words > (1ll << 26))
         return fail(p, VVHIP_ERR_INVALID, "modes: the table would have " + std::to_string((long long) L.words) + " words (num_lags + 1 rows of 1 + G^2 K), above 2^26: "
                                           "record fewer lags, modes or groups");
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "modes: a sharded plan holds its own particles only: the shards' sums would have to be combined before the products "
-                                              "are formed (an exchange of the sums is not implemented); record on an unsharded plan");
-    N.index.resize((size_t) first[G]); N.weight.resize((size_t) first[G]);
-    {
-        int32_t next[vv::MODES_MAX_GROUPS];
-        std::copy(first, first + vv::MODES_MAX_GROUPS, next);
-        for (int32_t i = 0; i < hp.num_atoms; i++) {        // ascending by particle inside every group
-            const int g = d->group ? (int) d->group[i] : 0;
-            if (g < 0) continue;
-            N.index[(size_t) next[g]] = i; N.weight[(size_t) next[g]] = d->weight[i];
-            next[g]++;
-        }
-    }
+    TRY(no_sums_across_shards(p, "modes"));
+    N.index = std::move(S.index); N.weight = std::move(S.weight);
     N.modes.assign(d->modes, d->modes + 3 * (size_t) K);
     // the work list: per group its sites in runs of block_threads * sites_per_thread, the modes in runs of k_tile.  First choices (nothing
     // here has been scanned on a device yet: TUNING_LOG.md): blocks of 256 threads; 4 sites per thread and 32 modes per item where that
@@ -1166,20 +1212,14 @@ int vvhip_modes_info(const vvhip_plan* p, vvhip_modes_layout* out) { return reco
 int vvhip_contacts_start(vvhip_plan* p, const vvhip_contacts_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
     if (!d) return fail(p, VVHIP_ERR_INVALID, "contacts: null description");
-    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "contacts: interval must be >= 1 step");
-    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "contacts: num_lags must be in [1, 4096]");
-    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "contacts: origin_every must be in [1, num_lags]");
+    TRY(check_lags(p, "contacts", d->interval, d->num_lags, d->origin_every));
     if (d->num_groups < 1 || d->num_groups > vv::CONTACTS_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "contacts: num_groups must be in [1, 16]");
     if (d->num_classes < 1 || d->num_classes > vv::CONTACTS_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "contacts: num_classes must be in [1, 8]");
     if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "contacts: classes must not be NULL");
     if (!d->r_cut) return fail(p, VVHIP_ERR_INVALID, "contacts: r_cut must not be NULL");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "contacts: max_samples must be >= 1");
-    const vv::HostPlan& hp = p->hp;
+    TRY(check_max_samples(p, "contacts", d->max_samples));
     TRY(check_groups(p, "contacts", d->group, d->num_groups));
-    for (int32_t c = 0; c < d->num_classes; c++)
-        for (int q = 0; q < 2; q++)
-            if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= d->num_groups)
-                return fail(p, VVHIP_ERR_INVALID, "contacts: classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(d->classes[2 * c + q]) + " is outside [0, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_classes(p, "contacts", d->classes, d->num_classes, d->num_groups));
     for (int32_t c = 0; c < d->num_classes; c++)
         if (!(d->r_cut[c] > 0) || !std::isfinite(d->r_cut[c]))
             return fail(p, VVHIP_ERR_INVALID, "contacts: r_cut[" + std::to_string(c) + "] must be finite and > 0");
@@ -1190,11 +1230,9 @@ int vvhip_contacts_start(vvhip_plan* p, const vvhip_contacts_desc* d) {
     L.num_classes = d->num_classes; L.exclude_same_molecule = d->exclude_same_molecule != 0; L.continuous = d->continuous != 0;
     L.max_samples = d->max_samples; L.words = (int64_t) d->num_classes * d->num_lags * 4;
     L.rows_per_tile = p->contacts_rows_per_tile; L.words_per_item = p->contacts_words_per_item; L.skip_zero_words = p->contacts_skip_zero;
-    for (int32_t i = 0; i < hp.num_atoms; i++) {
-        const int g = d->group ? (int) d->group[i] : 0;
-        if (g >= 0) L.num_sites[g]++;
-    }
-    for (int g = 0; g < d->num_groups; g++) N.first[g + 1] = N.first[g] + L.num_sites[g];
+    Sites S = sites_by_group(p->hp, d->group, d->num_groups, L.exclude_same_molecule != 0, nullptr, false);
+    std::copy(S.count, S.count + d->num_groups, L.num_sites);
+    std::copy(S.first, S.first + vv::CONTACTS_MAX_GROUPS + 1, N.first);
     int64_t largest = 0;
     double longest = 0;
     for (int32_t c = 0; c < d->num_classes; c++) {
@@ -1210,33 +1248,14 @@ int vvhip_contacts_start(vvhip_plan* p, const vvhip_contacts_desc* d) {
     L.num_origins = G.num_origins; L.sample_words = G.sample_words;
     for (int32_t c = 0; c < d->num_classes; c++) L.class_words[c] = G.class_words[c];
     L.words_bytes = G.words_bytes; L.scratch_bytes = G.scratch_bytes; L.total_bytes = G.total_bytes;
-    if (L.num_origins > 1024)
-        return fail(p, VVHIP_ERR_INVALID, "contacts: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
-    if ((unsigned __int128) largest * (unsigned __int128) d->max_samples >= ((unsigned __int128) 1 << 62))
-        return fail(p, VVHIP_ERR_INVALID, "contacts: " + std::to_string((long long) largest) + " pairs per sample times max_samples = " + std::to_string((long long) d->max_samples) +
-                                          " reaches 2^62: a word could overflow; lower max_samples");
+    TRY(check_origins(p, "contacts", L.num_origins));
+    TRY(check_pair_count(p, "contacts", largest, d->max_samples, "word"));
     if (L.total_bytes > VVHIP_CONTACTS_MAX_BYTES)
         return fail(p, VVHIP_ERR_INVALID, "contacts: the recorder would hold " + std::to_string((long long) L.total_bytes) + " bytes (" + std::to_string(L.num_origins) + " slots of " +
                                           std::to_string((long long) L.sample_words * 8) + " bytes" + (L.continuous ? ", twice" : "") + "), above VVHIP_CONTACTS_MAX_BYTES = 2^32: raise origin_every, record fewer lags or fewer sites");
-    if (!rdf_box_holds(p->box, longest))
-        return fail(p, VVHIP_ERR_INVALID, "contacts: the cutoff " + std::to_string(longest) + " nm is above half the shortest edge of the box (" +
-                                          std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm): a pair would have more than one image in range");
-    if (cmm_sharded(p))
-        return fail(p, VVHIP_ERR_UNSUPPORTED, "contacts: a sharded plan holds its own particles' positions only, so the pairs across shards exist on no device; "
-                                              "a partial matrix is not recorded (run the analysis on an unsharded plan)");
-    N.index.resize((size_t) N.first[d->num_groups]);
-    if (L.exclude_same_molecule) N.mol.resize(N.index.size());
-    {
-        int32_t next[vv::CONTACTS_MAX_GROUPS];
-        std::copy(N.first, N.first + vv::CONTACTS_MAX_GROUPS, next);
-        for (int32_t i = 0; i < hp.num_atoms; i++) {      // ascending by particle inside every group
-            const int g = d->group ? (int) d->group[i] : 0;
-            if (g < 0) continue;
-            N.index[(size_t) next[g]] = i;
-            if (L.exclude_same_molecule) N.mol[(size_t) next[g]] = hp.mol_id[(size_t) i];
-            next[g]++;
-        }
-    }
+    TRY(check_half_box(p, "contacts", "the cutoff ", longest));
+    TRY(no_pairs_across_shards(p, "contacts", "matrix"));
+    N.index = std::move(S.index); N.mol = std::move(S.mol);
     // the work lists (vv_layout.h): per class, tile of rows and run of column words a block of the mask kernel; per class and run of
     // CONTACTS_CORR_PAIRS pairs of words a block of the correlate kernel for every slot
     N.mask_items.resize((size_t) vv::contacts_mask_items(G, L.num_classes, L.rows_per_tile, L.words_per_item, nullptr));
@@ -1264,111 +1283,54 @@ int vvhip_contacts_info(const vvhip_plan* p, vvhip_contacts_layout* out) { retur
 int vvhip_acf_start(vvhip_plan* p, const vvhip_acf_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;
     if (!d) return fail(p, VVHIP_ERR_INVALID, "acf: null description");
-    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "acf: interval must be >= 1 step");
-    if (d->num_lags < 1 || d->num_lags > 4096) return fail(p, VVHIP_ERR_INVALID, "acf: num_lags must be in [1, 4096]");
-    if (d->origin_every < 1 || d->origin_every > d->num_lags) return fail(p, VVHIP_ERR_INVALID, "acf: origin_every must be in [1, num_lags]");
+    TRY(check_lags(p, "acf", d->interval, d->num_lags, d->origin_every));
     if (d->mode != VVHIP_ACF_VELOCITY_PARTICLES && d->mode != VVHIP_ACF_VELOCITY_MOLECULES && d->mode != VVHIP_ACF_ORIENTATION)
         return fail(p, VVHIP_ERR_INVALID, "acf: mode must be VVHIP_ACF_VELOCITY_PARTICLES, VVHIP_ACF_VELOCITY_MOLECULES or VVHIP_ACF_ORIENTATION");
     if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "acf: num_groups must be in [1, 16]");
-    if (d->max_samples < 1) return fail(p, VVHIP_ERR_INVALID, "acf: max_samples must be >= 1");
+    TRY(check_max_samples(p, "acf", d->max_samples));
     if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "acf: limit must be finite and >= 0 (0: the default of 64 nm/ps)");
-    const bool orientation = d->mode == VVHIP_ACF_ORIENTATION, molecules = d->mode == VVHIP_ACF_VELOCITY_MOLECULES;
+    const bool orientation = d->mode == VVHIP_ACF_ORIENTATION;
     if (orientation && d->limit != 0) return fail(p, VVHIP_ERR_INVALID, "acf: limit must be 0 in orientation mode (a unit vector has no range to choose)");
     if (orientation && (d->num_pairs < 0 || (d->num_pairs > 0 && !d->pairs))) return fail(p, VVHIP_ERR_INVALID, "acf: orientation mode needs pairs[2 * num_pairs] and num_pairs >= 0");
     if (!orientation && (d->pairs || d->num_pairs != 0)) return fail(p, VVHIP_ERR_INVALID, "acf: pairs and num_pairs belong to orientation mode only");
     const vv::HostPlan& hp = p->hp;
-    if (!orientation) TRY(check_groups(p, "acf", d->group, d->num_groups));
-    for (int32_t u = 0; orientation && d->group && u < d->num_pairs; u++)
-        if (d->group[u] < -1 || d->group[u] >= d->num_groups)
-            return fail(p, VVHIP_ERR_INVALID, "acf: group[" + std::to_string(u) + "] = " + std::to_string((int) d->group[u]) + " is outside [-1, num_groups = " + std::to_string(d->num_groups) + ")");
+    TRY(check_groups(p, "acf", d->group, d->num_groups, orientation ? d->num_pairs : -1));      // (of the particles, or of the pairs)
     // ---- the units this plan records, the layout and the fixed point, host only
     vvhip_plan::Acf N;
     vvhip_acf_layout& L = N.lay;
-    N.grouped = d->group != nullptr;
-    auto group_of = [&](int32_t i) { return d->group ? (int) d->group[i] : 0; };      // (of a particle, or of a pair)
-    auto in_shard = [&](int32_t i) { return i >= hp.shard_begin && i < hp.shard_end; };
-    struct Unit { int group; int32_t id; };      // id: the particle, the molecule, or the pair
-    std::vector<Unit> units;                      // of this plan
-    long long described = 0;                      // U: the units the DESCRIPTION records, of the whole System
-    std::vector<std::vector<int32_t>> members;    // molecules: per molecule id its massive particles, ascending
-    bool cut = false;
-    if (orientation) {
-        for (int32_t u = 0; u < d->num_pairs; u++) {
-            const int32_t h = d->pairs[2 * u], t = d->pairs[2 * u + 1];
-            const std::string name = "acf: pair " + std::to_string(u) + " (head " + std::to_string(h) + ", tail " + std::to_string(t) + ")";
-            if (h < 0 || h >= hp.num_atoms || t < 0 || t >= hp.num_atoms) return fail(p, VVHIP_ERR_INVALID, name + " names a particle outside the System's " + std::to_string(hp.num_atoms));
-            if (h == t) return fail(p, VVHIP_ERR_INVALID, name + " has head = tail: no direction");
-            if (hp.mol_id[(size_t) h] != hp.mol_id[(size_t) t])
-                return fail(p, VVHIP_ERR_INVALID, name + " joins molecules " + std::to_string(hp.mol_id[(size_t) h]) + " and " + std::to_string(hp.mol_id[(size_t) t]) + ": no minimum image is taken, head and tail must lie in one molecule");
-            if (group_of(u) < 0) continue;
-            described++;
-            const int here = in_shard(h) + in_shard(t);
-            cut = cut || here == 1;
-            if (here == 2) units.push_back({group_of(u), u});
-        }
-    } else if (!molecules) {
-        for (int32_t i = 0; i < hp.num_atoms; i++) {
-            if (group_of(i) < 0) continue;
-            described++;
-            if (in_shard(i)) units.push_back({group_of(i), i});
-        }
-    } else {
-        int32_t nmol = 0;
-        for (int32_t i = 0; i < hp.num_atoms; i++) nmol = std::max(nmol, hp.mol_id[(size_t) i] + 1);
-        members.resize((size_t) nmol);
-        for (int32_t i = 0; i < hp.num_atoms; i++)
-            if (hp.masses[(size_t) i] > 0) members[(size_t) hp.mol_id[(size_t) i]].push_back(i);
-        for (int32_t m = 0; m < nmol; m++) {
-            const std::vector<int32_t>& mem = members[(size_t) m];
-            if (mem.empty()) continue;
-            int here = 0;
-            for (int32_t i : mem) {
-                here += in_shard(i);
-                if (group_of(i) != group_of(mem[0]))
-                    return fail(p, VVHIP_ERR_INVALID, "acf: molecule " + std::to_string(m) + " has massive particles in different groups (particle " + std::to_string(mem[0]) + ": " +
-                                                      std::to_string(group_of(mem[0])) + ", particle " + std::to_string(i) + ": " + std::to_string(group_of(i)) + ")");
-            }
-            cut = cut || (here != 0 && here != (int) mem.size());
-            if (group_of(mem[0]) < 0) continue;
-            described++;
-            if (here == (int) mem.size()) units.push_back({group_of(mem[0]), m});
-        }
+    N.grouped = d->group != nullptr; N.molecules = d->mode == VVHIP_ACF_VELOCITY_MOLECULES;
+    PlanUnits U;
+    if (!orientation) TRY(plan_units(p, "acf", d->group, N.molecules, U));
+    // orientation: the pairs in place of the particles.  Every pair is validated before its group is looked at
+    for (int32_t u = 0; orientation && u < d->num_pairs; u++) {
+        const int32_t h = d->pairs[2 * u], t = d->pairs[2 * u + 1];
+        const std::string name = "acf: pair " + std::to_string(u) + " (head " + std::to_string(h) + ", tail " + std::to_string(t) + ")";
+        if (h < 0 || h >= hp.num_atoms || t < 0 || t >= hp.num_atoms) return fail(p, VVHIP_ERR_INVALID, name + " names a particle outside the System's " + std::to_string(hp.num_atoms));
+        if (h == t) return fail(p, VVHIP_ERR_INVALID, name + " has head = tail: no direction");
+        if (hp.mol_id[(size_t) h] != hp.mol_id[(size_t) t])
+            return fail(p, VVHIP_ERR_INVALID, name + " joins molecules " + std::to_string(hp.mol_id[(size_t) h]) + " and " + std::to_string(hp.mol_id[(size_t) t]) + ": no minimum image is taken, head and tail must lie in one molecule");
+        const int g = d->group ? (int) d->group[u] : 0;
+        if (g < 0) continue;
+        U.described++;
+        const int here = (h >= hp.shard_begin && h < hp.shard_end) + (t >= hp.shard_begin && t < hp.shard_end);
+        U.cut = U.cut || here == 1;
+        if (here == 2) U.units.push_back({g, u});
     }
-    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.group < y.group; });      // by group, then by index
     L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.mode = d->mode; L.num_groups = d->num_groups;
     L.max_samples = d->max_samples;
-    L.num_units = (int32_t) units.size();
-    L.num_origins = (d->num_lags + d->origin_every - 1) / d->origin_every;
+    L.num_units = (int32_t) U.units.size();
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every);
     L.row_words = orientation ? 5 : 4;
     L.words = (int64_t) L.num_groups * L.num_lags * L.row_words;
     L.limit = orientation ? 1.0 : d->limit > 0 ? pow2_at_least(d->limit) : 64.0;
     L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
-    const long long max_origins = samples_plus(L.max_samples, L.origin_every - 1) / L.origin_every;
-    L.frac_bits = std::min(40, 62 - ceil_log2(described + 1) - ceil_log2(max_origins + 1) - 2 * std::ilogb(L.limit));
-    if (L.frac_bits < 8)
-        return fail(p, VVHIP_ERR_INVALID, "acf: the sums would keep " + std::to_string(L.frac_bits) + " fraction bits (< 8) with " + std::to_string(described) + " units, max_samples = " +
-                                          std::to_string((long long) L.max_samples) + ", origin_every = " + std::to_string(L.origin_every) + " and limit " + std::to_string(L.limit) +
-                                          ": lower max_samples or the limit");
-    if (L.num_origins > 1024)
-        return fail(p, VVHIP_ERR_INVALID, "acf: num_origins = ceil(num_lags / origin_every) = " + std::to_string(L.num_origins) + " is above 1024: raise origin_every");
-    if (molecules && cut)
+    TRY(units_frac_bits(p, "acf", U.described, L.max_samples, L.origin_every, L.limit, &L.frac_bits));
+    TRY(check_origins(p, "acf", L.num_origins));
+    if (N.molecules && U.cut)
         return fail(p, VVHIP_ERR_UNSUPPORTED, "acf: the particle shard cuts a molecule: its centre-of-mass velocity needs particles of another shard");
-    if (orientation && cut)
+    if (orientation && U.cut)
         return fail(p, VVHIP_ERR_UNSUPPORTED, "acf: the particle shard cuts a recorded pair: its vector needs a particle of another shard (shard on molecule boundaries)");
-    for (const Unit& u : units) {
-        if (N.grouped) N.group.push_back((unsigned char) u.group);
-        if (orientation) { N.index.push_back(d->pairs[2 * u.id] - hp.shard_begin); N.index.push_back(d->pairs[2 * u.id + 1] - hp.shard_begin); continue; }
-        if (!molecules) { N.index.push_back(u.id - hp.shard_begin); continue; }
-        N.first.push_back((int32_t) N.index.size());
-        double M = 0;
-        for (int32_t i : members[(size_t) u.id]) {
-            N.index.push_back(i - hp.shard_begin); N.weight.push_back(hp.masses[(size_t) i]);
-            M = M + hp.masses[(size_t) i];
-        }
-        N.total.push_back(M);
-    }
-    if (molecules) N.first.push_back((int32_t) N.index.size());
-    if (!molecules && !orientation && !N.grouped && L.num_units == hp.shard_end - hp.shard_begin) N.index.clear();      // (every particle of the shard, in order: the thread's own index)
+    fill_units(hp, N, U, orientation ? d->pairs : nullptr);
     return recorder_install(p, &vvhip_plan::acf, "acf", N, d->interval);
 }
 int vvhip_acf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_acf_counts* out, int32_t reset) {

@@ -366,6 +366,10 @@ struct vvhip_plan {
     //   bytes()                of d_words
     //   alloc(s, &asked)       d_words, zeroed on stream s, and dev from the host tables; a request that fails leaves its bytes in `asked`
     //   reset(s)               what *_read's reset enqueues
+    // Stated once below them: Units, the unit tables and all of the above for the two recorders of per-unit vectors (msd, acf); Slotted,
+    // "no slot holds a sample" and the reset for the three whose ring slots carry a word of their own (current, modes, contacts).  Rdf and
+    // Contacts keep their own index / mol / stride(): a shared base would cost more lines than the four it saves.  The host tables come
+    // from vv_observe.cpp's "shared pieces of a start".
     struct Recorder {
         bool on = false, described = false;
         Schedule when;                            // (linear)
@@ -375,6 +379,20 @@ struct vvhip_plan {
         static hipError_t put(vv::DevBuf<T>& buf, const std::vector<U>& v, size_t* asked, size_t floor = 16) {
             *asked = std::max(floor, v.size() * sizeof(U));
             return vv::upload(buf, v, floor);
+        }
+    };
+    // A recorder D whose ring slots have a word each that is -1 while the slot holds no sample: D::slots() = {first word, words} of them in
+    // d_words, D::front_words() what lies in front of the ring.  alloc() ends with empty_slots(); a reset zeroes the front and empties the
+    // slots, so the ring may keep its bits.  (No slots -- density modes without lags --: nothing is enqueued for them.)
+    template <class D>
+    struct Slotted : Recorder {
+        hipError_t empty_slots(hipStream_t s) {
+            const std::pair<size_t, size_t> w = static_cast<const D*>(this)->slots();
+            return w.second == 0 ? hipSuccess : hipMemsetAsync(d_words.get() + w.first, 0xFF, w.second * sizeof(long long), s);
+        }
+        hipError_t reset(hipStream_t s) {
+            const hipError_t e = hipMemsetAsync(d_words.get(), 0, static_cast<const D*>(this)->front_words() * sizeof(long long), s);
+            return e == hipSuccess ? empty_slots(s) : e;
         }
     };
     // Profiles (vvhip_profile_*; vv_dev_profile.inc), scheduled by cur.step_count
@@ -397,24 +415,26 @@ struct vvhip_plan {
         }
         hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, bytes(), s); }
     } profile;
-    // Mean-squared displacements (vvhip_msd_*; vv_dev_msd.inc), scheduled by cur.step_count.  The unit tables are built from the plan's
-    // molecules when the recorder starts: units ordered by group, then by particle / molecule index
-    struct Msd : Recorder {
-        bool grouped = false;
-        vvhip_msd_layout lay{};
-        std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending
+    // A recorder of one vector per unit, of layout L with Head count words: mean-squared displacements (vvhip_msd_*; vv_dev_msd.inc) and
+    // autocorrelations (vvhip_acf_*; vv_dev_acf.inc), scheduled by cur.step_count.  The unit tables are built from the plan's molecules
+    // when the recorder starts (vv_observe.cpp: plan_units, fill_units): units ordered by group, then by particle / molecule / pair index
+    template <class L, int Head>
+    struct Units : Recorder {
+        bool grouped = false, molecules = false;  // molecules: the start's mode is the recorder's molecule mode (first, weight, total exist)
+        L lay{};
+        std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending; orientation: head, tail per unit
         std::vector<int32_t> first;               // molecules: [num_units + 1] offsets into index / weight
         std::vector<double> weight, total;        // molecules: the members' masses; [num_units] their sums M in the members' order
         std::vector<unsigned char> group;         // [num_units] (grouped)
         struct Dev { vv::DevBuf<int32_t> index, first; vv::DevBuf<double> weight, total; vv::DevBuf<unsigned char> group; } dev;
-        static constexpr int kHead = vv::MSD_HEAD;          // d_words: [kHead + lay.words] counts, floor and table, then the ring of origins
+        static constexpr int kHead = Head;                  // d_words: [kHead + lay.words] counts, floor and table, then the ring of origins
         size_t table_offset() const { return kHead; }
         int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
         size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
         hipError_t alloc(hipStream_t s, size_t* asked) {
             hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
             if (e == hipSuccess && !index.empty()) e = put(dev.index, index, asked);
-            if (lay.mode == VVHIP_MSD_MOLECULES) {
+            if (molecules) {
                 if (e == hipSuccess) e = put(dev.first, first, asked);
                 if (e == hipSuccess) e = put(dev.weight, weight, asked);
                 if (e == hipSuccess) e = put(dev.total, total, asked);
@@ -424,7 +444,10 @@ struct vvhip_plan {
         }
         // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
         hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, (size_t) (kHead + lay.words) * sizeof(long long), s); }
-    } msd;
+    };
+    using Msd = Units<vvhip_msd_layout, vv::MSD_HEAD>;
+    using Acf = Units<vvhip_acf_layout, vv::ACF_HEAD>;
+    Msd msd;
     // Radial distribution functions (vvhip_rdf_*; vv_dev_rdf.inc), scheduled by cur.step_count.  The site list (ordered by group, inside a
     // group ascending by particle), the sites' molecules and the pair kernel's work items are built when the recorder starts
     struct Rdf : Recorder {
@@ -453,7 +476,7 @@ struct vvhip_plan {
     } rdf;
     // Collective current correlations (vvhip_current_*; vv_dev_current.inc), scheduled by cur.step_count.  The compact list of the recorded
     // particles, ordered by group, then by index, is built when the recorder starts
-    struct Current : Recorder {
+    struct Current : Slotted<Current> {
         bool two_level = false;                   // vvhip_plan::current_two_level as the start found it
         vvhip_current_layout lay{};
         std::vector<int32_t> index;               // [num_particles] the recorded particles
@@ -471,10 +494,7 @@ struct vvhip_plan {
         size_t sums_words() const { return (size_t) lay.num_groups * 6; }
         size_t front_words() const { return (size_t) kHead + sums_words() + (size_t) lay.words; }      // what a reset zeroes
         size_t bytes() const { return front_words() * sizeof(long long) + (size_t) lay.ring_bytes; }
-        // no slot holds a sample: the slots' words, the allocation's last num_origins, are -1
-        hipError_t empty_slots(hipStream_t s) {
-            return hipMemsetAsync(d_words.get() + bytes() / sizeof(long long) - lay.num_origins, 0xFF, (size_t) lay.num_origins * sizeof(long long), s);
-        }
+        std::pair<size_t, size_t> slots() const { return {bytes() / sizeof(long long) - lay.num_origins, (size_t) lay.num_origins}; }      // the allocation's last words
         hipError_t alloc(hipStream_t s, size_t* asked) {
             hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
             if (e == hipSuccess) e = put(dev.index, index, asked);
@@ -483,16 +503,11 @@ struct vvhip_plan {
             if (e == hipSuccess && two_level) e = vv::zeros(dev.slabs, *asked = slab_words() * sizeof(long long), s);
             return e == hipSuccess ? empty_slots(s) : e;
         }
-        // (head, sums and table to zero, the slots' words to -1, so the ring may keep its bits)
-        hipError_t reset(hipStream_t s) {
-            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
-            return e == hipSuccess ? empty_slots(s) : e;
-        }
     } current;
     // Density modes for the structure factors (vvhip_modes_*; vv_dev_modes.inc), scheduled by cur.step_count.  The compact list of the
     // recorded sites (ordered by group, then by index), the modes and the mode kernel's work items are built when the recorder starts;
     // lay holds the shape the items were built for (sites_per_thread, k_tile, block_threads)
-    struct Modes : Recorder {
+    struct Modes : Slotted<Modes> {
         vvhip_modes_layout lay{};
         std::vector<int32_t> index;               // [num_particles] the recorded sites
         std::vector<double> weight;               // beside index
@@ -510,11 +525,7 @@ struct vvhip_plan {
         size_t sums_words() const { return (size_t) lay.num_groups * (size_t) lay.num_modes * 2; }
         size_t front_words() const { return (size_t) kHead + sums_words() + (size_t) lay.words; }      // what a reset zeroes
         size_t bytes() const { return front_words() * sizeof(long long) + (size_t) lay.ring_bytes; }
-        // no slot holds a sample: the slots' words, the allocation's last num_origins, are -1
-        hipError_t empty_slots(hipStream_t s) {
-            if (lay.num_origins == 0) return hipSuccess;
-            return hipMemsetAsync(d_words.get() + bytes() / sizeof(long long) - lay.num_origins, 0xFF, (size_t) lay.num_origins * sizeof(long long), s);
-        }
+        std::pair<size_t, size_t> slots() const { return {bytes() / sizeof(long long) - lay.num_origins, (size_t) lay.num_origins}; }      // the allocation's last words
         hipError_t alloc(hipStream_t s, size_t* asked) {
             hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
             if (e == hipSuccess) e = vv::zeros(dev.turns, *asked = std::max<size_t>(16, (size_t) lay.scratch_bytes), s);
@@ -524,16 +535,11 @@ struct vvhip_plan {
             if (e == hipSuccess) e = put(dev.items, items, asked, 32);
             return e == hipSuccess ? empty_slots(s) : e;
         }
-        // (head, sums and table to zero, the slots' words to -1, so the ring may keep its bits)
-        hipError_t reset(hipStream_t s) {
-            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
-            return e == hipSuccess ? empty_slots(s) : e;
-        }
     } modes;
     // Contact lifetime correlations (vvhip_contacts_*; vv_dev_contacts.inc), scheduled by cur.step_count.  The site list (ordered by group,
     // inside a group ascending by particle), the sites' molecules and the two kernels' work items are built when the recorder starts;
     // lay holds the shape the mask items were built for (rows_per_tile, words_per_item)
-    struct Contacts : Recorder {
+    struct Contacts : Slotted<Contacts> {
         vvhip_contacts_layout lay{};
         vv::ContactsLayout geo{};                 // where every word lies (vv_layout.h)
         int32_t first[vv::CONTACTS_MAX_GROUPS + 1] = {0};      // where a group's sites start in the list
@@ -552,8 +558,7 @@ struct vvhip_plan {
         int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
         size_t front_words() const { return (size_t) kHead + (size_t) lay.words; }      // what a reset zeroes
         size_t bytes() const { return (size_t) geo.words_bytes; }
-        // no slot holds a sample: the ord words are -1
-        hipError_t empty_slots(hipStream_t s) { return hipMemsetAsync(d_words.get() + front_words(), 0xFF, (size_t) geo.ord_words * sizeof(long long), s); }
+        std::pair<size_t, size_t> slots() const { return {front_words(), (size_t) geo.ord_words}; }      // the ord words, right behind the front
         hipError_t alloc(hipStream_t s, size_t* asked) {
             hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
             if (e == hipSuccess) e = vv::zeros(dev.scratch, *asked = std::max<size_t>(16, 3 * (size_t) stride() * sizeof(double)), s);
@@ -564,40 +569,8 @@ struct vvhip_plan {
             if (e == hipSuccess) e = put(dev.corr_items, corr_items, asked, 32);
             return e == hipSuccess ? empty_slots(s) : e;
         }
-        // (head and table to zero, the ord words to -1, so the rings may keep their bits)
-        hipError_t reset(hipStream_t s) {
-            const hipError_t e = hipMemsetAsync(d_words.get(), 0, front_words() * sizeof(long long), s);
-            return e == hipSuccess ? empty_slots(s) : e;
-        }
     } contacts;
-    // Autocorrelations of a per-unit vector (vvhip_acf_*; vv_dev_acf.inc), scheduled by cur.step_count: the MSD recorder's sibling.  The
-    // unit tables are built when the recorder starts: units ordered by group, then by particle / molecule / pair index
-    struct Acf : Recorder {
-        bool grouped = false;
-        vvhip_acf_layout lay{};
-        std::vector<int32_t> index;               // particles: shard-relative index per unit, empty: unit u is particle u; molecules: the member lists, each ascending; orientation: head, tail per unit
-        std::vector<int32_t> first;               // molecules: [num_units + 1] offsets into index / weight
-        std::vector<double> weight, total;        // molecules: the members' masses; [num_units] their sums M in the members' order
-        std::vector<unsigned char> group;         // [num_units] (grouped)
-        struct Dev { vv::DevBuf<int32_t> index, first; vv::DevBuf<double> weight, total; vv::DevBuf<unsigned char> group; } dev;
-        static constexpr int kHead = vv::ACF_HEAD;          // d_words: [kHead + lay.words] counts, floor and table, then the ring of origins
-        size_t table_offset() const { return kHead; }
-        int32_t stride() const { return (lay.num_units + 15) / 16 * 16; }
-        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long) + (size_t) lay.ring_bytes; }
-        hipError_t alloc(hipStream_t s, size_t* asked) {
-            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
-            if (e == hipSuccess && !index.empty()) e = put(dev.index, index, asked);
-            if (lay.mode == VVHIP_ACF_VELOCITY_MOLECULES) {
-                if (e == hipSuccess) e = put(dev.first, first, asked);
-                if (e == hipSuccess) e = put(dev.weight, weight, asked);
-                if (e == hipSuccess) e = put(dev.total, total, asked);
-            }
-            if (e == hipSuccess && grouped) e = put(dev.group, group, asked);
-            return e;
-        }
-        // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
-        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, (size_t) (kHead + lay.words) * sizeof(long long), s); }
-    } acf;
+    Acf acf;                                      // (Units, beside the MSD recorder above)
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -686,6 +659,8 @@ inline size_t sizeof_mixed(int prec) { return prec == VVHIP_SINGLE ? 4 : 8; }
 inline int acc_stride(const vvhip_plan* p) { return (p->hp.params.cos_acceleration != 0 ? vv::NUM_ACC : 4) * vv::ACC_SLOTS; }
 inline bool periodic_b(const vvhip_plan* p) { return p->hp.per.enabled && p->periodic_kernels && p->periodic_b; }
 inline bool cos_on(const vvhip_plan* p) { return p->hp.params.cos_acceleration != 0; }
+// the positions' low halves as a kernel argument: mixed precision only
+inline void* posq_corr(const vvhip_plan* p) { return p->hp.precision == VVHIP_MIXED ? p->buf.posq_correction : nullptr; }
 // No source of extra forces in a step: its kick adds whatever forceExtra still holds (see Cursor::fextra_virtual)
 inline uint32_t stale_fextra(const vvhip_plan* p) { return (p->cur.fextra_dirty || p->fextra_external) ? vv::A_FE_LOAD : 0u; }
 inline bool shake_on(const vvhip_plan* p) { return !p->hp.slot_shake.empty(); }
@@ -728,10 +703,10 @@ int run_application_fused(vvhip_plan* p, const ThermoApp& t, uint32_t random_ind
 int step_begin(vvhip_plan* p);
 int step_done(vvhip_plan* p);
 int quiesce(vvhip_plan* p, const char* who, bool sync, bool drop);
-int acf_velocities_rewritten(vvhip_plan* p);      // vvhip_set_velocities_to_temperature: a velocity autocorrelation recorder's origins so far are dead
-int msd_positions_rewritten(vvhip_plan* p);      // vvhip_barostat_scale / _restore: an MSD recorder's origins so far are dead
-int modes_positions_rewritten(vvhip_plan* p);    // ... and a density-mode recorder's
-int current_positions_rewritten(vvhip_plan* p);  // ... and a current recorder's
+// The positions (vvhip_barostat_scale / _restore) or the velocities (vvhip_set_velocities_to_temperature) were rewritten outside the steps:
+// the origins that the recorders of that quantity stored so far are dead
+enum class Rewrote { POSITIONS, VELOCITIES };
+int origins_dead(vvhip_plan* p, Rewrote what);
 // One of the device work items that hang on the plan's step counter.  A new one is a descriptor in riders() with its enqueue function and its
 // entry points: the step hooks, the graph keys (vv_run.cpp) and the recovery (recovery_items) walk the list.
 struct Rider {

@@ -400,6 +400,7 @@ def _load():
         "vvhip_debug_read_accumulators": [vp, P(dbl * 4), C.c_int],
         "vvhip_debug_set_scales": [vp, P(dbl * 4)],
         "vvhip_debug_old_delta": [vp, P(vp)], "vvhip_debug_live_buffers": [P(C.c_int64), P(C.c_int64)],
+        "vvhip_debug_recorder_digest": [vp, C.c_char_p, P(C.c_uint64)],
         "vvhip_set_trace": [vp, C.c_int],
         "vvhip_debug_span": [vp, C.c_int, C.c_uint32, C.c_int, P(C.c_double * 8)],
         "vvhip_debug_timestamps": [vp, C.c_uint32, C.c_int, P(C.c_longlong * 128)],
