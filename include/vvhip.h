@@ -1131,6 +1131,98 @@ int vvhip_acf_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words,
 int vvhip_acf_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_acf_info(const vvhip_plan* plan, vvhip_acf_layout* out);
+/* ---------------------------------------------------------------- self van Hove functions accumulated on the device
+ * The distribution of single-particle displacements G_s(r, t), of which the MSD keeps the second moment only: from it follow the
+ * non-Gaussian parameter alpha_2(t), the self-intermediate scattering function F_s(k, t) and the self-overlap Q_s(t), the standard measures
+ * of dynamic heterogeneity and of the cage-to-diffusion crossover that the example scripts' logarithmic GroReporter frames exist to cover.
+ * A stand-alone host needs float64 frames for it, 24 B per unit and sample, and a histogram per lag over O(samples x origins x N) pairs; on
+ * the device it is an accumulating table of a few MB however long the run.  After every full step whose count is a multiple of `interval`
+ * -- counted exactly as for the other riders; a sample "after step k" is enqueued behind that step's autocorrelation sample, the eleventh
+ * and last rider -- the step entry point enqueues one accumulating kernel (csrc/vv_dev_vanhove.inc) and a one-thread kernel that advances
+ * the sample ordinal: two launches, no memset, no host work.  Inside a captured graph both are part of the graph and the steps that take a
+ * sample are part of the graph-cache key.  The recorder reads posq and posqCorrection and writes its own words, nothing else; a plan that
+ * never starts one launches what it launched before and allocates nothing.
+ * Units.  VVHIP_VANHOVE_PARTICLES and VVHIP_VANHOVE_MOLECULES are the MSD's two modes, word for word: the float64 position, the sequential
+ * centre-of-mass sum in ascending particle index with M summed in the same order, the group of a molecule, the refusals.
+ * Schedule.  The MSD's, word for word: ordinal j, every E-th sample an origin in slot (j / E) mod num_origins, num_origins = ceil(num_lags /
+ * E), row l the lag of (l + 1) * interval steps; at sample j every origin k E contributes to row l = j - k E - 1 provided origin_floor <=
+ * k E < j and j - k E <= num_lags.  Accumulation comes first, the store second.
+ * Displacement.  Delta_a = c_a(now) - c_a(origin) in float64.  A pair with any Delta_a that is NaN or has |Delta_a| >= limit is out of
+ * range: it is left out of every word and adds 1 to out_of_range.  limit is in nm, rounded up to a power of two; 0 takes the default of 16.
+ * r2 = (Delta_x * Delta_x + Delta_y * Delta_y) + Delta_z * Delta_z, in this order, without contraction.
+ * Bins.  edges[num_bins + 1] in nm, finite, strictly ascending, edges[0] >= 0: uniform or logarithmic or anything else.  The host forms
+ * e2[k] = edges[k] * edges[k]; a pair adds the integer 1 to bin b where e2[b] <= r2 < e2[b + 1], decided by comparisons against e2 alone (no
+ * square root decides a bin); a pair with r2 < e2[0] adds 1 to `below`, one with r2 >= e2[num_bins] adds 1 to `beyond`; both still enter
+ * the moments.
+ * Table: int64 head[num_groups][num_lags][6], then int64 hist[num_groups][num_lags][num_bins]; words = head_words + hist_words, at most 2^22
+ * (32 MiB).  The six head words: pairs, below, beyond, sum r2 as llrint(r2 * 2^frac2_bits), and sum r2 * r2 in two words: with x = (r2 * r2)
+ * * 2^r4_hi_bits,  hi = floor(x),  lo = llrint((x - hi) * 2^r4_lo_bits)  -- every step exact or correctly rounded in float64, so device and
+ * host agree bit for bit --, value = (hi + lo * 2^-r4_lo_bits) * 2^-r4_hi_bits.  For every (group, lag): below + sum_b hist + beyond ==
+ * pairs.  With cu = ceil_log2(U + 1), U the recorded units of the WHOLE System in that mode, and co = ceil_log2(ceil(max_samples / E) + 1):
+ *     frac2_bits  = min(40, 62 - cu - co - 2 log2(limit) - 2)        (r2 < 3 limit^2 < 2^(2 log2(limit) + 2))
+ *     r4_hi_bits  = min(40, 62 - cu - co - 4 log2(limit) - 4)        (r2 r2 < 9 limit^4 < 2^(4 log2(limit) + 4))
+ *     r4_lo_bits  = min(52, 61 - cu - co)                            (lo <= 2^r4_lo_bits)
+ * so that no word can overflow within max_samples samples.  Past max_samples a sample adds nothing, stores no origin and counts as
+ * dropped.  Every word is an integer sum: the table is the same bits for any grid, block size, unit order, add path or shard split; a
+ * sharded plan records the units of its own shard and the shards' tables add to the unsharded one.
+ * What rewrites positions outside the steps, and recovery: as for the MSD.  vvhip_barostat_scale / _restore set origin_floor to the current
+ * ordinal; vvhip_checkpoint_load is refused while a recorder runs; the rider's recovery words are the WHOLE allocation, (4 + words) * 8 B +
+ * ring_bytes with ring_bytes = num_origins x 3 x stride x 8 B, stride = num_units rounded up to 16. */
+#define VVHIP_VANHOVE_PARTICLES 0
+#define VVHIP_VANHOVE_MOLECULES 1
+#define VVHIP_VANHOVE_MAX_WORDS (1ll << 22)
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096: row l is the lag of (l + 1) * interval steps */
+    int32_t origin_every;           /* E, 1 .. num_lags: every E-th sample is stored as an origin */
+    int32_t mode;                   /* VVHIP_VANHOVE_PARTICLES, VVHIP_VANHOVE_MOLECULES */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t num_bins;               /* 1 .. 1024 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: not recorded; NULL: everything in group 0 */
+    const double* edges;            /* [num_bins + 1] nm: finite, strictly ascending, edges[0] >= 0 */
+    int64_t max_samples;            /* >= 1 */
+    double limit;                   /* nm: a displacement component at or beyond it is out of range; rounded up to a power of two; 0: 16 */
+} vvhip_vanhove_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset (at most max_samples): the next sample's ordinal */
+    int64_t dropped;                /* samples that were due past max_samples: nothing was added or stored for them */
+    int64_t out_of_range;           /* unit-pairs left out of every word */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+} vvhip_vanhove_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, mode, num_groups;
+    int32_t num_units;              /* units this plan records (those of its shard) */
+    int32_t num_origins;            /* ceil(num_lags / origin_every) */
+    int32_t num_bins;
+    int32_t frac2_bits;             /* sum r2 = word * 2^-frac2_bits */
+    int32_t r4_hi_bits, r4_lo_bits; /* sum r2 r2 = (hi + lo * 2^-r4_lo_bits) * 2^-r4_hi_bits */
+    int64_t max_samples;
+    int64_t words;                  /* head_words + hist_words */
+    int64_t head_words;             /* num_groups * num_lags * 6 */
+    int64_t hist_words;             /* num_groups * num_lags * num_bins */
+    int64_t ring_bytes;             /* num_origins * 3 * stride * 8 */
+    int64_t start_step;             /* the plan's step count at vvhip_vanhove_start */
+    double limit;                   /* as applied */
+} vvhip_vanhove_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, an unknown mode, num_groups outside 1 ..
+ * 16, max_samples < 1, a limit that is negative or not finite, a group entry outside -1 .. num_groups - 1; num_bins outside 1 .. 1024,
+ * edges NULL, an edge that is not finite or negative, edges that do not ascend strictly (VVHIP_ERR_INVALID naming the argument); in
+ * molecule mode a molecule whose massive particles lie in different groups (VVHIP_ERR_INVALID naming it); frac2_bits below 8, r4_hi_bits
+ * below 0 (VVHIP_ERR_INVALID naming the exponent); more than VVHIP_VANHOVE_MAX_WORDS words (VVHIP_ERR_INVALID with the count); num_origins
+ * above 1024 (VVHIP_ERR_INVALID); in molecule mode a shard that cuts a molecule (VVHIP_ERR_UNSUPPORTED); an unbound plan; inside a graph
+ * capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description that passes the checks in
+ * front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_vanhove_info answers for it, for sizing. */
+int vvhip_vanhove_start(vvhip_plan* plan, const vvhip_vanhove_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words, head then hist (words_out may be NULL with
+ * capacity_words = 0; a capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the
+ * ordinal at 0 with no live origin: the step schedule continues without gap or repeat. */
+int vvhip_vanhove_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_vanhove_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and ring are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_vanhove_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_vanhove_info(const vvhip_plan* plan, vvhip_vanhove_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the
@@ -1509,12 +1601,13 @@ int vvhip_debug_old_delta(vvhip_plan* plan, void** device_ptr);                 
  * everything without watching the device's free memory, which moves under other processes' work.  Host only. */
 int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes);
 /* FNV-1a 64 over the host tables that the last accepted vvhip_<name>_start built, name = "profile", "msd", "rdf", "current", "modes",
- * "contacts" or "acf"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
+ * "contacts", "acf" or "vanhove"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
  * Per vector its size as uint64, then its bytes; flags as one byte; in this order:
  *   profile   grouped, index, group, mass                 msd, acf   grouped, index, first, weight, total, group
  *   rdf       index, mol, items, max_jsites (int32)       current    two_level, index, weight, group
  *   modes     index, weight, modes, items                 contacts   first[0 .. 16], index, mol, mask_items, corr_items, then the fields
- *                                                                    of the word layout (csrc/vv_layout.h: ContactsLayout) one by one */
+ *                                                                    of the word layout (csrc/vv_layout.h: ContactsLayout) one by one
+ *   vanhove   grouped, index, first, weight, total, group (as msd), then e2 */
 int vvhip_debug_recorder_digest(const vvhip_plan* plan, const char* name, uint64_t* out);
 
 #ifdef __cplusplus

@@ -549,4 +549,31 @@ struct AcfArgs {
     double scale, limit;            // 2^frac_bits; the velocity modes: |component| at or beyond it is bad
 };
 
+// Self van Hove sample (vv_dev_vanhove.inc, include/vvhip.h: vvhip_vanhove_* states the units, the schedule, the bins and the moments).  The
+// sample ordinal and the origin floor are read from the device-side words, as for the MSD.  One allocation: count words, head[G][L][6],
+// hist[G][L][num_bins], ring.
+enum { VANHOVE_SAMPLES = 0, VANHOVE_DROPPED = 1, VANHOVE_OUT_OF_RANGE = 2, VANHOVE_FLOOR = 3, VANHOVE_HEAD = 4 };      // the words in front of the table
+enum { VANHOVE_PAIRS = 0, VANHOVE_BELOW = 1, VANHOVE_BEYOND = 2, VANHOVE_R2 = 3, VANHOVE_R4_HI = 4, VANHOVE_R4_LO = 5, VANHOVE_ROW = 6 };   // the words of head[g][l]
+constexpr int VANHOVE_MAX_BINS = 1024;
+constexpr int VANHOVE_LDS_WORDS = 4096;      // the block's private histogram: 32-bit words, 16 KiB (num_bins x the groups that fit; vv_dev_vanhove.inc)
+struct VanHoveArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // as MsdArgs: particles [n] or null; molecules: the member lists
+    const int32_t* first;           // molecules: [n + 1]
+    const double* weight;           // molecules: the mass of every member, beside index
+    const double* total;            // molecules: [n] M
+    const unsigned char* group;     // [n] group of unit u (GROUPED kernels only); ascending in u
+    const double* e2;               // [num_bins + 1] the squared edges
+    long long* words;               // [VANHOVE_HEAD + head_words + hist_words]
+    double* ring;                   // [num_origins][3][stride] the origins' positions, behind the table in the same allocation
+    int64_t max_samples;
+    int64_t head_words;             // num_groups * num_lags * 6: where hist starts behind the count words
+    int32_t n, stride;              // recorded units; n rounded up to 16
+    int32_t num_lags, origin_every;
+    int32_t num_origins, num_bins;  // ceil(num_lags / origin_every); 1 .. VANHOVE_MAX_BINS
+    int32_t wave_reduce, lds_groups;// 1: a wave whose lanes share a group adds its six head words once; groups whose bins the block's LDS histogram holds, 0: every increment is a global add
+    double scale2, scale_hi, scale_lo, limit;      // 2^frac2_bits, 2^r4_hi_bits, 2^r4_lo_bits; |delta| at or beyond limit is out of range
+};
+
 }  // namespace vv

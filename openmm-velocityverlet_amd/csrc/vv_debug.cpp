@@ -297,6 +297,10 @@ int vvhip_debug_recorder_digest(const vvhip_plan* p, const char* name, uint64_t*
     } else if (which == "acf") {
         described = p->acf.described;
         digest_units(f, p->acf);
+    } else if (which == "vanhove") {
+        described = p->vanhove.described;
+        digest_units(f, p->vanhove);
+        f.vec(p->vanhove.e2);
     } else if (which == "rdf") {
         const vvhip_plan::Rdf& R = p->rdf;
         described = R.described;

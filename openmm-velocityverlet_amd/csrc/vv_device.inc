@@ -25,3 +25,4 @@
 #include "vv_dev_modes.inc"
 #include "vv_dev_contacts.inc"
 #include "vv_dev_acf.inc"
+#include "vv_dev_vanhove.inc"

@@ -618,6 +618,29 @@ hipError_t launch_acf_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_acf_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+template <bool MOLECULES, bool GROUPED>
+static auto pick_vanhove(int precision, bool lds) {
+    return lds ? VV_PICK(precision, vv_kernel_vanhove, MOLECULES, GROUPED, true) : VV_PICK(precision, vv_kernel_vanhove, MOLECULES, GROUPED, false);
+}
+hipError_t launch_vanhove(int precision, const VanHoveArgs& a, int block_threads, int grid_cap, hipStream_t s) {
+    if (block_threads < 64 || block_threads > 512 || block_threads % 64) return hipErrorInvalidValue;
+    // what the kernel relies on: the ring's columns hold the units, the edges fit its LDS copy, the groups it counts in LDS fit the histogram
+    if (a.n < 0 || a.stride < a.n || a.num_origins < 1 || a.num_bins < 1 || a.num_bins > VANHOVE_MAX_BINS || !a.e2) return hipErrorInvalidValue;
+    if (a.lds_groups < 0 || (long long) a.lds_groups * a.num_bins > VANHOVE_LDS_WORDS) return hipErrorInvalidValue;
+    const dim3 g((unsigned) std::max(1, std::min((a.n + block_threads - 1) / block_threads, std::max(1, grid_cap))));
+    const bool lds = a.lds_groups > 0;
+    const auto k = a.first ? (a.group ? pick_vanhove<true, true>(precision, lds) : pick_vanhove<true, false>(precision, lds))
+                           : (a.group ? pick_vanhove<false, true>(precision, lds) : pick_vanhove<false, false>(precision, lds));
+    hipLaunchKernelGGL(k, g, dim3((unsigned) block_threads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_vanhove_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_vanhove_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_vanhove_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

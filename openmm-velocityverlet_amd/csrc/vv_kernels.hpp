@@ -111,5 +111,11 @@ hipError_t launch_contacts(int precision, const ContactsArgs& a, int grid_cap, h
 hipError_t launch_acf(int precision, const AcfArgs& a, int mode, int block_threads, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as AcfArgs::words.
 hipError_t launch_acf_floor(long long* words, hipStream_t s);
+// One self van Hove sample (vv_dev_vanhove.inc): the accumulating kernel over a.n units in blocks of block_threads (64 .. 512, a multiple
+// of 64), at most grid_cap of them, then the one-thread kernel that advances the sample ordinal.  a.first and a.group select the kernel;
+// a.lds_groups > 0 the one that counts in a block-private LDS histogram (lds_groups * num_bins <= VANHOVE_LDS_WORDS), 0 the plain one.
+hipError_t launch_vanhove(int precision, const VanHoveArgs& a, int block_threads, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as VanHoveArgs::words.
+hipError_t launch_vanhove_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

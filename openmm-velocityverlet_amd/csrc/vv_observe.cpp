@@ -1,9 +1,9 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, density modes, contact lifetimes, autocorrelations, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The seven accumulating recorders
-// share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for five,
-// units for two, sites ordered by group for four, classes for two); origins_dead tells the four with origins that the state was rewritten.
+// correlations, density modes, contact lifetimes, autocorrelations, self van Hove functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The eight accumulating recorders
+// share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for six,
+// units for three, sites ordered by group for four, classes for two); origins_dead tells the five with origins that the state was rewritten.
 #include "vv_plan.hpp"
 
 #include <algorithm>
@@ -244,14 +244,37 @@ static int acf_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_acf(p->hp.precision, a, L.mode, block_threads_for(p->acf_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ self van Hove functions (vvhip_vanhove_*)
+// One sample behind the step just enqueued (or captured), and behind its autocorrelation sample: the accumulating kernel and the one-thread
+// kernel that advances the ordinal.  Two launches, no memset and no host synchronisation.
+static int vanhove_enqueue(vvhip_plan* p) {
+    const vvhip_plan::VanHove& V = p->vanhove;
+    const vvhip_vanhove_layout& L = V.lay;
+    vv::VanHoveArgs a{};
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
+    const bool molecules = V.molecules;
+    a.index = V.index.empty() ? nullptr : V.dev.index.get();
+    a.first = molecules ? V.dev.first.get() : nullptr; a.weight = molecules ? V.dev.weight.get() : nullptr; a.total = molecules ? V.dev.total.get() : nullptr;
+    a.group = V.grouped ? V.dev.group.get() : nullptr;
+    a.e2 = V.d_e2.get();
+    a.words = V.d_words.get(); a.ring = (double*) (V.d_words.get() + V.table_offset() + L.words);
+    a.max_samples = L.max_samples; a.head_words = L.head_words;
+    a.n = L.num_units; a.stride = V.stride(); a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
+    a.num_bins = L.num_bins; a.wave_reduce = p->vanhove_wave_reduce;
+    a.lds_groups = p->vanhove_lds ? std::min(L.num_groups, vv::VANHOVE_LDS_WORDS / L.num_bins) : 0;
+    a.scale2 = std::ldexp(1.0, L.frac2_bits); a.scale_hi = std::ldexp(1.0, L.r4_hi_bits); a.scale_lo = std::ldexp(1.0, L.r4_lo_bits); a.limit = L.limit;
+    HIP_TRY(p, vv::launch_vanhove(p->hp.precision, a, block_threads_for(p->vanhove_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
+    return VVHIP_OK;
+}
 // The positions or the velocities were rewritten outside the steps (vv_barostat.cpp; vvhip_set_velocities_to_temperature): the origins that
-// the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, their floors raised in this order; velocities:
+// the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, vanhove, their floors raised in this order; velocities:
 // acf, unless it records orientations.  A contact set belongs to a configuration, not to a displacement: contacts reacts to neither.
 int origins_dead(vvhip_plan* p, Rewrote what) {
     if (what == Rewrote::POSITIONS) {
         if (p->msd.on) HIP_TRY(p, vv::launch_msd_floor(p->msd.d_words.get(), p->stream));
         if (p->current.on) HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
         if (p->modes.on) HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
+        if (p->vanhove.on) HIP_TRY(p, vv::launch_vanhove_floor(p->vanhove.d_words.get(), p->stream));
     } else if (p->acf.on && p->acf.lay.mode != VVHIP_ACF_ORIENTATION) HIP_TRY(p, vv::launch_acf_floor(p->acf.d_words.get(), p->stream));
     return VVHIP_OK;
 }
@@ -300,10 +323,11 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   6 current sample    behind the RDF sample; all of d_words: head, sums, table, the ring of origins and the slots' words
 //   7 density-mode sample   behind the current sample; all of d_words likewise (its turns are scratch, rewritten by every sample)
 //   8 contact sample    behind the density-mode sample; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
-//   9 autocorrelation sample   last; all of d_words, the ring of origins included, as for the MSD
-// Riders 3 .. 9 are the seven accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
-// host tables come from "the shared pieces of a start" below (units: 4 and 9; sites ordered by group: 5 .. 8; the lag schedule: 4, 6 .. 9),
-// and origins_dead above reaches 4, 6, 7 (positions) and 9 (velocities).
+//   9 autocorrelation sample   behind the contact sample; all of d_words, the ring of origins included, as for the MSD
+//  10 self van Hove sample   last; all of d_words likewise: head, histogram and the ring of origins
+// Riders 3 .. 10 are the eight accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
+// host tables come from "the shared pieces of a start" below (units: 4, 9 and 10; sites ordered by group: 5 .. 8; the lag schedule: 4, 6 .. 10),
+// and origins_dead above reaches 4, 6, 7, 10 (positions) and 9 (velocities).
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -312,7 +336,7 @@ Riders riders(vvhip_plan* p) {
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
              recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue),
-             recorder_rider(p->acf, acf_enqueue)}};
+             recorder_rider(p->acf, acf_enqueue), recorder_rider(p->vanhove, vanhove_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -334,7 +358,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the seven accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the eight accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -402,9 +426,9 @@ static int recorder_info(const vvhip_plan* p, R vvhip_plan::* which, L* out, L b
 // ------------------------------------------------------------------------------------------ the shared pieces of a start
 // The host-only part of the accumulating recorders' *_start, stated once; `name` is the prefix of the messages.  What a recorder still
 // writes itself: its own argument checks, its layout, its fixed point (but for units_frac_bits), its work list, its enqueue.
-//   check_groups, check_max_samples   all seven               check_lags            msd, acf, current, modes, contacts
-//   num_origins_of                    msd, acf, current, modes; check_origins       msd, acf, contacts
-//   plan_units, units_frac_bits, fill_units   msd, acf        sites_by_group        rdf, current, modes, contacts
+//   check_groups, check_max_samples   all eight               check_lags            msd, acf, vanhove, current, modes, contacts
+//   num_origins_of                    msd, acf, vanhove, current, modes; check_origins       msd, acf, vanhove, contacts
+//   plan_units, fill_units   msd, acf, vanhove; units_frac_bits   msd, acf        sites_by_group        rdf, current, modes, contacts
 //   check_classes, check_pair_count, check_half_box (beside box_holds), no_pairs_across_shards   rdf, contacts;   no_sums_across_shards   current, modes
 // group[i] of every particle of the System (or, count >= 0, of `count` entries) against [-1, num_groups) (group = null: everything in group 0)
 static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups, int32_t count = -1) {
@@ -998,6 +1022,67 @@ int vvhip_msd_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vv
 }
 int vvhip_msd_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::msd, "msd"); }
 int vvhip_msd_info(const vvhip_plan* p, vvhip_msd_layout* out) { return recorder_info(p, &vvhip_plan::msd, out); }
+
+int vvhip_vanhove_start(vvhip_plan* p, const vvhip_vanhove_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "vanhove: null description");
+    TRY(check_lags(p, "vanhove", d->interval, d->num_lags, d->origin_every));
+    if (d->mode != VVHIP_VANHOVE_PARTICLES && d->mode != VVHIP_VANHOVE_MOLECULES) return fail(p, VVHIP_ERR_INVALID, "vanhove: mode must be VVHIP_VANHOVE_PARTICLES or VVHIP_VANHOVE_MOLECULES");
+    if (d->num_groups < 1 || d->num_groups > 16) return fail(p, VVHIP_ERR_INVALID, "vanhove: num_groups must be in [1, 16]");
+    TRY(check_max_samples(p, "vanhove", d->max_samples));
+    if (!(d->limit >= 0) || !std::isfinite(d->limit)) return fail(p, VVHIP_ERR_INVALID, "vanhove: limit must be finite and >= 0 (0: the default of 16 nm)");
+    TRY(check_groups(p, "vanhove", d->group, d->num_groups));
+    if (d->num_bins < 1 || d->num_bins > vv::VANHOVE_MAX_BINS) return fail(p, VVHIP_ERR_INVALID, "vanhove: num_bins must be in [1, 1024]");
+    if (!d->edges) return fail(p, VVHIP_ERR_INVALID, "vanhove: edges is null (num_bins + 1 bin edges in nm)");
+    for (int32_t k = 0; k <= d->num_bins; k++) {
+        if (!std::isfinite(d->edges[k]) || d->edges[k] < 0) return fail(p, VVHIP_ERR_INVALID, "vanhove: edges[" + std::to_string(k) + "] must be finite and >= 0");
+        if (k > 0 && !(d->edges[k] > d->edges[k - 1])) return fail(p, VVHIP_ERR_INVALID, "vanhove: edges must ascend strictly (edges[" + std::to_string(k) + "] <= edges[" + std::to_string(k - 1) + "])");
+    }
+    // ---- the units this plan records, the layout and the fixed point, host only
+    vvhip_plan::VanHove N;
+    vvhip_vanhove_layout& L = N.lay;
+    N.grouped = d->group != nullptr; N.molecules = d->mode == VVHIP_VANHOVE_MOLECULES;
+    PlanUnits U;
+    TRY(plan_units(p, "vanhove", d->group, N.molecules, U));
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.mode = d->mode; L.num_groups = d->num_groups;
+    L.num_bins = d->num_bins; L.max_samples = d->max_samples;
+    L.num_units = (int32_t) U.units.size();
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every);
+    L.head_words = (int64_t) L.num_groups * L.num_lags * vv::VANHOVE_ROW;
+    L.hist_words = (int64_t) L.num_groups * L.num_lags * L.num_bins;
+    L.words = L.head_words + L.hist_words;
+    L.limit = d->limit > 0 ? pow2_at_least(d->limit) : 16.0;
+    L.ring_bytes = (int64_t) L.num_origins * 3 * N.stride() * (int64_t) sizeof(double);
+    // (r2 < 3 limit^2 < 2^(2 log2(limit) + 2), r2 r2 < 9 limit^4 < 2^(4 log2(limit) + 4), summed over at most U units and the origins that
+    // max_samples samples store; the low word of r2 r2 is at most 2^r4_lo_bits per pair)
+    const long long max_origins = samples_plus(L.max_samples, L.origin_every - 1) / L.origin_every;
+    const int sum_bits = ceil_log2(U.described + 1) + ceil_log2(max_origins + 1), limit_bits = std::ilogb(L.limit);
+    L.frac2_bits = std::min(40, 62 - sum_bits - 2 * limit_bits - 2);
+    L.r4_hi_bits = std::min(40, 62 - sum_bits - 4 * limit_bits - 4);
+    L.r4_lo_bits = std::min(52, 61 - sum_bits);
+    const std::string with = " with " + std::to_string(U.described) + " units, max_samples = " + std::to_string((long long) L.max_samples) + ", origin_every = " + std::to_string(L.origin_every) +
+                             " and limit " + std::to_string(L.limit) + ": lower max_samples or the limit";
+    if (L.frac2_bits < 8) return fail(p, VVHIP_ERR_INVALID, "vanhove: the sums of r2 would keep frac2_bits = " + std::to_string(L.frac2_bits) + " fraction bits (< 8)" + with);
+    if (L.r4_hi_bits < 0) return fail(p, VVHIP_ERR_INVALID, "vanhove: the sums of r2 r2 would keep r4_hi_bits = " + std::to_string(L.r4_hi_bits) + " fraction bits (< 0)" + with);
+    if (L.words > VVHIP_VANHOVE_MAX_WORDS)
+        return fail(p, VVHIP_ERR_INVALID, "vanhove: the table would have " + std::to_string((long long) L.words) + " words (num_groups * num_lags * (6 + num_bins)), above the cap of " +
+                                          std::to_string((long long) VVHIP_VANHOVE_MAX_WORDS) + " (32 MiB): fewer lags, bins or groups");
+    TRY(check_origins(p, "vanhove", L.num_origins));
+    if (N.molecules && U.cut)
+        return fail(p, VVHIP_ERR_UNSUPPORTED, "vanhove: the particle shard cuts a molecule: its centre of mass needs particles of another shard");
+    fill_units(p->hp, N, U);
+    N.e2.resize((size_t) L.num_bins + 1);
+    for (int32_t k = 0; k <= L.num_bins; k++) N.e2[(size_t) k] = d->edges[k] * d->edges[k];
+    return recorder_install(p, &vvhip_plan::vanhove, "vanhove", N, d->interval);
+}
+int vvhip_vanhove_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_vanhove_counts* out, int32_t reset) {
+    long long head[vv::VANHOVE_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::vanhove, "vanhove", words_out, capacity_words, head));
+    if (out) *out = {head[vv::VANHOVE_SAMPLES], head[vv::VANHOVE_DROPPED], head[vv::VANHOVE_OUT_OF_RANGE], head[vv::VANHOVE_FLOOR]};
+    return reset ? recorder_reset(p, p->vanhove) : VVHIP_OK;
+}
+int vvhip_vanhove_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::vanhove, "vanhove"); }
+int vvhip_vanhove_info(const vvhip_plan* p, vvhip_vanhove_layout* out) { return recorder_info(p, &vvhip_plan::vanhove, out); }
 
 int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;

@@ -8,9 +8,9 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the ten scheduled riders in ride order (riders) --
-//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact / autocorrelation sample, with their
-//                    late words: the rings' cursors, the removals' record, the seven recorders' d_words; the recorders' one life cycle
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the eleven scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact / autocorrelation / self van Hove sample, with their
+//                    late words: the rings' cursors, the removals' record, the eight recorders' d_words; the recorders' one life cycle
 //                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -84,8 +84,8 @@ static_assert(vv::ACF_VELOCITY_PARTICLES == VVHIP_ACF_VELOCITY_PARTICLES && vv::
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 // The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
 //   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
-//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample   9 autocorrelation sample (3 .. 9: all of d_words)
-constexpr int kRiders = 10;
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample   9 autocorrelation sample   10 self van Hove sample (3 .. 10: all of d_words)
+constexpr int kRiders = 11;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -166,6 +166,9 @@ struct vvhip_plan {
     int contacts_skip_zero = 1;         // the correlate kernel loads neither the sample's nor the surviving words behind a zero origin word (test hook "contacts_skip_zero"; same bits)
     int acf_block_threads = 0;          // threads per block of an autocorrelation sample's accumulating kernel, 0: by the number of units (acf_enqueue; test hook "acf_block_threads")
     int acf_wave_reduce = 1;            // an autocorrelation sample's waves whose units share a group add their sums once (test hook "acf_wave_reduce": 0 = every lane adds; same bits)
+    int vanhove_block_threads = 0;      // threads per block of a self van Hove sample's accumulating kernel, 0: by the number of units (vanhove_enqueue; test hook "vanhove_block_threads")
+    int vanhove_lds = 1;                // that kernel counts a slot in a block-private LDS histogram and flushes the non-zero bins (test hook "vanhove_lds": 0 = every increment is a global add; same bits)
+    int vanhove_wave_reduce = 1;        // its waves whose units share a group add their six head words once (test hook "vanhove_wave_reduce": 0 = every lane adds; same bits)
     int acf_slots_in_flight = 4;        // ring slots whose loads that kernel issues before it uses the first, 1 .. 8 (test hook "acf_slots_in_flight"; same bits; TUNING_LOG.md)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
@@ -185,8 +188,8 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // all ten riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode, contact and autocorrelation sample.  A
-        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the seven recorders' d_words
+        // all eleven riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation and self van Hove sample.  A
+        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the eight recorders' d_words
         long long step_count = 0;
     } cur;
     bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
@@ -358,7 +361,7 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // What the seven accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // What the eight accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
     // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
     // `on`: the recorder runs and the device buffers exist.  Each recorder adds
     //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
@@ -366,7 +369,7 @@ struct vvhip_plan {
     //   bytes()                of d_words
     //   alloc(s, &asked)       d_words, zeroed on stream s, and dev from the host tables; a request that fails leaves its bytes in `asked`
     //   reset(s)               what *_read's reset enqueues
-    // Stated once below them: Units, the unit tables and all of the above for the two recorders of per-unit vectors (msd, acf); Slotted,
+    // Stated once below them: Units, the unit tables and all of the above for the three recorders of per-unit vectors (msd, acf, vanhove); Slotted,
     // "no slot holds a sample" and the reset for the three whose ring slots carry a word of their own (current, modes, contacts).  Rdf and
     // Contacts keep their own index / mol / stride(): a shared base would cost more lines than the four it saves.  The host tables come
     // from vv_observe.cpp's "shared pieces of a start".
@@ -571,6 +574,16 @@ struct vvhip_plan {
         }
     } contacts;
     Acf acf;                                      // (Units, beside the MSD recorder above)
+    // The self van Hove function (vvhip_vanhove_*; vv_dev_vanhove.inc): the MSD recorder's units, ring and life cycle, and the squared bin
+    // edges as one more device table
+    struct VanHove : Units<vvhip_vanhove_layout, vv::VANHOVE_HEAD> {
+        std::vector<double> e2;                   // [num_bins + 1] edges[k] * edges[k]
+        vv::DevBuf<double> d_e2;
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            const hipError_t e = Units::alloc(s, asked);
+            return e == hipSuccess ? put(d_e2, e2, asked) : e;
+        }
+    } vanhove;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -730,7 +743,7 @@ Riders riders(vvhip_plan* p);
 // recorder counts and table; its gather scratch is rewritten by every sample and is not saved.  For a current recorder the whole
 // allocation again: head, sums, table and the ring of origins.  For a density-mode recorder likewise.  For a contact recorder head, table,
 // the slots' ordinals and both rings of bit matrices: the surviving contacts are not idempotent under the repeat either.  For an
-// autocorrelation recorder the whole allocation as for the MSD: head, table and the ring of origins.
+// autocorrelation recorder the whole allocation as for the MSD: head, table and the ring of origins; for a self van Hove recorder likewise.
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

@@ -199,6 +199,21 @@ def acf_sum(acfs):
     return dataclasses.replace(first, words=np.sum([m.words for m in acfs], axis=0, dtype=np.int64), out_of_range=sum(m.out_of_range for m in acfs))
 
 
+def vanhove_sum(tables):
+    """The self van Hove table of a sharded run from its shards' tables (Context.vanhove_read of every shard, the same description and the
+    same steps behind each): head and hist added as int64 -- the result is the unsharded table bit for bit -- and out_of_range added;
+    samples, dropped and the origin floor are the same on every shard."""
+    import dataclasses
+    first = tables[0]
+    key = lambda m: (m.head.shape, m.hist.shape, m.edges.tobytes(), m.frac2_bits, m.r4_hi_bits, m.r4_lo_bits, m.interval, m.origin_every,
+                     m.molecules, m.samples, m.dropped, m.origin_floor)
+    for m in tables[1:]:
+        if key(m) != key(first):
+            raise ValueError("the self van Hove tables differ in layout, bins, fixed point, schedule or number of samples: not shards of one run")
+    return dataclasses.replace(first, head=np.sum([m.head for m in tables], axis=0, dtype=np.int64),
+                               hist=np.sum([m.hist for m in tables], axis=0, dtype=np.int64), out_of_range=sum(m.out_of_range for m in tables))
+
+
 def drude_temperature_series(ctx, group=None, reset=False):
     """A sharded run's series (Context.series_read): every rank's raw rows -- six fixed-point sums and the overflow flag per row, of its
     own particles -- summed over the process group in one all-reduce, then turned into KE / T with the whole system's DOFs.  Every rank

@@ -527,6 +527,132 @@ def acf_from_words(words, layout, counts) -> Autocorrelations:
                             frac_bits=int(layout.frac_bits), mode=ACF_MODES[int(layout.mode)], words=words)
 
 
+def vanhove_edges(r_max: float, num_bins: int, r_min=None) -> np.ndarray:
+    """float64 [num_bins + 1]: bin edges in nm for Context.vanhove_start.  r_min=None: uniform from 0 to r_max, edge k = k * (r_max /
+    num_bins); else logarithmic from r_min > 0 to r_max (displacements below r_min are counted in `below`)."""
+    if r_min is None:
+        return np.arange(int(num_bins) + 1, dtype=np.float64) * (np.float64(r_max) / np.float64(num_bins))
+    if not 0 < float(r_min) < float(r_max):
+        raise ValueError("logarithmic edges need 0 < r_min < r_max")
+    return np.geomspace(np.float64(r_min), np.float64(r_max), int(num_bins) + 1)
+
+
+@dataclasses.dataclass
+class VanHove:
+    """The self part of the van Hove function per group and lag (Context.vanhove_read; include/vvhip.h: vvhip_vanhove_* states the units,
+    the schedule, the bins and the moments).  `head` and `hist` are the device's table as it stands: int64 [groups, lags, 6] -- pairs,
+    below, beyond, sum r2 scaled by 2^frac2_bits, sum r2 r2 as hi and lo -- and int64 [groups, lags, bins]."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples: nothing was added or stored for them
+    out_of_range: int                      # unit-pairs left out (a displacement component NaN or at / beyond the limit)
+    origin_floor: int                      # origins with an ordinal below it are dead (a barostat move rewrote the positions)
+    interval: int
+    origin_every: int
+    frac2_bits: int
+    r4_hi_bits: int
+    r4_lo_bits: int
+    molecules: bool
+    edges: np.ndarray                      # float64 [bins + 1] nm
+    head: np.ndarray                       # int64 [groups, lags, 6]
+    hist: np.ndarray                       # int64 [groups, lags, bins]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [lags]: row l is the lag of (l + 1) * interval steps."""
+        return (np.arange(self.head.shape[1], dtype=np.int64) + 1) * self.interval
+
+    @property
+    def pairs(self) -> np.ndarray:
+        """int64 [groups, lags]: unit-pairs behind every row = below + hist summed over the bins + beyond."""
+        return self.head[:, :, 0]
+
+    @property
+    def below(self) -> np.ndarray:
+        """int64 [groups, lags]: pairs with r < edges[0]."""
+        return self.head[:, :, 1]
+
+    @property
+    def beyond(self) -> np.ndarray:
+        """int64 [groups, lags]: pairs with r >= edges[-1]."""
+        return self.head[:, :, 2]
+
+    def _per_pair(self, values: np.ndarray) -> np.ndarray:
+        n = self.pairs.reshape(self.pairs.shape + (1,) * (values.ndim - 2))
+        return np.where(n > 0, values / np.where(n > 0, n, 1), np.nan)
+
+    @property
+    def P(self) -> np.ndarray:
+        """float64 [groups, lags, bins]: the probability of a displacement in every bin = hist / pairs, NaN where a row has no pairs."""
+        return self._per_pair(self.hist.astype(np.float64))
+
+    @property
+    def G_s(self) -> np.ndarray:
+        """float64 [groups, lags, bins]: G_s(r, t) in nm^-3 = P divided by the shell volume 4 pi / 3 (e_{b+1}^3 - e_b^3)."""
+        e = self.edges
+        return self.P / (4.0 * np.pi / 3.0 * (e[1:] ** 3 - e[:-1] ** 3))
+
+    @property
+    def msd(self) -> np.ndarray:
+        """float64 [groups, lags]: <r^2> in nm^2 = word * 2^-frac2_bits / pairs (every pair in range, the ones below and beyond too)."""
+        return self._per_pair(self.head[:, :, 3].astype(np.float64) * 2.0 ** -self.frac2_bits)
+
+    @property
+    def r4(self) -> np.ndarray:
+        """float64 [groups, lags]: <r^4> in nm^4 = (hi + lo * 2^-r4_lo_bits) * 2^-r4_hi_bits / pairs."""
+        total = (self.head[:, :, 4].astype(np.float64) + self.head[:, :, 5].astype(np.float64) * 2.0 ** -self.r4_lo_bits) * 2.0 ** -self.r4_hi_bits
+        return self._per_pair(total)
+
+    @property
+    def alpha2(self) -> np.ndarray:
+        """float64 [groups, lags]: the non-Gaussian parameter 3 <r^4> / (5 <r^2>^2) - 1 (0 for a Gaussian G_s in three dimensions)."""
+        m = self.msd
+        return 3.0 * self.r4 / (5.0 * m * m) - 1.0
+
+    def Fs(self, k: float):
+        """(F float64 [groups, lags], excluded float64 [groups, lags]): the self-intermediate scattering function at wave number k (nm^-1)
+        from the histogram, F = sum_b P_b sin(k r_b) / (k r_b) at the bin midpoints r_b -- limited by the bin width: it is good while
+        k * width << 1 --, and the share of the pairs below edges[0] or beyond edges[-1], which are in no bin and not in F."""
+        r = 0.5 * (self.edges[1:] + self.edges[:-1])
+        F = (self.P * np.sinc(float(k) * r / np.pi)).sum(axis=2)
+        return F, self._per_pair((self.below + self.beyond).astype(np.float64))
+
+    def overlap(self, a: float) -> np.ndarray:
+        """float64 [groups, lags]: the self-overlap Q_s(t) = the share of the pairs with r < a.  `a` must be one of `edges`: the
+        histogram cannot split a bin."""
+        at = np.nonzero(self.edges == np.float64(a))[0]
+        if at.size == 0:
+            raise ValueError(f"overlap: a = {a} is not one of the bin edges")
+        inside = self.below + self.hist[:, :, : int(at[0])].sum(axis=2)
+        return self._per_pair(inside.astype(np.float64))
+
+    def relaxation_time(self, k: float, level: float = float(np.exp(-1.0)), dt: float = 1.0) -> np.ndarray:
+        """float64 [groups]: the first lag time at which Fs(k) falls below `level`, linearly interpolated between the two rows around it
+        (the zero lag, where F_s = 1, in front of row 0); NaN if it never does within the table.  `dt`: the step in the unit the time is
+        wanted in; the default of 1 gives the time in steps."""
+        F, _ = self.Fs(k)
+        t = np.concatenate([[0.0], self.lag_steps.astype(np.float64) * float(dt)])
+        out = np.full(F.shape[0], np.nan)
+        for g in range(F.shape[0]):
+            y = np.concatenate([[1.0], F[g]])
+            under = np.nonzero(y < level)[0]
+            if under.size and under[0] > 0:
+                i = int(under[0])
+                out[g] = t[i - 1] + (t[i] - t[i - 1]) * (y[i - 1] - level) / (y[i - 1] - y[i])
+        return out
+
+
+def vanhove_from_words(words, layout, counts, edges) -> VanHove:
+    """A VanHove from a table's int64 words (head [groups * lags * 6], then hist [groups * lags * bins]), its layout (H.VanHoveLayout),
+    counts (H.VanHoveCounts) and the bin edges it was started with."""
+    words = np.ascontiguousarray(words, dtype=np.int64)
+    G, L, B, hw = int(layout.num_groups), int(layout.num_lags), int(layout.num_bins), int(layout.head_words)
+    return VanHove(samples=int(counts.samples), dropped=int(counts.dropped), out_of_range=int(counts.out_of_range),
+                   origin_floor=int(counts.origin_floor), interval=int(layout.interval), origin_every=int(layout.origin_every),
+                   frac2_bits=int(layout.frac2_bits), r4_hi_bits=int(layout.r4_hi_bits), r4_lo_bits=int(layout.r4_lo_bits),
+                   molecules=layout.mode == H.VANHOVE_MOLECULES, edges=np.array(edges, dtype=np.float64),
+                   head=words[:hw].reshape(G, L, 6).copy(), hist=words[hw:hw + G * L * B].reshape(G, L, B).copy())
+
+
 def rdf_edges(r_max: float, nbins: int) -> np.ndarray:
     """float64 [nbins + 1]: the SQUARED bin edges e(k) = ((double) k * dr)^2 with dr = r_max / nbins, as include/vvhip.h defines them."""
     t = np.arange(int(nbins) + 1, dtype=np.float64) * (np.float64(r_max) / np.float64(nbins))
@@ -1207,7 +1333,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the seven accumulating recorders below share: profile, msd, acf, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the eight accumulating recorders below share: profile, msd, acf, vanhove, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1330,6 +1456,36 @@ class Context:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
         return self._recorder_read("acf", H.AcfLayout, H.AcfCounts, acf_from_words, reset)
+
+    # ---- self van Hove functions accumulated on the device inside the steps (include/vvhip.h: vvhip_vanhove_*)
+    def vanhove_start(self, interval: int, num_lags: int, edges, origin_every: int = 1, molecules: bool = False, groups=None,
+                      max_samples: int = 1 << 20, limit: float = 0.0):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), measure every recorded unit -- a
+        particle, or with molecules=True a molecule's centre of mass -- against the stored origins and add, per group and lag of 1 ..
+        `num_lags` samples, the pair to the bin of its displacement r between `edges` (nm, ascending, edges[0] >= 0: vanhove_edges gives
+        uniform or logarithmic ones) and r^2 and r^4 to the row's moments, all as integers, so that the table is the same bits for any
+        launch shape or shard split.  Every `origin_every`-th sample is stored as an origin.  `groups`: one int per particle of the System
+        (-1: not recorded), each group a table of its own; None: everything in group 0.  `limit` (nm, 0: 16): a displacement component at
+        or beyond it leaves the pair out and counts in out_of_range.  At most `max_samples` samples are taken (the fixed point is sized
+        for them).  No host synchronisation until vanhove_read."""
+        grp = self._groups(groups)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        desc = H.VanHoveDesc(int(interval), int(num_lags), int(origin_every), H.VANHOVE_MOLECULES if molecules else H.VANHOVE_PARTICLES,
+                             1 if grp is None else max(int(grp.max()) + 1, 1), int(e.size) - 1, None if grp is None else grp.ctypes.data,
+                             e.ctypes.data if e.size else None, int(max_samples), float(limit))
+        H.check(H.lib.vvhip_vanhove_start(self.plan, C.byref(desc)), self.plan)
+        self._vanhove_edges = e.copy()
+
+    def vanhove_stop(self):
+        self._recorder_stop("vanhove")
+
+    def vanhove_info(self) -> H.VanHoveLayout:
+        return self._recorder_info("vanhove", H.VanHoveLayout)
+
+    def vanhove_read(self, reset: bool = False) -> VanHove:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        return self._recorder_read("vanhove", H.VanHoveLayout, H.VanHoveCounts, vanhove_from_words, reset, getattr(self, "_vanhove_edges", None))
 
     # ---- radial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_rdf_*)
     def rdf_start(self, interval: int, r_max: float, nbins: int, classes, groups=None, exclude_same_molecule: bool = False,
@@ -1543,7 +1699,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode, contact or autocorrelation recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation or self van Hove recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

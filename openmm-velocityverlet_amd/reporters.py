@@ -20,6 +20,8 @@ latest three kept.
 
 ``write_msd`` writes a device-side mean-squared displacement table (``Context.msd_read``) as text columns, one line per lag.
 
+``write_vanhove`` writes a device-side self van Hove table (``Context.vanhove_read``) as text columns, one line per lag.
+
 ``write_rdf`` writes device-side radial distribution functions (``Context.rdf_read``) as text columns, one line per bin.
 
 ``write_current`` writes a device-side collective current correlation table (``Context.current_read``) as text columns, one line per lag.
@@ -246,6 +248,39 @@ def write_msd(file, msd, dt, append=False, header=True):
             print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"OriginFloor"\t%d' % (msd.samples, msd.dropped, msd.out_of_range, msd.origin_floor), file=out)
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for l in range(msd.words.shape[1]):
+            print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def vanhove_columns(vh, dt):
+    """[(name, values per lag)] of a self van Hove table's text file: the lag in ps, then per group the pairs, below, beyond, <r^2>, <r^4>,
+    alpha_2 and the probability of every bin."""
+    cols = [("lag (ps)", vh.lag_steps.astype(np.float64) * float(dt))]
+    msd, r4, alpha2, P = vh.msd, vh.r4, vh.alpha2, vh.P
+    for g in range(vh.head.shape[0]):
+        cols += [("%s[%d]" % (name, g), v[g].astype(np.float64)) for name, v in (("pairs", vh.pairs), ("below", vh.below), ("beyond", vh.beyond))]
+        cols += [("msd[%d] (nm^2)" % g, msd[g]), ("r4[%d] (nm^4)" % g, r4[g]), ("alpha2[%d]" % g, alpha2[g])]
+        cols += [("P[%d][%d]" % (g, b), P[g, :, b]) for b in range(vh.hist.shape[2])]
+    return cols
+
+
+def write_vanhove(file, vh, dt, append=False, header=True):
+    """A self van Hove table (Context.vanhove_read, distributed.vanhove_sum) as text: three comment lines (samples, dropped, out of range,
+    origin floor; the bin edges in nm; the column names) unless header=False, then one tab-separated line per lag -- the lag in ps (lag
+    steps x `dt`), then per group the pairs, those below and beyond the bins, <r^2>, <r^4>, alpha_2 and the probability P of every bin
+    (nan where a lag has no pairs; G_s is P divided by the shell volume of the edges).  Floats are written with repr, so np.loadtxt reads
+    back the bits.  `file`: a path or an open text stream."""
+    cols = vanhove_columns(vh, dt)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"OutOfRange"\t%d\t"OriginFloor"\t%d' % (vh.samples, vh.dropped, vh.out_of_range, vh.origin_floor), file=out)
+            print('#"Edges (nm)"\t' + "\t".join(repr(float(e)) for e in vh.edges), file=out)
+            print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
+        for l in range(vh.head.shape[1]):
             print(*[repr(float(v[l])) for _, v in cols], sep="\t", file=out)
         out.flush()
     finally:

@@ -267,6 +267,28 @@ class AcfLayout(C.Structure):
                 ("start_step", C.c_int64), ("limit", C.c_double)]
 
 
+VANHOVE_PARTICLES, VANHOVE_MOLECULES = 0, 1
+VANHOVE_MAX_WORDS = 1 << 22
+
+
+class VanHoveDesc(C.Structure):
+    """What a self van Hove recorder is to accumulate (include/vvhip.h: vvhip_vanhove_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32), ("num_groups", C.c_int32),
+                ("num_bins", C.c_int32), ("group", C.c_void_p), ("edges", C.c_void_p), ("max_samples", C.c_int64), ("limit", C.c_double)]
+
+
+class VanHoveCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("out_of_range", C.c_int64), ("origin_floor", C.c_int64)]
+
+
+class VanHoveLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("mode", C.c_int32),
+                ("num_groups", C.c_int32), ("num_units", C.c_int32), ("num_origins", C.c_int32), ("num_bins", C.c_int32),
+                ("frac2_bits", C.c_int32), ("r4_hi_bits", C.c_int32), ("r4_lo_bits", C.c_int32), ("max_samples", C.c_int64),
+                ("words", C.c_int64), ("head_words", C.c_int64), ("hist_words", C.c_int64), ("ring_bytes", C.c_int64),
+                ("start_step", C.c_int64), ("limit", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -365,6 +387,8 @@ def _load():
         "vvhip_contacts_info": [vp, P(ContactsLayout)], "vvhip_contacts_read": [vp, vp, C.c_int64, P(ContactsCounts), i32],
         "vvhip_acf_start": [vp, P(AcfDesc)], "vvhip_acf_stop": [vp], "vvhip_acf_info": [vp, P(AcfLayout)],
         "vvhip_acf_read": [vp, vp, C.c_int64, P(AcfCounts), i32],
+        "vvhip_vanhove_start": [vp, P(VanHoveDesc)], "vvhip_vanhove_stop": [vp], "vvhip_vanhove_info": [vp, P(VanHoveLayout)],
+        "vvhip_vanhove_read": [vp, vp, C.c_int64, P(VanHoveCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
