@@ -1223,6 +1223,111 @@ int vvhip_vanhove_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_wo
 int vvhip_vanhove_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_vanhove_info(const vvhip_plan* plan, vvhip_vanhove_layout* out);
+/* ---------------------------------------------------------------- distinct van Hove functions accumulated on the device
+ * G_d(r, t): the density of OTHER sites at distance r at time t from where a site was at time 0 -- how fast the counter-ion cage around an
+ * ion dissolves and what refills the hole the ion leaves; the real-space counterpart of F(k, t) (vvhip_modes_*), and with G_s
+ * (vvhip_vanhove_*) the G(r, t) that a scattering experiment measures.  A host cannot produce it during a run: every pair of sites of every
+ * sample against every stored origin, (live origins + 1) times the RDF's O(N_a N_b) pair work per sample, on float64 frames of 24 B per
+ * site and sample.  After every full step whose count is a multiple of `interval` -- counted exactly as for the other riders; a sample
+ * "after step k" is enqueued behind that step's self van Hove sample, the twelfth and last rider -- the step entry point enqueues three
+ * kernels (csrc/vv_dev_vanhove_distinct.inc): a gather of the sites' float64 positions into the planes of "now", the pair kernel over (work
+ * items) x (ring slots), and a one-thread kernel that counts the visits and advances the ordinal: no memset, no copy, no host work.  Inside
+ * a captured graph all three are graph nodes and the steps that take a sample are part of the graph-cache key.  The recorder reads posq and
+ * posqCorrection and writes its own words and planes, nothing else; a plan that never starts one launches what it launched before and
+ * allocates nothing.
+ * Sites, groups, position.  The RDF's, word for word: the particles with group[i] >= 0, NULL puts every particle into group 0, num_groups
+ * is 1 .. 16; X_i in float64 is (double) posq + (double) posqCorrection in mixed precision, (double) posq otherwise, unwrapped; the sites
+ * are ordered by group, ascending by particle inside a group.
+ * Classes.  num_classes (1 .. 32) ORDERED pairs classes[c] = {ga, gb}: the site at the origin time is in ga, the site at the later time in
+ * gb.  ga != gb counts all N_a N_b pairs; ga == gb counts every ordered pair (i, j) with i != j, P_c = N_a (N_a - 1): a site is never paired
+ * with its own earlier self (that pairing is G_s).  With exclude_same_molecule != 0 pairs whose particles have equal mol_id are left out of
+ * every class, as for the RDF (P_c is not lowered).
+ * Schedule.  The MSD's with a zero-lag row in front, as in the autocorrelation recorder: ordinal j, every E-th sample (E = origin_every) is
+ * stored as an origin, R = num_origins = ceil(num_lags / E) <= 1024 of them are alive; num_lags + 1 rows, row 0 the sample against itself,
+ * row l the lag of l * interval steps.  At sample j the origin k E adds to row l = j - k E provided origin_floor <= k E < j and j - k E <=
+ * num_lags; the sample itself always adds to row 0.  Accumulation comes first, the store second: where R E == num_lags the oldest origin
+ * still contributes at lag num_lags when the newest is stored (the ring has R + 1 slots, so the two never share one).
+ * Arithmetic.  The RDF's with i taken at the origin and j now, all float64, no contraction; per axis, with L the plan's box when the sample
+ * is enqueued and inv_L_a = 1.0 / L_a formed once per sample:
+ *     d = X_j,a(now) - X_i,a(origin);   n = rint(d * inv_L_a)  (round-half-even);   d = d - L_a * n
+ * and then  r2 = (dx * dx + dy * dy) + dz * dz.
+ * Bins.  Uniform in r: dr = r_max / nbins and edges e(k) = ((double) k * dr) * ((double) k * dr), k = 0 .. nbins, nbins 1 .. 8192.  A pair
+ * adds the integer 1 to the bin b of its class and row with  e(b) <= r2 < e(b + 1)  (comparisons decide, never a square root); a pair with
+ * r2 >= e(nbins) adds nothing; a pair whose r2 is NaN adds 1 to `invalid` and to no bin.
+ * Table: int64 head[num_lags + 1][2], then int64 hist[num_classes][num_lags + 1][nbins]; words = head_words + hist_words, at most 2^22
+ * (32 MiB).  head[l][0]: the (origin, sample) visits to row l; head[l][1]: the bits of a float64 that sums 1.0 / ((Lx * Ly) * Lz) over
+ * those visits -- a row receives at most one visit per sample, so the sum is sequential in sample order and reproducible.  Every hist
+ * word is an integer sum: the table is the same bits for any work list, tile shape, block size, histogram layout or arrival order.
+ *     G_d,c(l, b) = hist[c][l][b] / (P_c * shell(b) * inv_volume_sum[l]),   shell(b) = 4 pi / 3 (e(b + 1)^(3/2) - e(b)^(3/2)),
+ * which tends to 1 at large r; row 0 of a class with ga != gb is the RDF's table of that class, with ga == gb twice it.
+ * Box and positions changed outside the steps.  r_max must be finite, > 0 and <= min(Lx, Ly, Lz) / 2 of the plan's box at the start.
+ * vvhip_set_box (with a box that differs) and vvhip_barostat_scale / _restore set origin_floor to the current ordinal: an origin under
+ * another box has no minimum image with the present one; what else rewrites positions outside the steps is handled as for the MSD.  A sample
+ * enqueued while min(L) / 2 < r_max adds nothing, stores nothing, does not advance the ordinal, sets origin_floor to the ordinal and counts
+ * as dropped, so every row stays a true lag.  Past max_samples a sample adds nothing, stores no origin and counts as dropped.  The box is a
+ * kernel argument: what changes it drops the captured graphs.
+ * Overflow.  Refused at the start where the largest P_c times max_samples reaches 2^62.
+ * Sharded plans are refused (VVHIP_ERR_UNSUPPORTED), as for the RDF.  Recovery.  vvhip_checkpoint_load is refused while a recorder runs;
+ * the rider's recovery words are the WHOLE allocation, (4 + words) * 8 B + ring_bytes: counts, table and ring, with ring_bytes =
+ * (num_origins + 2) x 3 x stride x 8 B (the R + 1 slots and the spare plane set of a sample that is no origin), stride = the sites
+ * rounded up to 16. */
+#define VVHIP_VANHOVE_DISTINCT_MAX_WORDS (1ll << 22)
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t num_lags;               /* 1 .. 4096: rows 0 .. num_lags, row l the lag of l * interval steps */
+    int32_t origin_every;           /* E, 1 .. num_lags: every E-th sample is stored as an origin */
+    int32_t nbins;                  /* 1 .. 8192 */
+    int32_t num_groups;             /* 1 .. 16 */
+    int32_t num_classes;            /* 1 .. 32 */
+    int32_t exclude_same_molecule;  /* != 0: pairs inside one molecule (mol_id) are left out */
+    int32_t reserved;               /* 0 */
+    const signed char* group;       /* [num_atoms] the group of every particle of the System, -1: no site; NULL: everything in group 0 */
+    const int32_t* classes;         /* [num_classes][2] ga (at the origin), gb (now) of every class */
+    int64_t max_samples;            /* >= 1 */
+    double r_max;                   /* nm */
+} vvhip_vanhove_distinct_desc;
+typedef struct {
+    int64_t samples;                /* samples taken since the start or the last reset (at most max_samples): the next sample's ordinal */
+    int64_t dropped;                /* samples that were due past max_samples or in a box with min(L) / 2 < r_max: nothing was added or stored */
+    int64_t invalid;                /* pairs whose r2 was NaN */
+    int64_t origin_floor;           /* origins with an ordinal below it are dead */
+} vvhip_vanhove_distinct_counts;
+typedef struct {
+    int32_t active, interval, num_lags, origin_every, nbins, num_groups, num_classes, exclude_same_molecule;
+    int32_t tile;                   /* sites per tile of the pair kernel */
+    int32_t num_items;              /* work items: the pair kernel runs num_items * (num_origins + 1) blocks per sample */
+    int32_t num_origins;            /* ceil(num_lags / origin_every) */
+    int32_t num_rows;               /* num_lags + 1 */
+    int32_t num_sites[16];          /* per group */
+    int32_t classes[32][2];
+    int64_t pairs_per_sample[32];   /* per class: N_a N_b, or N_a (N_a - 1) */
+    int64_t max_samples;
+    int64_t words;                  /* head_words + hist_words */
+    int64_t head_words;             /* (num_lags + 1) * 2 */
+    int64_t hist_words;             /* num_classes * (num_lags + 1) * nbins */
+    int64_t ring_bytes;             /* (num_origins + 2) * 3 * stride * 8 */
+    int64_t start_step;             /* the plan's step count at vvhip_vanhove_distinct_start */
+    double r_max, dr;               /* dr = r_max / nbins */
+} vvhip_vanhove_distinct_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, num_lags outside 1 .. 4096, origin_every outside 1 .. num_lags, r_max not finite or <= 0, nbins outside
+ * 1 .. 8192, num_groups outside 1 .. 16, num_classes outside 1 .. 32, classes NULL, max_samples < 1, a group entry outside -1 ..
+ * num_groups - 1, a class entry outside 0 .. num_groups - 1 (VVHIP_ERR_INVALID naming the argument); more than
+ * VVHIP_VANHOVE_DISTINCT_MAX_WORDS words (VVHIP_ERR_INVALID with the count); num_origins above 1024; the largest class's pairs per sample
+ * times max_samples at or above 2^62; r_max above half the shortest edge of the plan's box (VVHIP_ERR_INVALID); a sharded plan
+ * (VVHIP_ERR_UNSUPPORTED); an unbound plan; inside a graph capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the
+ * byte count).  A description that passes the checks in front of "an unbound plan" is kept even where the start is then refused (active =
+ * 0): vvhip_vanhove_distinct_info answers for it, for sizing. */
+int vvhip_vanhove_distinct_start(vvhip_plan* plan, const vvhip_vanhove_distinct_desc* desc);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words, head then hist (words_out may be NULL with
+ * capacity_words = 0; a capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts, floor and table and restarts the
+ * ordinal at 0 with no live origin: the step schedule continues without gap or repeat. */
+int vvhip_vanhove_distinct_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_vanhove_distinct_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and ring are released, the description is forgotten; synchronises and drops the
+ * captured graphs. */
+int vvhip_vanhove_distinct_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_vanhove_distinct_info(const vvhip_plan* plan, vvhip_vanhove_distinct_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the
@@ -1601,13 +1706,13 @@ int vvhip_debug_old_delta(vvhip_plan* plan, void** device_ptr);                 
  * everything without watching the device's free memory, which moves under other processes' work.  Host only. */
 int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes);
 /* FNV-1a 64 over the host tables that the last accepted vvhip_<name>_start built, name = "profile", "msd", "rdf", "current", "modes",
- * "contacts", "acf" or "vanhove"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
+ * "contacts", "acf", "vanhove" or "vanhove_distinct"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
  * Per vector its size as uint64, then its bytes; flags as one byte; in this order:
  *   profile   grouped, index, group, mass                 msd, acf   grouped, index, first, weight, total, group
  *   rdf       index, mol, items, max_jsites (int32)       current    two_level, index, weight, group
  *   modes     index, weight, modes, items                 contacts   first[0 .. 16], index, mol, mask_items, corr_items, then the fields
  *                                                                    of the word layout (csrc/vv_layout.h: ContactsLayout) one by one
- *   vanhove   grouped, index, first, weight, total, group (as msd), then e2 */
+ *   vanhove   grouped, index, first, weight, total, group (as msd), then e2       vanhove_distinct   as rdf */
 int vvhip_debug_recorder_digest(const vvhip_plan* plan, const char* name, uint64_t* out);
 
 #ifdef __cplusplus

@@ -125,6 +125,9 @@ int vvhip_debug_tune(vvhip_plan* p, const char* key, int value) {
     else if (k == "vanhove_block_threads") { if (value != 0 && (value < 64 || value > 512 || value % 64)) return VVHIP_ERR_INVALID; p->vanhove_block_threads = value; }
     else if (k == "vanhove_lds") { if (value < 0 || value > 1) return VVHIP_ERR_INVALID; p->vanhove_lds = value; }
     else if (k == "vanhove_wave_reduce") { if (value < 0 || value > 1) return VVHIP_ERR_INVALID; p->vanhove_wave_reduce = value; }
+    else if (k == "vhd_hist_copies") { if (value != 1 && value != 4) return VVHIP_ERR_INVALID; p->vhd_hist_copies = value; }
+    else if (k == "vhd_items_target") { if (value < 1) return VVHIP_ERR_INVALID; p->vhd_items_target = value; }      // (read when a recorder starts: the work list is built there)
+    else if (k == "vhd_lds") { if (value < 0 || value > 1) return VVHIP_ERR_INVALID; p->vhd_lds = value; }
     else if (k == "rdf_hist_copies") { if (value != 1 && value != 4) return VVHIP_ERR_INVALID; p->rdf_hist_copies = value; }
     else if (k == "rdf_items_target") { if (value < 1) return VVHIP_ERR_INVALID; p->rdf_items_target = value; }      // (read when a recorder starts: the work list is built there)
     else return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_tune: unknown key " + k);
@@ -186,7 +189,7 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
         const bool same = b->velm == o.velm && b->posq == o.posq && b->posq_correction == o.posq_correction && b->force == o.force &&
                           b->pos_delta == o.pos_delta && b->random == o.random && b->random_size == o.random_size;
         if (b->velm != o.velm) p->mass_tab_valid = false;
-        const Riders rd = riders(p);      // (a series row, a scheduled removal, a frame and a profile sample read velm through their captured arguments too; an MSD, RDF, density-mode or contact sample posq, a current sample all three, an autocorrelation sample velm or posq, a self van Hove sample posq)
+        const Riders rd = riders(p);      // (a series row, a scheduled removal, a frame and a profile sample read velm through their captured arguments too; an MSD, RDF, density-mode or contact sample posq, a current sample all three, an autocorrelation sample velm or posq, a self or distinct van Hove sample posq)
         if (!same || std::any_of(rd.begin(), rd.end(), [](const Rider& r) { return r.on; })) drop_graphs(p);
     }
     // a re-bind that moves the plan to another stream: whatever the plan still has in flight on the old one (fills, steps) must be
@@ -306,7 +309,7 @@ int vvhip_set_box(vvhip_plan* p, const double box[3]) {
     if (p->box[0] == box[0] && p->box[1] == box[1] && p->box[2] == box[2]) return VVHIP_OK;      // hosts re-send it every step
     for (int i = 0; i < 3; i++) p->box[i] = box[i];
     drop_graphs(p);                                  // the box is baked into the captured kernel arguments
-    return VVHIP_OK;
+    return box_changed(p);                           // (an origin of pair distances under the old box has no minimum image with the new one)
 }
 
 int vvhip_masses_changed(vvhip_plan* p) {

@@ -576,4 +576,34 @@ struct VanHoveArgs {
     double scale2, scale_hi, scale_lo, limit;      // 2^frac2_bits, 2^r4_hi_bits, 2^r4_lo_bits; |delta| at or beyond limit is out of range
 };
 
+// Distinct van Hove sample (vv_dev_vanhove_distinct.inc, include/vvhip.h: vvhip_vanhove_distinct_* states the sites, the classes, the
+// schedule, the arithmetic and the bins).  The sample ordinal and the origin floor are read from the device-side words, as for the self
+// recorder; whether the box still holds r_max is the host's decision at enqueue (`live`), as for an RDF sample.  One allocation: count
+// words, head[num_lags + 1][2], hist[num_classes][num_lags + 1][nbins], then num_origins + 2 plane sets double[3][stride]: the ring of
+// num_origins + 1 slots and the spare set of a sample that is no origin.  The work items are the RDF's (RdfItem; same != 0: ga == gb, the
+// item lists every j-site and the pair of a site with itself is masked).
+enum { VHD_SAMPLES = 0, VHD_DROPPED = 1, VHD_INVALID = 2, VHD_FLOOR = 3, VHD_HEAD = 4 };      // the words in front of the table
+enum { VHD_VISITS = 0, VHD_INV_VOLUME = 1, VHD_ROW = 2 };                                     // the words of head[l] ([1]: the bits of a double)
+struct VhdArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // [n] particle of site s; the sites are ordered by group, inside a group ascending by particle
+    const int32_t* mol;             // [n] molecule of site s (exclusion on, else null)
+    const RdfItem* items;           // [num_items]
+    long long* words;               // [VHD_HEAD + head_words + hist_words]
+    double* ring;                   // [num_origins + 2][3][stride], behind the table in the same allocation
+    int64_t max_samples;
+    int64_t head_words;             // (num_lags + 1) * 2: where hist starts behind the count words
+    int32_t n, stride;              // sites; n rounded up to 16
+    int32_t nbins, num_items;
+    int32_t num_lags, origin_every;
+    int32_t num_origins, copies;    // R = ceil(num_lags / origin_every); private histograms per block (1, or one per wave)
+    int32_t live, max_jsites;       // 0: the box no longer holds r_max, the sample is dropped; no item has more j-sites
+    double L[3], inv_L[3];          // the plan's box at enqueue and 1.0 / L[a], formed on the host
+    double dr, cut2;                // r_max / nbins; e(nbins)
+    float inv_dr;                   // 1 / dr, for the guess of the bin only
+    float pad_;
+    double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
+};
+
 }  // namespace vv

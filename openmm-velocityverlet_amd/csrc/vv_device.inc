@@ -26,3 +26,4 @@
 #include "vv_dev_contacts.inc"
 #include "vv_dev_acf.inc"
 #include "vv_dev_vanhove.inc"
+#include "vv_dev_vanhove_distinct.inc"

@@ -641,6 +641,34 @@ hipError_t launch_vanhove_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_vanhove_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+hipError_t launch_vhd(int precision, const VhdArgs& a, bool lds_hist, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: a private word cannot wrap, the histograms fit the block's LDS, the planes hold the sites, the grid's y
+    // extent holds the ring's slots
+    if (a.max_jsites < 1 || (long long) a.max_jsites * RDF_TILE >= (1ll << 32)) return hipErrorInvalidValue;
+    if (a.nbins < 1 || a.copies < 1 || a.copies > RDF_TILE / 64 || rdf_lds_bytes(a.nbins, a.copies) > PROFILE_LDS_BYTES) return hipErrorInvalidValue;
+    if (a.n < 0 || a.stride < a.n || a.num_items < 0 || !a.ring) return hipErrorInvalidValue;
+    if (a.origin_every < 1 || a.num_lags < 1 || a.num_origins < 1 || a.num_origins > 1024 || (long long) a.num_origins * a.origin_every < a.num_lags) return hipErrorInvalidValue;
+    const dim3 gg((unsigned) std::max(1, std::min((a.n + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_vhd_gather), gg, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 gp((unsigned) std::max(1, a.num_items), (unsigned) (a.num_origins + 1));
+    const unsigned lds = (unsigned) rdf_lds_bytes(lds_hist ? a.nbins : 0, a.copies);
+    if (a.mol) {
+        if (lds_hist) hipLaunchKernelGGL((vv_kernel_vhd_pairs<true, false>), gp, dim3(RDF_TILE), lds, s, a);
+        else hipLaunchKernelGGL((vv_kernel_vhd_pairs<true, true>), gp, dim3(RDF_TILE), lds, s, a);
+    } else {
+        if (lds_hist) hipLaunchKernelGGL((vv_kernel_vhd_pairs<false, false>), gp, dim3(RDF_TILE), lds, s, a);
+        else hipLaunchKernelGGL((vv_kernel_vhd_pairs<false, true>), gp, dim3(RDF_TILE), lds, s, a);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_vhd_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_vhd_floor(long long* words, hipStream_t s) {
+    hipLaunchKernelGGL(vv_kernel_vhd_floor, dim3(1), dim3(64), 0, s, words);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

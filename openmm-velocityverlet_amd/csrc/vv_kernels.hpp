@@ -117,5 +117,13 @@ hipError_t launch_acf_floor(long long* words, hipStream_t s);
 hipError_t launch_vanhove(int precision, const VanHoveArgs& a, int block_threads, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as VanHoveArgs::words.
 hipError_t launch_vanhove_floor(long long* words, hipStream_t s);
+// One distinct van Hove sample (vv_dev_vanhove_distinct.inc): the gather over a.n sites in blocks of 256 threads, at most grid_cap of them,
+// into the plane set of "now"; the pair kernel with one block of RDF_TILE threads per (work item, ring slot), grid (items, num_origins + 1),
+// and dynamic LDS of rdf_lds_bytes (lds_hist: the staged j-tile and a.copies private histograms; else the tile alone and every pair a global
+// add); then the one-thread kernel that counts the visits and advances the ordinal.  hipErrorInvalidValue where a.max_jsites * RDF_TILE >=
+// 2^32 or the ring has fewer slots than the lags need.
+hipError_t launch_vhd(int precision, const VhdArgs& a, bool lds_hist, int grid_cap, hipStream_t s);
+// The origin floor becomes the current sample ordinal (one thread, in the stream): words as VhdArgs::words.
+hipError_t launch_vhd_floor(long long* words, hipStream_t s);
 
 }  // namespace vv

@@ -1,9 +1,9 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, density modes, contact lifetimes, autocorrelations, self van Hove functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The eight accumulating recorders
-// share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for six,
-// units for three, sites ordered by group for four, classes for two); origins_dead tells the five with origins that the state was rewritten.
+// correlations, density modes, contact lifetimes, autocorrelations, self and distinct van Hove functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The nine accumulating recorders
+// share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for seven,
+// units for three, sites ordered by group for five, classes for three); origins_dead tells the six with origins that the state was rewritten.
 #include "vv_plan.hpp"
 
 #include <algorithm>
@@ -266,8 +266,33 @@ static int vanhove_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_vanhove(p->hp.precision, a, block_threads_for(p->vanhove_block_threads, a.n), std::min(p->grid_cap_a, p->profile_grid_cap), p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ distinct van Hove functions (vvhip_vanhove_distinct_*)
+// One sample behind the step just enqueued (or captured), and behind its self van Hove sample: the gather into the planes of "now", the
+// pair kernel over (work items) x (ring slots) and the one-thread kernel that counts the visits and advances the ordinal.  Three launches,
+// no memset, no copy and no host synchronisation.  The box and whether it still holds r_max are arguments: what changes the box drops
+// the captured graphs.
+static int vhd_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Vhd& V = p->vhd;
+    const vvhip_vanhove_distinct_layout& L = V.lay;
+    vv::VhdArgs a{};
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
+    a.index = V.dev.index.get(); a.mol = L.exclude_same_molecule ? V.dev.mol.get() : nullptr; a.items = V.dev.items.get();
+    a.words = V.d_words.get(); a.ring = (double*) (V.d_words.get() + V.table_offset() + L.words);
+    a.max_samples = L.max_samples; a.head_words = L.head_words;
+    a.n = (int32_t) V.index.size(); a.stride = V.stride(); a.nbins = L.nbins; a.num_items = (int32_t) V.items.size();
+    a.num_lags = L.num_lags; a.origin_every = L.origin_every; a.num_origins = L.num_origins;
+    // (one histogram per wave only where all of them fit beside the staged tile)
+    a.copies = p->vhd_lds && p->vhd_hist_copies > 1 && vv::rdf_lds_bytes(L.nbins, vv::RDF_TILE / 64) <= vv::PROFILE_LDS_BYTES ? vv::RDF_TILE / 64 : 1;
+    a.live = box_holds(p->box, L.r_max) ? 1 : 0;
+    a.max_jsites = V.max_jsites;
+    for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
+    a.dr = L.dr; a.cut2 = ((double) L.nbins * L.dr) * ((double) L.nbins * L.dr); a.inv_dr = (float) (1.0 / L.dr);
+    a.inv_volume = 1.0 / ((p->box[0] * p->box[1]) * p->box[2]);
+    HIP_TRY(p, vv::launch_vhd(p->hp.precision, a, p->vhd_lds != 0, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
 // The positions or the velocities were rewritten outside the steps (vv_barostat.cpp; vvhip_set_velocities_to_temperature): the origins that
-// the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, vanhove, their floors raised in this order; velocities:
+// the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, vanhove, vhd, their floors raised in this order; velocities:
 // acf, unless it records orientations.  A contact set belongs to a configuration, not to a displacement: contacts reacts to neither.
 int origins_dead(vvhip_plan* p, Rewrote what) {
     if (what == Rewrote::POSITIONS) {
@@ -275,7 +300,14 @@ int origins_dead(vvhip_plan* p, Rewrote what) {
         if (p->current.on) HIP_TRY(p, vv::launch_current_floor(p->current.d_words.get(), p->stream));
         if (p->modes.on) HIP_TRY(p, vv::launch_modes_floor(p->modes.d_words.get(), p->stream));
         if (p->vanhove.on) HIP_TRY(p, vv::launch_vanhove_floor(p->vanhove.d_words.get(), p->stream));
+        if (p->vhd.on) HIP_TRY(p, vv::launch_vhd_floor(p->vhd.d_words.get(), p->stream));
     } else if (p->acf.on && p->acf.lay.mode != VVHIP_ACF_ORIENTATION) HIP_TRY(p, vv::launch_acf_floor(p->acf.d_words.get(), p->stream));
+    return VVHIP_OK;
+}
+// vvhip_set_box replaced the box with another one: the distinct van Hove recorder's origins have no minimum image with it.  (The recorders
+// of displacements keep theirs: an unwrapped displacement does not depend on the box.)
+int box_changed(vvhip_plan* p) {
+    if (p->vhd.on && !p->capturing) HIP_TRY(p, vv::launch_vhd_floor(p->vhd.d_words.get(), p->stream));
     return VVHIP_OK;
 }
 // ------------------------------------------------------------------------------------------ centre-of-mass motion (vvhip_cm_motion_*)
@@ -324,10 +356,11 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   7 density-mode sample   behind the current sample; all of d_words likewise (its turns are scratch, rewritten by every sample)
 //   8 contact sample    behind the density-mode sample; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
 //   9 autocorrelation sample   behind the contact sample; all of d_words, the ring of origins included, as for the MSD
-//  10 self van Hove sample   last; all of d_words likewise: head, histogram and the ring of origins
-// Riders 3 .. 10 are the eight accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
-// host tables come from "the shared pieces of a start" below (units: 4, 9 and 10; sites ordered by group: 5 .. 8; the lag schedule: 4, 6 .. 10),
-// and origins_dead above reaches 4, 6, 7, 10 (positions) and 9 (velocities).
+//  10 self van Hove sample   behind the autocorrelation sample; all of d_words likewise: head, histogram and the ring of origins
+//  11 distinct van Hove sample   last; all of d_words: counts, head, histogram, the ring of origins and the spare planes
+// Riders 3 .. 11 are the nine accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
+// host tables come from "the shared pieces of a start" below (units: 4, 9 and 10; sites ordered by group: 5 .. 8 and 11; the lag schedule: 4, 6 .. 11),
+// and origins_dead above reaches 4, 6, 7, 10, 11 (positions) and 9 (velocities).
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
 Riders riders(vvhip_plan* p) {
@@ -336,7 +369,7 @@ Riders riders(vvhip_plan* p) {
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
              recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue),
-             recorder_rider(p->acf, acf_enqueue), recorder_rider(p->vanhove, vanhove_enqueue)}};
+             recorder_rider(p->acf, acf_enqueue), recorder_rider(p->vanhove, vanhove_enqueue), recorder_rider(p->vhd, vhd_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -358,7 +391,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the eight accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the nine accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -426,10 +459,10 @@ static int recorder_info(const vvhip_plan* p, R vvhip_plan::* which, L* out, L b
 // ------------------------------------------------------------------------------------------ the shared pieces of a start
 // The host-only part of the accumulating recorders' *_start, stated once; `name` is the prefix of the messages.  What a recorder still
 // writes itself: its own argument checks, its layout, its fixed point (but for units_frac_bits), its work list, its enqueue.
-//   check_groups, check_max_samples   all eight               check_lags            msd, acf, vanhove, current, modes, contacts
-//   num_origins_of                    msd, acf, vanhove, current, modes; check_origins       msd, acf, vanhove, contacts
-//   plan_units, fill_units   msd, acf, vanhove; units_frac_bits   msd, acf        sites_by_group        rdf, current, modes, contacts
-//   check_classes, check_pair_count, check_half_box (beside box_holds), no_pairs_across_shards   rdf, contacts;   no_sums_across_shards   current, modes
+//   check_groups, check_max_samples   all nine                check_lags            msd, acf, vanhove, vhd, current, modes, contacts
+//   num_origins_of                    msd, acf, vanhove, vhd, current, modes; check_origins       msd, acf, vanhove, vhd, contacts
+//   plan_units, fill_units   msd, acf, vanhove; units_frac_bits   msd, acf        sites_by_group        rdf, vhd, current, modes, contacts
+//   check_classes, check_pair_count, check_half_box (beside box_holds), no_pairs_across_shards   rdf, vhd, contacts;   no_sums_across_shards   current, modes
 // group[i] of every particle of the System (or, count >= 0, of `count` entries) against [-1, num_groups) (group = null: everything in group 0)
 static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups, int32_t count = -1) {
     for (int32_t i = 0; group && i < (count < 0 ? p->hp.num_atoms : count); i++)
@@ -1083,6 +1116,80 @@ int vvhip_vanhove_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words
 }
 int vvhip_vanhove_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::vanhove, "vanhove"); }
 int vvhip_vanhove_info(const vvhip_plan* p, vvhip_vanhove_layout* out) { return recorder_info(p, &vvhip_plan::vanhove, out); }
+
+int vvhip_vanhove_distinct_start(vvhip_plan* p, const vvhip_vanhove_distinct_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: null description");
+    TRY(check_lags(p, "vanhove_distinct", d->interval, d->num_lags, d->origin_every));
+    if (!(d->r_max > 0) || !std::isfinite(d->r_max)) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: r_max must be finite and > 0");
+    if (d->nbins < 1 || d->nbins > 8192) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: nbins must be in [1, 8192]");
+    if (d->num_groups < 1 || d->num_groups > vv::RDF_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: num_groups must be in [1, 16]");
+    if (d->num_classes < 1 || d->num_classes > vv::RDF_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: num_classes must be in [1, 32]");
+    if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: classes must not be NULL");
+    TRY(check_max_samples(p, "vanhove_distinct", d->max_samples));
+    TRY(check_groups(p, "vanhove_distinct", d->group, d->num_groups));
+    TRY(check_classes(p, "vanhove_distinct", d->classes, d->num_classes, d->num_groups));
+    // ---- the sites, the layout and the pair kernel's work list, host only
+    vvhip_plan::Vhd N;
+    vvhip_vanhove_distinct_layout& L = N.lay;
+    L.interval = d->interval; L.num_lags = d->num_lags; L.origin_every = d->origin_every; L.nbins = d->nbins;
+    L.num_groups = d->num_groups; L.num_classes = d->num_classes;
+    L.exclude_same_molecule = d->exclude_same_molecule != 0; L.tile = vv::RDF_TILE;
+    L.num_origins = num_origins_of(d->num_lags, d->origin_every); L.num_rows = d->num_lags + 1;
+    L.max_samples = d->max_samples;
+    L.head_words = (int64_t) L.num_rows * vv::VHD_ROW;
+    L.hist_words = (int64_t) d->num_classes * L.num_rows * d->nbins;
+    L.words = L.head_words + L.hist_words;
+    L.r_max = d->r_max; L.dr = d->r_max / (double) d->nbins;
+    if (L.words > VVHIP_VANHOVE_DISTINCT_MAX_WORDS)
+        return fail(p, VVHIP_ERR_INVALID, "vanhove_distinct: the table would have " + std::to_string((long long) L.words) + " words ((num_lags + 1) * (2 + num_classes * nbins)), above the cap of " +
+                                          std::to_string((long long) VVHIP_VANHOVE_DISTINCT_MAX_WORDS) + " (32 MiB): fewer lags, bins or classes");
+    TRY(check_origins(p, "vanhove_distinct", L.num_origins));
+    Sites S = sites_by_group(p->hp, d->group, d->num_groups, L.exclude_same_molecule != 0, nullptr, false);
+    std::copy(S.count, S.count + d->num_groups, L.num_sites);
+    const int32_t* first = S.first;
+    int64_t largest = 0;
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int ga = d->classes[2 * c], gb = d->classes[2 * c + 1];
+        const int64_t na = L.num_sites[ga], nb = L.num_sites[gb];
+        L.classes[c][0] = ga; L.classes[c][1] = gb;
+        L.pairs_per_sample[c] = ga == gb ? na * (na - 1) : na * nb;
+        largest = std::max(largest, L.pairs_per_sample[c]);
+    }
+    TRY(check_pair_count(p, "vanhove_distinct", largest, d->max_samples, "bin"));
+    TRY(check_half_box(p, "vanhove_distinct", "r_max = ", d->r_max));
+    TRY(no_pairs_across_shards(p, "vanhove_distinct", "histogram"));
+    N.index = std::move(S.index); N.mol = std::move(S.mol);
+    L.ring_bytes = (int64_t) (L.num_origins + 2) * 3 * N.stride() * (int64_t) sizeof(double);
+    // the work list: per class and i-tile the j-sites in runs of `max_jsites`, a multiple of 64, as for the RDF -- but all j-sites for a
+    // class of one group with itself too (the pairs are ordered).  Every item runs once per ring slot, so the target counts items, not blocks
+    constexpr int T = vv::RDF_TILE;
+    long long runs = 0;                                     // of 64 j-sites, over all i-tiles
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int64_t na = L.num_sites[L.classes[c][0]], nb = L.num_sites[L.classes[c][1]];
+        runs += (na + T - 1) / T * ((nb + 63) / 64);
+    }
+    const int target = std::max(1, p->vhd_items_target);
+    N.max_jsites = 64 * (int) std::max<long long>(1, std::min<long long>(4096, (runs + target - 1) / target));
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int ga = L.classes[c][0], gb = L.classes[c][1];
+        const int32_t na = L.num_sites[ga], nb = L.num_sites[gb];
+        if (ga == gb && na < 2) continue;                  // (no pair)
+        for (int32_t i0 = 0; i0 < na; i0 += T)
+            for (int32_t j0 = 0; j0 < nb; j0 += N.max_jsites)
+                N.items.push_back({c, ga == gb ? 1 : 0, first[ga] + i0, std::min(T, na - i0), first[gb], j0, std::min(nb, j0 + N.max_jsites), 0});
+    }
+    L.num_items = (int32_t) N.items.size();
+    return recorder_install(p, &vvhip_plan::vhd, "vanhove_distinct", N, d->interval);
+}
+int vvhip_vanhove_distinct_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_vanhove_distinct_counts* out, int32_t reset) {
+    long long head[vv::VHD_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::vhd, "vanhove_distinct", words_out, capacity_words, head));
+    if (out) *out = {head[vv::VHD_SAMPLES], head[vv::VHD_DROPPED], head[vv::VHD_INVALID], head[vv::VHD_FLOOR]};
+    return reset ? recorder_reset(p, p->vhd) : VVHIP_OK;
+}
+int vvhip_vanhove_distinct_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::vhd, "vanhove_distinct"); }
+int vvhip_vanhove_distinct_info(const vvhip_plan* p, vvhip_vanhove_distinct_layout* out) { return recorder_info(p, &vvhip_plan::vhd, out); }
 
 int vvhip_rdf_start(vvhip_plan* p, const vvhip_rdf_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;

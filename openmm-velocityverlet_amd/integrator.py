@@ -725,6 +725,94 @@ def rdf_from_words(words, layout, counts) -> Rdf:
 
 
 @dataclasses.dataclass
+class VanHoveDistinct:
+    """The distinct part of the van Hove function per ordered class, lag and bin (Context.vanhove_distinct_read; include/vvhip.h:
+    vvhip_vanhove_distinct_* states the sites, the classes, the schedule, the arithmetic and the bins).  `head` and `hist` are the device's
+    table as it stands: int64 [rows, 2] -- the visits and the bits of the float64 sum of 1 / V over them -- and int64 [classes, rows, bins];
+    row 0 is the sample against itself, row l the lag of l * interval steps."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples or in a box too small for r_max: nothing was added or stored
+    invalid: int                           # pairs whose squared distance was NaN
+    origin_floor: int                      # origins with an ordinal below it are dead (the box or the positions were rewritten)
+    interval: int
+    origin_every: int
+    r_max: float
+    dr: float
+    classes: np.ndarray                    # int32 [classes, 2]: the group at the origin, the group now
+    num_sites: np.ndarray                  # int64 [groups]
+    pairs_per_sample: np.ndarray           # int64 [classes]: N_a N_b, or N_a (N_a - 1) for a class of one group with itself
+    head: np.ndarray                       # int64 [rows, 2]
+    hist: np.ndarray                       # int64 [classes, rows, bins]
+
+    @property
+    def lag_steps(self) -> np.ndarray:
+        """int64 [rows]: row l is the lag of l * interval steps."""
+        return np.arange(self.head.shape[0], dtype=np.int64) * self.interval
+
+    @property
+    def visits(self) -> np.ndarray:
+        """int64 [rows]: the (origin, sample) visits behind every row."""
+        return self.head[:, 0]
+
+    @property
+    def inv_volume_sum(self) -> np.ndarray:
+        """float64 [rows]: 1 / V in nm^-3 summed over the row's visits, in sample order."""
+        return np.ascontiguousarray(self.head[:, 1]).view(np.float64)
+
+    @property
+    def edges2(self) -> np.ndarray:
+        """float64 [bins + 1]: the squared edges e(k) the device compares against."""
+        return rdf_edges(self.r_max, self.hist.shape[2])
+
+    @property
+    def edges(self) -> np.ndarray:
+        """float64 [bins + 1]: the bin edges in nm, sqrt(e(k))."""
+        return np.sqrt(self.edges2)
+
+    @property
+    def r(self) -> np.ndarray:
+        """float64 [bins]: the bin centres in nm."""
+        e = self.edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    @property
+    def shell_volumes(self) -> np.ndarray:
+        """float64 [bins]: 4 pi / 3 (e+^3 - e-^3) in nm^3, exact for the edges as they are."""
+        e3 = self.edges ** 3
+        return 4.0 * np.pi / 3.0 * (e3[1:] - e3[:-1])
+
+    def G_d(self, c: int = 0) -> np.ndarray:
+        """float64 [rows, bins]: hist / (P_c * shell volume * inv_volume_sum of the row) -- G_d(r, t) over the mean density of the later
+        group, which tends to 1 at large r; NaN where the class has no pair or a row no visit."""
+        norm = float(self.pairs_per_sample[c]) * self.shell_volumes[None, :] * self.inv_volume_sum[:, None]
+        return np.where(norm > 0, self.hist[c] / np.where(norm > 0, norm, 1.0), np.nan)
+
+    def g(self, c: int = 0) -> np.ndarray:
+        """float64 [bins]: row 0 of G_d, the radial distribution function of the class (Rdf.g of the unordered class where ga == gb)."""
+        return self.G_d(c)[0]
+
+    def coordination(self, c: int = 0) -> np.ndarray:
+        """float64 [rows, bins]: the running integral up to every bin's outer edge: sites of the later group within that distance of where
+        a site of the origin group was, averaged over the row's visits and the origin group's sites."""
+        denom = float(self.num_sites[self.classes[c, 0]]) * self.visits.astype(np.float64)[:, None]
+        return np.where(denom > 0, np.cumsum(self.hist[c], axis=1) / np.where(denom > 0, denom, 1.0), np.nan)
+
+
+def vanhove_distinct_from_words(words, layout, counts) -> VanHoveDistinct:
+    """A VanHoveDistinct from a table's int64 words (head [rows * 2], then hist [classes * rows * bins]), its layout
+    (H.VanHoveDistinctLayout) and counts (H.VanHoveDistinctCounts)."""
+    words = np.ascontiguousarray(words, dtype=np.int64)
+    nc, ng, rows, nb, hw = int(layout.num_classes), int(layout.num_groups), int(layout.num_rows), int(layout.nbins), int(layout.head_words)
+    return VanHoveDistinct(samples=int(counts.samples), dropped=int(counts.dropped), invalid=int(counts.invalid),
+                           origin_floor=int(counts.origin_floor), interval=int(layout.interval), origin_every=int(layout.origin_every),
+                           r_max=float(layout.r_max), dr=float(layout.dr),
+                           classes=np.array([[layout.classes[c][0], layout.classes[c][1]] for c in range(nc)], dtype=np.int32).reshape(nc, 2),
+                           num_sites=np.array(layout.num_sites[:ng], dtype=np.int64),
+                           pairs_per_sample=np.array(layout.pairs_per_sample[:nc], dtype=np.int64),
+                           head=words[:hw].reshape(rows, 2).copy(), hist=words[hw:hw + nc * rows * nb].reshape(nc, rows, nb).copy())
+
+
+@dataclasses.dataclass
 class Contacts:
     """Contact lifetime correlations per class and lag (Context.contacts_read; include/vvhip.h: vvhip_contacts_* states the sites, the
     classes, the contact, the slots and the table).  `words` is the device's table as it stands, int64 [classes, lags, 4]: per lag the
@@ -1333,7 +1421,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the eight accumulating recorders below share: profile, msd, acf, vanhove, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the nine accumulating recorders below share: profile, msd, acf, vanhove, vanhove_distinct, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1486,6 +1574,36 @@ class Context:
         """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
         schedule continues without gap or repeat."""
         return self._recorder_read("vanhove", H.VanHoveLayout, H.VanHoveCounts, vanhove_from_words, reset, getattr(self, "_vanhove_edges", None))
+
+    # ---- distinct van Hove functions accumulated on the device inside the steps (include/vvhip.h: vvhip_vanhove_distinct_*)
+    def vanhove_distinct_start(self, interval: int, num_lags: int, r_max: float, nbins: int, classes, origin_every: int = 1, groups=None,
+                               exclude_same_molecule: bool = False, max_samples: int = 1 << 20):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), histogram, for every class and
+        every stored origin that is alive, the minimum-image distances between where the sites of the class's first group were at the
+        origin and where the sites of its second group are now, into `nbins` bins of width r_max / nbins (nm), in row l = the lag in
+        samples (0 .. `num_lags`; row 0 is the sample against itself), as integers, so that the table is the same bits for any launch
+        shape.  Every `origin_every`-th sample is stored as an origin.  `groups`: one int per particle of the System (-1: no site);
+        None: everything in group 0.  `classes`: ORDERED pairs of groups (ga at the origin, gb now); ga == gb counts every ordered pair of
+        two different sites.  exclude_same_molecule leaves out the pairs inside one molecule.  r_max must not exceed half the shortest
+        box edge.  A sharded context raises ERR_UNSUPPORTED.  No host synchronisation until vanhove_distinct_read."""
+        grp = self._groups(groups)
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1, 2)
+        num_groups = max(1, 0 if grp is None else int(grp.max()) + 1, int(cls.max()) + 1 if cls.size else 1)      # (a class may name a group without sites)
+        desc = H.VanHoveDistinctDesc(int(interval), int(num_lags), int(origin_every), int(nbins), num_groups, int(cls.shape[0]),
+                                     int(bool(exclude_same_molecule)), 0, None if grp is None else grp.ctypes.data, cls.ctypes.data,
+                                     int(max_samples), float(r_max))
+        H.check(H.lib.vvhip_vanhove_distinct_start(self.plan, C.byref(desc)), self.plan)
+
+    def vanhove_distinct_stop(self):
+        self._recorder_stop("vanhove_distinct")
+
+    def vanhove_distinct_info(self) -> H.VanHoveDistinctLayout:
+        return self._recorder_info("vanhove_distinct", H.VanHoveDistinctLayout)
+
+    def vanhove_distinct_read(self, reset: bool = False) -> VanHoveDistinct:
+        """The table accumulated so far (synchronises).  reset=True zeroes it and restarts the sample ordinal with no live origin; the step
+        schedule continues without gap or repeat."""
+        return self._recorder_read("vanhove_distinct", H.VanHoveDistinctLayout, H.VanHoveDistinctCounts, vanhove_distinct_from_words, reset)
 
     # ---- radial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_rdf_*)
     def rdf_start(self, interval: int, r_max: float, nbins: int, classes, groups=None, exclude_same_molecule: bool = False,
@@ -1699,7 +1817,7 @@ class Context:
     def loadCheckpoint(self, blob):
         """Put a blob of createCheckpoint back: the run continues with the bits of the run that wrote it.  The blob is verified (format,
         every section's digest), compared with this context's structure, uploaded, and the device state verified against its digests.  The
-        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation or self van Hove recorder must be stopped first and started again afterwards, as
+        integrator's parameters are NOT taken from the blob.  A running series, frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation, self or distinct van Hove recorder must be stopped first and started again afterwards, as
         must a removal schedule whose record is to start over; a sharded context refuses."""
         blob = bytes(blob)
         words = (C.c_uint64 * 4)()

@@ -22,6 +22,8 @@ latest three kept.
 
 ``write_vanhove`` writes a device-side self van Hove table (``Context.vanhove_read``) as text columns, one line per lag.
 
+``write_vanhove_distinct`` writes one class of a device-side distinct van Hove table (``Context.vanhove_distinct_read``) as text columns, one line per bin.
+
 ``write_rdf`` writes device-side radial distribution functions (``Context.rdf_read``) as text columns, one line per bin.
 
 ``write_current`` writes a device-side collective current correlation table (``Context.current_read``) as text columns, one line per lag.
@@ -366,6 +368,29 @@ def write_modes(file, dm, dt, g=0, h=0, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name in names), file=out)
         for m in range(F.shape[1]):
             print(*[str(int(c)) for c in dm.modes[m]], repr(float(k[m])), *[repr(float(v)) for v in F[:, m]], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_vanhove_distinct(file, vhd, dt, c=0, append=False, header=True):
+    """One class of a distinct van Hove table (Context.vanhove_distinct_read) as text: three comment lines (samples, dropped, invalid,
+    origin floor; per row the visits; the column names) unless header=False, then one tab-separated line per bin -- the bin centre in nm,
+    then G_d of class `c` for every row from the zero lag on (the lag times in ps, lag steps x `dt`, are in the column names; nan where a
+    row has no visit).  Floats are written with repr, so np.loadtxt reads back the bits.  `file`: a path or an open text stream."""
+    G = vhd.G_d(c)
+    r = vhd.r
+    lags = vhd.lag_steps.astype(np.float64) * float(dt)
+    tag = "%d-%d" % (int(vhd.classes[c, 0]), int(vhd.classes[c, 1]))
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"Invalid"\t%d\t"OriginFloor"\t%d' % (vhd.samples, vhd.dropped, vhd.invalid, vhd.origin_floor), file=out)
+            print('#"Visits"\t' + "\t".join(str(int(v)) for v in vhd.visits), file=out)
+            print("#" + "\t".join('"%s"' % name for name in ["r (nm)"] + ["G_d[%s](%r ps)" % (tag, float(t)) for t in lags]), file=out)
+        for b in range(G.shape[1]):
+            print(repr(float(r[b])), *[repr(float(v)) for v in G[:, b]], sep="\t", file=out)
         out.flush()
     finally:
         if own:

@@ -289,6 +289,29 @@ class VanHoveLayout(C.Structure):
                 ("start_step", C.c_int64), ("limit", C.c_double)]
 
 
+VANHOVE_DISTINCT_MAX_WORDS = 1 << 22
+
+
+class VanHoveDistinctDesc(C.Structure):
+    """What a distinct van Hove recorder is to accumulate (include/vvhip.h: vvhip_vanhove_distinct_desc)."""
+    _fields_ = [("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("nbins", C.c_int32),
+                ("num_groups", C.c_int32), ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("reserved", C.c_int32),
+                ("group", C.c_void_p), ("classes", C.c_void_p), ("max_samples", C.c_int64), ("r_max", C.c_double)]
+
+
+class VanHoveDistinctCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("invalid", C.c_int64), ("origin_floor", C.c_int64)]
+
+
+class VanHoveDistinctLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("num_lags", C.c_int32), ("origin_every", C.c_int32), ("nbins", C.c_int32),
+                ("num_groups", C.c_int32), ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("tile", C.c_int32),
+                ("num_items", C.c_int32), ("num_origins", C.c_int32), ("num_rows", C.c_int32), ("num_sites", C.c_int32 * 16),
+                ("classes", (C.c_int32 * 2) * 32), ("pairs_per_sample", C.c_int64 * 32), ("max_samples", C.c_int64), ("words", C.c_int64),
+                ("head_words", C.c_int64), ("hist_words", C.c_int64), ("ring_bytes", C.c_int64), ("start_step", C.c_int64),
+                ("r_max", C.c_double), ("dr", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -389,6 +412,9 @@ def _load():
         "vvhip_acf_read": [vp, vp, C.c_int64, P(AcfCounts), i32],
         "vvhip_vanhove_start": [vp, P(VanHoveDesc)], "vvhip_vanhove_stop": [vp], "vvhip_vanhove_info": [vp, P(VanHoveLayout)],
         "vvhip_vanhove_read": [vp, vp, C.c_int64, P(VanHoveCounts), i32],
+        "vvhip_vanhove_distinct_start": [vp, P(VanHoveDistinctDesc)], "vvhip_vanhove_distinct_stop": [vp],
+        "vvhip_vanhove_distinct_info": [vp, P(VanHoveDistinctLayout)],
+        "vvhip_vanhove_distinct_read": [vp, vp, C.c_int64, P(VanHoveDistinctCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
