@@ -1229,7 +1229,7 @@ int vvhip_vanhove_info(const vvhip_plan* plan, vvhip_vanhove_layout* out);
  * (vvhip_vanhove_*) the G(r, t) that a scattering experiment measures.  A host cannot produce it during a run: every pair of sites of every
  * sample against every stored origin, (live origins + 1) times the RDF's O(N_a N_b) pair work per sample, on float64 frames of 24 B per
  * site and sample.  After every full step whose count is a multiple of `interval` -- counted exactly as for the other riders; a sample
- * "after step k" is enqueued behind that step's self van Hove sample, the twelfth and last rider -- the step entry point enqueues three
+ * "after step k" is enqueued behind that step's self van Hove sample, the twelfth rider -- the step entry point enqueues three
  * kernels (csrc/vv_dev_vanhove_distinct.inc): a gather of the sites' float64 positions into the planes of "now", the pair kernel over (work
  * items) x (ring slots), and a one-thread kernel that counts the visits and advances the ordinal: no memset, no copy, no host work.  Inside
  * a captured graph all three are graph nodes and the steps that take a sample are part of the graph-cache key.  The recorder reads posq and
@@ -1328,6 +1328,122 @@ int vvhip_vanhove_distinct_read(vvhip_plan* plan, int64_t* words_out, int64_t ca
 int vvhip_vanhove_distinct_stop(vvhip_plan* plan);
 /* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
 int vvhip_vanhove_distinct_info(const vvhip_plan* plan, vvhip_vanhove_distinct_layout* out);
+/* ---------------------------------------------------------------- spatial distribution functions accumulated on the device
+ * Where the sites sit around a molecule in the molecule's own body frame -- for an imidazolium cation: the anions above the ring, at the
+ * C2-H, along the alkyl tail -- the one structure function g(r) cannot give, because g(r) averages exactly these directions.  Per sample
+ * it costs what an RDF costs, O(N_frames N_sites), plus a frame per molecule, and its table is three-dimensional, so it wants far more
+ * samples than a g(r) before the voxels are smooth: from downloaded frames that is hours on a host.  After every full step whose count is
+ * a multiple of `interval` -- counted exactly as for the other riders; a sample "after step k" is enqueued behind that step's distinct van
+ * Hove sample, the thirteenth and last rider -- the step entry point enqueues three kernels (csrc/vv_dev_sdf.inc): a gather of the sites'
+ * float64 positions and of the frames into planar scratch, the pair kernel, and a one-thread kernel that counts the sample: no memset, no
+ * host work.  Inside a captured graph all three are graph nodes and the steps that take a sample are part of the graph-cache key.  The
+ * recorder reads posq and posqCorrection and writes its own words and scratch, nothing else; a plan that never starts one launches what it
+ * launched before and allocates nothing.
+ * Position.  X_i in float64 exactly as for the RDF: (double) posq + (double) posqCorrection in mixed precision, (double) posq otherwise.
+ * Frames.  frames[f] = {o, a, b}, num_frames >= 0 triplets of particle indices of the System, pairwise different and in one molecule
+ * (vvhip_system_desc.mol_id).  frame_group[f] is one byte per frame, -1: not recorded; NULL puts every frame into group 0;
+ * num_frame_groups is 1 .. 16.  Molecules are stored whole and unwrapped (as for the orientation units of vvhip_acf_*), so no minimum image
+ * is taken inside a frame.  All float64, no contraction, every product rounded before its sum or difference is taken:
+ *     p = X_a - X_o;   q = X_b - X_o
+ *     n1 = (p_x p_x + p_y p_y) + p_z p_z;     e1 = p * acf_inverse_norm(n1)
+ *     t  = (q_x e1_x + q_y e1_y) + q_z e1_z;  w_c = q_c - t * e1_c
+ *     n2 = (w_x w_x + w_y w_y) + w_z w_z;     e2 = w * acf_inverse_norm(n2)
+ *     e3_x = e1_y e2_z - e1_z e2_y;   e3_y = e1_z e2_x - e1_x e2_z;   e3_z = e1_x e2_y - e1_y e2_x
+ * with acf_inverse_norm the one sequence of +, -, * of the orientation autocorrelation (csrc/vv_layout.h; tests/acf_reference.py:
+ * inverse_norm), the same bits on device and host.  e1 points from o to a, e2 lies in the plane of o, a, b on b's side, e3 = e1 x e2 is
+ * right-handed.  A frame is bad in a sample when n1 or n2 is NaN or outside [2^-40, 2^40) nm^2 (n2 is not formed where n1 is): it takes
+ * part in no pair of that sample and adds 1 to bad_frames; a good frame of a counted sample adds 1 to frame_visits[its group].
+ * Sites.  The particles with site_group[i] >= 0 over the whole System; NULL puts every particle into group 0; num_site_groups is 1 .. 16.
+ * Classes.  num_classes (1 .. 16) ordered pairs classes[c] = {frame group, site group}; every (good frame, site) pair of the two groups
+ * counts, pairs_per_sample[c] = N_frames N_sites.  With exclude_same_molecule != 0 a site whose mol_id is that of the frame's o is counted
+ * nowhere (not in `invalid` either); without it the frame's own atoms are sites like any other (o itself lands at xi = 0).
+ * Pair.  d = X_s - X_o per axis with the RDF's minimum image, L the plan's box when the sample is enqueued, inv_L_a = 1.0 / L_a formed once
+ * per sample:   n = rint(d * inv_L_a)  (round-half-even);   d = d - L_a * n.   Then  xi_k = (d_x e_k,x + d_y e_k,y) + d_z e_k,z,  k = 1, 2, 3.
+ * Voxels.  A cube of half-extent `extent` (h, nm) in frame coordinates with nbins (n, 1 .. 128) voxels per axis; inv_w = (double) n /
+ * (2.0 * h) formed once; u_k = (xi_k + h) * inv_w.  The pair is in range iff 0 <= u_k < n for all three k, and then adds the integer 1 to
+ * table[c][(int) u_1][(int) u_2][(int) u_3]; a pair out of range on any axis adds nothing; a pair of a good frame with a NaN among its u
+ * adds 1 to `invalid` and to no voxel.  These comparisons and conversions define the voxel.  The kernel puts a cheaper test in front of
+ * them, r2 = (d_x d_x + d_y d_y) + d_z d_z against 3 h^2 (1 + 2^-20) / (1 - delta) with delta bounding how far the frame's e_k as stored
+ * are from orthonormal (csrc/vv_dev_sdf.inc proves it conservative: it rejects only pairs the comparisons reject); it is no part of the
+ * definition.  (Positions are taken to be below 2^500 nm: beyond, a product overflows and the cheap test and the comparisons may differ.)
+ * Table: int64 table[num_classes][n][n][n], xi_1 outermost; words = num_classes n^3, at most VVHIP_SDF_MAX_WORDS = 2^23 (64 MiB).  Integer
+ * adds commute: the table is the same bits for any grid, tile shape or arrival order.
+ *     density_c(v) = table[c][v] / (frame_visits[frame group] * voxel^3),  voxel = 2 h / n;   g_c(v) = density_c(v) / (N_sites *
+ *     inv_volume_sum / samples), which tends to 1 far from the molecule.
+ * Range.  h is finite and > 0, and 3 h^2 < (min(Lx, Ly, Lz) / 2)^2 for the plan's box at the start: the cube's corners then lie inside
+ * one sphere that holds at most one image of any site, and that image is the per-axis minimum image.  A sample enqueued while the plan's
+ * box no longer satisfies this (vvhip_set_box, the barostat's moves) adds nothing -- no visit, no bad frame -- and counts as dropped; back
+ * in range the samples count again.  The box is a kernel argument: what changes it drops the captured graphs.
+ * Counts.  samples; dropped (due past max_samples, or in a box too small for the cube); invalid; bad_frames; inv_volume_sum, the RDF's
+ * sequential float64 sum  s = s + 1.0 / ((Lx * Ly) * Lz)  over the counted samples; frame_visits[16].
+ * Overflow.  Refused at the start where the largest class's N_frames N_sites times max_samples reaches 2^62.
+ * Sharded plans are refused (VVHIP_ERR_UNSUPPORTED): pairs across shards exist on no device.
+ * Recovery.  The rider's recovery words are the whole allocation, counts and table, (21 + words) * 8 B -- up to 64 MiB, and that is what a
+ * recovery snapshot copies per run call while the recorder runs; the scratch is rewritten by every sample and is not saved.
+ * vvhip_checkpoint_load is refused while a recorder runs, a re-bind drops the captured graphs, as for the RDF. */
+#define VVHIP_SDF_MAX_WORDS (1ll << 23)
+typedef struct {
+    int32_t interval;               /* a sample after every step whose count is a multiple of it */
+    int32_t nbins;                  /* n, 1 .. 128 voxels per axis */
+    int32_t num_frames;             /* >= 0 */
+    int32_t num_frame_groups;       /* 1 .. 16 */
+    int32_t num_site_groups;        /* 1 .. 16 */
+    int32_t num_classes;            /* 1 .. 16 */
+    int32_t exclude_same_molecule;  /* != 0: the sites of the frame's own molecule (mol_id) are left out */
+    int32_t reserved;               /* 0 */
+    const int32_t* frames;          /* [num_frames][3] the particles o, a, b of every frame */
+    const signed char* frame_group; /* [num_frames] the group of every frame, -1: not recorded; NULL: every frame in group 0 */
+    const signed char* site_group;  /* [num_atoms] the group of every particle of the System, -1: no site; NULL: everything in group 0 */
+    const int32_t* classes;         /* [num_classes][2] frame group, site group of every class */
+    int64_t max_samples;            /* >= 1 */
+    double extent;                  /* h, nm: the cube is [-h, h)^3 in frame coordinates */
+} vvhip_sdf_desc;
+typedef struct {
+    int64_t samples;                /* samples counted since the start or the last reset (at most max_samples) */
+    int64_t dropped;                /* samples that were due past max_samples or in a box too small for the cube: nothing was added */
+    int64_t invalid;                /* pairs of a good frame with a NaN among u_1, u_2, u_3 */
+    int64_t bad_frames;             /* (frame, counted sample) visits whose n1 or n2 was NaN or outside [2^-40, 2^40) */
+    double inv_volume_sum;          /* the counted samples' 1 / V, summed in sample order */
+    int64_t frame_visits[16];       /* per frame group: the good frames of the counted samples */
+} vvhip_sdf_counts;
+typedef struct {
+    int32_t active, interval, nbins, num_frame_groups, num_site_groups, num_classes, exclude_same_molecule;
+    int32_t tile;                   /* frames per tile of the pair kernel (a frame count of tile + 1 is the first with a second tile) */
+    int32_t num_items;              /* blocks of the pair kernel per sample */
+    int32_t reserved;               /* 0 */
+    int32_t num_frames[16];         /* per frame group */
+    int32_t num_sites[16];          /* per site group */
+    int32_t classes[16][2];
+    int64_t pairs_per_sample[16];   /* per class: N_frames N_sites (the exclusion does not lower it) */
+    int64_t max_samples;
+    int64_t words;                  /* num_classes * nbins^3 */
+    int64_t scratch_bytes;          /* the gather's planes: (3 x stride + 13 x fstride) x 8 B, the sites and the frames rounded up to 16 */
+    int64_t start_step;             /* the plan's step count at vvhip_sdf_start */
+    double extent, voxel;           /* voxel = 2 extent / nbins, the voxel's edge in nm */
+} vvhip_sdf_layout;
+/* Starts (or restarts, dropping what was accumulated) a recorder; synchronises and drops the captured graphs.  Refused, in this order: a
+ * null description, interval < 1, extent not finite or <= 0, nbins outside 1 .. 128, num_frames < 0, num_frame_groups or num_site_groups
+ * outside 1 .. 16, num_classes outside 1 .. 16, classes NULL, frames NULL with num_frames > 0, max_samples < 1, a frame_group entry outside
+ * -1 .. num_frame_groups - 1, a site_group entry outside -1 .. num_site_groups - 1, a class entry outside its group count, a frame with an
+ * index outside the System, with two equal indices or with particles of different molecules (VVHIP_ERR_INVALID naming the argument or the
+ * frame); more than VVHIP_SDF_MAX_WORDS words (VVHIP_ERR_INVALID with the count); the largest class's pairs per sample times max_samples at
+ * or above 2^62; 3 extent^2 not below (min(L) / 2)^2 of the plan's box (VVHIP_ERR_INVALID); a sharded plan (VVHIP_ERR_UNSUPPORTED); an
+ * unbound plan; inside a graph capture (VVHIP_ERR_INVALID); an allocation that fails (VVHIP_ERR_HIP, with the byte count).  A description
+ * that passes the checks in front of "an unbound plan" is kept even where the start is then refused (active = 0): vvhip_sdf_info answers
+ * for it, for sizing. */
+int vvhip_sdf_start(vvhip_plan* plan, const vvhip_sdf_desc* desc);
+/* Enqueues one sample now, behind what is queued, whatever the schedule says; it counts as a sample like a scheduled one.
+ * VVHIP_ERR_INVALID without a running recorder or inside a graph capture. */
+int vvhip_sdf_sample(vvhip_plan* plan);
+/* Synchronises and copies the counts (out may be NULL) and the table's `words` words (words_out may be NULL with capacity_words = 0; a
+ * capacity below the table's size is VVHIP_ERR_INVALID).  reset != 0 zeroes counts and table: the step schedule continues without gap or
+ * repeat. */
+int vvhip_sdf_read(vvhip_plan* plan, int64_t* words_out, int64_t capacity_words, vvhip_sdf_counts* out, int32_t reset);
+/* Stops the recorder: no more samples are enqueued, table and scratch are released, the description is forgotten; synchronises and drops
+ * the captured graphs. */
+int vvhip_sdf_stop(vvhip_plan* plan);
+/* The recorder as described (zeros with active = 0 if none was); host only, works on an unbound plan. */
+int vvhip_sdf_info(const vvhip_plan* plan, vvhip_sdf_layout* out);
 /* ---------------------------------------------------------------- removal of the centre-of-mass motion on the device
  * What OpenMM's CMMotionRemover does inside context->updateContextState() (VVIntegrator.cpp:234, 278): a stand-alone host has no such
  * service, and the thermostat already counts the 3 degrees of freedom as removed (has_cm_motion_remover).  Over ALL particles of the
@@ -1706,13 +1822,14 @@ int vvhip_debug_old_delta(vvhip_plan* plan, void** device_ptr);                 
  * everything without watching the device's free memory, which moves under other processes' work.  Host only. */
 int vvhip_debug_live_buffers(int64_t* count, int64_t* bytes);
 /* FNV-1a 64 over the host tables that the last accepted vvhip_<name>_start built, name = "profile", "msd", "rdf", "current", "modes",
- * "contacts", "acf", "vanhove" or "vanhove_distinct"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
+ * "contacts", "acf", "vanhove", "vanhove_distinct" or "sdf"; 0 when nothing is described.  Host only, an unbound plan included (it keeps a description that passed the checks).
  * Per vector its size as uint64, then its bytes; flags as one byte; in this order:
  *   profile   grouped, index, group, mass                 msd, acf   grouped, index, first, weight, total, group
  *   rdf       index, mol, items, max_jsites (int32)       current    two_level, index, weight, group
  *   modes     index, weight, modes, items                 contacts   first[0 .. 16], index, mol, mask_items, corr_items, then the fields
  *                                                                    of the word layout (csrc/vv_layout.h: ContactsLayout) one by one
- *   vanhove   grouped, index, first, weight, total, group (as msd), then e2       vanhove_distinct   as rdf */
+ *   vanhove   grouped, index, first, weight, total, group (as msd), then e2       vanhove_distinct   as rdf
+ *   sdf       index, mol, frames, fmol, fgroup, items, max_jsites (int32) */
 int vvhip_debug_recorder_digest(const vvhip_plan* plan, const char* name, uint64_t* out);
 
 #ifdef __cplusplus

@@ -128,6 +128,7 @@ int vvhip_debug_tune(vvhip_plan* p, const char* key, int value) {
     else if (k == "vhd_hist_copies") { if (value != 1 && value != 4) return VVHIP_ERR_INVALID; p->vhd_hist_copies = value; }
     else if (k == "vhd_items_target") { if (value < 1) return VVHIP_ERR_INVALID; p->vhd_items_target = value; }      // (read when a recorder starts: the work list is built there)
     else if (k == "vhd_lds") { if (value < 0 || value > 1) return VVHIP_ERR_INVALID; p->vhd_lds = value; }
+    else if (k == "sdf_items_target") { if (value < 1) return VVHIP_ERR_INVALID; p->sdf_items_target = value; }      // (read when a recorder starts: the work list is built there)
     else if (k == "rdf_hist_copies") { if (value != 1 && value != 4) return VVHIP_ERR_INVALID; p->rdf_hist_copies = value; }
     else if (k == "rdf_items_target") { if (value < 1) return VVHIP_ERR_INVALID; p->rdf_items_target = value; }      // (read when a recorder starts: the work list is built there)
     else return fail(p, VVHIP_ERR_INVALID, "vvhip_debug_tune: unknown key " + k);
@@ -189,7 +190,7 @@ int vvhip_bind(vvhip_plan* p, const vvhip_buffers* b) {
         const bool same = b->velm == o.velm && b->posq == o.posq && b->posq_correction == o.posq_correction && b->force == o.force &&
                           b->pos_delta == o.pos_delta && b->random == o.random && b->random_size == o.random_size;
         if (b->velm != o.velm) p->mass_tab_valid = false;
-        const Riders rd = riders(p);      // (a series row, a scheduled removal, a frame and a profile sample read velm through their captured arguments too; an MSD, RDF, density-mode or contact sample posq, a current sample all three, an autocorrelation sample velm or posq, a self or distinct van Hove sample posq)
+        const Riders rd = riders(p);      // (a series row, a scheduled removal, a frame and a profile sample read velm through their captured arguments too; an MSD, RDF, density-mode or contact sample posq, a current sample all three, an autocorrelation sample velm or posq, a self or distinct van Hove or a spatial distribution sample posq)
         if (!same || std::any_of(rd.begin(), rd.end(), [](const Rider& r) { return r.on; })) drop_graphs(p);
     }
     // a re-bind that moves the plan to another stream: whatever the plan still has in flight on the old one (fills, steps) must be

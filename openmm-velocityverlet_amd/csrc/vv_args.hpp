@@ -606,4 +606,34 @@ struct VhdArgs {
     double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
 };
 
+// Spatial distribution sample (vv_dev_sdf.inc, include/vvhip.h: vvhip_sdf_* states the frames, the sites, the classes, the arithmetic and
+// the voxels).  The sample count is read from the device-side words and whether the box still holds the cube is the host's decision at
+// enqueue (`live`), as for an RDF sample.  The work items are the RDF's (RdfItem; i: frames of the class's frame group, j: sites of its
+// site group, same = 0).  Scratch: the sites' planes double[3][stride], then the frames' double[SDF_FRAME_PLANES][fstride].
+enum { SDF_SAMPLES = 0, SDF_DROPPED = 1, SDF_INVALID = 2, SDF_BAD_FRAMES = 3, SDF_INV_VOLUME = 4, SDF_VISITS = 5, SDF_HEAD = 21 };      // the words in front of the table ([4]: the bits of a double; [5 .. 20]: frame_visits)
+constexpr int SDF_MAX_GROUPS = 16, SDF_MAX_CLASSES = 16, SDF_MAX_BINS = 128;      // (the arrays of vvhip_sdf_layout and vvhip_sdf_counts)
+constexpr int SDF_FRAME_PLANES = 13;      // origin, e1, e2, e3, and the frame's cutoff for the pair kernel's cheap test
+static_assert(SDF_VISITS + SDF_MAX_GROUPS == SDF_HEAD, "");
+struct SdfArgs {
+    const void* posq;               // real4 [shard particles]
+    const void* corr;               // real4, mixed precision only (else null)
+    const int32_t* index;           // [n] particle of site s; the sites are ordered by site group, inside a group ascending by particle
+    const int32_t* mol;             // [n] molecule of site s (exclusion on, else null)
+    const int32_t* frames;          // [nf][3] particles o, a, b of frame f; the frames are ordered by frame group, inside a group as given
+    const int32_t* fmol;            // [nf] molecule of frame f (exclusion on, else null)
+    const unsigned char* fgroup;    // [nf] frame group of frame f
+    const RdfItem* items;           // [num_items]
+    double* scratch;                // [3][stride], then [SDF_FRAME_PLANES][fstride]: rewritten by every sample's gather
+    long long* words;               // [SDF_HEAD + num_classes * nbins^3]
+    int64_t max_samples;
+    int32_t n, stride;              // sites; n rounded up to 16
+    int32_t nf, fstride;            // frames; nf rounded up to 16
+    int32_t nbins, num_items;
+    int32_t live, max_jsites;       // 0: the box no longer holds the cube, the sample is dropped; no item has more j-sites
+    double L[3], inv_L[3];          // the plan's box at enqueue and 1.0 / L[a], formed on the host
+    double h, inv_w;                // extent; (double) nbins / (2.0 * extent)
+    double cut2;                    // (3 h^2) (1 + 2^-20): the cheap test's cutoff of an exactly orthonormal frame
+    double inv_volume;              // 1.0 / ((Lx * Ly) * Lz), formed on the host
+};
+
 }  // namespace vv

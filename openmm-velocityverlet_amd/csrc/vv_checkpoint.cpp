@@ -140,6 +140,7 @@ int vvhip_checkpoint_load(vvhip_plan* p, const void* blob, size_t bytes, uint64_
     if (p->acf.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: an autocorrelation recorder is running: stop it, load, start it again (its origins belong to the old velocities, positions and step counter)");
     if (p->vanhove.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: a self van Hove recorder is running: stop it, load, start it again (its origins belong to the old positions and step counter)");
     if (p->vhd.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: a distinct van Hove recorder is running: stop it, load, start it again (its origins belong to the old positions and step counter)");
+    if (p->sdf.on) return fail(p, VVHIP_ERR_INVALID, "checkpoint: a spatial distribution recorder is running: stop it, load, start it again (its first sample belongs to the old step counter)");
     if (sharded(p) || p->comm || p->mb_on || p->mb_local)
         return fail(p, VVHIP_ERR_UNSUPPORTED, "checkpoint: loading into a sharded plan or one with a communicator / mailbox is not supported (the peers' exchange counters would have to move together)");
     // ---- the blob's structure against the plan's

@@ -309,6 +309,10 @@ int vvhip_debug_recorder_digest(const vvhip_plan* p, const char* name, uint64_t*
         const vvhip_plan::Vhd& R = p->vhd;
         described = R.described;
         f.vec(R.index); f.vec(R.mol); f.vec(R.items); f.scalar((int32_t) R.max_jsites);
+    } else if (which == "sdf") {
+        const vvhip_plan::Sdf& R = p->sdf;
+        described = R.described;
+        f.vec(R.index); f.vec(R.mol); f.vec(R.frames); f.vec(R.fmol); f.vec(R.fgroup); f.vec(R.items); f.scalar((int32_t) R.max_jsites);
     } else if (which == "current") {
         const vvhip_plan::Current& R = p->current;
         described = R.described;

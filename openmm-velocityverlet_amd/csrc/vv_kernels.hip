@@ -669,6 +669,23 @@ hipError_t launch_vhd_floor(long long* words, hipStream_t s) {
     hipLaunchKernelGGL(vv_kernel_vhd_floor, dim3(1), dim3(64), 0, s, words);
     return hipGetLastError();
 }
+hipError_t launch_sdf(int precision, const SdfArgs& a, int grid_cap, hipStream_t s) {
+    // what the kernels rely on: the planes hold the sites and the frames, a voxel index stays inside the table's class
+    if (a.nbins < 1 || a.nbins > SDF_MAX_BINS || a.max_jsites < 1) return hipErrorInvalidValue;
+    if (a.n < 0 || a.stride < a.n || a.nf < 0 || a.fstride < a.nf || a.num_items < 0 || !a.scratch) return hipErrorInvalidValue;
+    const long long threads = (long long) a.n + a.nf;
+    const dim3 gg((unsigned) std::max<long long>(1, std::min<long long>((threads + 255) / 256, std::max(1, grid_cap))));
+    hipLaunchKernelGGL(VV_PICK(precision, vv_kernel_sdf_gather), gg, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const dim3 gp((unsigned) std::max(1, a.num_items));
+    const unsigned lds = (unsigned) rdf_lds_bytes(0, 0);      // (the staged j-tile alone)
+    if (a.mol) hipLaunchKernelGGL(vv_kernel_sdf_pairs<true>, gp, dim3(RDF_TILE), lds, s, a);
+    else hipLaunchKernelGGL(vv_kernel_sdf_pairs<false>, gp, dim3(RDF_TILE), lds, s, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(vv_kernel_sdf_advance, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
 #endif      // VV_KERNELS_PART != 2
 
 }  // namespace vv

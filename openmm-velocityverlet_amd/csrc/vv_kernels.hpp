@@ -125,5 +125,10 @@ hipError_t launch_vanhove_floor(long long* words, hipStream_t s);
 hipError_t launch_vhd(int precision, const VhdArgs& a, bool lds_hist, int grid_cap, hipStream_t s);
 // The origin floor becomes the current sample ordinal (one thread, in the stream): words as VhdArgs::words.
 hipError_t launch_vhd_floor(long long* words, hipStream_t s);
+// One spatial distribution sample (vv_dev_sdf.inc): the gather over a.n sites and a.nf frames in blocks of 256 threads, at most grid_cap
+// of them (the kernel strides beyond), the pair kernel with one block of RDF_TILE threads per work item (one idle block where there is
+// none) and dynamic LDS for the staged j-tile, then the one-thread kernel that counts the sample.  Every in-range pair is an agent-scope
+// add to the int64 table: no private histogram, nothing that could wrap.
+hipError_t launch_sdf(int precision, const SdfArgs& a, int grid_cap, hipStream_t s);
 
 }  // namespace vv

@@ -1,9 +1,9 @@
 // vv_observe.cpp -- what rides beside the step, scheduled by the plan's step counter or called between steps: the Drude temperature report,
 // the series of its rows, trajectory frames, profiles, mean-squared displacements, radial distribution functions, collective current
-// correlations, density modes, contact lifetimes, autocorrelations, self and distinct van Hove functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
-// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The nine accumulating recorders
+// correlations, density modes, contact lifetimes, autocorrelations, self and distinct van Hove functions, spatial distribution functions, the removal of the centre-of-mass motion, Maxwell-Boltzmann start velocities.  The scheduled ones are listed once (riders:
+// when each is due is vv_schedule.hpp's business); step_begin / step_done enqueue them around a step.  The ten accumulating recorders
 // share one life cycle (recorder_*) and the host-only pieces of their starts ("the shared pieces of a start": the lag schedule for seven,
-// units for three, sites ordered by group for five, classes for three); origins_dead tells the six with origins that the state was rewritten.
+// units for three, sites ordered by group for six, classes for three); origins_dead tells the six with origins that the state was rewritten.
 #include "vv_plan.hpp"
 
 #include <algorithm>
@@ -291,6 +291,36 @@ static int vhd_enqueue(vvhip_plan* p) {
     HIP_TRY(p, vv::launch_vhd(p->hp.precision, a, p->vhd_lds != 0, p->grid_cap_a, p->stream));
     return VVHIP_OK;
 }
+// ------------------------------------------------------------------------------------------ spatial distribution functions (vvhip_sdf_*)
+// The cube against the box: its corners lie 3^(1/2) h from the frame's origin, and a sphere of that radius must hold one image per site
+static bool box_holds_cube(const double box[3], double h) {
+    const double half = std::min(box[0], std::min(box[1], box[2])) / 2;
+    return 3.0 * (h * h) < half * half;
+}
+// One sample behind the step just enqueued (or captured), and behind its distinct van Hove sample -- or behind what is queued
+// (vvhip_sdf_sample): the gather of sites and frames, the pair kernel and the one-thread kernel that counts the sample.  Three launches, no
+// memset and no host synchronisation.  The box and whether it still holds the cube are arguments: what changes the box drops the
+// captured graphs.
+static int sdf_enqueue(vvhip_plan* p) {
+    const vvhip_plan::Sdf& R = p->sdf;
+    const vvhip_sdf_layout& L = R.lay;
+    vv::SdfArgs a{};
+    a.posq = p->buf.posq; a.corr = posq_corr(p);
+    a.index = R.dev.index.get(); a.mol = L.exclude_same_molecule ? R.dev.mol.get() : nullptr;
+    a.frames = R.dev.frames.get(); a.fmol = L.exclude_same_molecule ? R.dev.fmol.get() : nullptr; a.fgroup = R.dev.fgroup.get();
+    a.items = R.dev.items.get(); a.scratch = R.dev.scratch.get(); a.words = R.d_words.get();
+    a.max_samples = L.max_samples;
+    a.n = (int32_t) R.index.size(); a.stride = R.stride(); a.nf = (int32_t) R.fgroup.size(); a.fstride = R.fstride();
+    a.nbins = L.nbins; a.num_items = (int32_t) R.items.size();
+    a.live = box_holds_cube(p->box, L.extent) ? 1 : 0;
+    a.max_jsites = R.max_jsites;
+    for (int k = 0; k < 3; k++) { a.L[k] = p->box[k]; a.inv_L[k] = 1.0 / p->box[k]; }
+    a.h = L.extent; a.inv_w = (double) L.nbins / (2.0 * L.extent);
+    a.cut2 = (3.0 * (L.extent * L.extent)) * (1.0 + 0x1p-20);
+    a.inv_volume = 1.0 / ((p->box[0] * p->box[1]) * p->box[2]);
+    HIP_TRY(p, vv::launch_sdf(p->hp.precision, a, p->grid_cap_a, p->stream));
+    return VVHIP_OK;
+}
 // The positions or the velocities were rewritten outside the steps (vv_barostat.cpp; vvhip_set_velocities_to_temperature): the origins that
 // the recorders of that quantity stored so far are dead.  Positions: msd, current, modes, vanhove, vhd, their floors raised in this order; velocities:
 // acf, unless it records orientations.  A contact set belongs to a configuration, not to a displacement: contacts reacts to neither.
@@ -357,9 +387,10 @@ static int cmm_one_off(vvhip_plan* p, double v[3]) {
 //   8 contact sample    behind the density-mode sample; all of d_words: head, table, the slots' ordinals and both rings (the sample's matrix and planes are scratch)
 //   9 autocorrelation sample   behind the contact sample; all of d_words, the ring of origins included, as for the MSD
 //  10 self van Hove sample   behind the autocorrelation sample; all of d_words likewise: head, histogram and the ring of origins
-//  11 distinct van Hove sample   last; all of d_words: counts, head, histogram, the ring of origins and the spare planes
-// Riders 3 .. 11 are the nine accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
-// host tables come from "the shared pieces of a start" below (units: 4, 9 and 10; sites ordered by group: 5 .. 8 and 11; the lag schedule: 4, 6 .. 11),
+//  11 distinct van Hove sample   behind the self van Hove sample; all of d_words: counts, head, histogram, the ring of origins and the spare planes
+//  12 spatial distribution sample   last; all of d_words, counts and table (its gather scratch is rewritten by every sample)
+// Riders 3 .. 12 are the ten accumulating recorders: one descriptor shape (recorder_rider), bytes() of d_words as the late words.  Their
+// host tables come from "the shared pieces of a start" below (units: 4, 9 and 10; sites ordered by group: 5 .. 8, 11 and 12; the lag schedule: 4, 6 .. 11),
 // and origins_dead above reaches 4, 6, 7, 10, 11 (positions) and 9 (velocities).
 template <class R>
 static Rider recorder_rider(const R& r, int (*enqueue)(vvhip_plan*)) { return {r.on, r.when, false, r.on ? r.d_words.get() : nullptr, r.bytes(), enqueue}; }
@@ -369,7 +400,8 @@ Riders riders(vvhip_plan* p) {
              {p->frames.on, p->frames.when, false, p->frames.on ? p->frames.ring.d_cursor.get() : nullptr, sizeof(unsigned long long[2]), frame_enqueue},
              recorder_rider(p->profile, profile_enqueue), recorder_rider(p->msd, msd_enqueue), recorder_rider(p->rdf, rdf_enqueue),
              recorder_rider(p->current, current_enqueue), recorder_rider(p->modes, modes_enqueue), recorder_rider(p->contacts, contacts_enqueue),
-             recorder_rider(p->acf, acf_enqueue), recorder_rider(p->vanhove, vanhove_enqueue), recorder_rider(p->vhd, vhd_enqueue)}};
+             recorder_rider(p->acf, acf_enqueue), recorder_rider(p->vanhove, vanhove_enqueue), recorder_rider(p->vhd, vhd_enqueue),
+             recorder_rider(p->sdf, sdf_enqueue)}};
 }
 // A full step is about to be enqueued (or captured) / has been: the riders in front of it / the count, then the riders behind it.  The two
 // hooks of every entry point that starts / ends a step.
@@ -391,7 +423,7 @@ static int ceil_log2(long long n) { int k = 0; while (k < 62 && (1ll << k) < n) 
 static long long samples_plus(long long max_samples, long long more) { return max_samples < (1ll << 62) ? max_samples + more : (1ll << 62); }
 
 // ------------------------------------------------------------------------------------------ the recorders' one life cycle
-// What the series, the frame recorder and the nine accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
+// What the series, the frame recorder and the ten accumulating recorders (vvhip_plan::Recorder) go through, stated once; `which` is the
 // plan's member, `name` the prefix of its messages and the middle of its entry points' names.
 // One that runs is settled and goes first (its rows, frames or samples may still be in flight); the description an unbound plan kept goes
 // with it.  All of *_stop, and the front of a start over a running recorder.
@@ -459,10 +491,10 @@ static int recorder_info(const vvhip_plan* p, R vvhip_plan::* which, L* out, L b
 // ------------------------------------------------------------------------------------------ the shared pieces of a start
 // The host-only part of the accumulating recorders' *_start, stated once; `name` is the prefix of the messages.  What a recorder still
 // writes itself: its own argument checks, its layout, its fixed point (but for units_frac_bits), its work list, its enqueue.
-//   check_groups, check_max_samples   all nine                check_lags            msd, acf, vanhove, vhd, current, modes, contacts
+//   check_groups, check_max_samples   all ten                 check_lags            msd, acf, vanhove, vhd, current, modes, contacts
 //   num_origins_of                    msd, acf, vanhove, vhd, current, modes; check_origins       msd, acf, vanhove, vhd, contacts
-//   plan_units, fill_units   msd, acf, vanhove; units_frac_bits   msd, acf        sites_by_group        rdf, vhd, current, modes, contacts
-//   check_classes, check_pair_count, check_half_box (beside box_holds), no_pairs_across_shards   rdf, vhd, contacts;   no_sums_across_shards   current, modes
+//   plan_units, fill_units   msd, acf, vanhove; units_frac_bits   msd, acf        sites_by_group        rdf, vhd, sdf, current, modes, contacts
+//   check_classes, check_half_box (beside box_holds)   rdf, vhd, contacts;   check_pair_count, no_pairs_across_shards   these and sdf;   no_sums_across_shards   current, modes
 // group[i] of every particle of the System (or, count >= 0, of `count` entries) against [-1, num_groups) (group = null: everything in group 0)
 static int check_groups(vvhip_plan* p, const char* name, const signed char* group, int32_t num_groups, int32_t count = -1) {
     for (int32_t i = 0; group && i < (count < 0 ? p->hp.num_atoms : count); i++)
@@ -1267,6 +1299,122 @@ int vvhip_rdf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vv
 }
 int vvhip_rdf_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::rdf, "rdf"); }
 int vvhip_rdf_info(const vvhip_plan* p, vvhip_rdf_layout* out) { return recorder_info(p, &vvhip_plan::rdf, out); }
+
+int vvhip_sdf_start(vvhip_plan* p, const vvhip_sdf_desc* d) {
+    if (!p) return VVHIP_ERR_INVALID;
+    if (!d) return fail(p, VVHIP_ERR_INVALID, "sdf: null description");
+    if (d->interval < 1) return fail(p, VVHIP_ERR_INVALID, "sdf: interval must be >= 1 step");
+    if (!(d->extent > 0) || !std::isfinite(d->extent)) return fail(p, VVHIP_ERR_INVALID, "sdf: extent must be finite and > 0");
+    if (d->nbins < 1 || d->nbins > vv::SDF_MAX_BINS) return fail(p, VVHIP_ERR_INVALID, "sdf: nbins must be in [1, 128]");
+    if (d->num_frames < 0) return fail(p, VVHIP_ERR_INVALID, "sdf: num_frames must be >= 0");
+    if (d->num_frame_groups < 1 || d->num_frame_groups > vv::SDF_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "sdf: num_frame_groups must be in [1, 16]");
+    if (d->num_site_groups < 1 || d->num_site_groups > vv::SDF_MAX_GROUPS) return fail(p, VVHIP_ERR_INVALID, "sdf: num_site_groups must be in [1, 16]");
+    if (d->num_classes < 1 || d->num_classes > vv::SDF_MAX_CLASSES) return fail(p, VVHIP_ERR_INVALID, "sdf: num_classes must be in [1, 16]");
+    if (!d->classes) return fail(p, VVHIP_ERR_INVALID, "sdf: classes must not be NULL");
+    if (!d->frames && d->num_frames > 0) return fail(p, VVHIP_ERR_INVALID, "sdf: frames must not be NULL with num_frames > 0");
+    TRY(check_max_samples(p, "sdf", d->max_samples));
+    for (int32_t f = 0; d->frame_group && f < d->num_frames; f++)
+        if (d->frame_group[f] < -1 || d->frame_group[f] >= d->num_frame_groups)
+            return fail(p, VVHIP_ERR_INVALID, "sdf: frame_group[" + std::to_string(f) + "] = " + std::to_string((int) d->frame_group[f]) + " is outside [-1, num_frame_groups = " + std::to_string(d->num_frame_groups) + ")");
+    for (int32_t i = 0; d->site_group && i < p->hp.num_atoms; i++)
+        if (d->site_group[i] < -1 || d->site_group[i] >= d->num_site_groups)
+            return fail(p, VVHIP_ERR_INVALID, "sdf: site_group[" + std::to_string(i) + "] = " + std::to_string((int) d->site_group[i]) + " is outside [-1, num_site_groups = " + std::to_string(d->num_site_groups) + ")");
+    for (int32_t c = 0; c < d->num_classes; c++)
+        for (int q = 0; q < 2; q++) {
+            const int32_t count = q ? d->num_site_groups : d->num_frame_groups;
+            if (d->classes[2 * c + q] < 0 || d->classes[2 * c + q] >= count)
+                return fail(p, VVHIP_ERR_INVALID, "sdf: classes[" + std::to_string(c) + "][" + std::to_string(q) + "] = " + std::to_string(d->classes[2 * c + q]) + " is outside [0, " +
+                                                  (q ? "num_site_groups = " : "num_frame_groups = ") + std::to_string(count) + ")");
+        }
+    for (int32_t f = 0; f < d->num_frames; f++) {
+        const int32_t* t = d->frames + 3 * (size_t) f;
+        const std::string who = "sdf: frames[" + std::to_string(f) + "] = {" + std::to_string(t[0]) + ", " + std::to_string(t[1]) + ", " + std::to_string(t[2]) + "}";
+        for (int q = 0; q < 3; q++)
+            if (t[q] < 0 || t[q] >= p->hp.num_atoms) return fail(p, VVHIP_ERR_INVALID, who + " has an index outside the System's " + std::to_string(p->hp.num_atoms) + " particles");
+        if (t[0] == t[1] || t[0] == t[2] || t[1] == t[2]) return fail(p, VVHIP_ERR_INVALID, who + " names a particle twice");
+        const int32_t m = p->hp.mol_id[(size_t) t[0]];
+        if (p->hp.mol_id[(size_t) t[1]] != m || p->hp.mol_id[(size_t) t[2]] != m) return fail(p, VVHIP_ERR_INVALID, who + " spans molecules (mol_id): a frame lies in one molecule");
+    }
+    // ---- the sites, the frames, the layout and the pair kernel's work list, host only
+    vvhip_plan::Sdf N;
+    vvhip_sdf_layout& L = N.lay;
+    L.interval = d->interval; L.nbins = d->nbins; L.num_frame_groups = d->num_frame_groups; L.num_site_groups = d->num_site_groups;
+    L.num_classes = d->num_classes; L.exclude_same_molecule = d->exclude_same_molecule != 0; L.tile = vv::RDF_TILE;
+    L.max_samples = d->max_samples; L.words = (int64_t) d->num_classes * d->nbins * d->nbins * d->nbins;
+    L.extent = d->extent; L.voxel = 2.0 * d->extent / (double) d->nbins;
+    if (L.words > VVHIP_SDF_MAX_WORDS)
+        return fail(p, VVHIP_ERR_INVALID, "sdf: the table would have " + std::to_string((long long) L.words) + " words (num_classes * nbins^3), above the cap of " +
+                                          std::to_string((long long) VVHIP_SDF_MAX_WORDS) + " (64 MiB, which a recovery snapshot copies too): fewer voxels or classes");
+    Sites S = sites_by_group(p->hp, d->site_group, d->num_site_groups, L.exclude_same_molecule != 0, nullptr, false);
+    std::copy(S.count, S.count + d->num_site_groups, L.num_sites);
+    int32_t ffirst[vv::SDF_MAX_GROUPS + 1] = {0};
+    auto fgroup_of = [&](int32_t f) { return d->frame_group ? (int) d->frame_group[f] : 0; };
+    for (int32_t f = 0; f < d->num_frames; f++)
+        if (fgroup_of(f) >= 0) L.num_frames[fgroup_of(f)]++;
+    for (int g = 0; g < d->num_frame_groups; g++) ffirst[g + 1] = ffirst[g] + L.num_frames[g];
+    int64_t largest = 0;
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        L.classes[c][0] = d->classes[2 * c]; L.classes[c][1] = d->classes[2 * c + 1];
+        L.pairs_per_sample[c] = (int64_t) L.num_frames[L.classes[c][0]] * L.num_sites[L.classes[c][1]];
+        largest = std::max(largest, L.pairs_per_sample[c]);
+    }
+    TRY(check_pair_count(p, "sdf", largest, d->max_samples, "voxel"));
+    if (!box_holds_cube(p->box, d->extent))
+        return fail(p, VVHIP_ERR_INVALID, "sdf: extent = " + std::to_string(d->extent) + " nm is too large for the box: 3 extent^2 must be below (min(L) / 2)^2 with min(L) = " +
+                                          std::to_string(std::min(p->box[0], std::min(p->box[1], p->box[2]))) + " nm, or a site would have more than one image in the cube");
+    TRY(no_pairs_across_shards(p, "sdf", "table"));
+    N.index = std::move(S.index); N.mol = std::move(S.mol);
+    // the frames ordered by group, inside a group as given
+    const size_t nf = (size_t) ffirst[d->num_frame_groups];
+    N.frames.resize(3 * nf); N.fgroup.resize(nf);
+    if (L.exclude_same_molecule) N.fmol.resize(nf);
+    int32_t next[vv::SDF_MAX_GROUPS];
+    std::copy(ffirst, ffirst + vv::SDF_MAX_GROUPS, next);
+    for (int32_t f = 0; f < d->num_frames; f++) {
+        const int g = fgroup_of(f);
+        if (g < 0) continue;
+        const size_t at = (size_t) next[g]++;
+        std::copy(d->frames + 3 * (size_t) f, d->frames + 3 * (size_t) f + 3, N.frames.begin() + 3 * at);
+        N.fgroup[at] = (unsigned char) g;
+        if (L.exclude_same_molecule) N.fmol[at] = p->hp.mol_id[(size_t) d->frames[3 * (size_t) f]];
+    }
+    // the work list, as the RDF's: per class and i-tile of frames the j-sites in runs of `max_jsites`, a multiple of 64.  A small
+    // workload gets runs of 64, so that its blocks fill the device; beyond sdf_items_target blocks a run grows
+    constexpr int T = vv::RDF_TILE;
+    long long runs = 0;                                     // of 64 j-sites, over all i-tiles
+    for (int32_t c = 0; c < d->num_classes; c++)
+        runs += ((long long) L.num_frames[L.classes[c][0]] + T - 1) / T * (((long long) L.num_sites[L.classes[c][1]] + 63) / 64);
+    const int target = std::max(1, p->sdf_items_target);
+    N.max_jsites = 64 * (int) std::max<long long>(1, std::min<long long>(4096, (runs + target - 1) / target));
+    for (int32_t c = 0; c < d->num_classes; c++) {
+        const int fg = L.classes[c][0], sg = L.classes[c][1];
+        const int32_t na = L.num_frames[fg], nb = L.num_sites[sg];
+        for (int32_t i0 = 0; i0 < na; i0 += T)
+            for (int32_t j0 = 0; j0 < nb; j0 += N.max_jsites)
+                N.items.push_back({c, 0, ffirst[fg] + i0, std::min(T, na - i0), S.first[sg], j0, std::min(nb, j0 + N.max_jsites), 0});
+    }
+    L.num_items = (int32_t) N.items.size();
+    L.scratch_bytes = ((int64_t) 3 * N.stride() + (int64_t) vv::SDF_FRAME_PLANES * N.fstride()) * (int64_t) sizeof(double);
+    return recorder_install(p, &vvhip_plan::sdf, "sdf", N, d->interval);
+}
+int vvhip_sdf_sample(vvhip_plan* p) {
+    NEED_BOUND(p);
+    if (!p->sdf.on) return fail(p, VVHIP_ERR_INVALID, "sdf: none started (vvhip_sdf_start)");
+    TRY(quiesce(p, "sdf", false, false));
+    return sdf_enqueue(p);
+}
+int vvhip_sdf_read(vvhip_plan* p, int64_t* words_out, int64_t capacity_words, vvhip_sdf_counts* out, int32_t reset) {
+    long long head[vv::SDF_HEAD];
+    TRY(recorder_fetch(p, &vvhip_plan::sdf, "sdf", words_out, capacity_words, head));
+    if (out) {
+        *out = {head[vv::SDF_SAMPLES], head[vv::SDF_DROPPED], head[vv::SDF_INVALID], head[vv::SDF_BAD_FRAMES], 0.0, {0}};
+        std::memcpy(&out->inv_volume_sum, &head[vv::SDF_INV_VOLUME], sizeof(double));
+        std::copy(head + vv::SDF_VISITS, head + vv::SDF_VISITS + vv::SDF_MAX_GROUPS, out->frame_visits);
+    }
+    return reset ? recorder_reset(p, p->sdf) : VVHIP_OK;
+}
+int vvhip_sdf_stop(vvhip_plan* p) { return recorder_stop(p, &vvhip_plan::sdf, "sdf"); }
+int vvhip_sdf_info(const vvhip_plan* p, vvhip_sdf_layout* out) { return recorder_info(p, &vvhip_plan::sdf, out); }
 
 int vvhip_current_start(vvhip_plan* p, const vvhip_current_desc* d) {
     if (!p) return VVHIP_ERR_INVALID;

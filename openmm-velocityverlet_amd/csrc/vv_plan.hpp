@@ -8,9 +8,9 @@
 //                    vvhip_generic_launches, vvhip_set_trace, vvhip_rtc_*
 //   vv_steps.cpp     the thermostat application (compose_application, run_application*), every step entry point, the split
 //                    (kernel-interface) entry points, vvhip_algorithmic_bytes, vvhip_accumulators
-//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the twelve scheduled riders in ride order (riders) --
-//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact / autocorrelation / self van Hove / distinct van Hove sample, with their
-//                    late words: the rings' cursors, the removals' record, the nine recorders' d_words; the recorders' one life cycle
+//   vv_observe.cpp   what rides beside the step: the Drude report, start velocities, and the thirteen scheduled riders in ride order (riders) --
+//                    series row, removal of the centre-of-mass motion, trajectory frame, profile / MSD / RDF / current / density-mode / contact / autocorrelation / self van Hove / distinct van Hove / spatial distribution sample, with their
+//                    late words: the rings' cursors, the removals' record, the ten recorders' d_words; the recorders' one life cycle
 //                    (recorder_*), step_begin / step_done, quiesce; the riders' one schedule is vv_schedule.hpp (integers only, no HIP)
 //   vv_barostat.cpp  the device half of a Monte Carlo barostat attempt: vvhip_barostat_scale / _restore / _read
 //   vv_run.cpp       the plan-driven loops: random slices, recovery from a missed rendezvous, plan_step, graph capture and replay,
@@ -84,8 +84,8 @@ static_assert(vv::ACF_VELOCITY_PARTICLES == VVHIP_ACF_VELOCITY_PARTICLES && vv::
 static_assert(SCHEDULE_LINEAR == VVHIP_FRAMES_LINEAR && SCHEDULE_LOG10 == VVHIP_FRAMES_LOG10, "vv_schedule.hpp states the ABI's two kinds");
 // The step's scheduled riders (riders()) in ride order, each with its late words, what a recovery puts back with the step counter:
 //   0 series row (the ring's cursor)   1 removal of the centre-of-mass motion, in front of its step (the schedule's record)
-//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample   9 autocorrelation sample   10 self van Hove sample   11 distinct van Hove sample (3 .. 11: all of d_words)
-constexpr int kRiders = 12;
+//   2 trajectory frame (the ring's cursor)   3 profile sample   4 MSD sample   5 RDF sample   6 current sample   7 density-mode sample   8 contact sample   9 autocorrelation sample   10 self van Hove sample   11 distinct van Hove sample   12 spatial distribution sample (3 .. 12: all of d_words)
+constexpr int kRiders = 13;
 
 // How a thermostat application (sums in kernel A -> exchange between the ranks -> chain -> scaling in kernel B) runs for the plan as it
 // stands; thermo_mode is the one place that derives it.
@@ -173,6 +173,7 @@ struct vvhip_plan {
     int vhd_hist_copies = 1;       // private histograms per block of a distinct van Hove sample's pair kernel: 1, or 4 = one per wave where they fit (test hook "vhd_hist_copies"; same bits)
     int vhd_items_target = 4096;   // its work list aims at about this many items before it gives one more than 64 j-sites (test hook "vhd_items_target"; read at the start)
     int vhd_lds = 1;               // that kernel counts into a block-private LDS histogram (test hook "vhd_lds": 0 = every pair is a global add; same bits)
+    int sdf_items_target = 4096;   // a spatial distribution sample's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "sdf_items_target"; read at the start)
     int rdf_items_target = 4096;   // the pair kernel's work list aims at about this many blocks before it gives a block more than 64 j-sites (test hook "rdf_items_target")
     int split_chain_waves = 44000;  // systems with at least this many waves (~2.6 M particles) run the chain as its own launch.  Round 4, with two blocks of seven tile
                                      // waves per CU below it (profiles/r04zd_mid_sizes.txt; chain in kernel B | own launch, steps/s): 888 k particles 20.8 | 18.9 k,
@@ -191,8 +192,8 @@ struct vvhip_plan {
         bool fextra_dirty = false;     // forceExtra holds something since the last reset (split entry points)
         bool fextra_virtual = false;   // forceExtra SHOULD hold the cos force of the last fused step (see above)
         // full steps counted since vvhip_bind (the step entry points advance it, a replay advances it by the graph's length): the schedule of
-        // all twelve riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation, self van Hove and distinct van Hove sample.  A
-        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the nine recorders' d_words
+        // all thirteen riders -- series row, removal of the centre-of-mass motion, trajectory frame, profile, MSD, RDF, current, density-mode, contact, autocorrelation, self van Hove, distinct van Hove and spatial distribution sample.  A
+        // recovery puts it back together with their late words: the two rings' cursors, the removals' record, the ten recorders' d_words
         long long step_count = 0;
     } cur;
     bool trace = false;            // roctx range + one stderr line per launch group (the reference's setDebugEnabled, VVIntegrator.h:417-419)
@@ -364,7 +365,7 @@ struct vvhip_plan {
         Ring ring;                                // of frame_bytes each
         vv::DevBuf<int32_t> d_subset;             // [num_particles] shard-relative indices (with a subset)
     } frames;
-    // What the nine accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
+    // What the ten accumulating recorders below share, and the shape vv_observe.cpp's recorder_* skeleton works on.  `described`: `lay` is
     // the layout of the last description that passed the recorder's *_start checks (kept for an unbound plan too: *_info answers from it);
     // `on`: the recorder runs and the device buffers exist.  Each recorder adds
     //   lay, dev               its vvhip_*_layout; its device tables besides d_words (`dev = {}` drops them all)
@@ -373,7 +374,7 @@ struct vvhip_plan {
     //   alloc(s, &asked)       d_words, zeroed on stream s, and dev from the host tables; a request that fails leaves its bytes in `asked`
     //   reset(s)               what *_read's reset enqueues
     // Stated once below them: Units, the unit tables and all of the above for the three recorders of per-unit vectors (msd, acf, vanhove); Slotted,
-    // "no slot holds a sample" and the reset for the three whose ring slots carry a word of their own (current, modes, contacts).  Rdf, Vhd and
+    // "no slot holds a sample" and the reset for the three whose ring slots carry a word of their own (current, modes, contacts).  Rdf, Vhd, Sdf and
     // Contacts keep their own index / mol / stride(): a shared base would cost more lines than the four it saves.  The host tables come
     // from vv_observe.cpp's "shared pieces of a start".
     struct Recorder {
@@ -612,6 +613,39 @@ struct vvhip_plan {
         // (counts, floor and table; with the ordinal back at 0 no slot of the ring is live, so the ring may keep its bits)
         hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, (size_t) (kHead + lay.words) * sizeof(long long), s); }
     } vhd;
+    // Spatial distribution functions (vvhip_sdf_*; vv_dev_sdf.inc): the RDF recorder's sites and work items with frames for i-sites.  The
+    // frame tables (ordered by frame group, inside a group as given) are built when the recorder starts
+    struct Sdf : Recorder {
+        vvhip_sdf_layout lay{};
+        std::vector<int32_t> index, mol;          // [sites] particle and molecule of every site (mol: with the exclusion on)
+        std::vector<int32_t> frames, fmol;        // [frames][3] particles o, a, b; [frames] the frame's molecule (with the exclusion on)
+        std::vector<unsigned char> fgroup;        // [frames]
+        std::vector<vv::RdfItem> items;
+        int max_jsites = 64;                      // no item has more j-sites
+        struct Dev {
+            vv::DevBuf<int32_t> index, mol, frames, fmol;
+            vv::DevBuf<unsigned char> fgroup;
+            vv::DevBuf<vv::RdfItem> items;
+            vv::DevBuf<double> scratch;           // [3][stride()], then [13][fstride()]: rewritten by every sample, not saved
+        } dev;
+        static constexpr int kHead = vv::SDF_HEAD;          // d_words: [kHead + lay.words] counts, then the table
+        size_t table_offset() const { return kHead; }
+        int32_t stride() const { return ((int32_t) index.size() + 15) / 16 * 16; }
+        int32_t fstride() const { return ((int32_t) fgroup.size() + 15) / 16 * 16; }
+        size_t bytes() const { return (size_t) (kHead + lay.words) * sizeof(long long); }
+        hipError_t alloc(hipStream_t s, size_t* asked) {
+            hipError_t e = vv::zeros(d_words, *asked = bytes(), s);
+            if (e == hipSuccess) e = vv::zeros(dev.scratch, *asked = std::max<size_t>(16, (size_t) lay.scratch_bytes), s);
+            if (e == hipSuccess) e = put(dev.index, index, asked);
+            if (e == hipSuccess) e = put(dev.frames, frames, asked);
+            if (e == hipSuccess) e = put(dev.fgroup, fgroup, asked);
+            if (e == hipSuccess && lay.exclude_same_molecule) e = put(dev.mol, mol, asked);
+            if (e == hipSuccess && lay.exclude_same_molecule) e = put(dev.fmol, fmol, asked);
+            if (e == hipSuccess) e = put(dev.items, items, asked, 32);
+            return e;
+        }
+        hipError_t reset(hipStream_t s) { return hipMemsetAsync(d_words.get(), 0, bytes(), s); }
+    } sdf;
     // Removal of the centre-of-mass motion (vvhip_cm_motion_*; vv_dev_cmm.inc), scheduled by step_count: scratch and records of its own,
     // allocated by the first call that needs them
     struct CmMotion {
@@ -774,7 +808,7 @@ Riders riders(vvhip_plan* p);
 // allocation again: head, sums, table and the ring of origins.  For a density-mode recorder likewise.  For a contact recorder head, table,
 // the slots' ordinals and both rings of bit matrices: the surviving contacts are not idempotent under the repeat either.  For an
 // autocorrelation recorder the whole allocation as for the MSD: head, table and the ring of origins; for a self van Hove recorder likewise; for a distinct van Hove recorder
-// counts, table, ring and spare planes.
+// counts, table, ring and spare planes; for a spatial distribution recorder counts and table, as for the RDF (up to 64 MiB).
 // particle_words: 32-bit words per particle of a per-particle array (its digest's base is shard_begin x that), else 0.
 struct RecItem { void* live; vv::DevBuf<void>* saved; size_t bytes; bool late; uint32_t particle_words = 0; };
 std::vector<RecItem> recovery_items(vvhip_plan* p, const bool with[kRiders]);

@@ -813,6 +813,91 @@ def vanhove_distinct_from_words(words, layout, counts) -> VanHoveDistinct:
 
 
 @dataclasses.dataclass
+class Sdf:
+    """Spatial distribution functions per class and voxel (Context.sdf_read; include/vvhip.h: vvhip_sdf_* states the frames, the sites,
+    the classes, the arithmetic and the voxels).  `counts` is the device's table as it stands, int64 [classes, n, n, n], indexed by the
+    voxel along the frame axes xi1 (o -> a), xi2 (in the plane of o, a, b, on b's side), xi3 = xi1 x xi2."""
+    samples: int
+    dropped: int                           # samples that were due past max_samples or in a box too small for the cube: nothing was added
+    invalid: int                           # pairs of a good frame whose frame coordinates held a NaN
+    bad_frames: int                        # (frame, sample) visits whose frame was degenerate: they took part in no pair
+    inv_volume_sum: float                  # the counted samples' 1 / V in nm^-3, summed in sample order
+    frame_visits: np.ndarray               # int64 [frame groups]: the good frames of the counted samples
+    interval: int
+    extent: float                          # h in nm: the cube is [-h, h)^3
+    classes: np.ndarray                    # int32 [classes, 2]: frame group, site group
+    num_frames: np.ndarray                 # int64 [frame groups]
+    num_sites: np.ndarray                  # int64 [site groups]
+    pairs_per_sample: np.ndarray           # int64 [classes]: N_frames N_sites
+    counts: np.ndarray                     # int64 [classes, n, n, n]
+
+    @property
+    def nbins(self) -> int:
+        return int(self.counts.shape[1])
+
+    @property
+    def voxel(self) -> float:
+        """The voxel's edge in nm, 2 h / n."""
+        return 2.0 * self.extent / self.nbins
+
+    @property
+    def edges(self) -> np.ndarray:
+        """float64 [n + 1]: the voxel edges along one frame axis in nm, -h .. h."""
+        return -self.extent + self.voxel * np.arange(self.nbins + 1, dtype=np.float64)
+
+    @property
+    def centres(self) -> np.ndarray:
+        """float64 [n]: the voxel centres along one frame axis in nm."""
+        e = self.edges
+        return 0.5 * (e[1:] + e[:-1])
+
+    def density(self, c: int = 0) -> np.ndarray:
+        """float64 [n, n, n] in nm^-3: counts / (frame_visits of the class's frame group * voxel volume) -- the mean number density of
+        the class's sites around a frame; NaN where no frame was visited."""
+        norm = float(self.frame_visits[self.classes[c, 0]]) * self.voxel ** 3
+        return self.counts[c] / norm if norm > 0 else np.full(self.counts[c].shape, np.nan)
+
+    def g(self, c: int = 0) -> np.ndarray:
+        """float64 [n, n, n]: density / (N_sites * inv_volume_sum / samples), the density over the mean density of the class's site
+        group, which tends to 1 far from the molecule.  The exclusion does not lower N_sites, and the mean density is taken over all
+        counted samples while the density counts the good frames only, so with bad frames -- under a barostat -- this is approximate."""
+        bulk = float(self.num_sites[self.classes[c, 1]]) * self.inv_volume_sum / self.samples if self.samples > 0 else 0.0
+        return self.density(c) / bulk if bulk > 0 else np.full(self.counts[c].shape, np.nan)
+
+    def symmetrized(self, c: int = 0, axes=(2,), quantity: str = "g") -> np.ndarray:
+        """float64 [n, n, n]: the mean of `quantity` ("g", "density" or "counts") with its mirror images along the given frame axes (0, 1,
+        2 = xi1, xi2, xi3), all 2^len(axes) of them: axes=(2,) for a planar ring, whose two faces are equivalent."""
+        out = {"g": self.g, "density": self.density, "counts": lambda k: self.counts[k].astype(np.float64)}[quantity](c)
+        for ax in axes:
+            out = 0.5 * (out + np.flip(out, axis=int(ax)))
+        return out
+
+    def plane(self, c: int = 0, axis: int = 2, lo: float = None, hi: float = None, quantity: str = "g") -> np.ndarray:
+        """float64 [n, n]: the mean of `quantity` over the slab of voxels whose centres lie in [lo, hi] nm along frame axis `axis`
+        (default: the two central layers, or the central one for odd n) -- a 2-D map over the two remaining axes in their order."""
+        out = {"g": self.g, "density": self.density, "counts": lambda k: self.counts[k].astype(np.float64)}[quantity](c)
+        x = self.centres
+        if lo is None and hi is None:
+            lo, hi = -0.75 * self.voxel, 0.75 * self.voxel
+        take = (x >= (-np.inf if lo is None else lo)) & (x <= (np.inf if hi is None else hi))
+        if not take.any():
+            raise ValueError("plane: no voxel centre lies in [lo, hi]")
+        return np.take(out, np.nonzero(take)[0], axis=int(axis)).mean(axis=int(axis))
+
+
+def sdf_from_words(words, layout, counts) -> Sdf:
+    """An Sdf from a table's int64 words [classes * n^3], its layout (H.SdfLayout) and counts (H.SdfCounts)."""
+    nc, n, nfg, nsg = int(layout.num_classes), int(layout.nbins), int(layout.num_frame_groups), int(layout.num_site_groups)
+    return Sdf(samples=int(counts.samples), dropped=int(counts.dropped), invalid=int(counts.invalid), bad_frames=int(counts.bad_frames),
+               inv_volume_sum=float(counts.inv_volume_sum), frame_visits=np.array(counts.frame_visits[:nfg], dtype=np.int64),
+               interval=int(layout.interval), extent=float(layout.extent),
+               classes=np.array([[layout.classes[c][0], layout.classes[c][1]] for c in range(nc)], dtype=np.int32).reshape(nc, 2),
+               num_frames=np.array(layout.num_frames[:nfg], dtype=np.int64), num_sites=np.array(layout.num_sites[:nsg], dtype=np.int64),
+               pairs_per_sample=np.array(layout.pairs_per_sample[:nc], dtype=np.int64),
+               counts=np.ascontiguousarray(words, dtype=np.int64).reshape(nc, n, n, n))
+
+
+@dataclasses.dataclass
 class Contacts:
     """Contact lifetime correlations per class and lag (Context.contacts_read; include/vvhip.h: vvhip_contacts_* states the sites, the
     classes, the contact, the slots and the table).  `words` is the device's table as it stands, int64 [classes, lags, 4]: per lag the
@@ -1421,7 +1506,7 @@ class Context:
         return Frames(step=step[:count].copy(), box=box, particles=particles, positions=planes(info.off_positions),
                       velocities=planes(info.off_velocities), dropped=int(dropped.value))
 
-    # ---- what the nine accumulating recorders below share: profile, msd, acf, vanhove, vanhove_distinct, rdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
+    # ---- what the ten accumulating recorders below share: profile, msd, acf, vanhove, vanhove_distinct, rdf, sdf, contacts, current, modes (include/vvhip.h: vvhip_<name>_*)
     def _groups(self, groups):
         """`groups` as the int8 array the descriptions point to (keep it alive across the call), None for None."""
         if groups is None:
@@ -1636,6 +1721,44 @@ class Context:
         """The histograms accumulated so far (synchronises).  reset=True zeroes counts and table; the step schedule continues without gap
         or repeat."""
         return self._recorder_read("rdf", H.RdfLayout, H.RdfCounts, rdf_from_words, reset)
+
+    # ---- spatial distribution functions accumulated on the device inside the steps (include/vvhip.h: vvhip_sdf_*)
+    def sdf_start(self, interval: int, extent: float, nbins: int, frames, classes, frame_groups=None, site_groups=None,
+                  exclude_same_molecule: bool = False, max_samples: int = 1 << 20):
+        """After every step whose number is a multiple of `interval` (steps counted as for the series), count where the sites sit around
+        every frame in the frame's own axes, into `nbins`^3 voxels of the cube [-extent, extent)^3 nm, as integers, so that the table is
+        the same bits for any launch shape.  `frames`: triplets (o, a, b) of particles of one molecule -- the origin, xi1 points to a, b
+        fixes the xi1-xi2 plane; `frame_groups`: one int per frame (-1: not recorded; None: all in group 0); `site_groups`: one int per
+        particle of the System (-1: no site; None: everything in group 0); `classes`: pairs (frame group, site group).
+        exclude_same_molecule leaves out the sites of the frame's own molecule.  3 extent^2 must stay below (half the shortest box
+        edge)^2.  At most `max_samples` samples are taken.  A sharded context raises ERR_UNSUPPORTED.  No host synchronisation until
+        sdf_read."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1, 3)
+        fgrp = None if frame_groups is None else np.ascontiguousarray(frame_groups, dtype=np.int8).reshape(-1)
+        if fgrp is not None and fgrp.size != fr.shape[0]:
+            raise ValueError("frame_groups must have one entry per frame")
+        sgrp = self._groups(site_groups)
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1, 2)
+        count = lambda grp, col: max(1, 0 if grp is None or not grp.size else int(grp.max()) + 1, int(cls[:, col].max()) + 1 if cls.size else 1)      # (a class may name a group without members)
+        desc = H.SdfDesc(int(interval), int(nbins), int(fr.shape[0]), count(fgrp, 0), count(sgrp, 1), int(cls.shape[0]),
+                         int(bool(exclude_same_molecule)), 0, fr.ctypes.data if fr.size else None, None if fgrp is None else fgrp.ctypes.data,
+                         None if sgrp is None else sgrp.ctypes.data, cls.ctypes.data, int(max_samples), float(extent))
+        H.check(H.lib.vvhip_sdf_start(self.plan, C.byref(desc)), self.plan)
+
+    def sdf_sample(self):
+        """One sample now, behind what is queued, whatever the schedule says (a configuration the host has just uploaded)."""
+        H.check(H.lib.vvhip_sdf_sample(self.plan), self.plan)
+
+    def sdf_stop(self):
+        self._recorder_stop("sdf")
+
+    def sdf_info(self) -> H.SdfLayout:
+        return self._recorder_info("sdf", H.SdfLayout)
+
+    def sdf_read(self, reset: bool = False) -> Sdf:
+        """The table accumulated so far (synchronises).  reset=True zeroes counts and table; the step schedule continues without gap or
+        repeat."""
+        return self._recorder_read("sdf", H.SdfLayout, H.SdfCounts, sdf_from_words, reset)
 
     # ---- contact lifetime correlations accumulated on the device inside the steps (include/vvhip.h: vvhip_contacts_*)
     def contacts_start(self, interval: int, num_lags: int, classes, r_cut, origin_every: int = 1, groups=None,

@@ -26,6 +26,9 @@ latest three kept.
 
 ``write_rdf`` writes device-side radial distribution functions (``Context.rdf_read``) as text columns, one line per bin.
 
+``write_sdf`` writes one class of a device-side spatial distribution function (``Context.sdf_read``) as text, one line per non-zero voxel;
+``write_sdf_cube`` writes it as a Gaussian cube file for isosurface viewers.
+
 ``write_current`` writes a device-side collective current correlation table (``Context.current_read``) as text columns, one line per lag.
 
 ``write_modes`` writes device-side density-mode correlations (``Context.modes_read``), S(k) and F(k, t), as text columns, one line per mode.
@@ -45,7 +48,8 @@ import numpy as np
 
 HEADER = '#"Step"\t"T_COM"\t"T_Atom"\t"T_Drude"\t"KE_COM"\t"KE_Atom"\t"KE_Drude"'
 CM_MOTION_HEADER = '#"Step"\t"Removals"\t"Skipped"\t"Vx (nm/ps)"\t"Vy (nm/ps)"\t"Vz (nm/ps)"'
-VISCOSITY_HEADER = '#"Step"\t"Acceleration (nm/ps^2)"\t"VelocityAmplitude (nm/ps)"\t"1/Viscosity (1/Pa.s)"'
+BOHR_NM = 0.0529177210903      # 1 bohr in nm (CODATA 2018): cube files carry lengths in bohr
+VISCOSITY_HEADER ='#"Step"\t"Acceleration (nm/ps^2)"\t"VelocityAmplitude (nm/ps)"\t"1/Viscosity (1/Pa.s)"'
 # 1/viscosity as the integrator returns it, in nm ps / (Da item), to 1/(Pa s): 1 Da nm^-1 ps^-1 = 1e18 / N_A Pa s
 INV_VISCOSITY_TO_PER_PA_S = 6.02214076e23 * 1e-18
 
@@ -313,6 +317,57 @@ def write_rdf(file, rdf, append=False, header=True):
             print("#" + "\t".join('"%s"' % name for name, _ in cols), file=out)
         for b in range(rdf.counts.shape[1]):
             print(*[repr(float(v[b])) for _, v in cols], sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_sdf(file, sdf, c=0, append=False, header=True):
+    """One class of a spatial distribution function (Context.sdf_read) as text: two comment lines (samples, dropped, invalid, bad frames,
+    the frame visits of the class's frame group, the sum of 1 / V, extent and voxels per axis; the column names) unless header=False, then
+    one tab-separated line per NON-ZERO voxel in the table's order -- its three indices, its centre in nm along xi1, xi2, xi3, the count,
+    the density in nm^-3 and g.  Floats are written with repr, so np.loadtxt reads back the bits.  `file`: a path or an open text stream."""
+    x, rho, g = sdf.centres, sdf.density(c), sdf.g(c)
+    out, own = _open(file, append)
+    try:
+        if header:
+            print('#"Samples"\t%d\t"Dropped"\t%d\t"Invalid"\t%d\t"BadFrames"\t%d\t"FrameVisits"\t%d\t"InvVolumeSum"\t%r\t"Extent (nm)"\t%r\t"Bins"\t%d\t"Class"\t"%d-%d"'
+                  % (sdf.samples, sdf.dropped, sdf.invalid, sdf.bad_frames, int(sdf.frame_visits[sdf.classes[c, 0]]), float(sdf.inv_volume_sum),
+                     float(sdf.extent), sdf.nbins, int(sdf.classes[c, 0]), int(sdf.classes[c, 1])), file=out)
+            print("#" + "\t".join('"%s"' % name for name in ("i1", "i2", "i3", "xi1 (nm)", "xi2 (nm)", "xi3 (nm)", "count", "density (nm^-3)", "g")), file=out)
+        for i, j, k in np.argwhere(sdf.counts[c] != 0):
+            print(i, j, k, repr(float(x[i])), repr(float(x[j])), repr(float(x[k])), int(sdf.counts[c, i, j, k]), repr(float(rho[i, j, k])),
+                  repr(float(g[i, j, k])), sep="\t", file=out)
+        out.flush()
+    finally:
+        if own:
+            out.close()
+
+
+def write_sdf_cube(file, sdf, c=0, quantity="g"):
+    """One class of a spatial distribution function as a Gaussian cube file, which VMD and similar viewers open as an isosurface:
+    `quantity` is "g", "density" (nm^-3) or "counts".  Two comment lines; one atom record (a carbon, for the viewer's sake) at the frame's
+    origin, which is the centre of the cube; the grid's origin at the first voxel's centre, (-h + voxel / 2) on every axis; the voxel
+    vectors along xi1, xi2, xi3; lengths in bohr; the data in the table's own C order (xi1 outermost, xi3 fastest), six values per line,
+    a new line after every xi3 run.  NaN (no visit, no sample) is written as 0."""
+    n, step = sdf.nbins, sdf.voxel / BOHR_NM
+    data = {"g": sdf.g, "density": sdf.density, "counts": lambda k: sdf.counts[k].astype(np.float64)}[quantity](c)
+    data = np.where(np.isnan(data), 0.0, data)
+    first = (-sdf.extent + 0.5 * sdf.voxel) / BOHR_NM
+    out, own = _open(file, False)
+    try:
+        print("spatial distribution function, %s, class %d-%d (frame group - site group)" % (quantity, int(sdf.classes[c, 0]), int(sdf.classes[c, 1])), file=out)
+        print("samples %d, frame visits %d, extent %r nm, axes xi1 xi2 xi3, lengths in bohr" % (sdf.samples, int(sdf.frame_visits[sdf.classes[c, 0]]), float(sdf.extent)), file=out)
+        print("%5d %12.6f %12.6f %12.6f" % (1, first, first, first), file=out)
+        for a in range(3):
+            print("%5d %12.6f %12.6f %12.6f" % ((n,) + tuple(step if b == a else 0.0 for b in range(3))), file=out)
+        print("%5d %12.6f %12.6f %12.6f %12.6f" % (6, 6.0, 0.0, 0.0, 0.0), file=out)
+        for i in range(n):
+            for j in range(n):
+                row = data[i, j]
+                for k0 in range(0, n, 6):
+                    print(" ".join("%13.5E" % v for v in row[k0:k0 + 6]), file=out)
         out.flush()
     finally:
         if own:

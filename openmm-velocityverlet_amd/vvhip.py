@@ -312,6 +312,30 @@ class VanHoveDistinctLayout(C.Structure):
                 ("r_max", C.c_double), ("dr", C.c_double)]
 
 
+SDF_MAX_WORDS = 1 << 23
+
+
+class SdfDesc(C.Structure):
+    """What a spatial distribution recorder is to accumulate (include/vvhip.h: vvhip_sdf_desc)."""
+    _fields_ = [("interval", C.c_int32), ("nbins", C.c_int32), ("num_frames", C.c_int32), ("num_frame_groups", C.c_int32),
+                ("num_site_groups", C.c_int32), ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("reserved", C.c_int32),
+                ("frames", C.c_void_p), ("frame_group", C.c_void_p), ("site_group", C.c_void_p), ("classes", C.c_void_p),
+                ("max_samples", C.c_int64), ("extent", C.c_double)]
+
+
+class SdfCounts(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("dropped", C.c_int64), ("invalid", C.c_int64), ("bad_frames", C.c_int64),
+                ("inv_volume_sum", C.c_double), ("frame_visits", C.c_int64 * 16)]
+
+
+class SdfLayout(C.Structure):
+    _fields_ = [("active", C.c_int32), ("interval", C.c_int32), ("nbins", C.c_int32), ("num_frame_groups", C.c_int32),
+                ("num_site_groups", C.c_int32), ("num_classes", C.c_int32), ("exclude_same_molecule", C.c_int32), ("tile", C.c_int32),
+                ("num_items", C.c_int32), ("reserved", C.c_int32), ("num_frames", C.c_int32 * 16), ("num_sites", C.c_int32 * 16),
+                ("classes", (C.c_int32 * 2) * 16), ("pairs_per_sample", C.c_int64 * 16), ("max_samples", C.c_int64), ("words", C.c_int64),
+                ("scratch_bytes", C.c_int64), ("start_step", C.c_int64), ("extent", C.c_double), ("voxel", C.c_double)]
+
+
 class CmMotionRecord(C.Structure):
     """The record of the scheduled removals of the centre-of-mass motion (include/vvhip.h: vvhip_cm_motion_record)."""
     _fields_ = [("frequency", C.c_int32), ("reserved", C.c_int32), ("removals", C.c_int64), ("skipped", C.c_int64),
@@ -415,6 +439,8 @@ def _load():
         "vvhip_vanhove_distinct_start": [vp, P(VanHoveDistinctDesc)], "vvhip_vanhove_distinct_stop": [vp],
         "vvhip_vanhove_distinct_info": [vp, P(VanHoveDistinctLayout)],
         "vvhip_vanhove_distinct_read": [vp, vp, C.c_int64, P(VanHoveDistinctCounts), i32],
+        "vvhip_sdf_start": [vp, P(SdfDesc)], "vvhip_sdf_sample": [vp], "vvhip_sdf_stop": [vp], "vvhip_sdf_info": [vp, P(SdfLayout)],
+        "vvhip_sdf_read": [vp, vp, C.c_int64, P(SdfCounts), i32],
         "vvhip_cm_motion_start": [vp, i32], "vvhip_cm_motion_stop": [vp], "vvhip_remove_cm_motion": [vp, P(dbl * 3)],
         "vvhip_cm_motion_read": [vp, P(CmMotionRecord)],
         "vvhip_set_velocities_to_temperature": [vp, dbl, dbl, C.c_uint64, u32, P(ThermalizeRecord)],
